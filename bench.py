@@ -44,7 +44,7 @@ sys.path.insert(0, ROOT)
 
 from tests import cases  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2.0  # wave64 VALU instructions per second: 1024 SIMD-32s, one per 2 cycles, 2.4 GHz
 SIMD_CYCLES_PER_S = 256 * 4 * 2.4e9        # cycles of all 1024 SIMDs per second
 WORKLOADS = {
@@ -69,6 +69,25 @@ def algorithmic_bytes_per_photon(c, n, nc):
 
 
 CPU_BATCH = 100000  # the reference tallies in float32: batches must stay small
+DUMP_BUDGET_BYTES = 64 * 2 ** 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, stats):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step -- the driver's statistics of the
+    moment arrays (every tally's mean and standard error, photon and batch counts) -- as DIR/<name>.npy in float64, so that
+    two builds run with the same arguments can be compared output for output.  Every array is written whole while all of
+    them fit in DUMP_BUDGET_BYTES; beyond that an array larger than its share is cut to a fixed, seeded sample of its
+    elements (the same flat indices in every run, written beside it as DIR/<name>_sample_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in stats.items()}
+    share = DUMP_BUDGET_BYTES // (2 * len(arrays))
+    sample = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    for name, a in sorted(arrays.items()):
+        if sample and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, share // 16, replace=False)).astype(np.int64)
+            np.save(os.path.join(path, name + "_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _cpu_worker(args):
@@ -236,7 +255,7 @@ def roofline_block(workload, cnt, per_step, nc, launch_ms, pipeline=False, block
     return out
 
 
-XGMI_LINK_BYTES_PER_S = 153e9  # one xGMI link of an MI355X (7 per GPU), /opt/skills/guides/MI355X_MICROARCH.md
+XGMI_LINK_BYTES_PER_S = 153e9  # one xGMI link of an MI355X (7 per GPU), spec figure
 
 
 def one_rank_allreduce_ms(torch, tensor, device, reps=5):
@@ -464,6 +483,8 @@ def lw_bench(a, M, torch, dist, dev, rank, local_rank, world, rehearse):
     out = None
     if rank == 0:
         stats = driver.statistics(driver.unpack_moments(moments.cpu().numpy(), nx, ny, nz), solarFlux=flux)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, stats)
         reduced_photons = int(stats["totalPhotons"])
         if world > 1:  # parity is quoted on one rank's 1e8 photons
             run.bindMoments(0)
@@ -579,8 +600,10 @@ def dry_run(a, rank, world):
     seen = torch.zeros(world, dtype=torch.float64)
     seen[rank] = 1.0 + rank
     dist.barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.warmup + a.steps):
+    t0 = None
+    for i in range(a.warmup + a.steps):
+        if i == a.warmup:  # (the timed region: the --steps steps after the warm-up)
+            t0 = time.perf_counter()
         buf = torch.zeros(8 + 2 * 16, dtype=torch.float64)
         buf[0], buf[1] = per_step, w["batches"]
         dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # sumAcrossProcesses
@@ -590,7 +613,7 @@ def dry_run(a, rank, world):
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     if rank == 0:
         print(json.dumps({"metric": "photons/sec", "value": 0.0, "unit": "photons/s", "n_gpus": world, "steps": a.steps,
-                          "warmup": a.warmup, "ms_per_step": 1e3 * float(tt.item()) / max(1, a.steps), "higher_is_better": True,
+                          "warmup": a.warmup, "ms_per_step": 1e3 * float(tt.item()) / a.steps, "higher_is_better": True,
                           "scaling": a.scaling, "vs_baseline": None, "dtype": "f32/f64", "data": "synthetic", "dry_run": True,
                           "config": {"workload": a.workload, "world_size": dist.get_world_size(), "backend": "gloo",
                                      "ranks_seen": [int(x) - 1 for x in seen.tolist()],
@@ -624,7 +647,12 @@ def main():
                     help="weak (default, the driver's contract): every rank traces the workload's photons per step; strong: the "
                          "step's photons are one fixed job whose batches are split over the ranks (monteCarloDriver.f95:665-880)")
     ap.add_argument("--dry-run", action="store_true", help="rehearse launcher + collective on CPU (gloo), no tracing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the statistics of its moment "
+                         "arrays) as DIR/<name>.npy, float64, at most 64 MB in all; inputs are the same in every run")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if a.gpus > 1 and not under_launcher:
@@ -799,6 +827,8 @@ def main():
     if rank == 0:
         # the moment arrays now hold the last step: world * per_step photons, reduced over ranks
         stats = driver.statistics(driver.unpack_moments(moments.cpu().numpy(), nx, ny, nz))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, stats)
         reduced_photons = int(stats["totalPhotons"])
         integ.bindMoments(0)
         if not a.no_cpu_baseline:

@@ -7,6 +7,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -44,3 +47,34 @@ def test_under_a_launcher_the_env_decides():
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
     assert json.loads(lines[0])["config"]["ranks_seen"] == [0, 1]
+
+
+def test_steps_must_be_at_least_one():
+    """--steps is the number of timed steps that ms_per_step divides by: none is refused, not reported."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900, method="thread")
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the statistics of the last timed step's moments, float64, one .npy per name; the same arguments
+    give the same photons, and the fixed-point tallies the same numbers bit for bit."""
+    args = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"]
+    outs = [_run(*args, "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    for out in outs:
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+    names = sorted(f for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    for k in ("totalPhotons", "batches", "meanFluxUp", "meanFluxDown", "meanFluxAbsorbed", "fluxUp", "fluxUp_StdErr",
+              "absorbedVolume"):
+        assert k + ".npy" in names, k
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 2 ** 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    for f in names:
+        assert got[f[:-4]].dtype == np.float64, f
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    assert got["totalPhotons"] == outs[0]["config"]["photons_in_reduced_moments_last_step"] == 10 ** 7
+    assert got["fluxUp"].shape == (32, 1) and got["absorbedVolume"].shape == (32, 1, 32)
+    assert abs(got["meanFluxUp"] + got["meanFluxDown"] + got["meanFluxAbsorbed"] - 1.0) < 0.03
