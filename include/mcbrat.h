@@ -166,6 +166,9 @@ double *mcbrat_moments_device_pointer(mcbrat_ctx *ctx);
  * element d % 4; d counts from firstDraw), drawn and counted on the device.  cdf and distribution are host arrays. */
 int mcbrat_frequency_distribution(mcbrat_ctx *ctx, uint64_t seed, uint64_t firstDraw, int32_t numLambda, const double *cdf,
                                   int64_t totalPhotons, int64_t *distribution);
+/* The device's Philox4x32-10 (the generator every kernel draws from), for its known-answer test: block i of n from
+ * in[6 i .. 6 i + 5] = counter[4], key[2] into out[4 i .. 4 i + 3].  Host arrays; returns when out is written. */
+int mcbrat_philox4x32_10(mcbrat_ctx *ctx, int32_t n, const uint32_t *in, uint32_t *out);
 int mcbrat_reset_moments(mcbrat_ctx *ctx); /* stream-ordered: enqueued before whatever the context does next; a caller
                                               that reads a bound buffer itself calls mcbrat_synchronize first */
 int mcbrat_get_moments(mcbrat_ctx *ctx, double *hostBuffer);
@@ -226,6 +229,8 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
 /* Scheduling options by name (none of them changes a result: the same photons, the same arithmetic per photon, integer
  * tallies -- tests/test_gpu_tunings.py holds random choices against the defaults bit for bit).  ABI 3.
  *   "jumpThreshold", "crossThreshold"  lanes queued before transitions of the layer-skipping walk / block crossings are served
+ *   "batchUnits"  1: the block walk cuts its workgroups' work units inside batches, as the flat walk does (default 0: units
+ *                 across the launch, two batches' tallies per workgroup where they fit; environment MCBRAT_BATCH_UNITS)
  * The reference has no counterpart (its loop is one photon at a time, monteCarloRadiativeTransfer.f95:463-466). */
 int mcbrat_set_option(mcbrat_ctx *ctx, const char *name, int32_t value);
 

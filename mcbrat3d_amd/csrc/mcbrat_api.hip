@@ -80,6 +80,7 @@ struct mcbrat_ctx {
   bool blockOpticsUniform = false;
   int nBlocks = 0;
   int crossThreshold = 8;      // MCBRAT_CROSS_THRESHOLD
+  int batchUnits = 0;          // MCBRAT_BATCH_UNITS / option "batchUnits": 1 cuts the block walk's work units inside batches (launch_block_s)
   int jumpThreshold = 8;       // MCBRAT_JUMP_THRESHOLD
   float *dExtB = nullptr, *dCumB = nullptr, *dSsaB = nullptr, *dBgExt = nullptr, *dBgCum = nullptr, *dBgSsa = nullptr;
   uint16_t *dPfiB = nullptr, *dBgPfi = nullptr;
@@ -771,22 +772,38 @@ bool block_walk_applies(const mcbrat_ctx *c, const LaunchPlan &L) {
   return blocks_worth_it(c) && ((L.priv && L.gridLds) || L.blockLite);
 }
 
+// Work units of the block walk.  Launch-wide (the default): every resident workgroup gets the same share of the launch's photons,
+// cut across batch boundaries, and keeps the tallies of the two batches its share may touch in two LDS slabs -- no workgroup
+// slot stays empty (cut inside batches, 100 batches of the step cloud make 500 units for 512 slots) and all units end together.
+// Per batch (units_per_batch): where a share would be longer than a batch, or where two slabs would cost residency or not fit.
 template <int BLOCK, bool TBL, bool DBG, bool EMIT, int SIMPLE, int OPT = 0>
 int launch_block_s(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
   auto kernel = trace_block_kernel<BLOCK, TBL, DBG, EMIT, SIMPLE, OPT>;
   if (lds + 512 > c->ldsPerCU) return fail(c, "computeRadiativeTransfer: the block-walk tables do not fit the LDS of a compute unit.");
-  if (lds > kLdsBudget)
-    HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int perCU = c->blocksPerCU;
   if (perCU <= 0) {
+    if (lds > kLdsBudget)
+      HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_OK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, BLOCK, lds));
     perCU = std::max(1, std::min(perCU, 8));
   }
   unsigned long long blocks = (unsigned long long)perCU * c->numCUs;
-  const unsigned long long upb = units_per_batch(blocks, p.ppb, nBatches, BLOCK);
-  p.unitsPerBatch = upb;
-  p.nUnits = upb * (unsigned long long)nBatches;
-  blocks = std::min(blocks, p.nUnits);
+  // (the kernel's own layout with both slabs; 512 bytes: its static LDS)
+  const size_t lds2 = block_lds_layout(p.nx, p.ny, p.nz, SIMPLE != 0 ? 1 : p.nc, 2 * (size_t)p.slabStride, p.nBlocks, TBL ? (size_t)p.tblTotalFloats : 0,
+                                       OPT, EMIT && p.cdfTopLds != 0).total;
+  const unsigned long long units = std::max<unsigned long long>(1, std::min(blocks, p.total));
+  p.unitsWide = !c->batchUnits && (p.total + units - 1) / units <= p.ppb && (size_t)perCU * (lds2 + 512) <= c->ldsPerCU;
+  if (p.unitsWide) {
+    lds = lds2;
+    p.nUnits = blocks = units;
+  } else {
+    const unsigned long long upb = units_per_batch(blocks, p.ppb, nBatches, BLOCK);
+    p.unitsPerBatch = upb;
+    p.nUnits = upb * (unsigned long long)nBatches;
+    blocks = std::min(blocks, p.nUnits);
+  }
+  if (lds > kLdsBudget)
+    HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   p.ldsBytes = (unsigned)lds;
   hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<unsigned long long>(1, blocks)), dim3(BLOCK), lds, c->L().stream, p);
   HIP_OK(c, hipGetLastError());
@@ -947,6 +964,7 @@ mcbrat_ctx *mcbrat_create(int device) {
   if (const char *e = getenv("MCBRAT_WIDE")) c->wideDefault = c->wideMode = std::max(0, std::min(2, atoi(e)));
   if (const char *e = getenv("MCBRAT_JUMP_THRESHOLD")) c->jumpThreshold = std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MCBRAT_CROSS_THRESHOLD")) c->crossThreshold = std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MCBRAT_BATCH_UNITS")) c->batchUnits = atoi(e) != 0;
   if (const char *e = getenv("MCBRAT_RAY_DEFER")) c->rayDefer = atoi(e);
   if (const char *e = getenv("MCBRAT_RAY_SHORT")) c->rayShort = std::max(1, atoi(e));
   if (const char *e = getenv("MCBRAT_RAY_PASS_ITERS")) c->rayPassIters = std::max(1, atoi(e));
@@ -1419,6 +1437,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   const std::string n(name);
   if (n == "jumpThreshold") c->jumpThreshold = std::max(1, std::min(64, (int)value));
   else if (n == "crossThreshold") c->crossThreshold = std::max(1, std::min(64, (int)value));
+  else if (n == "batchUnits") c->batchUnits = value != 0;
   else return fail(c, "set_option: unknown option '" + n + "'");
   return 0;
 }
@@ -1491,6 +1510,28 @@ int mcbrat_frequency_distribution(mcbrat_ctx *c, uint64_t seed, uint64_t firstDr
   HIP_OK(c, hipMemcpyAsync(h.data(), dCounts, sizeof(unsigned long long) * numLambda, hipMemcpyDeviceToHost, st));
   HIP_OK(c, hipStreamSynchronize(st));
   for (int i = 0; i < numLambda; ++i) distribution[i] = (int64_t)h[i];
+  return 0;
+}
+
+int mcbrat_philox4x32_10(mcbrat_ctx *c, int32_t n, const uint32_t *in, uint32_t *out) {
+  if (!c) return 1;
+  if (n < 0 || (n > 0 && (!in || !out))) return fail(c, "philox4x32_10: invalid arguments.");
+  if (n == 0) return 0;
+  (void)hipSetDevice(c->device);
+  if (init_lane(c, 0)) return 1;
+  hipStream_t st = c->lane[0].stream;
+  uint32_t *dIn = nullptr, *dOut = nullptr;
+  HIP_OK(c, dev_malloc((void **)&dIn, sizeof(uint32_t) * 6 * (size_t)n));
+  if (dev_malloc((void **)&dOut, sizeof(uint32_t) * 4 * (size_t)n) != hipSuccess) { (void)hipFree(dIn); return fail(c, "philox4x32_10: out of device memory."); }
+  hipError_t e = hipMemcpyAsync(dIn, in, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(philox_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dIn, (int)n, dOut);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(dIn); (void)hipFree(dOut);
+  HIP_OK(c, e);
   return 0;
 }
 

@@ -121,8 +121,9 @@ trace_block_kernel(const DevParams p) {
   const int ncol = p.nx * p.ny;
   const int nvox = ncol * p.nz;
   const int slabLen = (int)p.slabStride;
+  const int slabsLen = p.unitsWide ? 2 * slabLen : slabLen;  // launch-wide units: the slabs of the two batches a unit may touch, side by side
   const bool cdfTop = EMIT && p.cdfTopLds != 0;  // (wave-uniform)
-  const BlockLds lay = block_lds_layout(p.nx, p.ny, p.nz, nc, (size_t)slabLen, p.nBlocks, TBL_LDS ? (size_t)p.tblTotalFloats : 0, OPT, cdfTop);
+  const BlockLds lay = block_lds_layout(p.nx, p.ny, p.nz, nc, (size_t)slabsLen, p.nBlocks, TBL_LDS ? (size_t)p.tblTotalFloats : 0, OPT, cdfTop);
   const int nB4 = (p.nBlocks + 3) & ~3;
   long long *s_slab = reinterpret_cast<long long *>(smem_raw + lay.slab);
   unsigned *s_cursor = reinterpret_cast<unsigned *>(smem_raw + lay.cursor);
@@ -145,7 +146,7 @@ trace_block_kernel(const DevParams p) {
   for (int i = threadIdx.x; i < nEdges; i += BLOCK) s_edge[i] = p.edges[i];
   if (TBL_LDS)
     for (int i = threadIdx.x; i < p.tblTotalFloats; i += BLOCK) s_tbl[i] = p.tables[i];
-  for (int i = threadIdx.x; i < slabLen; i += BLOCK) s_slab[i] = 0;
+  for (int i = threadIdx.x; i < slabsLen; i += BLOCK) s_slab[i] = 0;
   if (threadIdx.x == 0) s_cursor[0] = 0;
   for (int i = threadIdx.x; i < p.nBlocks; i += BLOCK) s_blockRec[i] = p.blockRec[i];
   for (int i = threadIdx.x; i < nvox; i += BLOCK) s_blockOf[i] = p.blockOf[i];
@@ -181,14 +182,16 @@ trace_block_kernel(const DevParams p) {
   const int lane = threadIdx.x & (kWave - 1);
   const unsigned long long laneBelow = (1ull << lane) - 1ull;
 
-  // this workgroup's unit = photons [unitFirst, unitFirst + unitCount) of ONE batch
+  // this workgroup's unit = photons [unitFirst, unitFirst + unitCount) of the launch; the first unitSplit of them belong to the
+  // batch of unitSlab, the others (launch-wide units only) to the next batch, whose tallies go to the second LDS slab
   unsigned long long unitFirst = 0;
-  unsigned unitCount = 0;
+  unsigned unitCount = 0, unitSplit = 0;
   long long *unitSlab = nullptr;
 
   // lane state --------------------------------------------------------------------------
   int state = BW_DEAD;
   bool more = true;
+  int slabOff = 0;                     // the LDS slab of the lane's photon: 0, or slabLen for the second batch of a launch-wide unit
   uint32_t idLo = 0, idHi = 0, event = 0;
   double px = 0, py = 0, pz = 0;      // leg origin (in the periodic image the leg is currently in)
   float dx = 0, dy = 0, dz = 1;       // direction cosines
@@ -292,18 +295,23 @@ trace_block_kernel(const DevParams p) {
 #endif
   for (unsigned long long unit = blockIdx.x;; unit += gridDim.x) {
     if (unit >= p.nUnits) break;  // workgroup-uniform
-    uint32_t batch;
-    {
+    if (p.unitsWide) {  // (hi - lo <= ppb, the host's condition: at most one batch boundary inside the unit)
+      const unsigned long long lo = p.total * unit / p.nUnits, hi = p.total * (unit + 1) / p.nUnits;
+      const unsigned long long b = lo / p.ppb, end = (b + 1) * p.ppb;
+      unitFirst = lo;
+      unitCount = (unsigned)(hi - lo);
+      unitSplit = (unsigned)((hi < end ? hi : end) - lo);
+      unitSlab = p.slabs + b * p.slabStride;
+    } else {
       const unsigned long long b = unit / p.unitsPerBatch, s = unit % p.unitsPerBatch;
       const unsigned long long bp = (p.total - b * p.ppb) < p.ppb ? (p.total - b * p.ppb) : p.ppb;
       const unsigned long long lo = (bp * s) / p.unitsPerBatch, hi = (bp * (s + 1)) / p.unitsPerBatch;
       unitFirst = b * p.ppb + lo;
       unitCount = (unsigned)(hi - lo);
+      unitSplit = unitCount;
       unitSlab = p.slabs + b * p.slabStride;
-      batch = (uint32_t)b;
-      more = true;
     }
-    (void)batch;
+    more = true;
 
     for (;;) {
       bool needLeg = false;
@@ -348,7 +356,7 @@ trace_block_kernel(const DevParams p) {
             }
           }
         }
-        atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + (top ? 0 : ncol) + (ix + p.nx * iy)), weight_to_fixed(w));
+        atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + slabOff + (top ? 0 : ncol) + (ix + p.nx * iy)), weight_to_fixed(w));
         if (top) {
           if (DEBUG) {
             cTop++;
@@ -410,6 +418,7 @@ trace_block_kernel(const DevParams p) {
             const unsigned long long id = p.firstPhoton + myIdx;
             idLo = (uint32_t)id; idHi = (uint32_t)(id >> 32);
             event = 0; nScat = 0; nLegs = 0;
+            slabOff = k < unitSplit ? 0 : slabLen;
             uint32_t r[4];
             philox4x32_10(0u, 0u, idLo, idHi, p.seedLo, p.seedHi, r);
             double lx, ly, lz;  // fractional launch position in [0,1]
@@ -484,7 +493,7 @@ trace_block_kernel(const DevParams p) {
               pz = s_edge[offZ + iz] + (t - fl) * (s_edge[offZ + iz + 1] - s_edge[offZ + iz]);
             }
             if (EMIT && p.lwFlag && pz > 0.0)  // :504-508 emission counts as negative absorption
-              atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + 2 * ncol + (ix + p.nx * (iy + p.ny * iz))), to_fixed(-1.0));
+              atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + slabOff + 2 * ncol + (ix + p.nx * (iy + p.ny * iz))), to_fixed(-1.0));
             needLeg = true;
           } else {
             more = false;
@@ -542,7 +551,7 @@ trace_block_kernel(const DevParams p) {
         }
         if (DEBUG) countCrossings(px, py, iz);  // (after the fold of the look-ups above: px, py are the collision point)
         if (ssa < 1.0f) {  // absorption :765-771
-          atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + 2 * ncol + cell), weight_to_fixed(w * (1.0f - ssa)));
+          atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + slabOff + 2 * ncol + cell), weight_to_fixed(w * (1.0f - ssa)));
           w = w * ssa;
           if (DEBUG) cAbs++;
         }
@@ -712,9 +721,10 @@ trace_block_kernel(const DevParams p) {
       STAMP(7);
     }
 
-    // flush this unit's private tallies into the batch slab, once
+    // flush this unit's private tallies into the batch slab, once (launch-wide units: the second LDS slab into the next
+    // batch's, which follows in memory; it holds nothing unless the unit reached that batch)
     __syncthreads();
-    for (int i = threadIdx.x; i < slabLen; i += BLOCK) {
+    for (int i = threadIdx.x; i < slabsLen; i += BLOCK) {
       const long long v = s_slab[i];
       if (v != 0) {
         atomicAdd(reinterpret_cast<unsigned long long *>(unitSlab + i), (unsigned long long)v);

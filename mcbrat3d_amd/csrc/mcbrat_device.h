@@ -156,6 +156,8 @@ struct DevParams {
   unsigned long long slabStride;  // in elements
   unsigned long long nUnits;      // PRIV mode: work units (each inside one batch) ...
   unsigned long long unitsPerBatch;  // ... and how many of them a batch is cut into
+  int unitsWide;                  // block walk: unit k is photons [k total / nUnits, (k+1) total / nUnits) of the launch instead, no more
+                                  // than a batch long, so it touches two batches at most: two tally slabs in LDS (unitsPerBatch unused)
   int eventThreshold;             // process events when fewer than this many lanes are walking
   int launchThreshold;            // idle lanes queued before new photons are launched
   int surfaceThreshold;           // lanes queued before exits (top / surface) are served

@@ -26,6 +26,8 @@
                      asm volatile(op " %0, %0, %0, %0" : "+v"(d4)); asm volatile(op " %0, %0, %0, %0" : "+v"(d5)); asm volatile(op " %0, %0, %0, %0" : "+v"(d6)); asm volatile(op " %0, %0, %0, %0" : "+v"(d7));
 #define EIGHT_U(op) asm volatile(op " %0, %0, %0" : "+v"(u0)); asm volatile(op " %0, %0, %0" : "+v"(u1)); asm volatile(op " %0, %0, %0" : "+v"(u2)); asm volatile(op " %0, %0, %0" : "+v"(u3)); \
                     asm volatile(op " %0, %0, %0" : "+v"(u4)); asm volatile(op " %0, %0, %0" : "+v"(u5)); asm volatile(op " %0, %0, %0" : "+v"(u6)); asm volatile(op " %0, %0, %0" : "+v"(u7));
+#define EIGHT_U3(op) asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u0)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u1)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u2)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u3)); \
+                     asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u4)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u5)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u6)); asm volatile(op " %0, %0, %0, %0 bitop3:0x96" : "+v"(u7));
 #define MAD64(q, u) asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, 0" : "+v"(q) : "v"(u) : "vcc");
 #define EIGHT_MAD MAD64(q0, u0) MAD64(q1, u1) MAD64(q2, u2) MAD64(q3, u3) MAD64(q4, u4) MAD64(q5, u5) MAD64(q6, u6) MAD64(q7, u7)
 #define CVT_FD(d, a) asm volatile("v_cvt_f64_f32 %0, %1" : "=v"(d) : "v"(a));
@@ -36,6 +38,7 @@
 KERNEL(k_fma_f32, EIGHT_F("v_fmac_f32"))
 KERNEL(k_mul_f32, EIGHT_F("v_mul_f32"))
 KERNEL(k_xor, EIGHT_U("v_xor_b32"))
+KERNEL(k_bitop3, EIGHT_U3("v_bitop3_b32"))  // three-input xor (truth table 0x96): Philox's a ^ b ^ c in one instruction
 KERNEL(k_add_u32, EIGHT_U("v_add_u32"))
 KERNEL(k_mul_lo, EIGHT_U("v_mul_lo_u32"))
 KERNEL(k_mul_hi, EIGHT_U("v_mul_hi_u32"))
@@ -132,7 +135,8 @@ int main() {
     run("v_swap_b32", k_v_swap, out, w); run("v_cndmask_b32", k_v_cndmask, out, w); run("v_accvgpr write+read (pairs)", k_v_accvgpr, out, w);
   }
   for (int w : {1, 8}) {
-    run("v_fmac_f32", k_fma_f32, out, w); run("v_mul_f32", k_mul_f32, out, w); run("v_xor_b32", k_xor, out, w); run("v_add_u32", k_add_u32, out, w);
+    run("v_fmac_f32", k_fma_f32, out, w); run("v_mul_f32", k_mul_f32, out, w); run("v_xor_b32", k_xor, out, w); run("v_bitop3_b32 (xor3)", k_bitop3, out, w);
+    run("v_add_u32", k_add_u32, out, w);
     run("v_mul_lo_u32", k_mul_lo, out, w); run("v_mul_hi_u32", k_mul_hi, out, w); run("v_mad_u64_u32", k_mad64, out, w);
     run("v_rcp_f32", k_rcp, out, w); run("v_log_f32", k_log, out, w); run("v_sqrt_f32", k_sqrt, out, w); run("v_sin_f32", k_sin, out, w);
     run("v_add_f64", k_add_f64, out, w); run("v_mul_f64", k_mul_f64, out, w); run("v_fma_f64", k_fma_f64, out, w);
