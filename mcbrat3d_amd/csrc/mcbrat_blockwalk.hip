@@ -180,7 +180,6 @@ trace_block_kernel(const DevParams p) {
   const double invDz = (double)p.nz / (p.zMax - p.z0);
 
   const int lane = threadIdx.x & (kWave - 1);
-  const unsigned long long laneBelow = (1ull << lane) - 1ull;
 
   // this workgroup's unit = photons [unitFirst, unitFirst + unitCount) of the launch; the first unitSplit of them belong to the
   // batch of unitSlab, the others (launch-wide units only) to the next batch, whose tallies go to the second LDS slab
@@ -190,9 +189,12 @@ trace_block_kernel(const DevParams p) {
 
   // lane state --------------------------------------------------------------------------
   int state = BW_DEAD;
-  bool more = true;
+  // lanes that may still take a photon of this unit: a wave-uniform mask, not a per-lane flag -- ballots and the lane
+  // test of the launch then combine it with scalar logic (a per-lane flag turns each ballot of it into a select + compare)
+  unsigned long long moreMask = ~0ull;
   int slabOff = 0;                     // the LDS slab of the lane's photon: 0, or slabLen for the second batch of a launch-wide unit
   uint32_t idLo = 0, idHi = 0, event = 0;
+  unsigned long long idP1 = 0;         // philox_p1(idLo): the first round's product shared by every block of the photon's stream
   double px = 0, py = 0, pz = 0;      // leg origin (in the periodic image the leg is currently in)
   float dx = 0, dy = 0, dz = 1;       // direction cosines
   float ivx = 0, ivy = 0, ivz = 0;    // 1/direction
@@ -255,9 +257,16 @@ trace_block_kernel(const DevParams p) {
   const bool legacyNoClamp = (DEBUG || kTestBounds) && (p.legacyTies & 1) != 0, legacyMoveNaN = (DEBUG || kTestBounds) && (p.legacyTies & 2) != 0,
              legacyKeepSpans = (DEBUG || kTestBounds) && (p.legacyTies & 4) != 0;
   auto inRangeX = [&](int j, unsigned r) { return legacyNoClamp ? j : inRange(j, r); };  // clamp of a block crossing
+  // cell number of (ix, iy, iz): 24-bit multiplies (full rate; a 32-bit one is a 64-bit multiply-add on this target), exact
+  // because the grid is resident in LDS -- every index and product is below 2^17
+  const unsigned nx24 = (unsigned)p.nx, ncol24 = (unsigned)ncol;
+  auto cellOf = [&](int ix, int iy, int iz) -> int {
+    if (NOY) return ix + (int)__umul24(ncol24, (unsigned)iz);
+    return ix + (int)__umul24(nx24, (unsigned)(iy + (int)__umul24((unsigned)p.ny, (unsigned)iz)));
+  };
   // Distances along the leg to the faces of the block that holds cell (ix, iy, iz); its extinction.
   auto enterBlock = [&](int ix, int iy, int iz) {
-    const int cell = ix + p.nx * (iy + p.ny * iz);
+    const int cell = cellOf(ix, iy, iz);
     const unsigned blk = s_blockOf[cell];
     const uint4 rec = s_blockRec[blk];
     if constexpr (OPT == 0) extCur = s_ext[cell]; else extCur = s_ext[blk];
@@ -268,9 +277,11 @@ trace_block_kernel(const DevParams p) {
     const int fz = dz >= 0.0f ? (int)(rz >> 16) : (int)(rz & 0xffffu);
     // a block that spans a whole periodic axis has no face on it (the lane's position runs through the images)
     spans |= rec.w;  // (in such a block the lane may leave the principal image: folded when it leaves the block)
-    tnx = ((rec.w & 1u) || ivx == 0.0f) ? FLT_MAX : (float)(s_edge[fx] - px) * ivx;
+    // (the edges are read whether or not the select keeps them -- every face index is in the table: selects, no branches)
+    const float ex = (float)(s_edge[fx] - px), ez = (float)(s_edge[offZ + fz] - pz);
+    tnx = ((rec.w & 1u) || ivx == 0.0f) ? FLT_MAX : ex * ivx;
     tny = (NOY || (rec.w & 2u) || ivy == 0.0f) ? FLT_MAX : (float)(s_edge[offY + fy] - py) * ivy;
-    tnz = ivz == 0.0f ? FLT_MAX : (float)(s_edge[offZ + fz] - pz) * ivz;
+    tnz = ivz == 0.0f ? FLT_MAX : ez * ivz;
   };
 
   // Why the loop ends.  In one iteration a lane in BW_MOVE always leaves that state (collision, block face, exit or
@@ -311,7 +322,7 @@ trace_block_kernel(const DevParams p) {
       unitSplit = unitCount;
       unitSlab = p.slabs + b * p.slabStride;
     }
-    more = true;
+    moreMask = ~0ull;
 
     for (;;) {
       bool needLeg = false;
@@ -373,7 +384,7 @@ trace_block_kernel(const DevParams p) {
             mu = sqrtf(uZ);
             uint32_t r[4];
             for (uint32_t j = 0; !(fabsf(mu) > 2.0f * FLT_MIN); j++) {
-              if ((j & 3u) == 0) philox4x32_10(event, 2u + (j >> 2), idLo, idHi, p.seedLo, p.seedHi, r);
+              if ((j & 3u) == 0) philox4x32_10_p1(event, 2u + (j >> 2), idP1, idHi, p.seedLo, p.seedHi, r);
               mu = sqrtf(u01(pick4(r, j & 3u)));
             }
           }
@@ -393,7 +404,7 @@ trace_block_kernel(const DevParams p) {
         }
       }
       STAMP(5);
-      const unsigned long long mDead = __ballot(state == BW_DEAD && more);
+      const unsigned long long mDead = __ballot(state == BW_DEAD) & moreMask;
       const bool doLaunch = __popcll(mDead) >= p.launchThreshold || idle;
       const unsigned long long want = doLaunch ? mDead : 0ull;
       if (DEBUG) {
@@ -405,22 +416,24 @@ trace_block_kernel(const DevParams p) {
       }
       if (want != 0ull) {  // wave-uniform
         const int nWant = __popcll(want);
-        const int rank = __popcll(want & laneBelow);
+        const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(want >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)want, 0u));  // lanes of `want` below this one
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(&s_cursor[0], (unsigned)nWant);
         base = (unsigned)__shfl((int)base, 0);
-        const unsigned k = base + (unsigned)rank;
+        const unsigned k = base + rank;
         const bool valid = k < unitCount;
         const unsigned long long myIdx = unitFirst + k;
-        if (state == BW_DEAD && more) {
+        const unsigned long long mValid = __ballot(valid);
+        if (__builtin_amdgcn_inverse_ballot_w64(want)) {  // (this lane is in `want`: dead, and may take a photon)
           if (valid) {
             // ---- launch: getNextPhoton + computeRT :466-508 (as in trace_kernel, bit for bit) ----
             const unsigned long long id = p.firstPhoton + myIdx;
             idLo = (uint32_t)id; idHi = (uint32_t)(id >> 32);
+            idP1 = philox_p1(idLo);
             event = 0; nScat = 0; nLegs = 0;
             slabOff = k < unitSplit ? 0 : slabLen;
             uint32_t r[4];
-            philox4x32_10(0u, 0u, idLo, idHi, p.seedLo, p.seedHi, r);
+            philox4x32_10_p1(0u, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
             double lx, ly, lz;  // fractional launch position in [0,1]
             if (!EMIT) {  // newPhotonStream_Directional, monteCarloIllumination.f95:88-96
               lx = (double)u01(r[0]);
@@ -436,7 +449,7 @@ trace_block_kernel(const DevParams p) {
                 lz = 0.0;
                 uint32_t r1[4];
                 for (uint32_t j = 0;; j++) {
-                  if ((j & 3u) == 0) philox4x32_10(0u, 1u + (j >> 2), idLo, idHi, p.seedLo, p.seedHi, r1);
+                  if ((j & 3u) == 0) philox4x32_10_p1(0u, 1u + (j >> 2), idP1, idHi, p.seedLo, p.seedHi, r1);
                   mu = sqrtf(u01(pick4(r1, j & 3u)));
                   if (fabsf(mu) > 2.0f * FLT_MIN) break;
                 }
@@ -449,7 +462,7 @@ trace_block_kernel(const DevParams p) {
                 const int ij = cdfTop ? find_cdf(s_cdfRow + p.ny * (ik - 1), p.ny, 1, rn) : find_cdf(p.voxelCDF + ((long long)p.nx - 1) + nxy * (ik - 1), p.ny, p.nx, rn);
                 const int ii = find_cdf(p.voxelCDF + (long long)p.nx * ((ij - 1) + (long long)p.ny * (ik - 1)), p.nx, 1, rn);
                 uint32_t r1[4];
-                philox4x32_10(0u, 1u, idLo, idHi, p.seedLo, p.seedHi, r1);
+                philox4x32_10_p1(0u, 1u, idP1, idHi, p.seedLo, p.seedHi, r1);
                 lz = ((double)(ik - 1) * 1.0 / (double)p.nz) + (double)(u01(r[2]) / (float)p.nz);
                 if (ik == 1 && lz == 0.0) lz = 2.220446049250313e-16;
                 if (ik == p.nz && lz > 1.0 - 2.0 * 2.220446049250313e-16) lz = lz - 2.0 * 2.220446049250313e-16;
@@ -460,7 +473,7 @@ trace_block_kernel(const DevParams p) {
                   uint32_t uu;
                   if (j < 2) uu = j ? r1[3] : r1[2];
                   else {
-                    if (((j - 2) & 3u) == 0) philox4x32_10(0u, 2u + ((j - 2) >> 2), idLo, idHi, p.seedLo, p.seedHi, r2);
+                    if (((j - 2) & 3u) == 0) philox4x32_10_p1(0u, 2u + ((j - 2) >> 2), idP1, idHi, p.seedLo, p.seedHi, r2);
                     uu = pick4(r2, (j - 2) & 3u);
                   }
                   mu = 1.0f - (2.0f * u01(uu));
@@ -495,10 +508,9 @@ trace_block_kernel(const DevParams p) {
             if (EMIT && p.lwFlag && pz > 0.0)  // :504-508 emission counts as negative absorption
               atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + slabOff + 2 * ncol + (ix + p.nx * (iy + p.ny * iz))), to_fixed(-1.0));
             needLeg = true;
-          } else {
-            more = false;
           }
         }
+        moreMask &= ~want | mValid;  // a lane refused a photon takes none again
       }
       STAMP(0);
       // ---- scattering event, computeRT :703-821 ----
@@ -522,7 +534,7 @@ trace_block_kernel(const DevParams p) {
           ix = locX(xw, (spans & 1u) != 0);
           iy = locY(yw, (spans & 2u) != 0);
         }
-        int cell = ix + p.nx * (iy + p.ny * iz);
+        int cell = cellOf(ix, iy, iz);
         nScat++;
         if (DEBUG) cColl++;
         int c = 0;  // component pick :759-760 (findIndex over [0, cumExt(:)]), uniform = slot Z of the leg's block
@@ -540,7 +552,7 @@ trace_block_kernel(const DevParams p) {
         if (ssa <= 0.0f && extOfCell(cell) != extCur) {
           ix = inRange(ix, rx); iz = inRange(iz, rz);
           if (!NOY) iy = inRange(iy, ry);
-          cell = ix + p.nx * (iy + p.ny * iz);
+          cell = cellOf(ix, iy, iz);
           c = 0;
           if (nc > 1) {
             for (int k = 0; k < nc - 1; k++)
@@ -559,7 +571,7 @@ trace_block_kernel(const DevParams p) {
           float uR = uZ;  // one component: Z decides nothing at the component pick and serves here (no second block; mcbrat_kernels.hip)
           if (nc != 1) {  // (wave-uniform; compile time in the SIMPLE instantiations)
             uint32_t r1[4];
-            philox4x32_10(event, 1u, idLo, idHi, p.seedLo, p.seedHi, r1);
+            philox4x32_10_p1(event, 1u, idP1, idHi, p.seedLo, p.seedHi, r1);
             uR = u01(r1[1]);
           }
           if (uR >= w) { w = 0.0f; if (DEBUG) cKill++; }
@@ -572,7 +584,8 @@ trace_block_kernel(const DevParams p) {
         } else {
           // computeScatteringAngle :1594-1621 (table point count N, floor-type lookup as written)
           const int n = s_tblNSteps[c];
-          const float *t = tbl + s_tblOffset[c] + (long long)pfEntry * n;
+          // (in LDS the table is below 2^16 floats: a 24-bit multiply)
+          const float *t = tbl + s_tblOffset[c] + (TBL_LDS ? (long long)__umul24((unsigned)pfEntry, (unsigned)n) : (long long)pfEntry * n);
           const int ai = (int)(uX * (float)n) + 1;
           float ang;
           if (ai < n) {
@@ -627,7 +640,7 @@ trace_block_kernel(const DevParams p) {
           dbgZ = iz;
         }
         uint32_t r[4];
-        philox4x32_10(event, 0u, idLo, idHi, p.seedLo, p.seedHi, r);
+        philox4x32_10_p1(event, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
 #ifdef MCBRAT_PRECISE_MATH
         tau = -logf(fmaxf(FLT_MIN, u01(r[0])));
 #else
@@ -683,7 +696,7 @@ trace_block_kernel(const DevParams p) {
       }
       STAMP(1);
       // wave-uniform exit: nothing alive and every lane has already been refused a new photon
-      if (__ballot(state != BW_DEAD || more) == 0ull) break;
+      if ((__ballot(state != BW_DEAD) | moreMask) == 0ull) break;
 
 #ifdef MCBRAT_STUCK_PROBE  // development aid: a wave still looping after 3e6 iterations records 64 iterations of its first live lane, then drops it
       if (DEBUG && p.traceBuf && wIters > 3000000ull) {
@@ -707,16 +720,17 @@ trace_block_kernel(const DevParams p) {
         const bool isZ = tnz < m2;
         const float tmin = isZ ? tnz : m2;
         const float accNew = acc + (tmin - tcur) * extCur;  // :1743
-        if (accNew > tau) {
-          state = BW_COLLIDE;  // :1729-1738: the stop point is resolved at the head of the next iteration
-        } else if (!(tmin < FLT_MAX)) {
+        const bool coll = accNew > tau;  // :1729-1738: the stop point is resolved at the head of the next iteration
+        // (selects, not nested branches: every outcome but the drop is a few moves, and the wave nearly always holds several)
+        const bool up = dz >= 0.0f;
+        const bool out = isZ && (up ? (int)(rz >> 16) == p.nz : (rz & 0xffffu) == 0u);  // :1801-1812
+        const int next = coll ? BW_COLLIDE : (out ? (up ? BW_TOP : BW_SURFACE) : BW_CROSS);
+        acc = coll ? acc : accNew;
+        tcur = coll ? tcur : tmin;
+        if (!coll && !(tmin < FLT_MAX))
           MCBRAT_BW_DROP(DROP_VACUUM);    // no face ahead and nothing to collide with (a horizontal leg through vacuum): the reference walks for ever
-        } else {
-          acc = accNew;
-          tcur = tmin;
-          state = BW_CROSS;
-          if (isZ && (dz >= 0.0f ? (int)(rz >> 16) == p.nz : (rz & 0xffffu) == 0u)) state = dz >= 0.0f ? BW_TOP : BW_SURFACE;  // :1801-1812
-        }
+        else
+          state = next;
       }
       STAMP(7);
     }
