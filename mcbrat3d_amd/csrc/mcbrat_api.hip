@@ -80,8 +80,9 @@ struct mcbrat_ctx {
   bool blockOpticsUniform = false;
   int nBlocks = 0;
   int crossThreshold = 8;      // MCBRAT_CROSS_THRESHOLD
-  int batchUnits = 0;          // MCBRAT_BATCH_UNITS / option "batchUnits": 1 cuts the block walk's work units inside batches (launch_block_s)
+  int batchUnits = 0;          // MCBRAT_BATCH_UNITS / option "batchUnits": 1 cuts the block walk's work units inside batches (launch_kernel)
   int jumpThreshold = 8;       // MCBRAT_JUMP_THRESHOLD
+  bool noSimple3 = false;      // MCBRAT_NO_SIMPLE3 (tests): the block walk's near-uniform grids run the general kernel, not SIMPLE = 3
   float *dExtB = nullptr, *dCumB = nullptr, *dSsaB = nullptr, *dBgExt = nullptr, *dBgCum = nullptr, *dBgSsa = nullptr;
   uint16_t *dPfiB = nullptr, *dBgPfi = nullptr;
   int nbx = 0, nby = 0, nbz = 0;
@@ -141,7 +142,7 @@ struct mcbrat_ctx {
   unsigned long long tuneTrialPhotons = 1ull << 26;  // MCBRAT_TUNE_PHOTONS
   int regularWalk = 1;         // equally spaced grids: incremental face distances (MCBRAT_REGULAR_WALK=0 turns it off)
   int gridLdsMode = 1;         // stage the optical grid in LDS when it fits (private-tally mode)
-  int rayShort = 0, rayPassIters = 0, rayPassAt = 0;  // 0: chosen in launch_trace_b (MCBRAT_RAY_SHORT, MCBRAT_RAY_PASS_ITERS, MCBRAT_RAY_PASS_AT)
+  int rayShort = 0, rayPassIters = 0, rayPassAt = 0;  // 0: chosen in launch_trace (MCBRAT_RAY_SHORT, MCBRAT_RAY_PASS_ITERS, MCBRAT_RAY_PASS_AT)
   int rayDefer = 1;            // radiance: long rays are put aside and finished in dense passes (MCBRAT_RAY_DEFER=0: inside their event phase)
   int blockWalk = 1;           // LDS-resident grids: blocks of cells with one extinction value are crossed in one step (MCBRAT_BLOCK_WALK=0 / mcbrat_set_walk_options)
   int layerSkip = 1;           // layers of one extinction value: cross z faces only; clear-air flight outside the brick columns' cloud
@@ -641,12 +642,14 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.block = c->blockSize > 0 ? c->blockSize : (L.gridLds ? 768 : ((L.tblLds || L.priv) && L.lds > 16 * 1024 ? 512 : 256));
   if (blocks_worth_it(c) && L.priv && L.gridLds && c->srcKind != 0)
     L.cdfTop = block_lds_layout(c->nx, c->ny, c->nz, c->nc, slabStride, c->nBlocks, L.tblLds ? (size_t)c->tblTotalFloats : 0, 0, true).total <= kLdsBudget;
+  // fill_params chose the brick arrays: private tallies give way.  Decided last, so that tblLds, block and cdfTop stay
+  // those of the plan with private tallies.  (No flight over bricks: the LDS is the edge, layer and table part.)
+  if (L.priv && L.brick) {
+    L.priv = false;
+    L.gridLds = false;
+    L.lds = edges + bg + (L.tblLds ? tbl : 0);
+  }
   return L;
-}
-
-size_t plan_launch_lds(const mcbrat_ctx *c, const LaunchPlan &L) {
-  return sizeof(double) * (size_t)(c->nx + c->ny + c->nz + 3) + per_layer_lds(c->nz, L.fly ? c->flyNbx * c->flyNby : 0) +
-         (L.tblLds ? sizeof(float) * (size_t)c->tblTotalFloats : 0);
 }
 
 // Units per batch for the kernels whose workgroups keep one batch's tallies in LDS (a workgroup traces photons of one
@@ -670,99 +673,120 @@ inline unsigned long long units_per_batch(unsigned long long blocks, unsigned lo
   return best;
 }
 
-template <int BLOCK, bool TBL, int PRIV, bool BRICK, bool DBG, bool INTEN, bool EMIT, int SPEC = 0>
-int launch_trace_e(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
-  if (lds + kStaticLds > c->ldsPerCU && lds > kLdsBudget) return fail(c, "computeRadiativeTransfer: the grid's edge and layer tables do not fit the LDS of a compute unit.");
-  if (lds > kLdsBudget)  // (very tall grids: the per-layer tables alone can pass the default limit of a workgroup)
-    HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(trace_kernel<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, EMIT, SPEC>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// How a launch cuts its photons into work units
+enum class Units {
+  PerBlock,   // tallies in global memory: one workgroup per `block` photons, no more than are resident
+  PerBatch,   // every workgroup traces photons of one batch at a time: each batch cut into units_per_batch units
+  // The block walk.  Launch-wide (the default): every resident workgroup gets the same share of the launch's photons, cut
+  // across batch boundaries, and keeps the tallies of the two batches its share may touch in two LDS slabs -- no workgroup
+  // slot stays empty (cut inside batches, 100 batches of the step cloud make 500 units for 512 slots) and all units end
+  // together.  Per batch: where a share would be longer than a batch, or where two slabs would cost residency or not fit.
+  BlockWalk,
+};
+
+// Launches one instantiation of trace_kernel or trace_block_kernel on the lane's stream: as many workgroups as are resident
+// at `lds` bytes of dynamic LDS (the occupancy query, or the option blocksPerCU), and no more than there are work units.
+// ldsTwoSlabs: the block walk's layout with the slabs of launch-wide units.
+int launch_kernel(mcbrat_ctx *c, DevParams &p, const void *kernel, int block, size_t lds, Units units, int nBatches,
+                  size_t ldsTwoSlabs = 0) {
+  size_t allowed = kLdsBudget;  // dynamic LDS the kernel may take (above the default limit of a workgroup: by attribute)
   int perCU = c->blocksPerCU;
   if (perCU <= 0) {
-    HIP_OK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, trace_kernel<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, EMIT, SPEC>, BLOCK, lds));
+    if (lds > allowed) {
+      HIP_OK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allowed = lds;
+    }
+    HIP_OK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, block, lds));
     perCU = std::max(1, std::min(perCU, 8));
   }
   unsigned long long blocks = (unsigned long long)perCU * c->numCUs;
-  if (PRIV) {
-    // every workgroup traces photons of one batch at a time: cut each batch into units so that
-    // there is about one unit per resident workgroup
-    const unsigned long long upb = units_per_batch(blocks, p.ppb, nBatches, BLOCK);
+  bool launchWide = false;
+  if (units == Units::BlockWalk) {  // (512 bytes: the kernel's static LDS)
+    const unsigned long long n = std::max<unsigned long long>(1, std::min(blocks, p.total));
+    launchWide = !c->batchUnits && (p.total + n - 1) / n <= p.ppb && (size_t)perCU * (ldsTwoSlabs + 512) <= c->ldsPerCU;
+    p.unitsWide = launchWide;
+    if (launchWide) {
+      lds = ldsTwoSlabs;
+      p.nUnits = blocks = n;
+    }
+  }
+  if (units == Units::PerBlock) {
+    blocks = std::min(blocks, (p.total + block - 1) / block);
+  } else if (!launchWide) {  // about one unit per resident workgroup
+    const unsigned long long upb = units_per_batch(blocks, p.ppb, nBatches, block);
     p.unitsPerBatch = upb;
     p.nUnits = upb * (unsigned long long)nBatches;
     blocks = std::min(blocks, p.nUnits);
-  } else {
-    blocks = std::min(blocks, (p.total + BLOCK - 1) / BLOCK);
   }
-  const unsigned grid = (unsigned)std::max<unsigned long long>(1, blocks);
+  if (lds > allowed) HIP_OK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   p.ldsBytes = (unsigned)lds;
-  hipLaunchKernelGGL((trace_kernel<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, EMIT, SPEC>), dim3(grid), dim3(BLOCK), lds, c->L().stream, p);
-  HIP_OK(c, hipGetLastError());
+  void *args[] = {&p};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)std::max<unsigned long long>(1, blocks)), dim3(block), args, lds, c->L().stream);
+  HIP_OK(c, hipGetLastError());  // (the launch's error, if any)
   return 0;
 }
 
-template <int BLOCK, bool TBL, int PRIV, bool BRICK, bool DBG, bool INTEN = false>
-int launch_trace_t(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
-  // (the source kind is a template parameter: the emission launch code costs the solar instantiations registers)
-  if constexpr (BLOCK == 256 && PRIV == 0 && !BRICK && !DBG && !INTEN) {
+// trace_kernel with the table and source flags picked at run time (every value of both is built).  (The source kind is a
+// template parameter: the emission launch code costs the solar instantiations registers.)
+template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false>
+const void *trace_ptr(bool tbl, bool emit) {
+  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false>;
+  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false>;
+}
+
+// trace_kernel of 256 or 512 lanes.  Instantiated combinations: private tallies (small domains) and bricks (large ones) never
+// coincide; radiance runs read dense grids and are not instrumented.
+template <int BLOCK, bool DBG>
+const void *trace_kernel_for(const mcbrat_ctx *c, const DevParams &p, const LaunchPlan &L) {
+  const bool tbl = L.tblLds, emit = c->srcKind != 0;
+  if (c->nDir > 0) {
+    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true>(tbl, emit);
+    return trace_ptr<BLOCK, 0, false, false, true>(tbl, emit);
+  }
+  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, DBG>(tbl, emit) : trace_ptr<BLOCK, 1, false, DBG>(tbl, emit);
+  if (L.brick) return trace_ptr<BLOCK, 0, true, DBG>(tbl, emit);
+  if constexpr (BLOCK == 256 && !DBG) {
     // the large flux runs: dense grid in global memory, collision records (nc <= 2), layer-skipping walk, albedo
     // surface -- with the walk's spacing flags decided at compile time too (SPEC, mcbrat_kernels.hip)
     // A solar run with roulette (every bench workload) also has its component count and the roulette decided at compile
-    // time (SPEC bits 2-3 and 4); without roulette it runs the general kernel.
+    // time (SPEC bits 2-3 and 4); without roulette it runs the general kernel.  (Each SPEC is built for one source: EMIT = SPEC < 16.)
     if (p.rec != nullptr && p.layerSkip && p.fly && p.surfNumX == 0 && (p.xyRegularWalk || !p.zRegularWalk)) {
       const int walk = p.xyRegularWalk ? (p.zRegularWalk ? 2 : 3) : 1;
-      if (c->srcKind != 0) {
-        if (walk == 1) return launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, true, 1>(c, p, lds, nBatches);
-        if (walk == 2) return launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, true, 2>(c, p, lds, nBatches);
-        return launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, true, 3>(c, p, lds, nBatches);
-      }
-      if (p.useRR && (p.nc == 1 || p.nc == 2)) {
-        const int spec = walk | p.nc << 2 | 16;
-        switch (spec) {
-#define MCBRAT_SPEC_CASE(S) case S: return launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, false, S>(c, p, lds, nBatches)
-          MCBRAT_SPEC_CASE(1 | 1 << 2 | 16); MCBRAT_SPEC_CASE(2 | 1 << 2 | 16); MCBRAT_SPEC_CASE(3 | 1 << 2 | 16);
-          MCBRAT_SPEC_CASE(1 | 2 << 2 | 16); MCBRAT_SPEC_CASE(2 | 2 << 2 | 16); MCBRAT_SPEC_CASE(3 | 2 << 2 | 16);
+      switch (emit ? walk : (p.useRR && (p.nc == 1 || p.nc == 2) ? walk | p.nc << 2 | 16 : 0)) {
+#define MCBRAT_SPEC_CASE(S) \
+  case S: return tbl ? (const void *)trace_kernel<256, true, 0, false, false, false, ((S) < 16), (S)> : (const void *)trace_kernel<256, false, 0, false, false, false, ((S) < 16), (S)>
+        MCBRAT_SPEC_CASE(1); MCBRAT_SPEC_CASE(2); MCBRAT_SPEC_CASE(3);
+        MCBRAT_SPEC_CASE(1 | 1 << 2 | 16); MCBRAT_SPEC_CASE(2 | 1 << 2 | 16); MCBRAT_SPEC_CASE(3 | 1 << 2 | 16);
+        MCBRAT_SPEC_CASE(1 | 2 << 2 | 16); MCBRAT_SPEC_CASE(2 | 2 << 2 | 16); MCBRAT_SPEC_CASE(3 | 2 << 2 | 16);
 #undef MCBRAT_SPEC_CASE
-        }
       }
     }
   }
-  return c->srcKind == 0 ? launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, false>(c, p, lds, nBatches)
-                         : launch_trace_e<BLOCK, TBL, PRIV, BRICK, DBG, INTEN, true>(c, p, lds, nBatches);
+  return trace_ptr<BLOCK, 0, false, DBG>(tbl, emit);
 }
 
-template <int BLOCK, bool DBG>
-int launch_trace_b(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, int nBatches) {
-  // radiance runs: dense grids, no instrumentation
-  if (c->nDir > 0) {
-    if (DBG) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with intensity directions.");
-    // the waves' buffers of unfinished long rays (80 B per ray) take what LDS is left at the residency the kernel is built
-    // for: 4 workgroups of 256 lanes per CU on grids in global memory, 2 workgroups otherwise
-    const size_t waves = BLOCK / 64, base = (L.lds + 15) & ~(size_t)15;
-    const size_t budget = c->ldsPerCU / (L.priv ? 2 : (BLOCK == 256 ? 4 : 2));
-    size_t cap = (c->rayDefer && budget > base + 64) ? std::min<size_t>(64, (budget - base - 64) / (waves * 80)) : 0;
-    if (cap < 24 || c->nx + c->ny + c->nz + 3 > 0xffff || c->nDir > 0xffff) cap = 0;  // (a ray record packs edge-table indices and the direction in 16 bits)
-    p.rayCap = (int)cap;
-    // measured on the 128x128x64 cloud field, 4 directions: with roulette most rays end within a few cells and the long
-    // ones are best served in short, dense passes; without it every ray runs to the boundary and long passes pay
-    p.rayShort = c->rayShort > 0 ? c->rayShort : (c->useRRIntensity ? 4 : 8);
-    p.rayPassIters = c->rayPassIters > 0 ? c->rayPassIters : (c->useRRIntensity ? 16 : 64);
-    p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
-    const size_t lds = base + waves * cap * 80;
-    if (L.priv && L.gridLds) return L.tblLds ? launch_trace_t<BLOCK, true, 2, false, false, true>(c, p, lds, nBatches)
-                                             : launch_trace_t<BLOCK, false, 2, false, false, true>(c, p, lds, nBatches);
-    if (L.priv) return L.tblLds ? launch_trace_t<BLOCK, true, 1, false, false, true>(c, p, lds, nBatches)
-                                : launch_trace_t<BLOCK, false, 1, false, false, true>(c, p, lds, nBatches);
-    return L.tblLds ? launch_trace_t<BLOCK, true, 0, false, false, true>(c, p, lds, nBatches)
-                    : launch_trace_t<BLOCK, false, 0, false, false, true>(c, p, lds, nBatches);
+// trace_block_kernel with the table and source flags picked at run time (every value of both is built)
+template <int BLOCK, bool DBG, int SIMPLE, int OPT>
+const void *block_ptr(bool tbl, bool emit) {
+  if (tbl) return emit ? (const void *)trace_block_kernel<BLOCK, true, DBG, true, SIMPLE, OPT> : (const void *)trace_block_kernel<BLOCK, true, DBG, false, SIMPLE, OPT>;
+  return emit ? (const void *)trace_block_kernel<BLOCK, false, DBG, true, SIMPLE, OPT> : (const void *)trace_block_kernel<BLOCK, false, DBG, false, SIMPLE, OPT>;
+}
+
+template <int BLOCK, bool DBG, int OPT = 0>
+const void *block_kernel_for(const mcbrat_ctx *c, const DevParams &p, bool tbl) {
+  const bool emit = c->srcKind != 0;
+  // equally spaced axes, one component, no surface description: the instantiation with those decided at compile time
+  const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
+  if constexpr (OPT == 0 && BLOCK != 1024) {
+    if (simple && c->ny == 1 && !DBG) return block_ptr<BLOCK, DBG, 2, OPT>(tbl, emit);  // an x-z problem
   }
-  // instantiated combinations: private tallies (small domains) and bricks (large ones) never coincide
-  if (L.priv && L.gridLds) return L.tblLds ? launch_trace_t<BLOCK, true, 2, false, DBG>(c, p, L.lds, nBatches)
-                                           : launch_trace_t<BLOCK, false, 2, false, DBG>(c, p, L.lds, nBatches);
-  if (L.priv) return L.tblLds ? launch_trace_t<BLOCK, true, 1, false, DBG>(c, p, L.lds, nBatches)
-                              : launch_trace_t<BLOCK, false, 1, false, DBG>(c, p, L.lds, nBatches);
-  if (L.brick) return L.tblLds ? launch_trace_t<BLOCK, true, 0, true, DBG>(c, p, L.lds, nBatches)
-                               : launch_trace_t<BLOCK, false, 0, true, DBG>(c, p, L.lds, nBatches);
-  return L.tblLds ? launch_trace_t<BLOCK, true, 0, false, DBG>(c, p, L.lds, nBatches)
-                  : launch_trace_t<BLOCK, false, 0, false, DBG>(c, p, L.lds, nBatches);
+  if constexpr (!DBG && (BLOCK == 1024 || BLOCK == 768)) {
+    // no axis equally spaced by the reference's single-precision test, every axis equally spaced to 1e-6 of a cell (0.1 km cells):
+    // the same cells as the general instantiation finds, with nothing left to decide at run time (SIMPLE = 3)
+    if (!c->xyRegular && !c->zRegular && p.xyNearUniform && p.zNearUniform && c->nc == 1 && c->surfNumX == 0 && !c->noSimple3)
+      return block_ptr<BLOCK, DBG, 3, OPT>(tbl, emit);
+  }
+  return simple ? block_ptr<BLOCK, DBG, 1, OPT>(tbl, emit) : block_ptr<BLOCK, DBG, 0, OPT>(tbl, emit);
 }
 
 // The block walk applies where the face-by-face plan already keeps grid, tallies (and tables) in LDS -- or, in the wide
@@ -772,123 +796,76 @@ bool block_walk_applies(const mcbrat_ctx *c, const LaunchPlan &L) {
   return blocks_worth_it(c) && ((L.priv && L.gridLds) || L.blockLite);
 }
 
-// Work units of the block walk.  Launch-wide (the default): every resident workgroup gets the same share of the launch's photons,
-// cut across batch boundaries, and keeps the tallies of the two batches its share may touch in two LDS slabs -- no workgroup
-// slot stays empty (cut inside batches, 100 batches of the step cloud make 500 units for 512 slots) and all units end together.
-// Per batch (units_per_batch): where a share would be longer than a batch, or where two slabs would cost residency or not fit.
-template <int BLOCK, bool TBL, bool DBG, bool EMIT, int SIMPLE, int OPT = 0>
-int launch_block_s(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
-  auto kernel = trace_block_kernel<BLOCK, TBL, DBG, EMIT, SIMPLE, OPT>;
-  if (lds + 512 > c->ldsPerCU) return fail(c, "computeRadiativeTransfer: the block-walk tables do not fit the LDS of a compute unit.");
-  int perCU = c->blocksPerCU;
-  if (perCU <= 0) {
-    if (lds > kLdsBudget)
-      HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_OK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, BLOCK, lds));
-    perCU = std::max(1, std::min(perCU, 8));
-  }
-  unsigned long long blocks = (unsigned long long)perCU * c->numCUs;
-  // (the kernel's own layout with both slabs; 512 bytes: its static LDS)
-  const size_t lds2 = block_lds_layout(p.nx, p.ny, p.nz, SIMPLE != 0 ? 1 : p.nc, 2 * (size_t)p.slabStride, p.nBlocks, TBL ? (size_t)p.tblTotalFloats : 0,
-                                       OPT, EMIT && p.cdfTopLds != 0).total;
-  const unsigned long long units = std::max<unsigned long long>(1, std::min(blocks, p.total));
-  p.unitsWide = !c->batchUnits && (p.total + units - 1) / units <= p.ppb && (size_t)perCU * (lds2 + 512) <= c->ldsPerCU;
-  if (p.unitsWide) {
-    lds = lds2;
-    p.nUnits = blocks = units;
-  } else {
-    const unsigned long long upb = units_per_batch(blocks, p.ppb, nBatches, BLOCK);
-    p.unitsPerBatch = upb;
-    p.nUnits = upb * (unsigned long long)nBatches;
-    blocks = std::min(blocks, p.nUnits);
-  }
-  if (lds > kLdsBudget)
-    HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  p.ldsBytes = (unsigned)lds;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<unsigned long long>(1, blocks)), dim3(BLOCK), lds, c->L().stream, p);
-  HIP_OK(c, hipGetLastError());
-  return 0;
-}
-
-template <int BLOCK, bool TBL, bool DBG, bool EMIT, int OPT = 0>
-int launch_block_e(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
-  // equally spaced axes, one component, no surface description: the instantiation with those decided at compile time
-  const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
-  if constexpr (OPT == 0 && BLOCK != 1024) {
-    if (simple && c->ny == 1 && !DBG) return launch_block_s<BLOCK, TBL, DBG, EMIT, 2, OPT>(c, p, lds, nBatches);  // an x-z problem
-  }
-  if constexpr (!DBG && (BLOCK == 1024 || BLOCK == 768)) {
-    // no axis equally spaced by the reference's single-precision test, every axis equally spaced to 1e-6 of a cell (0.1 km cells):
-    // the same cells as the general instantiation finds, with nothing left to decide at run time (SIMPLE = 3)
-    if (!c->xyRegular && !c->zRegular && p.xyNearUniform && p.zNearUniform && c->nc == 1 && c->surfNumX == 0 && !getenv("MCBRAT_NO_SIMPLE3"))
-      return launch_block_s<BLOCK, TBL, DBG, EMIT, 3, OPT>(c, p, lds, nBatches);
-  }
-  return simple ? launch_block_s<BLOCK, TBL, DBG, EMIT, 1, OPT>(c, p, lds, nBatches) : launch_block_s<BLOCK, TBL, DBG, EMIT, 0, OPT>(c, p, lds, nBatches);
-}
-
-template <int BLOCK, bool TBL, bool DBG, int OPT = 0>
-int launch_block_t(mcbrat_ctx *c, DevParams &p, size_t lds, int nBatches) {
-  return c->srcKind == 0 ? launch_block_e<BLOCK, TBL, DBG, false, OPT>(c, p, lds, nBatches) : launch_block_e<BLOCK, TBL, DBG, true, OPT>(c, p, lds, nBatches);
-}
-
 int launch_block(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool debug, int nBatches) {
   p.cdfTopLds = L.cdfTop ? 1 : 0;
-  const size_t lds = block_lds_layout(c->nx, c->ny, c->nz, c->nc, (size_t)p.slabStride, c->nBlocks,
-                                      L.tblLds ? (size_t)c->tblTotalFloats : 0, L.blockLite ? L.optics : 0, L.cdfTop).total;
+  const int opt = L.blockLite ? L.optics : 0;
+  const auto lds = [&](size_t slabs) {  // the kernel's layout with the tallies of one batch, or of two (launch-wide units)
+    return block_lds_layout(c->nx, c->ny, c->nz, c->nc, slabs * (size_t)p.slabStride, c->nBlocks, L.tblLds ? (size_t)c->tblTotalFloats : 0,
+                            opt, L.cdfTop).total;
+  };
+  if (lds(1) + 512 > c->ldsPerCU) return fail(c, "computeRadiativeTransfer: the block-walk tables do not fit the LDS of a compute unit.");
+  const void *kernel;
+  int block;
   if (L.wide) {  // one workgroup per compute unit: 1024 lanes (the instrumented instantiation: 512)
-    if (L.blockLite && L.optics == 2) {
-      if (debug) return L.tblLds ? launch_block_t<512, true, true, 2>(c, p, lds, nBatches) : launch_block_t<512, false, true, 2>(c, p, lds, nBatches);
-      return L.tblLds ? launch_block_t<1024, true, false, 2>(c, p, lds, nBatches) : launch_block_t<1024, false, false, 2>(c, p, lds, nBatches);
-    }
-    if (L.blockLite) {
-      if (debug) return L.tblLds ? launch_block_t<512, true, true, 1>(c, p, lds, nBatches) : launch_block_t<512, false, true, 1>(c, p, lds, nBatches);
-      return L.tblLds ? launch_block_t<1024, true, false, 1>(c, p, lds, nBatches) : launch_block_t<1024, false, false, 1>(c, p, lds, nBatches);
-    }
-    if (debug) return L.tblLds ? launch_block_t<512, true, true>(c, p, lds, nBatches) : launch_block_t<512, false, true>(c, p, lds, nBatches);
-    return L.tblLds ? launch_block_t<1024, true, false>(c, p, lds, nBatches) : launch_block_t<1024, false, false>(c, p, lds, nBatches);
+    block = debug ? 512 : 1024;
+    if (opt == 2) kernel = debug ? block_kernel_for<512, true, 2>(c, p, L.tblLds) : block_kernel_for<1024, false, 2>(c, p, L.tblLds);
+    else if (opt == 1) kernel = debug ? block_kernel_for<512, true, 1>(c, p, L.tblLds) : block_kernel_for<1024, false, 1>(c, p, L.tblLds);
+    else kernel = debug ? block_kernel_for<512, true>(c, p, L.tblLds) : block_kernel_for<1024, false>(c, p, L.tblLds);
+  } else {
+    const int want = c->blockSize > 0 ? c->blockSize : 768;
+    block = debug ? 512 : (want == 768 || want == 256 ? want : 512);
+    if (debug) kernel = block_kernel_for<512, true>(c, p, L.tblLds);
+    else if (block == 768) kernel = block_kernel_for<768, false>(c, p, L.tblLds);
+    else if (block == 256) kernel = block_kernel_for<256, false>(c, p, L.tblLds);
+    else kernel = block_kernel_for<512, false>(c, p, L.tblLds);
   }
-  const int block = c->blockSize > 0 ? c->blockSize : 768;
-  if (debug) return L.tblLds ? launch_block_t<512, true, true>(c, p, lds, nBatches) : launch_block_t<512, false, true>(c, p, lds, nBatches);
-  if (block == 768) return L.tblLds ? launch_block_t<768, true, false>(c, p, lds, nBatches) : launch_block_t<768, false, false>(c, p, lds, nBatches);
-  if (block == 256) return L.tblLds ? launch_block_t<256, true, false>(c, p, lds, nBatches) : launch_block_t<256, false, false>(c, p, lds, nBatches);
-  return L.tblLds ? launch_block_t<512, true, false>(c, p, lds, nBatches) : launch_block_t<512, false, false>(c, p, lds, nBatches);
+  return launch_kernel(c, p, kernel, block, lds(1), Units::BlockWalk, nBatches, lds(2));
 }
 
 int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
-  LaunchPlan L = plan_launch(c, (size_t)p.slabStride);
-  if (L.priv && L.brick) {  // fill_params chose the brick arrays: private tallies give way
-    L.priv = false;
-    L.gridLds = false;
-    L.lds = plan_launch_lds(c, L);
-  }
+  const LaunchPlan L = plan_launch(c, (size_t)p.slabStride);
   if (L.fly) {
     p.fly = 1; p.flyNbx = c->flyNbx; p.flyNby = c->flyNby; p.extWalk = c->dExtWalk;
     p.flyInvBrickX = (float)(c->flyNbx / p.Lx); p.flyInvBrickY = (float)(c->flyNby / p.Ly);
   }
-#ifdef MCBRAT_DEV_MAIN_ONLY  // development builds (seconds instead of minutes, scripts/kernel_resources.py --main): only the two
-  // instantiations that carry the bench workloads exist -- the step cloud's block walk and the 128x128x64 flux kernel
-  if (block_walk_applies(c, L))
-    return launch_block_s<768, true, false, false, 2>(c, p, block_lds_layout(c->nx, c->ny, c->nz, c->nc, (size_t)p.slabStride, c->nBlocks, (size_t)c->tblTotalFloats).total, nBatches);
-  if (debug) return launch_trace_e<256, false, 0, false, true, false, false, 0>(c, p, L.lds, nBatches);
-  if (!(p.rec != nullptr && p.layerSkip && p.fly && p.surfNumX == 0)) return fail(c, "development build: only the bench workloads' kernels exist");
-  if (p.xyRegularWalk && !p.zRegularWalk) return launch_trace_e<256, false, 0, false, false, false, false, 3>(c, p, L.lds, nBatches);
-  if (!p.xyRegularWalk && !p.zRegularWalk) return launch_trace_e<256, false, 0, false, false, false, false, 1>(c, p, L.lds, nBatches);  // (the 128x128x64 bench fields)
-  return fail(c, "development build: only the bench workloads' kernels exist");
-#else
   if (block_walk_applies(c, L)) return launch_block(c, p, L, debug, nBatches);
-  if (L.wide) {  // one workgroup of 1024 lanes per compute unit, tallies (and what else fits) in its LDS; instrumented: 512 lanes
-    if (debug) return launch_trace_b<512, true>(c, p, L, nBatches);
-    if (L.gridLds) return L.tblLds ? launch_trace_t<1024, true, 2, false, false>(c, p, L.lds, nBatches) : launch_trace_t<1024, false, 2, false, false>(c, p, L.lds, nBatches);
-    return L.tblLds ? launch_trace_t<1024, true, 1, false, false>(c, p, L.lds, nBatches) : launch_trace_t<1024, false, 1, false, false>(c, p, L.lds, nBatches);
+  const bool tbl = L.tblLds, emit = c->srcKind != 0;
+  const void *kernel;
+  int block;
+  size_t lds = L.lds;
+  if (L.wide && !debug) {  // one workgroup of 1024 lanes per compute unit, tallies (and what else fits) in its LDS; instrumented: 512 lanes
+    block = 1024;
+    kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
+  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug) {
+    // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
+    // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
+    // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
+    block = 768;
+    kernel = trace_ptr<768, 2, false, false>(tbl, emit);
+  } else {
+    block = L.block >= 512 ? 512 : 256;
+    if (c->nDir > 0) {  // radiance runs
+      if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with intensity directions.");
+      // the waves' buffers of unfinished long rays (80 B per ray) take what LDS is left at the residency the kernel is built
+      // for: 4 workgroups of 256 lanes per CU on grids in global memory, 2 workgroups otherwise
+      const size_t waves = block / 64, base = (L.lds + 15) & ~(size_t)15;
+      const size_t budget = c->ldsPerCU / (L.priv ? 2 : (block == 256 ? 4 : 2));
+      size_t cap = (c->rayDefer && budget > base + 64) ? std::min<size_t>(64, (budget - base - 64) / (waves * 80)) : 0;
+      if (cap < 24 || c->nx + c->ny + c->nz + 3 > 0xffff || c->nDir > 0xffff) cap = 0;  // (a ray record packs edge-table indices and the direction in 16 bits)
+      p.rayCap = (int)cap;
+      // measured on the 128x128x64 cloud field, 4 directions: with roulette most rays end within a few cells and the long
+      // ones are best served in short, dense passes; without it every ray runs to the boundary and long passes pay
+      p.rayShort = c->rayShort > 0 ? c->rayShort : (c->useRRIntensity ? 4 : 8);
+      p.rayPassIters = c->rayPassIters > 0 ? c->rayPassIters : (c->useRRIntensity ? 16 : 64);
+      p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
+      lds = base + waves * cap * 80;
+    }
+    if (block == 512) kernel = debug ? trace_kernel_for<512, true>(c, p, L) : trace_kernel_for<512, false>(c, p, L);
+    else kernel = debug ? trace_kernel_for<256, true>(c, p, L) : trace_kernel_for<256, false>(c, p, L);
   }
-  // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
-  // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
-  // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
-  if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug)
-    return L.tblLds ? launch_trace_t<768, true, 2, false, false>(c, p, L.lds, nBatches) : launch_trace_t<768, false, 2, false, false>(c, p, L.lds, nBatches);
-  if (L.block >= 512) return debug ? launch_trace_b<512, true>(c, p, L, nBatches) : launch_trace_b<512, false>(c, p, L, nBatches);
-  return debug ? launch_trace_b<256, true>(c, p, L, nBatches) : launch_trace_b<256, false>(c, p, L, nBatches);
-#endif
+  // (very tall grids: the per-layer tables alone can pass the default limit of a workgroup)
+  if (lds + kStaticLds > c->ldsPerCU && lds > kLdsBudget) return fail(c, "computeRadiativeTransfer: the grid's edge and layer tables do not fit the LDS of a compute unit.");
+  return launch_kernel(c, p, kernel, block, lds, L.priv ? Units::PerBatch : Units::PerBlock, nBatches);
 }
 
 int check_ready(mcbrat_ctx *c) {
@@ -965,6 +942,7 @@ mcbrat_ctx *mcbrat_create(int device) {
   if (const char *e = getenv("MCBRAT_JUMP_THRESHOLD")) c->jumpThreshold = std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MCBRAT_CROSS_THRESHOLD")) c->crossThreshold = std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MCBRAT_BATCH_UNITS")) c->batchUnits = atoi(e) != 0;
+  if (getenv("MCBRAT_NO_SIMPLE3")) c->noSimple3 = true;
   if (const char *e = getenv("MCBRAT_RAY_DEFER")) c->rayDefer = atoi(e);
   if (const char *e = getenv("MCBRAT_RAY_SHORT")) c->rayShort = std::max(1, atoi(e));
   if (const char *e = getenv("MCBRAT_RAY_PASS_ITERS")) c->rayPassIters = std::max(1, atoi(e));
@@ -1540,8 +1518,7 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   int m = (c->layerSkip ? 1 : 0) | (c->blockWalk ? 2 : 0);
   if (c->haveGrid && c->haveOptics) {  // what a flux launch of the loaded domain would do (the plan decides, as launch_trace does)
     const size_t ncol = (size_t)c->nx * c->ny;
-    LaunchPlan L = plan_launch(c, 2 * ncol + ncol * c->nz);
-    if (L.priv && L.brick) { L.priv = false; L.gridLds = false; }
+    const LaunchPlan L = plan_launch(c, 2 * ncol + ncol * c->nz);
     m = (c->layerSkip ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);

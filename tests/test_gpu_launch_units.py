@@ -1,7 +1,7 @@
 """Work units of the block walk and the device's Philox generator.
 
 The block walk deals each resident workgroup an equal share of the launch's photons, cut across batch boundaries, with the
-tallies of the two batches a share may touch in two LDS slabs (mcbrat_api.hip: launch_block_s).  Only the schedule changes:
+tallies of the two batches a share may touch in two LDS slabs (mcbrat_api.hip: launch_kernel).  Only the schedule changes:
 every photon keeps its arithmetic and tallies are integers, so the moment arrays must equal those of the per-batch cut
 (option "batchUnits") bit for bit.  Run on the MI355X box with `-m gpu`."""
 import ctypes as C
