@@ -62,7 +62,7 @@ program mcbrat_driver
   real,    allocatable :: table(:,:)
   real(8), allocatable :: moments(:)
   real(8), allocatable :: meanStats(:,:), fluxUpStats(:,:,:), fluxDownStats(:,:,:), fluxAbsorbedStats(:,:,:), &
-                          absorbedProfileStats(:,:), RadianceStats(:,:,:,:)
+                          absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:)
   real,    allocatable :: forwardTable(:,:), legendreCoefficients(:)
   integer :: numRadDir, off
   logical :: computeIntensity
@@ -104,6 +104,12 @@ program mcbrat_driver
     call check("specifyParameters")
     call setForwardTable(mcIntegrator, 1, forwardTable, forwardTable, ierr); call check("setForwardTable")
   end if
+  ! scattering orders (:98-115): a negative numRecScatOrd means off (:284-287)
+  if (recScatOrd .and. numRecScatOrd >= 0) then
+    call specifyScatteringOrders(mcIntegrator, numRecScatOrd, ierr); call check("specifyParameters")
+  else
+    numRecScatOrd = -1
+  end if
   call setSolarSource(mcIntegrator, solarMu, solarAzimuth, ierr); call check("setSolarSource")
   call resetMoments(mcIntegrator, ierr); call check("resetMoments")
   call cpu_time(t1)
@@ -137,6 +143,23 @@ program mcbrat_driver
 
   print '(A,3(2X,F9.6,A,F9.6))', " mean flux up/down/absorbed:", meanStats(1,1), " +-", meanStats(1,2), &
         meanStats(2,1), " +-", meanStats(2,2), meanStats(3,1), " +-", meanStats(3,2)
+  if (numRecScatOrd >= 0) then   ! domain-mean fluxes by scattering order: the moment tail's first 2 (N+1) entries
+    allocate(meanByScatOrdStats(0:numRecScatOrd, 2, 2))
+    off = 3 + 3*ncol + nz + ncol*nz + merge(ncol*numRadDir, 0, computeIntensity)
+    do k = 1, 2
+      do j = 1, 2
+        meanByScatOrdStats(:, j, k) = moments(8 + (k-1)*M + off + (j-1)*(numRecScatOrd+1) + 1 : &
+                                              8 + (k-1)*M + off + j*(numRecScatOrd+1))
+      end do
+    end do
+    do j = 1, 2
+      call momentsToStats1(meanByScatOrdStats(:, j, :))
+    end do
+    do i = 0, numRecScatOrd
+      print '(A,I3,A,2(2X,F9.6,A,F9.6))', " order ", i, " mean flux up/down:", meanByScatOrdStats(i, 1, 1), " +-", &
+            meanByScatOrdStats(i, 1, 2), meanByScatOrdStats(i, 2, 1), " +-", meanByScatOrdStats(i, 2, 2)
+    end do
+  end if
   if (len_trim(outputFluxFile) > 0) call writeFluxASCII()
   if (computeIntensity) then   ! RadianceStats :1047-1050, :1221-1228
     allocate(RadianceStats(nx, ny, numRadDir, 2))

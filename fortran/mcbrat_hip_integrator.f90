@@ -18,6 +18,7 @@ module mcbrat_hip_integrator
     private
     type(c_ptr) :: ctx = c_null_ptr
     integer     :: numX = 0, numY = 0, numZ = 0
+    integer     :: numRecScatOrd = -1   ! highest scattering order recorded, -1 off (specifyScatteringOrders)
     logical     :: readyToCompute = .false.
   end type integrator
 
@@ -27,7 +28,8 @@ module mcbrat_hip_integrator
             resetMoments, getMoments, momentsLength, lastMessage, &
             inverseTableLegendre, lastTraceMilliseconds, setAsynchronous, synchronize, &
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
-            setSurfaceDescription, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons
+            setSurfaceDescription, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
+            specifyScatteringOrders, reportResultsByScatOrd
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -156,6 +158,18 @@ module mcbrat_hip_integrator
       import :: c_ptr, c_int, c_float
       type(c_ptr), value :: ctx
       real(c_float), intent(out) :: meanIntensity(*), intensity(*)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_specify_scattering_orders(ctx, numRecScatOrd) bind(C, name="mcbrat_specify_scattering_orders") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: numRecScatOrd
+      integer(c_int) :: rc
+    end function
+    function mcbrat_report_scattering_orders(ctx, mUp, mDown, fUp, fDown, mI, inten) &
+        bind(C, name="mcbrat_report_scattering_orders") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, mUp, mDown, fUp, fDown, mI, inten   ! (c_null_ptr: not wanted)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -472,6 +486,59 @@ contains
   ! computeRT's nBad (Integrators/monteCarloRadiativeTransfer.f95:420, :562-563: photons dropped because their step was not
   ! positive): here the photons dropped because a loop bound of the kernels was reached, since this integrator was created
   ! (mcbrat_counters.badPhotons, include/mcbrat.h).  Synchronises.
+  ! specifyParameters(recScatOrd, numRecScatOrd) (:1159-1171, :1293-1330): fluxes and radiances by scattering order
+  ! 0..numRecScatOrd; numRecScatOrd < 0 records nothing.  Changes momentsLength().
+  subroutine specifyScatteringOrders(this, numRecScatOrd, ierr)
+    type(integrator), intent(inout) :: this
+    integer,          intent(in)    :: numRecScatOrd
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_specify_scattering_orders(this%ctx, int(numRecScatOrd, c_int32_t))
+    if (ierr == 0) this%numRecScatOrd = max(numRecScatOrd, -1)
+  end subroutine specifyScatteringOrders
+
+  ! reportResults(meanFluxUpByScatOrd, meanFluxDownByScatOrd, fluxUpByScatOrd, fluxDownByScatOrd, meanIntensityByScatOrd,
+  ! intensityByScatOrd) (:850-864, :887-903, :1010-1040) for the last batch; the reference's shapes, order last
+  subroutine reportResultsByScatOrd(this, meanFluxUpByScatOrd, meanFluxDownByScatOrd, fluxUpByScatOrd, fluxDownByScatOrd, &
+                                    meanIntensityByScatOrd, intensityByScatOrd, ierr)
+    type(integrator), intent(inout) :: this
+    real, dimension(0:),          contiguous, optional, target, intent(out) :: meanFluxUpByScatOrd, meanFluxDownByScatOrd
+    real, dimension(:, :, 0:),    contiguous, optional, target, intent(out) :: fluxUpByScatOrd, fluxDownByScatOrd
+    real, dimension(:, 0:),       contiguous, optional, target, intent(out) :: meanIntensityByScatOrd
+    real, dimension(:, :, :, 0:), contiguous, optional, target, intent(out) :: intensityByScatOrd
+    integer,                      intent(out) :: ierr
+    type(c_ptr) :: mUp, mDown, fUp, fDown, mI, inten
+    integer :: n
+    n = this%numRecScatOrd + 1
+    mUp = c_null_ptr; mDown = c_null_ptr; fUp = c_null_ptr; fDown = c_null_ptr; mI = c_null_ptr; inten = c_null_ptr
+    ierr = 2   ! "reportResults: ...ByScatOrd is the wrong size"
+    if (present(meanFluxUpByScatOrd)) then
+      if (size(meanFluxUpByScatOrd) /= n) return
+      mUp = c_loc(meanFluxUpByScatOrd)
+    end if
+    if (present(meanFluxDownByScatOrd)) then
+      if (size(meanFluxDownByScatOrd) /= n) return
+      mDown = c_loc(meanFluxDownByScatOrd)
+    end if
+    if (present(fluxUpByScatOrd)) then
+      if (any(shape(fluxUpByScatOrd) /= (/ this%numX, this%numY, n /))) return
+      fUp = c_loc(fluxUpByScatOrd)
+    end if
+    if (present(fluxDownByScatOrd)) then
+      if (any(shape(fluxDownByScatOrd) /= (/ this%numX, this%numY, n /))) return
+      fDown = c_loc(fluxDownByScatOrd)
+    end if
+    if (present(meanIntensityByScatOrd)) then
+      if (size(meanIntensityByScatOrd, 2) /= n) return
+      mI = c_loc(meanIntensityByScatOrd)
+    end if
+    if (present(intensityByScatOrd)) then
+      if (size(intensityByScatOrd, 1) /= this%numX .or. size(intensityByScatOrd, 2) /= this%numY .or. &
+          size(intensityByScatOrd, 4) /= n) return
+      inten = c_loc(intensityByScatOrd)
+    end if
+    ierr = mcbrat_report_scattering_orders(this%ctx, mUp, mDown, fUp, fDown, mI, inten)
+  end subroutine reportResultsByScatOrd
+
   integer(8) function numBadPhotons(this)
     type(integrator), intent(in) :: this
     integer(c_int64_t), dimension(15) :: counters

@@ -141,6 +141,28 @@ int mcbrat_set_forward_table(mcbrat_ctx *ctx, int32_t component, int32_t nAngles
  * [nDirections][ny][nx] (x fastest).  Either pointer may be NULL. */
 int mcbrat_report_intensity(mcbrat_ctx *ctx, float *meanIntensity, float *intensity);
 
+/* ---- fluxes and radiances by scattering order ---------------------------------------------------
+ * specifyParameters(recScatOrd, numRecScatOrd) (:1159-1171, :1293-1330).  numRecScatOrd < 0 turns the
+ * recording off; >= 0 records orders 0..numRecScatOrd (no overflow bin: a higher order is not recorded,
+ * :611).  A photon's order starts at 0 at launch and grows by one at every surface reflection (after the
+ * fluxDown tally, :643) and every scattering event (before the local estimate, :713).  fluxUpByScatOrd gets
+ * the weight of a top exit at the photon's order (:595-599), fluxDownByScatOrd that of a surface arrival at
+ * the order before the reflection (:611-614, :635-638), intensityByScatOrd every local estimate at the order
+ * the photon has when it is taken (:527-531, :688-692, :792-796).  Normalised as fluxUp and intensity
+ * (:352-356, :381-387).  Fails together with limitIntensityContributions: the reference's redistribution
+ * (:307-313) would add each clipped excess to every order.  Fails where one batch's order tallies would
+ * not fit the tally budget.  Changes mcbrat_moments_length(): a caller-bound moment buffer must be bound
+ * again.  Flux runs of small domains then run on the face-by-face kernels, not the block walk. */
+int mcbrat_specify_scattering_orders(mcbrat_ctx *ctx, int32_t numRecScatOrd);
+/* reportResults(meanFluxUpByScatOrd, meanFluxDownByScatOrd, fluxUpByScatOrd, fluxDownByScatOrd,
+ * meanIntensityByScatOrd, intensityByScatOrd) (:850-864, :887-903, :1010-1040) for the LAST batch, Fortran
+ * order with the order slowest: mean*(0:N), flux*(nx, ny, 0:N), meanIntensityByScatOrd(nDirections, 0:N),
+ * intensityByScatOrd(nx, ny, nDirections, 0:N), N = numRecScatOrd.  Domain means are sums over the columns
+ * divided by their number.  Any pointer may be NULL; the intensity ones must be NULL without directions. */
+int mcbrat_report_scattering_orders(mcbrat_ctx *ctx, float *meanFluxUpByScatOrd, float *meanFluxDownByScatOrd,
+                                    float *fluxUpByScatOrd, float *fluxDownByScatOrd,
+                                    float *meanIntensityByScatOrd, float *intensityByScatOrd);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:
@@ -148,7 +170,10 @@ int mcbrat_report_intensity(mcbrat_ctx *ctx, float *meanIntensity, float *intens
  *   then S1 = sum n*x and S2 = sum n*x^2, each of length mcbrat_moments_length():
  *   meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp[nx*ny], fluxDown[nx*ny],
  *   fluxAbsorbed[nx*ny], absorbedProfile[nz], absorbedVolume[nx*ny*nz],
- *   intensity[nDirections*nx*ny] (RadianceStats, monteCarloDriver.f95:1047-1050).
+ *   intensity[nDirections*nx*ny] (RadianceStats, monteCarloDriver.f95:1047-1050),
+ *   and with scattering orders (N = numRecScatOrd): meanFluxUpByScatOrd[N+1], meanFluxDownByScatOrd[N+1],
+ *   fluxUpByScatOrd[(N+1)*nx*ny], fluxDownByScatOrd[(N+1)*nx*ny], meanIntensityByScatOrd[(N+1)*nDirections],
+ *   intensityByScatOrd[(N+1)*nDirections*nx*ny] (order slowest, x fastest).
  * Total doubles = 8 + 2*length.  The buffer is device memory; a caller that
  * wants to all-reduce it with RCCL binds its own device buffer. */
 int64_t mcbrat_moments_length(const mcbrat_ctx *ctx);

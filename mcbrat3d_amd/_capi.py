@@ -60,6 +60,8 @@ SYMBOLS = {
     "mcbrat_specify_intensity": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _f, _i32, _i32, _i32, _f]),
     "mcbrat_set_forward_table": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "mcbrat_report_intensity": (C.c_int, [_vp, _vp, _vp]),
+    "mcbrat_specify_scattering_orders": (C.c_int, [_vp, _i32]),
+    "mcbrat_report_scattering_orders": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcbrat_forward_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_forward_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
     "mcbrat_hybrid_phase_functions": (C.c_int, [_i32, _i32, _vp, _f, _vp]),

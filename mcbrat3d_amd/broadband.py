@@ -92,6 +92,9 @@ class SpectralRun:
         wavelength's photons.  Bitwise the results of overlap=False (every call waited for by the host)."""
         if not domains:
             raise McbratError("SpectralRun: no wavelength domains")
+        if parameters.get("recScatOrd") or (parameters.get("numRecScatOrd") is not None and parameters["numRecScatOrd"] >= 0):
+            raise McbratError("SpectralRun: fluxes and radiances by scattering order (recScatOrd) are not available for "
+                              "spectrally integrated runs")
         self.overlap = bool(overlap)
         self.M, self.domains = M, list(domains)
         self.integrators = [M.new_Integrator(d, device=device) for d in self.domains]

@@ -116,6 +116,8 @@ struct mcbrat_ctx {
   bool fwdDirty = true;
   int useHybrid = 0, numOrdersOrig = 0, useRRIntensity = 0, limitContrib = 0;
   float zetaMin = 0.3f, maxContrib = FLT_MAX;
+  // fluxes and radiances by scattering order (mcbrat_specify_scattering_orders): highest order recorded, -1 off
+  int numRecScatOrd = -1;
   // parameters
   float albedo = 0.f;
   int useRR = 1;
@@ -240,10 +242,28 @@ int upload(mcbrat_ctx *c, T **dst, const T *src, size_t n) {
   return 0;
 }
 
+bool orders_on(const mcbrat_ctx *c) { return c->numRecScatOrd >= 0; }
+
+// [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest
 long long moments_len(const mcbrat_ctx *c) {
   const long long ncol = (long long)c->nx * c->ny;
-  return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol;
+  return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol +
+         (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0);
 }
+
+// Elements of one batch's tally slab: [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:)
+// intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1)]
+// fluxRun: the slab of a flux launch of the loaded domain (no intensity parts), what mcbrat_get_walk_mode reports on.
+size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
+  const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz, nDir = fluxRun ? 0 : (size_t)c->nDir;
+  return 2 * ncol + nvox + nDir * ncol + (c->limitContrib && !fluxRun ? (size_t)(c->nc + 1) * nDir * (ncol + 1) : 0) +
+         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0);
+}
+constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
+// The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
+const char *const kOrdersLimitMsg =
+    "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
+    "redistribution adds each direction's clipped excess to every order, which would count it numRecScatOrd + 1 times.";
 
 int ensure_moments(mcbrat_ctx *c) {
   if (c->dMoments) return 0;
@@ -467,7 +487,7 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
 // dense grid is as fast or 1-3 % faster, so the automatic rule only switches
 // for grids of 64 MiB and more.
 bool use_bricks(const mcbrat_ctx *c) {
-  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0) return false;  // (radiance rays read the dense grid)
+  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0 || orders_on(c)) return false;  // (radiance rays read the dense grid; no ORD kernel reads bricks)
   if (c->brickMode == 1) return true;
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   // automatic: the dense layout is the faster one wherever measured (128x128x64: equal; 512x512x128: 83 vs 105 ms per
@@ -551,6 +571,7 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
     if (c->testRayMaxLen > 0.0f) p.rayMaxLen = c->testRayMaxLen;  // TEST ONLY (MCBRAT_TEST_RAY_MAX_LEN): drive the bound on purpose
   }
   p.counter = c->L().dCounter;
+  p.numRecScatOrd = -1;  // (mcbrat_compute_radiative_transfer switches the order tallies on)
   p.eventThreshold = std::max(1, std::min(64, c->eventThreshold));
   // The thermal source's launch is several hundred instructions (three searches of the emission CDF, double divisions,
   // sine and cosine in full precision) for photons that live two or three legs: served eight lanes at a time it was half
@@ -592,7 +613,7 @@ struct LaunchPlan {
 };
 
 bool blocks_worth_it(const mcbrat_ctx *c) {
-  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0) return false;
+  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c)) return false;  // (the block walk has no ORD variant)
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   return (size_t)c->nBlocks * 4 <= nvox || c->blockWalk == 2;  // (2: forced, for tests of heterogeneous media)
 }
@@ -612,10 +633,16 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   const size_t grid = nvox * 4 + (size_t)c->nc * nvox * (4 + 4) + (((size_t)c->nc * nvox + 1) & ~(size_t)1) * 2;
   L.gridLds = L.priv && c->gridLdsMode != 0 && edges + bg + slab + grid + (L.tblLds ? tbl : 0) <= kLdsBudget;
+  // scattering orders: where the order bins leave room for the grid or the tables but not both, the grid stays in LDS (every walk
+  // step reads it, a collision one table entry) and the tables go to L2 (the step cloud: DESIGN.md section 4.9)
+  if (orders_on(c) && L.priv && L.tblLds && !L.gridLds && c->gridLdsMode != 0 && edges + bg + slab + grid <= kLdsBudget) {
+    L.tblLds = false;
+    L.gridLds = true;
+  }
   L.lds = edges + bg + (L.priv ? slab : 0) + (L.gridLds ? grid : 0) + (L.tblLds ? tbl : 0);
   // the wide plan: the slab did not fit beside another workgroup, but it fits a compute unit
   const size_t cuLds = c->ldsPerCU > kStaticLds ? c->ldsPerCU - kStaticLds : 0;
-  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
+  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !orders_on(c) && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
     L.wide = true; L.priv = true; L.fly = false;
     size_t need = edges + bg + slab;
     L.tblLds = need + tbl <= cuLds;
@@ -728,10 +755,22 @@ int launch_kernel(mcbrat_ctx *c, DevParams &p, const void *kernel, int block, si
 
 // trace_kernel with the table and source flags picked at run time (every value of both is built).  (The source kind is a
 // template parameter: the emission launch code costs the solar instantiations registers.)
-template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false>
+template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false, bool ORD = false>
 const void *trace_ptr(bool tbl, bool emit) {
-  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false>;
-  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false>;
+  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
+  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
+}
+
+// the ORD instantiations (scattering orders): BLOCK 256 / 512 x PRIV 0 / 1 / 2 x INTEN x table x source, dense grids, not instrumented
+template <int BLOCK>
+const void *trace_kernel_ord(const mcbrat_ctx *c, const LaunchPlan &L) {
+  const bool tbl = L.tblLds, emit = c->srcKind != 0;
+  if (c->nDir > 0) {
+    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true, true>(tbl, emit);
+    return trace_ptr<BLOCK, 0, false, false, true, true>(tbl, emit);
+  }
+  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, false, true>(tbl, emit);
+  return trace_ptr<BLOCK, 0, false, false, false, true>(tbl, emit);
 }
 
 // trace_kernel of 256 or 512 lanes.  Instantiated combinations: private tallies (small domains) and bricks (large ones) never
@@ -836,7 +875,7 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   if (L.wide && !debug) {  // one workgroup of 1024 lanes per compute unit, tallies (and what else fits) in its LDS; instrumented: 512 lanes
     block = 1024;
     kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
-  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug) {
+  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0) {
     // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
     // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
     // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
@@ -860,7 +899,10 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
       p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
       lds = base + waves * cap * 80;
     }
-    if (block == 512) kernel = debug ? trace_kernel_for<512, true>(c, p, L) : trace_kernel_for<512, false>(c, p, L);
+    if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
+      if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with scattering orders.");
+      kernel = block == 512 ? trace_kernel_ord<512>(c, L) : trace_kernel_ord<256>(c, L);
+    } else if (block == 512) kernel = debug ? trace_kernel_for<512, true>(c, p, L) : trace_kernel_for<512, false>(c, p, L);
     else kernel = debug ? trace_kernel_for<256, true>(c, p, L) : trace_kernel_for<256, false>(c, p, L);
   }
   // (very tall grids: the per-layer tables alone can pass the default limit of a workgroup)
@@ -1251,6 +1293,7 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   if (limitIntensityContributions && !(maxIntensityContribution > 0.f))
     return fail(c, "specifyParameters: maxIntensityContribution must be > 0");
   if (zetaMin < 0.f) return fail(c, "specifyParameters: zetaMin must be >= 0.");
+  if (limitIntensityContributions && orders_on(c)) return fail(c, kOrdersLimitMsg);
   if (numOrdersOrigPhaseFunIntenCalcs < 0) return fail(c, "specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0");
   if (useRussianRouletteForIntensity)
     for (int i = 0; i < nDirections; ++i)
@@ -1285,6 +1328,53 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   c->useHybrid = useHybridPhaseFunsForIntenCalcs ? 1 : 0;
   c->numOrdersOrig = numOrdersOrigPhaseFunIntenCalcs;
   c->fwdDirty = true;
+  return 0;
+}
+
+int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
+  const int n = numRecScatOrd < 0 ? -1 : numRecScatOrd;
+  if (n >= 0 && c->limitContrib) return fail(c, kOrdersLimitMsg);
+  if (n >= 0) {  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
+    const size_t ncol = (size_t)c->nx * c->ny;
+    if ((double)(n + 1) * (2 + c->nDir) * ncol * sizeof(long long) > (double)kSlabBudget)
+      return fail(c, "specifyParameters: numRecScatOrd is too large: the tallies of one batch by scattering order would not fit the 4 GiB tally budget.");
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (n != c->numRecScatOrd) {  // the moment arrays change length: start them afresh (as mcbrat_specify_intensity does)
+    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+    c->dMoments = nullptr;
+    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+    c->haveLast = false;
+  }
+  c->numRecScatOrd = n;
+  return 0;
+}
+
+int mcbrat_report_scattering_orders(mcbrat_ctx *c, float *meanFluxUpByScatOrd, float *meanFluxDownByScatOrd, float *fluxUpByScatOrd,
+                                    float *fluxDownByScatOrd, float *meanIntensityByScatOrd, float *intensityByScatOrd) {
+  if (!c) return 1;
+  if (!orders_on(c)) return fail(c, "reportResults: scattering-order information not available");
+  if ((meanIntensityByScatOrd || intensityByScatOrd) && c->nDir == 0)
+    return fail(c, "reportResults: intensityByScatOrd information not available");
+  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  // the tail of the last batch's results: [meanUp | meanDown | up | down | meanIntensity | intensity], already in Fortran order
+  const size_t ncol = (size_t)c->nx * c->ny, nOrd = (size_t)c->numRecScatOrd + 1, nDir = (size_t)c->nDir;
+  const size_t base = 3 + 3 * ncol + c->nz + ncol * c->nz + nDir * ncol;
+  std::vector<float> h((size_t)moments_len(c) - base);
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+  const float *q = h.data();
+  const auto take = [&](float *dst, size_t n) { if (dst) std::memcpy(dst, q, sizeof(float) * n); q += n; };
+  take(meanFluxUpByScatOrd, nOrd);
+  take(meanFluxDownByScatOrd, nOrd);
+  take(fluxUpByScatOrd, ncol * nOrd);
+  take(fluxDownByScatOrd, ncol * nOrd);
+  take(meanIntensityByScatOrd, nDir * nOrd);
+  take(intensityByScatOrd, ncol * nDir * nOrd);
   return 0;
 }
 
@@ -1517,8 +1607,8 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   if (!c) return 0;
   int m = (c->layerSkip ? 1 : 0) | (c->blockWalk ? 2 : 0);
   if (c->haveGrid && c->haveOptics) {  // what a flux launch of the loaded domain would do (the plan decides, as launch_trace does)
-    const size_t ncol = (size_t)c->nx * c->ny;
-    const LaunchPlan L = plan_launch(c, 2 * ncol + ncol * c->nz);
+    // (the flux run's slab: with scattering orders its order bins too, so that private tallies give way where they no longer fit)
+    const LaunchPlan L = plan_launch(c, slab_stride(c, true));
     m = (c->layerSkip ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
@@ -1545,18 +1635,21 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     c->cur = 0;
   }
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
-  // [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:) intensity by component, excess]
-  const size_t slabStride = 2 * ncol + nvox + (size_t)c->nDir * ncol +
-                            (c->limitContrib ? (size_t)(c->nc + 1) * c->nDir * (ncol + 1) : 0);
+  const size_t slabStride = slab_stride(c);
+  if (orders_on(c) && slabStride * sizeof(long long) > kSlabBudget)
+    return fail(c, "computeRadiativeTransfer: numRecScatOrd is too large: one batch's tallies by scattering order need more than the 4 GiB tally budget.");
+  if (orders_on(c) && c->countersOn)
+    return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
-  size_t inFlight = std::max<size_t>(1, (size_t)(4ull << 30) / (slabStride * sizeof(long long)));
+  size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
   inFlight = std::min<size_t>(inFlight, (size_t)nBatches);
   // asynchronous mode sizes every lane at once: allocation synchronises the device, so it must not recur
   for (int li = 0; li < mcbrat_ctx::kLanes; ++li) {
     mcbrat_ctx::Lane &L = c->lane[li];
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
-    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz) * inFlight;
+    const size_t nOrdMeans = orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + c->nDir) : 0;  // (domain means by order, behind the scalars)
+    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans) * inFlight;
     if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
     HIP_OK(c, hipStreamSynchronize(L.stream));
     if (L.slabCapacity < needSlab) {
@@ -1584,6 +1677,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   fill_params(c, p);
   p.seedLo = (uint32_t)seed; p.seedHi = (uint32_t)(seed >> 32);
   p.slabs = c->L().dSlabs; p.slabStride = slabStride;
+  p.numRecScatOrd = c->numRecScatOrd;
   p.ppb = (unsigned long long)ppb;
   p.fates = nullptr;
   p.counters = c->countersOn ? c->dEventCounters : nullptr;
@@ -1628,11 +1722,16 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.gatherIntensity = (unsigned)((ncol * (size_t)c->nDir + kFinishBlock - 1) / kFinishBlock);
     f.foldColumns = (unsigned)((3 * ncol + kFinishBlock - 1) / kFinishBlock);
     f.foldScalars = (unsigned)((3 + c->nz + kFinishBlock - 1) / kFinishBlock);
+    f.nOrd = orders_on(c) ? c->numRecScatOrd + 1 : 0;
+    f.ordVals = f.scalVals + (size_t)(3 + c->nz) * nb;
+    f.gatherOrders = (unsigned)(((size_t)(2 + c->nDir) * ncol * f.nOrd + kFinishBlock - 1) / kFinishBlock);
+    f.gatherOrderMeans = (unsigned)((2 + c->nDir) * f.nOrd) * (unsigned)nb;
+    f.foldOrderMeans = (unsigned)(((2 + c->nDir) * f.nOrd + kFinishBlock - 1) / kFinishBlock);
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity), dim3(kFinishBlock), 0,
-                       c->L().stream, f);
-    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
+    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans),
+                       dim3(kFinishBlock), 0, c->L().stream, f);
+    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
     c->lastDone = c->L().evDone;

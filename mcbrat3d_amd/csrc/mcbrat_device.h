@@ -181,6 +181,10 @@ struct DevParams {
   double *traceBuf;               // DEBUG: per-collision records of one photon (12 doubles each)
   unsigned long long traceIndex;  // photon index to trace
   int traceCap;
+  // scattering orders (ORD instantiations of trace_kernel): highest order recorded, -1 off.  Its bins follow everything else
+  // in the batch slab: [upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1)], order slowest.
+  // (Last, in the padding behind traceCap: the parameter block keeps its size and every other member its offset.)
+  int numRecScatOrd;
 };
 
 }  // namespace mcbrat

@@ -30,13 +30,21 @@ def balanced_job(totalPhotons, numBatches, world):
     return ppb, nb
 
 
-def unpack_moments(buf, nx, ny, nz, nDirections=None):
-    """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order."""
+def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1):
+    """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order.
+
+    With scattering orders (numRecScatOrd >= 0) the arrays end in the order tail of include/mcbrat.h, unpacked with the order
+    as the LAST index, as the reference's (x, y, p) and (x, y, d, p) arrays: meanFluxUpByScatOrd[p], fluxUpByScatOrd[ix, iy, p],
+    meanIntensityByScatOrd[d, p], intensityByScatOrd[ix, iy, d, p].  nDirections must then be given: the length no longer
+    tells it."""
     ncol, nvox = nx * ny, nx * ny * nz
     M = 3 + 3 * ncol + nz + nvox
+    nOrd = int(numRecScatOrd) + 1 if numRecScatOrd is not None and int(numRecScatOrd) >= 0 else 0
     if nDirections is None:  # the length tells
+        if nOrd:
+            raise ValueError("unpack_moments: with numRecScatOrd >= 0 the number of directions must be given (nDirections=)")
         nDirections = ((len(buf) - 8) // 2 - M) // ncol
-    M += nDirections * ncol
+    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol)
     S1, S2 = buf[8:8 + M], buf[8 + M:8 + 2 * M]
     out = {"totalPhotons": buf[0], "batches": buf[1]}
     names = [("meanFluxUp", 1, None), ("meanFluxDown", 1, None), ("meanFluxAbsorbed", 1, None),
@@ -44,6 +52,14 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None):
              ("absorbedProfile", nz, None), ("absorbedVolume", nvox, (nz, ny, nx))]
     if nDirections > 0:
         names.append(("intensity", nDirections * ncol, (nDirections, ny, nx)))
+    if nOrd:
+        names += [("meanFluxUpByScatOrd", nOrd, (nOrd,)), ("meanFluxDownByScatOrd", nOrd, (nOrd,)),
+                  ("fluxUpByScatOrd", nOrd * ncol, (nOrd, ny, nx)), ("fluxDownByScatOrd", nOrd * ncol, (nOrd, ny, nx))]
+        if nDirections > 0:
+            names += [("meanIntensityByScatOrd", nOrd * nDirections, (nOrd, nDirections)),
+                      ("intensityByScatOrd", nOrd * nDirections * ncol, (nOrd, nDirections, ny, nx))]
+    if nOrd and len(buf) != 8 + 2 * M:
+        raise ValueError("unpack_moments: %d doubles, the layout asked for has %d" % (len(buf), 8 + 2 * M))
     o = 0
     for name, n, shp in names:
         a, b = S1[o:o + n], S2[o:o + n]
@@ -150,4 +166,7 @@ def run(integrator, domain, photons, numPhotonsPerBatch, numBatches, randomNumbe
     else:
         buf = integrator.moments()
     nx, ny, nz = integrator._dims
+    nOrd = getattr(integrator, "numRecScatOrd", -1)
+    if nOrd >= 0:
+        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd), solarFlux)
     return statistics(unpack_moments(buf, nx, ny, nz), solarFlux)

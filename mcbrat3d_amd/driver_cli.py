@@ -20,7 +20,7 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     "algorithms": dict(useraytracing=True, userussianroulette=True, usehybridphasefunsforintencalcs=False,
                        hybridphasefunwidth=7.0, numordersorigphasefunintencalcs=0, userussianrouletteforintensity=True,
                        zetamin=0.3, limitintensitycontributions=False, maxintensitycontribution=77.0),
-    "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False),
+    "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False, recscatord=False, numrecscatord=0),
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
 }
@@ -224,7 +224,13 @@ def main(argv=None):
     domfile = cfg["physdomainfile"] or cfg["domainfilename"]
     doms = load_domains(cfg)
     dom = doms[0]
+    # scattering orders (:98-115): recorded when asked for, and -- as the reference driver reads it (:284-287) -- not for a
+    # negative numRecScatOrd
+    numRecScatOrd = int(cfg["numrecscatord"]) if cfg["recscatord"] and int(cfg["numrecscatord"]) >= 0 else -1
     if len(doms) > 1 or cfg["lw_flag"] >= 0:
+        if numRecScatOrd >= 0:
+            raise SystemExit("recScatOrd: fluxes and radiances by scattering order are not available for spectrally integrated "
+                             "runs (numLambda > 1 or thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -263,6 +269,8 @@ def main(argv=None):
                                 useRussianRouletteForIntensity=cfg["userussianrouletteforintensity"], zetaMin=cfg["zetamin"],
                                 limitIntensityContributions=cfg["limitintensitycontributions"],
                                 maxIntensityContribution=cfg["maxintensitycontribution"])
+    if numRecScatOrd >= 0:
+        integ.specifyParameters(recScatOrd=True, numRecScatOrd=numRecScatOrd)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -275,6 +283,11 @@ def main(argv=None):
     if rank == 0:
         print(" mean flux up/down/absorbed: " + "  ".join("%9.6f +-%9.6f" % (stats[k], stats[k + "_StdErr"])
                                                             for k in ("meanFluxUp", "meanFluxDown", "meanFluxAbsorbed")))
+        if numRecScatOrd >= 0:  # domain-mean fluxes by scattering order, one line per order
+            for p in range(numRecScatOrd + 1):
+                print(" order %3d mean flux up/down: %9.6f +-%9.6f  %9.6f +-%9.6f" % (
+                    p, stats["meanFluxUpByScatOrd"][p], stats["meanFluxUpByScatOrd_StdErr"][p],
+                    stats["meanFluxDownByScatOrd"][p], stats["meanFluxDownByScatOrd_StdErr"][p]))
         xe, ye, ze = dom.xPosition, dom.yPosition, dom.zPosition
         if cfg["outputfluxfile"]:
             writeResults_ASCII(cfg["outputfluxfile"], cfg, domfile, stats, xe, ye, ze, 1.0, dom.surfaceAlbedo)

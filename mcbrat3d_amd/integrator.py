@@ -66,6 +66,9 @@ class Integrator:
         self.zetaMin = defaultZetaMin
         self.limitIntensityContributions = False
         self.maxIntensityContribution = float(np.finfo(np.float32).max)
+        # fluxes and radiances by scattering order (:1159-1171, :1293-1330): highest order recorded, -1 off
+        self.recScatOrd = False
+        self.numRecScatOrd = -1
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -105,7 +108,8 @@ class Integrator:
                               hybridPhaseFunWidth=self.hybridPhaseFunWidth,
                               numOrdersOrigPhaseFunIntenCalcs=self.numOrdersOrigPhaseFunIntenCalcs,
                               limitIntensityContributions=self.limitIntensityContributions,
-                              maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF)
+                              maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF,
+                              numRecScatOrd=self.numRecScatOrd)
         return new
 
     def _check(self, rc):
@@ -125,7 +129,7 @@ class Integrator:
                           useRussianRouletteForIntensity=None, zetaMin=None, useHybridPhaseFunsForIntenCalcs=None,
                           hybridPhaseFunWidth=None, numOrdersOrigPhaseFunIntenCalcs=None,
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
-                          **unsupported):
+                          recScatOrd=None, numRecScatOrd=None, **unsupported):
         # intensity keywords, :1130-1160 and :1186-1283
         if (intensityMus is None) != (intensityPhis is None):
             raise McbratError("specifyParameters: Both or neither of intensityMus, intensityPhis must be supplied")
@@ -161,6 +165,19 @@ class Integrator:
             if numOrdersOrigPhaseFunIntenCalcs < 0:
                 raise McbratError("specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0")
             self.numOrdersOrigPhaseFunIntenCalcs = int(numOrdersOrigPhaseFunIntenCalcs)
+        # scattering orders (:1159-1171): recScatOrd=True needs numRecScatOrd; numRecScatOrd decides when given (< 0: off)
+        if recScatOrd and numRecScatOrd is None:
+            raise McbratError("specifyParameters: set recScatOrd to true, but did not provide number of orders to track.")
+        orders = self.numRecScatOrd
+        if numRecScatOrd is not None:
+            orders = int(numRecScatOrd) if int(numRecScatOrd) >= 0 else -1
+        elif recScatOrd is not None and not recScatOrd:
+            orders = -1
+        limit = self.limitIntensityContributions if limitIntensityContributions is None else bool(limitIntensityContributions)
+        if orders >= 0 and limit:
+            raise McbratError("specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): "
+                              "the reference's redistribution adds each direction's clipped excess to every order, which would "
+                              "count it numRecScatOrd + 1 times.")
         if limitIntensityContributions is not None:
             self.limitIntensityContributions = bool(limitIntensityContributions)
         if maxIntensityContribution is not None and maxIntensityContribution > 0.0:
@@ -185,6 +202,7 @@ class Integrator:
             self.useRussianRoulette = bool(useRussianRoulette)
         if LW_flag is not None:
             self.LW_flag = float(LW_flag)
+        self.numRecScatOrd, self.recScatOrd = orders, orders >= 0
         self._push_parameters()
 
     def _push_parameters(self):
@@ -203,7 +221,10 @@ class Integrator:
                  self.useHybridPhaseFunsForIntenCalcs, self.numOrdersOrigPhaseFunIntenCalcs, self.limitIntensityContributions,
                  self.maxIntensityContribution)
         if token == self._intensity_token:
+            self._push_orders()
             return
+        if self.numRecScatOrd != getattr(self, "_orders_token", -1) and self.numRecScatOrd < 0:
+            self._push_orders()  # (orders off first: the new intensity settings may be ones the library refuses together with orders)
         self._check(self._lib.mcbrat_specify_intensity(
             self._ctx, n, ptr(self.intensityMus) if n else None, ptr(self.intensityPhis) if n else None,
             int(self.useRussianRouletteForIntensity), C.c_float(self.zetaMin), int(self.useHybridPhaseFunsForIntenCalcs),
@@ -211,6 +232,13 @@ class Integrator:
             C.c_float(self.maxIntensityContribution)))
         self._intensity_token = token
         self._domain_token = None  # forward tables go with the optics
+        self._push_orders()
+
+    def _push_orders(self):
+        # (after the intensity: the library refuses orders together with limitIntensityContributions in either order of calls)
+        if self.numRecScatOrd != getattr(self, "_orders_token", -1):
+            self._check(self._lib.mcbrat_specify_scattering_orders(self._ctx, int(self.numRecScatOrd)))
+            self._orders_token = self.numRecScatOrd
 
     def numIntensityDirections(self):
         return int(self.intensityMus.size) if self.computeIntensity else 0
@@ -373,6 +401,20 @@ class Integrator:
             inten = np.zeros(nd * nx * ny, np.float32)
             self._check(self._lib.mcbrat_report_intensity(self._ctx, ptr(mean_i), ptr(inten)))
             res.update(meanIntensity=mean_i, intensity=inten.reshape(nd, ny, nx).transpose(2, 1, 0))
+        if self.numRecScatOrd >= 0:  # reportResults(...ByScatOrd) :850-864, :887-903, :1010-1040; order last, as the reference's arrays
+            no = self.numRecScatOrd + 1
+            mu_o, md_o = np.zeros(no, np.float32), np.zeros(no, np.float32)
+            up_o, dn_o = np.zeros(no * nx * ny, np.float32), np.zeros(no * nx * ny, np.float32)
+            mi_o = np.zeros(no * nd, np.float32) if nd > 0 else None
+            in_o = np.zeros(no * nd * nx * ny, np.float32) if nd > 0 else None
+            self._check(self._lib.mcbrat_report_scattering_orders(self._ctx, ptr(mu_o), ptr(md_o), ptr(up_o), ptr(dn_o),
+                                                                  ptr(mi_o), ptr(in_o)))
+            res.update(meanFluxUpByScatOrd=mu_o, meanFluxDownByScatOrd=md_o,
+                       fluxUpByScatOrd=up_o.reshape(no, ny, nx).transpose(2, 1, 0),
+                       fluxDownByScatOrd=dn_o.reshape(no, ny, nx).transpose(2, 1, 0))
+            if nd > 0:
+                res.update(meanIntensityByScatOrd=mi_o.reshape(no, nd).T,
+                           intensityByScatOrd=in_o.reshape(no, nd, ny, nx).transpose(3, 2, 1, 0))
         return res
 
     # -- batch moments (what the driver keeps in *Stats and reduces over processes) -----

@@ -175,6 +175,10 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
         f.Cpu_time_total = np.float32(cpuTimeTotal)
         f.Cpu_time_setup = np.float32(cpuTimeSetup)
         f.Number_of_processors_used = np.int32(numProcs)
+        byOrder = "fluxUpByScatOrd" in stats  # scattering orders (:1610-1612, :1680-1697): only where the stats hold them
+        if byOrder:
+            nOrd = np.asarray(stats["fluxUpByScatOrd"]).shape[2]
+            f.Highest_recorded_scattering_order = np.int32(nOrd - 1)
         f.createDimension("x", len(xe) - 1)
         f.createDimension("y", len(ye) - 1)
         withZ = reportAbsorptionProfile or reportVolumeAbsorption
@@ -199,6 +203,15 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
             f.createVariable("intensityPhis", "f", ("direction",))[:] = np.asarray(intensityPhis, np.float32)
             f.createVariable("intensity", "f", ("direction", "y", "x"))[:] = np.asarray(stats["intensity"]).transpose(2, 1, 0)
             f.createVariable("intensity_StdErr", "f", ("direction", "y", "x"))[:] = np.asarray(stats["intensity_StdErr"]).transpose(2, 1, 0)
+        if byOrder:  # Fortran dims (x, y, numRecScatOrd) and (x, y, direction, numRecScatOrd) (:1680-1697, :1781-1801)
+            f.createDimension("numRecScatOrd", nOrd)
+            f.createVariable("Scattering_Order", "f", ("numRecScatOrd",))[:] = np.arange(nOrd, dtype=np.float32)
+            for name in ("fluxUpByScatOrd", "fluxDownByScatOrd"):
+                f.createVariable(name, "f", ("numRecScatOrd", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
+                f.createVariable(name + "_StdErr", "f", ("numRecScatOrd", "y", "x"))[:] = np.asarray(stats[name + "_StdErr"]).transpose(2, 1, 0)
+            if intensityMus is not None and "intensityByScatOrd" in stats:
+                for name in ("intensityByScatOrd", "intensityByScatOrd_StdErr"):
+                    f.createVariable(name, "f", ("numRecScatOrd", "direction", "y", "x"))[:] = np.asarray(stats[name]).transpose(3, 2, 1, 0)
     finally:
         f.close()
     return outputFileName
