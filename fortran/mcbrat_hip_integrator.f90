@@ -24,6 +24,7 @@ module mcbrat_hip_integrator
 
   public :: integrator, new_Integrator, isReady_Integrator, finalize_Integrator, &
             setOpticalProperties, setInverseTable, setSolarSource, setEmissionSource, &
+            setRandomAzimuthSource, setFluxSource, setSpotlightSource, &
             specifyParameters, computeRadiativeTransfer, reportResults, &
             resetMoments, getMoments, momentsLength, lastMessage, &
             inverseTableLegendre, lastTraceMilliseconds, setAsynchronous, synchronize, &
@@ -95,6 +96,23 @@ module mcbrat_hip_integrator
       import :: c_ptr, c_int, c_float
       type(c_ptr), value :: ctx
       real(c_float), value :: mu, azimuth
+      integer(c_int) :: rc
+    end function
+    function mcbrat_set_source_random_azimuth(ctx, mu) bind(C, name="mcbrat_set_source_random_azimuth") result(rc)
+      import :: c_ptr, c_int, c_float
+      type(c_ptr), value :: ctx
+      real(c_float), value :: mu
+      integer(c_int) :: rc
+    end function
+    function mcbrat_set_source_flux(ctx) bind(C, name="mcbrat_set_source_flux") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int) :: rc
+    end function
+    function mcbrat_set_source_spotlight(ctx, mu, azimuth, x, y) bind(C, name="mcbrat_set_source_spotlight") result(rc)
+      import :: c_ptr, c_int, c_float
+      type(c_ptr), value :: ctx
+      real(c_float), value :: mu, azimuth, x, y
       integer(c_int) :: rc
     end function
     function mcbrat_set_source_emission(ctx, voxelWeights, fracAtms) bind(C, name="mcbrat_set_source_emission") result(rc)
@@ -341,6 +359,26 @@ contains
     integer,          intent(out)   :: ierr
     ierr = mcbrat_set_source_solar(this%ctx, solarMu, solarAzimuth)
   end subroutine setSolarSource
+  !------------------------------------------------------------------------------------------
+  subroutine setRandomAzimuthSource(this, solarMu, ierr)   ! new_PhotonStream, RandomAzimuth
+    type(integrator), intent(inout) :: this
+    real,             intent(in)    :: solarMu
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_set_source_random_azimuth(this%ctx, solarMu)
+  end subroutine setRandomAzimuthSource
+  !------------------------------------------------------------------------------------------
+  subroutine setFluxSource(this, ierr)   ! new_PhotonStream, Flux (isotropic incidence)
+    type(integrator), intent(inout) :: this
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_set_source_flux(this%ctx)
+  end subroutine setFluxSource
+  !------------------------------------------------------------------------------------------
+  subroutine setSpotlightSource(this, solarMu, solarAzimuth, solarX, solarY, ierr)   ! new_PhotonStream, Spotlight
+    type(integrator), intent(inout) :: this
+    real,             intent(in)    :: solarMu, solarAzimuth, solarX, solarY   ! solarX, solarY: fractions of the domain in (0, 1]
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_set_source_spotlight(this%ctx, solarMu, solarAzimuth, solarX, solarY)
+  end subroutine setSpotlightSource
   !------------------------------------------------------------------------------------------
   subroutine setEmissionSource(this, voxelWeights, fracAtmsPower, ierr)   ! new_PhotonStream, BBEmission
     type(integrator),          intent(inout) :: this

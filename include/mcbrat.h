@@ -92,6 +92,19 @@ int mcbrat_specify_parameters(mcbrat_ctx *ctx, int32_t useRayTracing, int32_t us
 
 /* new_PhotonStream, Directional form (src/monteCarloIllumination.f95:62-101). */
 int mcbrat_set_source_solar(mcbrat_ctx *ctx, float solarMu, float solarAzimuthDeg);
+/* new_PhotonStream, RandomAzimuth form (:103-140): mu = -|solarMu|, azimuth
+ * uniform in [0, 2 pi) and position uniform per photon. */
+int mcbrat_set_source_random_azimuth(mcbrat_ctx *ctx, float solarMu);
+/* new_PhotonStream, Flux form (:142-176): isotropic (diffuse) incidence,
+ * mu = -sqrt(U), azimuth and position uniform per photon.  A draw of mu = 0
+ * is drawn again (the reference would launch that photon horizontally). */
+int mcbrat_set_source_flux(mcbrat_ctx *ctx);
+/* new_PhotonStream, Spotlight form (:178-216): every photon enters at the
+ * point (solarX, solarY), given as fractions of the domain in (0, 1], in the
+ * direction (solarMu, solarAzimuthDeg).  Negative fractions are refused (the
+ * reference tests their absolute values and launches outside the domain). */
+int mcbrat_set_source_spotlight(mcbrat_ctx *ctx, float solarMu, float solarAzimuthDeg, float solarX,
+                                float solarY);
 /* new_PhotonStream, BBEmission form (:431-522): the running voxel CDF and
  * atmosphere fraction from emission_weighting / getInfo_Weights. */
 int mcbrat_set_source_emission(mcbrat_ctx *ctx, const double *voxelWeights, double fracAtmsPower);

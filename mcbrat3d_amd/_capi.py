@@ -47,6 +47,9 @@ SYMBOLS = {
     "mcbrat_set_inverse_table": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mcbrat_specify_parameters": (C.c_int, [_vp, _i32, _i32, _f]),
     "mcbrat_set_source_solar": (C.c_int, [_vp, _f, _f]),
+    "mcbrat_set_source_random_azimuth": (C.c_int, [_vp, _f]),
+    "mcbrat_set_source_flux": (C.c_int, [_vp]),
+    "mcbrat_set_source_spotlight": (C.c_int, [_vp, _f, _f, _f, _f]),
     "mcbrat_set_source_emission": (C.c_int, [_vp, _vp, _d]),
     "mcbrat_compute_radiative_transfer": (C.c_int, [_vp, _u64, _u64, _i64, _i32, _vp]),
     "mcbrat_report_results": (C.c_int, [_vp] * 9),

@@ -123,6 +123,8 @@ struct mcbrat_ctx {
   int useRR = 1;
   float lwFlag = -1.f;
   int srcKind = 0;
+  int solarKind = 0;            // srcKind 0: 0 Directional, 1 RandomAzimuth, 2 Flux, 3 Spotlight
+  double spotX = 0, spotY = 0;  // spotlight: launch point as fractions of the domain
   float dir0[3] = {0, 0, -1};
   double zLaunch = 0;
   int izLaunch = 0;
@@ -550,6 +552,7 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.srcKind = c->srcKind;
   p.dir0[0] = c->dir0[0]; p.dir0[1] = c->dir0[1]; p.dir0[2] = c->dir0[2];
   p.zLaunch = c->zLaunch; p.izLaunch = c->izLaunch;
+  p.solarKind = c->solarKind; p.spotX = c->spotX; p.spotY = c->spotY;
   p.voxelCDF = c->dVoxelCDF; p.fracAtms = c->fracAtms;
   p.nDir = c->nDir;
   p.dirData = c->dDirData; p.fwdTables = c->dFwd; p.fwdOrig = c->dFwdOrig;
@@ -789,9 +792,10 @@ const void *trace_kernel_for(const mcbrat_ctx *c, const DevParams &p, const Laun
     // surface -- with the walk's spacing flags decided at compile time too (SPEC, mcbrat_kernels.hip)
     // A solar run with roulette (every bench workload) also has its component count and the roulette decided at compile
     // time (SPEC bits 2-3 and 4); without roulette it runs the general kernel.  (Each SPEC is built for one source: EMIT = SPEC < 16.)
+    // The solar SPEC kernels launch the Directional source only: the other solar kinds run the general kernel.
     if (p.rec != nullptr && p.layerSkip && p.fly && p.surfNumX == 0 && (p.xyRegularWalk || !p.zRegularWalk)) {
       const int walk = p.xyRegularWalk ? (p.zRegularWalk ? 2 : 3) : 1;
-      switch (emit ? walk : (p.useRR && (p.nc == 1 || p.nc == 2) ? walk | p.nc << 2 | 16 : 0)) {
+      switch (emit ? walk : (p.useRR && (p.nc == 1 || p.nc == 2) && p.solarKind == 0 ? walk | p.nc << 2 | 16 : 0)) {
 #define MCBRAT_SPEC_CASE(S) \
   case S: return tbl ? (const void *)trace_kernel<256, true, 0, false, false, false, ((S) < 16), (S)> : (const void *)trace_kernel<256, false, 0, false, false, false, ((S) < 16), (S)>
         MCBRAT_SPEC_CASE(1); MCBRAT_SPEC_CASE(2); MCBRAT_SPEC_CASE(3);
@@ -1161,17 +1165,9 @@ int mcbrat_specify_parameters(mcbrat_ctx *c, int32_t useRayTracing, int32_t useR
   return 0;
 }
 
-int mcbrat_set_source_solar(mcbrat_ctx *c, float solarMu, float solarAzimuthDeg) {
-  if (!c) return 1;
-  if (!c->haveGrid) return fail(c, "setIllumination: domain hasn't been initialized.");
-  if (solarAzimuthDeg < 0.f || solarAzimuthDeg > 360.f) return fail(c, "setIllumination: solarAzimuth out of bounds");
-  if (std::fabs(solarMu) > 1.f || std::fabs(solarMu) <= FLT_MIN) return fail(c, "setIllumination: solarMu out of bounds");
-  // newPhotonStream_Directional, monteCarloIllumination.f95:93-96, then makeDirectionCosines :1876-1894
-  const float mu = -std::fabs(solarMu);
-  const float phi = (solarAzimuthDeg * std::acos(-1.0f)) / 180.0f;
-  const float sinTheta = std::sqrt(1.0f - mu * mu);
-  c->dir0[0] = sinTheta * std::cos(phi); c->dir0[1] = sinTheta * std::sin(phi); c->dir0[2] = mu;
-  // launch height z = 1 - spacing(1.) of the column (:93), mapped as computeRT :484-493
+// The launch height every solar kind shares: z = 1 - spacing(1.) of the column (monteCarloIllumination.f95:93, :128, :167,
+// :207), mapped as computeRT :484-493.  Then the source is solar (srcKind 0) of the given kind.
+static int set_solar_launch(mcbrat_ctx *c, int kind) {
   const double frac = (double)(1.0f - 1.1920929e-07f);
   const double z0 = c->ze.front(), zMax = c->ze.back();
   if (c->zRegular) {
@@ -1190,8 +1186,56 @@ int mcbrat_set_source_solar(mcbrat_ctx *c, float solarMu, float solarAzimuthDeg)
   }
   if (c->srcKind != 0) c->tuned = false;
   c->srcKind = 0;
+  c->solarKind = kind;
   c->haveSource = true;
   return 0;
+}
+
+// -abs(solarMu) and the azimuth in degrees -> launch direction cosines (:95-96, then makeDirectionCosines :1876-1894)
+static void set_solar_direction(mcbrat_ctx *c, float solarMu, float solarAzimuthDeg) {
+  const float mu = -std::fabs(solarMu);
+  const float phi = (solarAzimuthDeg * std::acos(-1.0f)) / 180.0f;
+  const float sinTheta = std::sqrt(1.0f - mu * mu);
+  c->dir0[0] = sinTheta * std::cos(phi); c->dir0[1] = sinTheta * std::sin(phi); c->dir0[2] = mu;
+}
+
+int mcbrat_set_source_solar(mcbrat_ctx *c, float solarMu, float solarAzimuthDeg) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "setIllumination: domain hasn't been initialized.");
+  if (solarAzimuthDeg < 0.f || solarAzimuthDeg > 360.f) return fail(c, "setIllumination: solarAzimuth out of bounds");
+  if (std::fabs(solarMu) > 1.f || std::fabs(solarMu) <= FLT_MIN) return fail(c, "setIllumination: solarMu out of bounds");
+  set_solar_direction(c, solarMu, solarAzimuthDeg);  // newPhotonStream_Directional, monteCarloIllumination.f95:93-96
+  return set_solar_launch(c, 0);
+}
+
+int mcbrat_set_source_random_azimuth(mcbrat_ctx *c, float solarMu) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "setIllumination: domain hasn't been initialized.");
+  if (std::fabs(solarMu) > 1.f || std::fabs(solarMu) <= FLT_MIN) return fail(c, "setIllumination: solarMu out of bounds");
+  // newPhotonStream_RandomAzimuth :103-140: mu = -abs(solarMu); the azimuth is drawn per photon (solar_launch)
+  c->dir0[0] = 0.f; c->dir0[1] = 0.f; c->dir0[2] = -std::fabs(solarMu);
+  return set_solar_launch(c, 1);
+}
+
+int mcbrat_set_source_flux(mcbrat_ctx *c) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "setIllumination: domain hasn't been initialized.");
+  // newPhotonStream_Flux :142-176: mu and the azimuth are drawn per photon (solar_launch)
+  c->dir0[0] = 0.f; c->dir0[1] = 0.f; c->dir0[2] = -1.f;
+  return set_solar_launch(c, 2);
+}
+
+int mcbrat_set_source_spotlight(mcbrat_ctx *c, float solarMu, float solarAzimuthDeg, float solarX, float solarY) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "setIllumination: domain hasn't been initialized.");
+  if (solarAzimuthDeg < 0.f || solarAzimuthDeg > 360.f) return fail(c, "setIllumination: solarAzimuth out of bounds");
+  if (std::fabs(solarMu) > 1.f || std::fabs(solarMu) <= FLT_MIN) return fail(c, "setIllumination: solarMu out of bounds");
+  // :193-195 tests abs(solarX), abs(solarY) in (0, 1]; a negative fraction would launch outside the domain, so it is refused too
+  if (!(solarX > 0.f && solarX <= 1.f && solarY > 0.f && solarY <= 1.f))
+    return fail(c, "setIllumination: x and y positions must be between 0 and 1");
+  set_solar_direction(c, solarMu, solarAzimuthDeg);  // newPhotonStream_Spotlight :178-216
+  c->spotX = (double)solarX; c->spotY = (double)solarY;  // (real(8) = real)
+  return set_solar_launch(c, 3);
 }
 
 int mcbrat_set_source_emission(mcbrat_ctx *c, const double *voxelWeights, double fracAtmsPower) {

@@ -435,11 +435,19 @@ trace_block_kernel(const DevParams p) {
             uint32_t r[4];
             philox4x32_10_p1(0u, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
             double lx, ly, lz;  // fractional launch position in [0,1]
-            if (!EMIT) {  // newPhotonStream_Directional, monteCarloIllumination.f95:88-96
-              lx = (double)u01(r[0]);
-              ly = (double)u01(r[1]);
+            if (!EMIT) {
               lz = 0.0;
-              dx = p.dir0[0]; dy = p.dir0[1]; dz = p.dir0[2];
+              if (p.solarKind == 0) {  // newPhotonStream_Directional, monteCarloIllumination.f95:88-96
+                lx = (double)u01(r[0]);
+                ly = (double)u01(r[1]);
+                dx = p.dir0[0]; dy = p.dir0[1]; dz = p.dir0[2];
+              } else {  // RandomAzimuth, Flux, Spotlight (wave-uniform; mcbrat_kernels.hip)
+                solar_launch(p, r[0], r[1], r[2], r[3], [&](uint32_t b) {
+                  uint32_t o[4];
+                  philox4x32_10_p1(0u, b, idP1, idHi, p.seedLo, p.seedHi, o);
+                  return o[0] ? o[0] : (o[1] ? o[1] : (o[2] ? o[2] : o[3]));
+                }, lx, ly, dx, dy, dz);
+              }
             } else {  // newPhotonStream_BBEmission :481-516
               float mu = 0.f, phi = 0.f;
               const float sel = u01(r[0]);

@@ -127,7 +127,7 @@ struct DevParams {
   int useRR;
   int lwFlag;                     // LW_flag > 0
   int srcKind;                    // 0 directional, 1 BB emission
-  float dir0[3];                  // directional: launch direction cosines
+  float dir0[3];                  // directional, spotlight: launch direction cosines (random azimuth: dir0[2] = mu)
   double zLaunch;                 // directional: launch height
   int izLaunch;                   // directional: 0-based launch layer
   const double *voxelCDF;         // emission: running CDF [nvox]
@@ -185,6 +185,10 @@ struct DevParams {
   // in the batch slab: [upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1)], order slowest.
   // (Last, in the padding behind traceCap: the parameter block keeps its size and every other member its offset.)
   int numRecScatOrd;
+  // the solar source's kind (srcKind 0; solar_launch): 0 Directional, 1 RandomAzimuth, 2 Flux, 3 Spotlight, and the
+  // spotlight's launch point as fractions of the domain (solarX, solarY)
+  int solarKind;
+  double spotX, spotY;
 };
 
 }  // namespace mcbrat

@@ -1,5 +1,6 @@
-"""Photon sources.  Mirrors src/monteCarloIllumination.f95 (new_PhotonStream,
-Directional :62-101 and BBEmission :431-522 forms) and the part of
+"""Photon sources.  Mirrors src/monteCarloIllumination.f95 (new_PhotonStream:
+Directional :62-101, RandomAzimuth :103-140, Flux :142-176, Spotlight :178-216 and
+BBEmission :431-522 forms) and the part of
 src/emissionAndBroadBandWeights.f95 the thermal source needs (new_Weights,
 emission_weighting :424-550).
 
@@ -52,26 +53,59 @@ def emission_weighting(thisDomain, theseWeights, sfcTemp, dLambda=1.0):
     return flux.value
 
 
+def _check_mu(solarMu):
+    if abs(solarMu) > 1.0 or abs(solarMu) <= np.finfo(np.float32).tiny:
+        raise McbratError("setIllumination: solarMu out of bounds")
+
+
+def _check_azimuth(solarAzimuth):
+    if solarAzimuth < 0.0 or solarAzimuth > 360.0:
+        raise McbratError("setIllumination: solarAzimuth out of bounds")
+
+
 class PhotonStream:
-    def __init__(self, numberOfPhotons, solarMu=None, solarAzimuth=None, theseWeights=None):
+    """kind: "Directional", "RandomAzimuth", "Flux", "Spotlight" (the solar forms) or "BBEmission"."""
+
+    def __init__(self, numberOfPhotons, solarMu=None, solarAzimuth=None, theseWeights=None, solarX=None, solarY=None):
         if numberOfPhotons < 0:
             raise McbratError("setIllumination: must ask for non-negative number of photons.")
         self.numberOfPhotons = int(numberOfPhotons)
         self.currentPhoton = 1
-        if theseWeights is not None:
+        spot = solarX is not None or solarY is not None
+        if theseWeights is not None:  # (BBEmission: any solar geometry given with it is ignored, as it always was)
             if theseWeights.voxelWeights is None:
                 raise McbratError("setIllumination: weights have not been computed (call emission_weighting).")
             self.kind, self.weights = "BBEmission", theseWeights
-        else:
-            if solarAzimuth < 0.0 or solarAzimuth > 360.0:
-                raise McbratError("setIllumination: solarAzimuth out of bounds")
-            if abs(solarMu) > 1.0 or abs(solarMu) <= np.finfo(np.float32).tiny:
-                raise McbratError("setIllumination: solarMu out of bounds")
+        elif spot:
+            if solarMu is None or solarAzimuth is None or solarX is None or solarY is None:
+                raise McbratError("new_PhotonStream: a spotlight needs solarMu, solarAzimuth, solarX and solarY")
+            _check_azimuth(solarAzimuth)
+            _check_mu(solarMu)
+            # the reference tests abs(solarX), abs(solarY) (:193-195); a negative fraction is refused here as well
+            x, y = np.float32(solarX), np.float32(solarY)
+            if not (0.0 < x <= 1.0 and 0.0 < y <= 1.0):
+                raise McbratError("setIllumination: x and y positions must be between 0 and 1")
+            self.kind, self.solarMu, self.solarAzimuth = "Spotlight", float(solarMu), float(solarAzimuth)
+            self.solarX, self.solarY = float(solarX), float(solarY)
+        elif solarAzimuth is not None:
+            if solarMu is None:
+                raise McbratError("new_PhotonStream: solarAzimuth needs solarMu")
+            _check_azimuth(solarAzimuth)
+            _check_mu(solarMu)
             self.kind, self.solarMu, self.solarAzimuth = "Directional", float(solarMu), float(solarAzimuth)
+        elif solarMu is not None:
+            _check_mu(solarMu)
+            self.kind, self.solarMu = "RandomAzimuth", float(solarMu)
+        else:
+            self.kind = "Flux"
 
     def morePhotonsExist(self):
         return 0 < self.currentPhoton <= self.numberOfPhotons
 
 
-def new_PhotonStream(solarMu=None, solarAzimuth=None, numberOfPhotons=0, theseWeights=None):
-    return PhotonStream(numberOfPhotons, solarMu, solarAzimuth, theseWeights)
+def new_PhotonStream(solarMu=None, solarAzimuth=None, numberOfPhotons=0, theseWeights=None, solarX=None, solarY=None,
+                     randomNumbers=None):
+    """Resolves like the reference's overload, by the arguments given:
+    (solarMu, solarAzimuth) Directional; (solarMu) RandomAzimuth; () Flux; (solarMu, solarAzimuth, solarX=, solarY=)
+    Spotlight; (theseWeights=) BBEmission.  randomNumbers is accepted and ignored: photons are generated on the GPU."""
+    return PhotonStream(numberOfPhotons, solarMu, solarAzimuth, theseWeights, solarX, solarY)

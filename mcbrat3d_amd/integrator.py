@@ -20,6 +20,12 @@ defaultMinForwardTableSize = 9001
 defaultHybridPhaseFunWidth, maxHybridPhaseFunWidth = 7.0, 30.0  # :26-27
 defaultZetaMin = 0.3  # :29
 
+# the solar forms of new_PhotonStream: the stream's attributes each one passes, in order, and the C function that sets it
+_SOLAR_ARGS = {"Directional": ("solarMu", "solarAzimuth"), "RandomAzimuth": ("solarMu",), "Flux": (),
+               "Spotlight": ("solarMu", "solarAzimuth", "solarX", "solarY")}
+_SOLAR_SETTERS = {"Directional": "mcbrat_set_source_solar", "RandomAzimuth": "mcbrat_set_source_random_azimuth",
+                  "Flux": "mcbrat_set_source_flux", "Spotlight": "mcbrat_set_source_spotlight"}
+
 
 class RandomNumberSequence:
     """Stands where the reference passes type(randomNumberSequence): the Philox key and the
@@ -337,21 +343,22 @@ class Integrator:
         self._loaded_weights = None
 
     def _load_source(self, photons):
-        if photons.kind == "Directional":  # the geometry itself is the token
-            token = ("Directional", float(photons.solarMu), float(photons.solarAzimuth))
-        else:  # strong reference to the weights + their version (emission_weighting bumps it)
+        kind = photons.kind
+        if kind == "BBEmission":  # strong reference to the weights + their version (emission_weighting bumps it)
             token = ("BBEmission", photons.weights._version, float(photons.weights.fracAtmsPower))
             if photons.weights is not self._loaded_weights:
                 self._source_token = None
+        else:  # the solar kinds: the kind and its geometry are the token
+            token = (kind,) + tuple(float(getattr(photons, a)) for a in _SOLAR_ARGS[kind])
         if token == self._source_token:
             return
-        if photons.kind == "Directional":
-            self._check(self._lib.mcbrat_set_source_solar(self._ctx, C.c_float(photons.solarMu),
-                                                          C.c_float(photons.solarAzimuth)))
-        else:
+        if kind == "BBEmission":
             self._check(self._lib.mcbrat_set_source_emission(self._ctx, ptr(photons.weights.voxelWeights),
                                                              photons.weights.fracAtmsPower))
             self._loaded_weights = photons.weights
+        else:
+            setter = getattr(self._lib, _SOLAR_SETTERS[kind])
+            self._check(setter(self._ctx, *(C.c_float(v) for v in token[1:])))
         self._source_token = token
 
     def prepare(self, thisDomain, incomingPhotons):
