@@ -115,7 +115,14 @@ int mcbrat_set_source_emission(mcbrat_ctx *ctx, const double *voxelWeights, doub
  * batch.  Photon i of batch b has the global id firstPhotonId + b*photonsPerBatch + i;
  * its random numbers are Philox4x32-10(key = seed, counter = (event, block, id)),
  * so results do not depend on how photons are spread over GPUs.
- * numPhotonsProcessed (may be NULL) receives the total. */
+ * numPhotonsProcessed (may be NULL) receives the total.
+ * Capacity: the tallies are 64-bit integers of 2^-32 photon weights, so a bin holds
+ * less than 2^31 unit weights per batch.  photonsPerBatch > 2^31 - 1 is refused
+ * before anything is traced.  That bounds fluxUp and fluxDown over a black surface (a
+ * photon reaches them once, with a weight of at most 1), and the volume absorption
+ * without Russian roulette; it does NOT bound fluxDown over a reflecting surface (a
+ * photon may arrive many times), radiance, or the bins by scattering order of those
+ * two, which wrap around unreported. */
 int mcbrat_compute_radiative_transfer(mcbrat_ctx *ctx, uint64_t seed, uint64_t firstPhotonId,
                                       int64_t photonsPerBatch, int32_t nBatches,
                                       int64_t *numPhotonsProcessed);

@@ -262,6 +262,7 @@ size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
          (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0);
 }
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
+constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
 // The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
 const char *const kOrdersLimitMsg =
     "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
@@ -1666,6 +1667,9 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   (void)hipSetDevice(c->device);
   if (check_ready(c)) return 1;
   if (ppb < 1 || nBatches < 1) return fail(c, "computeRadiativeTransfer: Didn't process any photons.");
+  // the capacity of the tallies: a bin holds less than 2^31 unit weights (2^63 in 2^-32 units)
+  if (ppb > kMaxPhotonsPerBatch)
+    return fail(c, "computeRadiativeTransfer: numPhotonsPerBatch is too large: at most 2^31 - 1 photons per batch fit the tallies.");
   if (ensure_moments(c)) return 1;
   // the trial launches that choose the event threshold run synchronously, once, on the first call large enough
   const bool tuneNow = c->autoTune && !c->tuned && (unsigned long long)ppb * (unsigned long long)nBatches >= c->tuneTrialPhotons;
