@@ -29,7 +29,7 @@ module mcbrat_hip_integrator
             resetMoments, getMoments, momentsLength, lastMessage, &
             inverseTableLegendre, lastTraceMilliseconds, setAsynchronous, synchronize, &
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
-            setSurfaceDescription, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
+            setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
             specifyScatteringOrders, reportResultsByScatOrd
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
@@ -90,6 +90,15 @@ module mcbrat_hip_integrator
       integer(c_int32_t), value :: numX, numY
       real(c_double), dimension(*), intent(in) :: xPosition, yPosition
       real(c_float), dimension(*), intent(in) :: reflectance
+      integer(c_int) :: rc
+    end function
+    function mcbrat_set_surface_brdf(ctx, kind, numX, numY, xPosition, yPosition, nParams, params) &
+        bind(C, name="mcbrat_set_surface_brdf") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double, c_float
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: kind, numX, numY, nParams
+      real(c_double), dimension(*), intent(in) :: xPosition, yPosition
+      real(c_float), dimension(*), intent(in) :: params
       integer(c_int) :: rc
     end function
     function mcbrat_set_source_solar(ctx, mu, azimuth) bind(C, name="mcbrat_set_source_solar") result(rc)
@@ -352,6 +361,39 @@ contains
     ierr = mcbrat_set_surface_description(this%ctx, int(size(xPosition), c_int32_t), int(size(yPosition), c_int32_t), &
                                           xPosition, yPosition, reflectance)
   end subroutine setSurfaceDescription
+  !------------------------------------------------------------------------------------------
+  ! A surface BRDF per patch (DESIGN.md section 4.11): model "Lambertian" (1 parameter), "RPV" (rho0, k, Theta, rhoC) or
+  ! "RossLi" (fIso, fVol, fGeo); parameters(numberOfParameters, numX-1, numY-1) as the reference's BRDFParameters
+  subroutine setSurfaceBRDF(this, model, parameters, xPosition, yPosition, ierr)
+    type(integrator),        intent(inout) :: this
+    character(len=*),        intent(in)    :: model
+    real, dimension(:,:,:),  intent(in)    :: parameters
+    real(8), dimension(:),   intent(in)    :: xPosition, yPosition
+    integer,                 intent(out)   :: ierr
+    integer(c_int32_t) :: kind
+    real, dimension(size(parameters, 2), size(parameters, 3), size(parameters, 1)) :: packed   ! the C layout: x fastest, parameter slowest
+    integer :: k
+    select case (trim(model))
+    case ("Lambertian")
+      kind = 0
+    case ("RPV")
+      kind = 1
+    case ("RossLi")
+      kind = 2
+    case default
+      ierr = 2   ! "new_SurfaceDescription: unknown surface BRDF model"
+      return
+    end select
+    if (size(parameters, 2) /= size(xPosition) - 1 .or. size(parameters, 3) /= size(yPosition) - 1) then
+      ierr = 2   ! "new_SurfaceDescription: position vector(s) are incorrect length."
+      return
+    end if
+    do k = 1, size(parameters, 1)
+      packed(:, :, k) = parameters(k, :, :)
+    end do
+    ierr = mcbrat_set_surface_brdf(this%ctx, kind, int(size(xPosition), c_int32_t), int(size(yPosition), c_int32_t), &
+                                   xPosition, yPosition, int(size(parameters, 1), c_int32_t), packed)
+  end subroutine setSurfaceBRDF
   !------------------------------------------------------------------------------------------
   subroutine setSolarSource(this, solarMu, solarAzimuth, ierr)   ! new_PhotonStream, Directional
     type(integrator), intent(inout) :: this

@@ -121,8 +121,9 @@ int mcbrat_set_source_emission(mcbrat_ctx *ctx, const double *voxelWeights, doub
  * before anything is traced.  That bounds fluxUp and fluxDown over a black surface (a
  * photon reaches them once, with a weight of at most 1), and the volume absorption
  * without Russian roulette; it does NOT bound fluxDown over a reflecting surface (a
- * photon may arrive many times), radiance, or the bins by scattering order of those
- * two, which wrap around unreported. */
+ * photon may arrive many times), fluxUp over a BRDF surface (mcbrat_set_surface_brdf: a
+ * reflected weight may exceed 1), radiance, or the bins by scattering order of those,
+ * which wrap around unreported. */
 int mcbrat_compute_radiative_transfer(mcbrat_ctx *ctx, uint64_t seed, uint64_t firstPhotonId,
                                       int64_t photonsPerBatch, int32_t nBatches,
                                       int64_t *numPhotonsProcessed);
@@ -288,6 +289,27 @@ int mcbrat_set_option(mcbrat_ctx *ctx, const char *name, int32_t value);
  * numX <= 0 returns to the domain's albedo.  Error texts are the reference's. */
 int mcbrat_set_surface_description(mcbrat_ctx *ctx, int32_t numX, int32_t numY, const double *xPosition,
                                    const double *yPosition, const float *reflectance);
+
+/* A surface BRDF per patch (the reference's template, src/surfaceProperties.f95:8-14, with
+ * numberOfParameters > 1).  kind 0 Lambertian {a} (what mcbrat_set_surface_description sets), 1 RPV {rho0, k, Theta, rhoC},
+ * 2 Ross-Li (RossThick + LiSparse-Reciprocal) {fIso, fVol, fGeo}; `params` is BRDFParameters(nParams, numX-1, numY-1),
+ * x fastest, nParams 1 / 4 / 3.  A reflected photon keeps the Lambertian (cosine-weighted) draw of its direction and its
+ * weight is multiplied by the reflectance factor R = pi f of the patch for its arriving and leaving directions; the local
+ * estimates of radiance from a reflection use R / pi.  Refused: parameters outside RPV's 0 <= rho0 <= 1, 0.2 <= k <= 2,
+ * |Theta| <= 0.95, 0 <= rhoC <= 1, negative Ross-Li weights, and a patch whose directional-hemispherical albedo exceeds
+ * 1 + 1e-3 at mu_i = 0.1, 0.2, .., 1.  A non-Lambertian surface is refused together with the thermal source, event counters
+ * and photon fates (at computeRadiativeTransfer).  Over it fluxUp, like fluxDown, is not bounded by the capacity rule of
+ * mcbrat_compute_radiative_transfer (a reflected weight may exceed 1).  numX <= 0 returns to the domain's albedo. */
+int mcbrat_set_surface_brdf(mcbrat_ctx *ctx, int32_t kind, int32_t numX, int32_t numY, const double *xPosition,
+                            const double *yPosition, int32_t nParams, const float *params);
+
+/* The BRDF evaluator on the host (no context, no GPU): the reflectance factor R = pi f of one patch's parameters for the
+ * propagation directions dIn (arriving, dIn[2] < 0) and dOut (leaving, dOut[2] > 0), unit vectors; NaN for an unknown kind. */
+float mcbrat_brdf_reflectance(int32_t kind, const float *params, const double *dIn, const double *dOut);
+
+/* Directional-hemispherical albedo rho_dh(muIn) = (1/pi) int R mu_r dOmega (black-sky albedo at incidence cosine muIn),
+ * by Gauss quadrature; NaN for an unknown kind or muIn outside (0, 1]. */
+double mcbrat_brdf_albedo(int32_t kind, const float *params, double muIn);
 
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air

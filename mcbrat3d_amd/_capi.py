@@ -83,6 +83,9 @@ SYMBOLS = {
     "mcbrat_frequency_distribution": (C.c_int, [_vp, _u64, _u64, _i32, _vp, _i64, _vp]),
     "mcbrat_philox4x32_10": (C.c_int, [_vp, _i32, _vp, _vp]),
     "mcbrat_set_surface_description": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "mcbrat_set_surface_brdf": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "mcbrat_brdf_reflectance": (_f, [_i32, _vp, _vp, _vp]),
+    "mcbrat_brdf_albedo": (_d, [_i32, _vp, _d]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),
     "mcbrat_inverse_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_inverse_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
@@ -92,7 +95,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3)
+ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs are additions under 3)
 
 
 def hip_runtimes():

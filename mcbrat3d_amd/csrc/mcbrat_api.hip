@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -95,6 +96,8 @@ struct mcbrat_ctx {
   int surfNumX = 0, surfNumY = 0;
   double *dSurfX = nullptr, *dSurfY = nullptr;
   float *dSurfRefl = nullptr;
+  int surfKind = 0;                // mcbrat_set_surface_brdf: 0 Lambertian (dSurfRefl), 1 RPV, 2 Ross-Li (dSurfBrdf)
+  float4 *dSurfBrdf = nullptr;     // [numY-1][numX-1] the patches' parameters, padded to four
   double *dVoxelCDF = nullptr;
   unsigned long long *dEventCounters = nullptr;
   float *dLast = nullptr;
@@ -545,6 +548,8 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   }
   p.albedo = c->albedo;
   p.surfNumX = c->surfNumX; p.surfNumY = c->surfNumY; p.surfX = c->dSurfX; p.surfY = c->dSurfY; p.surfRefl = c->dSurfRefl;
+  p.surfKind = c->surfNumX > 0 ? c->surfKind : 0;
+  if (p.surfKind != 0) p.surfRefl = reinterpret_cast<const float *>(c->dSurfBrdf);  // (float4 per patch)
   p.tables = c->dTables;
   for (int k = 0; k < c->nc; ++k) { p.tblOffset[k] = c->tblOffset[k]; p.tblNSteps[k] = c->tblNSteps[k]; p.tblInvN[k] = 1.0f / (float)c->tblNSteps[k]; }
   p.tblTotalFloats = c->tblTotalFloats;
@@ -618,6 +623,7 @@ struct LaunchPlan {
 
 bool blocks_worth_it(const mcbrat_ctx *c) {
   if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c)) return false;  // (the block walk has no ORD variant)
+  if (c->surfNumX > 0 && c->surfKind != 0) return false;  // (nor a BRDF one: such surfaces go face by face)
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   return (size_t)c->nBlocks * 4 <= nvox || c->blockWalk == 2;  // (2: forced, for tests of heterogeneous media)
 }
@@ -759,22 +765,43 @@ int launch_kernel(mcbrat_ctx *c, DevParams &p, const void *kernel, int block, si
 
 // trace_kernel with the table and source flags picked at run time (every value of both is built).  (The source kind is a
 // template parameter: the emission launch code costs the solar instantiations registers.)
-template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false, bool ORD = false>
+template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false, bool ORD = false, bool BRDF = false>
 const void *trace_ptr(bool tbl, bool emit) {
+  if constexpr (BRDF) {  // (solar sources only: a BRDF surface is refused with the thermal one, check_ready)
+    static_assert(!DBG, "no instrumented BRDF instantiation");
+    (void)emit;
+    return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, false, INTEN, false, 0, ORD, true>
+               : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, false, INTEN, false, 0, ORD, true>;
+  }
   if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
   return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
 }
 
 // the ORD instantiations (scattering orders): BLOCK 256 / 512 x PRIV 0 / 1 / 2 x INTEN x table x source, dense grids, not instrumented
-template <int BLOCK>
+template <int BLOCK, bool BRDF = false>
 const void *trace_kernel_ord(const mcbrat_ctx *c, const LaunchPlan &L) {
   const bool tbl = L.tblLds, emit = c->srcKind != 0;
   if (c->nDir > 0) {
-    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true, true>(tbl, emit);
-    return trace_ptr<BLOCK, 0, false, false, true, true>(tbl, emit);
+    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, true, BRDF>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true, true, BRDF>(tbl, emit);
+    return trace_ptr<BLOCK, 0, false, false, true, true, BRDF>(tbl, emit);
   }
-  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, false, true>(tbl, emit);
-  return trace_ptr<BLOCK, 0, false, false, false, true>(tbl, emit);
+  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, true, BRDF>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, false, true, BRDF>(tbl, emit);
+  return trace_ptr<BLOCK, 0, false, false, false, true, BRDF>(tbl, emit);
+}
+
+// BRDF surfaces: the kernels the face-by-face plan picks for a surface description, from a solar source,
+// not instrumented -- BLOCK 256 / 512 x PRIV 0 / 1 / 2 / bricks x INTEN x ORD, the wide plan's 1024 and the 768-lane kernel, x table
+template <int BLOCK>
+const void *trace_kernel_brdf(const mcbrat_ctx *c, const LaunchPlan &L) {
+  const bool tbl = L.tblLds;
+  if (orders_on(c)) return trace_kernel_ord<BLOCK, true>(c, L);
+  if (c->nDir > 0) {
+    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, false, true>(tbl, false) : trace_ptr<BLOCK, 1, false, false, true, false, true>(tbl, false);
+    return trace_ptr<BLOCK, 0, false, false, true, false, true>(tbl, false);
+  }
+  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, false, true>(tbl, false) : trace_ptr<BLOCK, 1, false, false, false, false, true>(tbl, false);
+  if (L.brick) return trace_ptr<BLOCK, 0, true, false, false, false, true>(tbl, false);
+  return trace_ptr<BLOCK, 0, false, false, false, false, true>(tbl, false);
 }
 
 // trace_kernel of 256 or 512 lanes.  Instantiated combinations: private tallies (small domains) and bricks (large ones) never
@@ -874,18 +901,21 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   }
   if (block_walk_applies(c, L)) return launch_block(c, p, L, debug, nBatches);
   const bool tbl = L.tblLds, emit = c->srcKind != 0;
+  const bool brdf = p.surfKind != 0;
+  if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
   const void *kernel;
   int block;
   size_t lds = L.lds;
   if (L.wide && !debug) {  // one workgroup of 1024 lanes per compute unit, tallies (and what else fits) in its LDS; instrumented: 512 lanes
     block = 1024;
-    kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
+    if (brdf) kernel = L.gridLds ? trace_ptr<1024, 2, false, false, false, false, true>(tbl, false) : trace_ptr<1024, 1, false, false, false, false, true>(tbl, false);
+    else kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
   } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0) {
     // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
     // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
     // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
     block = 768;
-    kernel = trace_ptr<768, 2, false, false>(tbl, emit);
+    kernel = brdf ? trace_ptr<768, 2, false, false, false, false, true>(tbl, false) : trace_ptr<768, 2, false, false>(tbl, emit);
   } else {
     block = L.block >= 512 ? 512 : 256;
     if (c->nDir > 0) {  // radiance runs
@@ -904,7 +934,8 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
       p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
       lds = base + waves * cap * 80;
     }
-    if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
+    if (brdf) kernel = block == 512 ? trace_kernel_brdf<512>(c, L) : trace_kernel_brdf<256>(c, L);
+    else if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
       if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with scattering orders.");
       kernel = block == 512 ? trace_kernel_ord<512>(c, L) : trace_kernel_ord<256>(c, L);
     } else if (block == 512) kernel = debug ? trace_kernel_for<512, true>(c, p, L) : trace_kernel_for<512, false>(c, p, L);
@@ -919,6 +950,8 @@ int check_ready(mcbrat_ctx *c) {
   if (!c) return 1;
   if (!c->haveGrid || !c->haveOptics) return fail(c, "computeRadiativeTransfer: problem not completely specified.");
   if (!c->haveSource) return fail(c, "computeRadiativeTransfer: no photon source set.");
+  if (c->surfNumX > 0 && c->surfKind != 0 && c->srcKind != 0)
+    return fail(c, "computeRadiativeTransfer: a BRDF surface cannot be used with the thermal source (its emissivity would be 1 - rho_dh(mu)).");
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
 }
@@ -1025,7 +1058,7 @@ void mcbrat_destroy(mcbrat_ctx *c) {
   (void)sync_all(c);
   void *bufs[] = {c->dEdges, c->dExt, c->dCum, c->dSsa, c->dRelArea, c->dPfi, c->dTables, c->dVoxelCDF,
                   c->dEventCounters, c->dLast, c->dMomentsOwned, c->dBrickTable, c->dExtB,
-                  c->dBlockRec, c->dBlockOf, c->dBlockExt, c->dBlockSsa, c->dBlockCum, c->dBlockPfi, c->dCumB, c->dSsaB, c->dPfiB, c->dBgExt, c->dBgCum, c->dBgSsa, c->dBgPfi, c->dLayerExt, c->dRec, c->dLayerRun, c->dLayerRunT, c->dExtWalk, c->dBgVal, c->dFlyRange, c->dSurfX, c->dSurfY, c->dSurfRefl,
+                  c->dBlockRec, c->dBlockOf, c->dBlockExt, c->dBlockSsa, c->dBlockCum, c->dBlockPfi, c->dCumB, c->dSsaB, c->dPfiB, c->dBgExt, c->dBgCum, c->dBgSsa, c->dBgPfi, c->dLayerExt, c->dRec, c->dLayerRun, c->dLayerRunT, c->dExtWalk, c->dBgVal, c->dFlyRange, c->dSurfX, c->dSurfY, c->dSurfRefl, c->dSurfBrdf,
                   c->dBad, c->dFreqCdf, c->dFreqCounts, c->dDirData, c->dFwd, c->dFwdOrig};
   if (c->hBad) (void)hipHostFree(c->hBad);
   for (void *b : bufs) if (b) (void)hipFree(b);
@@ -1572,6 +1605,41 @@ int mcbrat_set_surface_description(mcbrat_ctx *c, int32_t numX, int32_t numY, co
       upload(c, &c->dSurfRefl, reflectance, (size_t)(numX - 1) * (numY - 1)))
     return 1;
   c->surfNumX = numX; c->surfNumY = numY;
+  c->surfKind = 0;
+  return 0;
+}
+
+int mcbrat_set_surface_brdf(mcbrat_ctx *c, int32_t kind, int32_t numX, int32_t numY, const double *xPosition, const double *yPosition,
+                            int32_t nParams, const float *params) {
+  if (!c) return 1;
+  if (kind == 0) {  // Lambertian: the surface description as it was
+    if (numX > 0 && numY > 0 && nParams != 1) return fail(c, "new_SurfaceDescription: Wrong number of parameters supplied for surface BRDF.");
+    return mcbrat_set_surface_description(c, numX, numY, xPosition, yPosition, params);
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (numX <= 0 || numY <= 0) { c->surfNumX = c->surfNumY = 0; c->surfKind = 0; return 0; }  // back to the domain's albedo
+  if (brdf_num_params(kind) == 0 || kind == BRDF_LAMBERTIAN) return fail(c, "new_SurfaceDescription: unknown surface BRDF model.");
+  if (nParams != brdf_num_params(kind)) return fail(c, "new_SurfaceDescription: Wrong number of parameters supplied for surface BRDF.");
+  if (numX < 2 || numY < 2 || !xPosition || !yPosition || !params)
+    return fail(c, "new_SurfaceDescription: position vector(s) are incorrect length.");
+  for (int i = 1; i < numX; ++i) if (!(xPosition[i] - xPosition[i - 1] > 0.)) return fail(c, "new_SurfaceDescription: positions must be unique, increasing.");
+  for (int i = 1; i < numY; ++i) if (!(yPosition[i] - yPosition[i - 1] > 0.)) return fail(c, "new_SurfaceDescription: positions must be unique, increasing.");
+  const size_t nPatch = (size_t)(numX - 1) * (numY - 1);
+  std::vector<float4> q(nPatch);
+  std::vector<std::array<float, 4>> seen;  // the parameter checks and the energy rule, once per distinct parameter vector
+  for (size_t i = 0; i < nPatch; ++i) {
+    std::array<float, 4> v = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < nParams; ++k) v[(size_t)k] = params[(size_t)k * nPatch + i];  // [nParams][numY-1][numX-1]
+    q[i] = make_float4(v[0], v[1], v[2], v[3]);
+    if (std::find(seen.begin(), seen.end(), v) != seen.end()) continue;
+    if (const char *err = brdf_param_error(kind, v.data())) return fail(c, err);
+    seen.push_back(v);
+  }
+  if (upload(c, &c->dSurfX, xPosition, (size_t)numX) || upload(c, &c->dSurfY, yPosition, (size_t)numY) || upload(c, &c->dSurfBrdf, q.data(), nPatch))
+    return 1;
+  c->surfNumX = numX; c->surfNumY = numY;
+  c->surfKind = kind;
   return 0;
 }
 

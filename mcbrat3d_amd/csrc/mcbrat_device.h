@@ -98,7 +98,7 @@ struct DevParams {
   // own x/y positions; surfNumX == 0: the domain's Lambertian albedo
   int surfNumX, surfNumY;
   const double *surfX, *surfY;
-  const float *surfRefl;          // [numY-1][numX-1]
+  const float *surfRefl;          // [numY-1][numX-1]; a BRDF surface (surfKind != 0): its patches' parameters, float4 per patch
   // brick layout of the optics (large, mostly-background domains): ext/cum/ssa/pfi then hold the
   // STORED bricks only (64 cells each, [component][nStored]); background cells use bg* [component][nz]
   const uint32_t *brickTable;     // [nbz][nby][nbx] offset of the brick's 64 cells, 0xffffffff = background
@@ -188,6 +188,9 @@ struct DevParams {
   // the solar source's kind (srcKind 0; solar_launch): 0 Directional, 1 RandomAzimuth, 2 Flux, 3 Spotlight, and the
   // spotlight's launch point as fractions of the domain (solarX, solarY)
   int solarKind;
+  // the surface description's model (BRDF instantiations of trace_kernel): 0 Lambertian, 1 RPV, 2 Ross-Li.
+  // (In the padding before spotX: the parameter block keeps its size and every other member its offset.)
+  int surfKind;
   double spotX, spotY;
 };
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mcbrat.h"
+#include "mcbrat_brdf.h"
 
 namespace {
 
@@ -462,4 +463,89 @@ extern "C" int mcbrat_flight_tables(int32_t nx, int32_t ny, int32_t nz, const fl
   depth[0] = 0.0;
   for (int k = 0; k < nz; ++k) depth[k + 1] = depth[k] + ((flyable[k] || uniform[k]) ? (double)background[k] * (zEdges[k + 1] - zEdges[k]) : 0.0);
   return 0;
+}
+
+// ---- surface BRDFs (mcbrat_brdf.h): the host side of the one evaluator ----
+namespace {
+
+// Gauss-Legendre nodes and weights of order n on [a, b] (Newton on the three-term recurrence)
+void gauss_legendre(int n, double a, double b, std::vector<double> &x, std::vector<double> &w) {
+  x.assign((size_t)n, 0.0);
+  w.assign((size_t)n, 0.0);
+  const double pi = 3.14159265358979323846;
+  for (int i = 0; i < (n + 1) / 2; ++i) {
+    double z = std::cos(pi * (i + 0.75) / (n + 0.5)), dp = 0.0;
+    for (int it = 0; it < 100; ++it) {
+      double p0 = 1.0, p1 = z;
+      for (int l = 2; l <= n; ++l) { const double p2 = ((2.0 * l - 1.0) * z * p1 - (l - 1.0) * p0) / l; p0 = p1; p1 = p2; }
+      dp = n * (z * p1 - p0) / (z * z - 1.0);
+      const double dz = p1 / dp;
+      z -= dz;
+      if (std::fabs(dz) < 1e-15) break;
+    }
+    const double wi = 2.0 / ((1.0 - z * z) * dp * dp);
+    x[(size_t)i] = 0.5 * (a + b) - 0.5 * (b - a) * z; x[(size_t)(n - 1 - i)] = 0.5 * (a + b) + 0.5 * (b - a) * z;
+    w[(size_t)i] = w[(size_t)(n - 1 - i)] = 0.5 * (b - a) * wi;
+  }
+}
+
+// rho_dh(mu_i) = (1/pi) int R mu_r dOmega: Gauss in mu_r on [0, mu_min], [mu_min, mu_i], [mu_i, 1] (R has kinks at the clamp and,
+// through the hot spot, at mu_r = mu_i) and Gauss in the relative azimuth on [0, pi] (R is symmetric about the principal plane)
+constexpr int kAlbedoNodesMu = 96, kAlbedoNodesPhi = 128;
+
+double brdf_albedo_of(int kind, const float *q, double mu_i) {
+  if (kind == mcbrat::BRDF_LAMBERTIAN) return (double)q[0];
+  static thread_local std::vector<double> px, pw;
+  if (px.empty()) gauss_legendre(kAlbedoNodesPhi, 0.0, 3.14159265358979323846, px, pw);
+  const double si = std::sqrt(std::max(0.0, 1.0 - mu_i * mu_i));
+  double cuts[4] = {0.0, mcbrat::kBrdfMuMin, mu_i, 1.0};
+  std::sort(cuts, cuts + 4);
+  std::vector<double> mx, mw;
+  double tot = 0.0;
+  for (int s = 0; s < 3; ++s) {
+    if (!(cuts[s + 1] > cuts[s])) continue;
+    gauss_legendre(kAlbedoNodesMu, cuts[s], cuts[s + 1], mx, mw);
+    for (size_t j = 0; j < mx.size(); ++j) {
+      const double mr = mx[j], sr = std::sqrt(std::max(0.0, 1.0 - mr * mr));
+      double acc = 0.0;
+      for (size_t k = 0; k < px.size(); ++k)  // d_in along +x going down; phi = 0: d_out straight back (-x, up)
+        acc += pw[k] * (double)mcbrat::brdf_reflectance(kind, q, si, 0.0, -mu_i, -sr * std::cos(px[k]), sr * std::sin(px[k]), mr);
+      tot += 2.0 * (acc / 3.14159265358979323846) * mr * mw[j];
+    }
+  }
+  return tot;
+}
+
+}  // namespace
+
+namespace mcbrat {
+// the parameter domains and the energy rule of set_surface_brdf and the Python mirror; null when q is allowed
+const char *brdf_param_error(int kind, const float *q) {
+  if (kind == BRDF_RPV) {
+    if (!(q[0] >= 0.f && q[0] <= 1.f && q[1] >= 0.2f && q[1] <= 2.f && std::fabs(q[2]) <= 0.95f && q[3] >= 0.f && q[3] <= 1.f))
+      return "new_SurfaceDescription: RPV parameters must satisfy 0 <= rho0 <= 1, 0.2 <= k <= 2, |Theta| <= 0.95, 0 <= rhoC <= 1";
+  } else if (kind == BRDF_ROSSLI) {
+    if (!(q[0] >= 0.f && q[1] >= 0.f && q[2] >= 0.f)) return "new_SurfaceDescription: Ross-Li kernel weights must not be negative";
+  } else {
+    return "new_SurfaceDescription: unknown surface BRDF model";
+  }
+  for (int i = 1; i <= kBrdfAlbedoGrid; ++i)
+    if (!(brdf_albedo_of(kind, q, (double)i / kBrdfAlbedoGrid) <= 1.0 + 1e-3))
+      return "new_SurfaceDescription: surface reflects more energy than it receives (directional-hemispherical albedo above 1)";
+  return nullptr;
+}
+}  // namespace mcbrat
+
+extern "C" float mcbrat_brdf_reflectance(int32_t kind, const float *params, const double *dIn, const double *dOut) {
+  if (!params || !dIn || !dOut || mcbrat::brdf_num_params(kind) == 0) return NAN;
+  float q[mcbrat::kBrdfMaxParams] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < mcbrat::brdf_num_params(kind); ++i) q[i] = params[i];
+  return mcbrat::brdf_reflectance(kind, q, dIn[0], dIn[1], dIn[2], dOut[0], dOut[1], dOut[2]);
+}
+
+extern "C" double mcbrat_brdf_albedo(int32_t kind, const float *params, double muIn) {
+  if (!params || mcbrat::brdf_num_params(kind) == 0 || !(muIn > 0.0 && muIn <= 1.0)) return NAN;
+  float q[mcbrat::kBrdfMaxParams] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < mcbrat::brdf_num_params(kind); ++i) q[i] = params[i];
+  return brdf_albedo_of(kind, q, muIn);
 }

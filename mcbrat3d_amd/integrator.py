@@ -192,8 +192,14 @@ class Integrator:
             if not (hasattr(surfaceBDRF, "isReady_surfaceDescription") and surfaceBDRF.isReady_surfaceDescription()):
                 raise McbratError("specifyParameters: surface description isn't valid.")
             x, y = surfaceBDRF.xPosition, surfaceBDRF.yPosition
-            refl = np.ascontiguousarray(surfaceBDRF.BRDFParameters[0].T, np.float32)  # x fastest
-            self._check(self._lib.mcbrat_set_surface_description(self._ctx, int(x.size), int(y.size), ptr(x), ptr(y), ptr(refl)))
+            kind = getattr(surfaceBDRF, "kind", 0)
+            if kind == 0:
+                refl = np.ascontiguousarray(surfaceBDRF.BRDFParameters[0].T, np.float32)  # x fastest
+                self._check(self._lib.mcbrat_set_surface_description(self._ctx, int(x.size), int(y.size), ptr(x), ptr(y), ptr(refl)))
+            else:  # RPV, Ross-Li: [nParams][numY-1][numX-1], x fastest
+                q = np.ascontiguousarray(np.transpose(surfaceBDRF.BRDFParameters, (0, 2, 1)), np.float32)
+                self._check(self._lib.mcbrat_set_surface_brdf(self._ctx, int(kind), int(x.size), int(y.size), ptr(x), ptr(y),
+                                                              int(q.shape[0]), ptr(q)))
             self.useSurfaceBDRF = True
             self.surfaceBDRF = surfaceBDRF
         for k, v in unsupported.items():
