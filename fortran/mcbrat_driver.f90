@@ -11,7 +11,7 @@
 ! (Domain-Files/i3rcStepCloud.f95, planeParallel.f95) or a flat binary written by
 ! mcbrat3d_amd.flatdomain.write_flat_domain (any domain the Python host layer can build).
 program mcbrat_driver
-  use mcbrat_hip_integrator
+  use mcbrat_hip_integrator, lastBatchLevelFluxes => reportLevelFluxes   ! (the /output/ namelist has a variable of that name)
   implicit none
   ! --- namelist variables (names and defaults of the reference driver) ---
   real     :: solarMu = 1., solarAzimuth = 0., LW_flag = -1.
@@ -34,6 +34,7 @@ program mcbrat_driver
   logical  :: reportVolumeAbsorption = .false., reportAbsorptionProfile = .false.
   logical  :: recScatOrd = .false.
   integer  :: numRecScatOrd = 0
+  logical  :: reportLevelFluxes = .false.
   character(len=256) :: auxhist01_radFile = "", auxhist01_fluxFile = ""
   character(len=256) :: solarSourceFile = "", instrResponseFile = "", physDomainFile = ""
   character(len=256), dimension(4) :: SSPfilename = ""
@@ -47,7 +48,7 @@ program mcbrat_driver
                                useRussianRouletteForIntensity, zetaMin, limitIntensityContributions, &
                                maxIntensityContribution
   namelist /output/            reportVolumeAbsorption, reportAbsorptionProfile, recScatOrd, numRecScatOrd, &
-                               auxhist01_fluxFile, auxhist01_radFile
+                               reportLevelFluxes, auxhist01_fluxFile, auxhist01_radFile
   namelist /fileNames/         solarSourceFile, instrResponseFile, SSPfilename, physDomainFile, &
                                outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, &
                                outputNetcdfFile
@@ -62,7 +63,8 @@ program mcbrat_driver
   real,    allocatable :: table(:,:)
   real(8), allocatable :: moments(:)
   real(8), allocatable :: meanStats(:,:), fluxUpStats(:,:,:), fluxDownStats(:,:,:), fluxAbsorbedStats(:,:,:), &
-                          absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:)
+                          absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:), &
+                          meanLevelStats(:,:,:)
   real,    allocatable :: forwardTable(:,:), legendreCoefficients(:)
   integer :: numRadDir, off
   logical :: computeIntensity
@@ -109,6 +111,10 @@ program mcbrat_driver
     call specifyScatteringOrders(mcIntegrator, numRecScatOrd, ierr); call check("specifyParameters")
   else
     numRecScatOrd = -1
+  end if
+  ! flux through every level of every column (refused together with intensity directions and scattering orders)
+  if (reportLevelFluxes) then
+    call specifyLevelFluxes(mcIntegrator, .true., ierr); call check("specifyParameters")
   end if
   call setSolarSource(mcIntegrator, solarMu, solarAzimuth, ierr); call check("setSolarSource")
   call resetMoments(mcIntegrator, ierr); call check("resetMoments")
@@ -158,6 +164,22 @@ program mcbrat_driver
     do i = 0, numRecScatOrd
       print '(A,I3,A,2(2X,F9.6,A,F9.6))', " order ", i, " mean flux up/down:", meanByScatOrdStats(i, 1, 1), " +-", &
             meanByScatOrdStats(i, 1, 2), meanByScatOrdStats(i, 2, 1), " +-", meanByScatOrdStats(i, 2, 2)
+    end do
+  end if
+  if (reportLevelFluxes) then   ! domain-mean fluxes through every level: the moment tail's first 2 (nz+1) entries
+    allocate(meanLevelStats(0:nz, 2, 2))
+    off = int(M) - 2*(nz+1)*(1+ncol)
+    do k = 1, 2
+      do j = 1, 2
+        meanLevelStats(:, j, k) = moments(8 + (k-1)*M + off + (j-1)*(nz+1) + 1 : 8 + (k-1)*M + off + j*(nz+1))
+      end do
+    end do
+    do j = 1, 2
+      call momentsToStats1(meanLevelStats(:, j, :))
+    end do
+    do i = nz, 0, -1
+      print '(A,I3,A,F9.4,A,2(2X,F9.6,A,F9.6))', " level ", i, " z ", zPosition(i+1), " mean flux up/down:", &
+            meanLevelStats(i, 1, 1), " +-", meanLevelStats(i, 1, 2), meanLevelStats(i, 2, 1), " +-", meanLevelStats(i, 2, 2)
     end do
   end if
   if (len_trim(outputFluxFile) > 0) call writeFluxASCII()

@@ -30,7 +30,7 @@ module mcbrat_hip_integrator
             inverseTableLegendre, lastTraceMilliseconds, setAsynchronous, synchronize, &
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
             setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
-            specifyScatteringOrders, reportResultsByScatOrd
+            specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -197,6 +197,17 @@ module mcbrat_hip_integrator
         bind(C, name="mcbrat_report_scattering_orders") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, mUp, mDown, fUp, fDown, mI, inten   ! (c_null_ptr: not wanted)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_specify_level_fluxes(ctx, enable) bind(C, name="mcbrat_specify_level_fluxes") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: enable
+      integer(c_int) :: rc
+    end function
+    function mcbrat_report_level_fluxes(ctx, mUp, mDown, fUp, fDown) bind(C, name="mcbrat_report_level_fluxes") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, mUp, mDown, fUp, fDown   ! (c_null_ptr: not wanted)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -618,6 +629,45 @@ contains
     end if
     ierr = mcbrat_report_scattering_orders(this%ctx, mUp, mDown, fUp, fDown, mI, inten)
   end subroutine reportResultsByScatOrd
+
+  ! specifyParameters(recLevelFluxes): upward and downward flux through every level (z face) of every column.  Refused together
+  ! with intensity directions, scattering orders and BRDF surfaces.  Changes momentsLength().
+  subroutine specifyLevelFluxes(this, enable, ierr)
+    type(integrator), intent(inout) :: this
+    logical,          intent(in)    :: enable
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_specify_level_fluxes(this%ctx, merge(1_c_int32_t, 0_c_int32_t, enable))
+  end subroutine specifyLevelFluxes
+
+  ! the last batch's level fluxes: meanLevelFlux*(0:numZ), levelFlux*(numX, numY, 0:numZ); level 0 is the surface, numZ the top
+  subroutine reportLevelFluxes(this, meanLevelFluxUp, meanLevelFluxDown, levelFluxUp, levelFluxDown, ierr)
+    type(integrator), intent(inout) :: this
+    real, dimension(0:),       contiguous, optional, target, intent(out) :: meanLevelFluxUp, meanLevelFluxDown
+    real, dimension(:, :, 0:), contiguous, optional, target, intent(out) :: levelFluxUp, levelFluxDown
+    integer,                   intent(out) :: ierr
+    type(c_ptr) :: mUp, mDown, fUp, fDown
+    integer :: n
+    n = this%numZ + 1
+    mUp = c_null_ptr; mDown = c_null_ptr; fUp = c_null_ptr; fDown = c_null_ptr
+    ierr = 2   ! "reportResults: levelFlux... is the wrong size"
+    if (present(meanLevelFluxUp)) then
+      if (size(meanLevelFluxUp) /= n) return
+      mUp = c_loc(meanLevelFluxUp)
+    end if
+    if (present(meanLevelFluxDown)) then
+      if (size(meanLevelFluxDown) /= n) return
+      mDown = c_loc(meanLevelFluxDown)
+    end if
+    if (present(levelFluxUp)) then
+      if (any(shape(levelFluxUp) /= (/ this%numX, this%numY, n /))) return
+      fUp = c_loc(levelFluxUp)
+    end if
+    if (present(levelFluxDown)) then
+      if (any(shape(levelFluxDown) /= (/ this%numX, this%numY, n /))) return
+      fDown = c_loc(levelFluxDown)
+    end if
+    ierr = mcbrat_report_level_fluxes(this%ctx, mUp, mDown, fUp, fDown)
+  end subroutine reportLevelFluxes
 
   integer(8) function numBadPhotons(this)
     type(integrator), intent(in) :: this

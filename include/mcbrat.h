@@ -184,6 +184,23 @@ int mcbrat_report_scattering_orders(mcbrat_ctx *ctx, float *meanFluxUpByScatOrd,
                                     float *fluxUpByScatOrd, float *fluxDownByScatOrd,
                                     float *meanIntensityByScatOrd, float *intensityByScatOrd);
 
+/* Upward and downward flux through every level of every column (specifyParameters(recLevelFluxes); an addition under ABI
+ * version 3).  Level k = 0 .. nz is the face zPosition[k]: 0 the surface, nz the top.  A photon that
+ * crosses level k adds its weight to levelFluxUp(x, y, k) or levelFluxDown(x, y, k) of the column it crosses in.  The launch of
+ * a solar photon counts as a downward crossing of level nz (weight 1), a top exit as an upward one (the fluxUp deposit), a
+ * surface arrival as a downward crossing of level 0 (the fluxDown deposit, before the albedo), the reflected photon as an
+ * upward one with the reflected weight, a surface-emitted thermal photon as an upward one with weight 1.  Normalised as
+ * fluxUp; levelFluxUp(:, :, nz) = fluxUp and levelFluxDown(:, :, 0) = fluxDown bit for bit.  Such runs use the face-by-face
+ * walk: no layer skipping, no clear-air flight, no block walk (mcbrat_get_walk_mode reports it).  Fails together with
+ * intensity directions, scattering orders, a BRDF surface, event counters / photon fates, and where one batch's level bins
+ * would not fit the tally budget -- whichever call comes first.  Changes mcbrat_moments_length(): a caller-bound moment
+ * buffer must be bound again. */
+int mcbrat_specify_level_fluxes(mcbrat_ctx *ctx, int32_t enable);
+/* The LAST batch, Fortran order with the level slowest: meanLevelFlux*(0:nz), levelFlux*(nx, ny, 0:nz).  Domain means are
+ * sums over the columns divided by their number.  Any pointer may be NULL. */
+int mcbrat_report_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxUp, float *meanLevelFluxDown, float *levelFluxUp,
+                               float *levelFluxDown);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:
@@ -194,7 +211,9 @@ int mcbrat_report_scattering_orders(mcbrat_ctx *ctx, float *meanFluxUpByScatOrd,
  *   intensity[nDirections*nx*ny] (RadianceStats, monteCarloDriver.f95:1047-1050),
  *   and with scattering orders (N = numRecScatOrd): meanFluxUpByScatOrd[N+1], meanFluxDownByScatOrd[N+1],
  *   fluxUpByScatOrd[(N+1)*nx*ny], fluxDownByScatOrd[(N+1)*nx*ny], meanIntensityByScatOrd[(N+1)*nDirections],
- *   intensityByScatOrd[(N+1)*nDirections*nx*ny] (order slowest, x fastest).
+ *   intensityByScatOrd[(N+1)*nDirections*nx*ny] (order slowest, x fastest),
+ *   and with level fluxes, after everything else: meanLevelFluxUp[nz+1], meanLevelFluxDown[nz+1],
+ *   levelFluxUp[(nz+1)*nx*ny], levelFluxDown[(nz+1)*nx*ny] (level slowest, x fastest).
  * Total doubles = 8 + 2*length.  The buffer is device memory; a caller that
  * wants to all-reduce it with RCCL binds its own device buffer. */
 int64_t mcbrat_moments_length(const mcbrat_ctx *ctx);

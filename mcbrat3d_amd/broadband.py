@@ -95,6 +95,8 @@ class SpectralRun:
         if parameters.get("recScatOrd") or (parameters.get("numRecScatOrd") is not None and parameters["numRecScatOrd"] >= 0):
             raise McbratError("SpectralRun: fluxes and radiances by scattering order (recScatOrd) are not available for "
                               "spectrally integrated runs")
+        if parameters.get("recLevelFluxes"):
+            raise McbratError("SpectralRun: level fluxes (recLevelFluxes) are not available for spectrally integrated runs")
         if getattr(parameters.get("surfaceBDRF"), "kind", 0) != 0:
             raise McbratError("SpectralRun: BRDF surfaces (RPV, Ross-Li) are not available for spectrally integrated runs: "
                               "their parameters do not vary with wavelength and the thermal source cannot use them")

@@ -121,6 +121,8 @@ struct mcbrat_ctx {
   float zetaMin = 0.3f, maxContrib = FLT_MAX;
   // fluxes and radiances by scattering order (mcbrat_specify_scattering_orders): highest order recorded, -1 off
   int numRecScatOrd = -1;
+  // upward and downward flux through every level of every column (mcbrat_specify_level_fluxes)
+  int levelFluxes = 0;
   // parameters
   float albedo = 0.f;
   int useRR = 1;
@@ -249,24 +251,42 @@ int upload(mcbrat_ctx *c, T **dst, const T *src, size_t n) {
 
 bool orders_on(const mcbrat_ctx *c) { return c->numRecScatOrd >= 0; }
 
-// [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest
+bool levels_on(const mcbrat_ctx *c) { return c->levelFluxes != 0; }
+// bins of one batch's level fluxes: [levelUp ncol (nz+1) | levelDown ncol (nz+1)], level slowest
+size_t level_bins(const mcbrat_ctx *c) { return levels_on(c) ? 2 * (size_t)c->nx * c->ny * ((size_t)c->nz + 1) : 0; }
+
+// [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest,
+// then the level fluxes: [meanLevelUp (nz+1) | meanLevelDown (nz+1) | levelUp ncol (nz+1) | levelDown ncol (nz+1)]
 long long moments_len(const mcbrat_ctx *c) {
   const long long ncol = (long long)c->nx * c->ny;
   return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol +
-         (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0);
+         (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0) +
+         (levels_on(c) ? 2LL * (c->nz + 1) * (1 + ncol) : 0);
 }
 
 // Elements of one batch's tally slab: [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:)
-// intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1)]
+// intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1) |
+// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1)]
 // fluxRun: the slab of a flux launch of the loaded domain (no intensity parts), what mcbrat_get_walk_mode reports on.
 size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz, nDir = fluxRun ? 0 : (size_t)c->nDir;
   return 2 * ncol + nvox + nDir * ncol + (c->limitContrib && !fluxRun ? (size_t)(c->nc + 1) * nDir * (ncol + 1) : 0) +
-         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0);
+         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0) + level_bins(c);
 }
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
 constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
 // The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
+// Level fluxes are tallied by the general flux kernels on the face-by-face walk only: what they are refused with
+const char *const kLevelsIntensityMsg =
+    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with intensity directions: the radiance kernels have no level tallies.";
+const char *const kLevelsOrdersMsg =
+    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with scattering orders (recScatOrd): no kernel tallies both.";
+const char *const kLevelsBrdfMsg =
+    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with a BRDF surface: a reflected weight may exceed 1, which the level tallies do not hold.";
+const char *const kLevelsCountersMsg =
+    "specifyParameters: level fluxes (recLevelFluxes) are not available together with event counters / photon fates: the instrumented kernels have no level tallies.";
+const char *const kLevelsBudgetMsg =
+    "specifyParameters: level fluxes (recLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
 const char *const kOrdersLimitMsg =
     "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
     "redistribution adds each direction's clipped excess to every order, which would count it numRecScatOrd + 1 times.";
@@ -493,7 +513,7 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
 // dense grid is as fast or 1-3 % faster, so the automatic rule only switches
 // for grids of 64 MiB and more.
 bool use_bricks(const mcbrat_ctx *c) {
-  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0 || orders_on(c)) return false;  // (radiance rays read the dense grid; no ORD kernel reads bricks)
+  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0 || orders_on(c) || levels_on(c)) return false;  // (radiance rays read the dense grid; no ORD or LVL kernel reads bricks)
   if (c->brickMode == 1) return true;
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   // automatic: the dense layout is the faster one wherever measured (128x128x64: equal; 512x512x128: 83 vs 105 ms per
@@ -518,7 +538,7 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.xyRegularWalk = (c->xyRegular && c->regularWalk) ? 1 : 0;
   p.zRegularWalk = (c->zRegular && c->regularWalk) ? 1 : 0;
   p.dXf = (float)((p.xMax - p.x0) / c->nx); p.dYf = (float)((p.yMax - p.y0) / c->ny); p.dZf = (float)((p.zMax - p.z0) / c->nz);
-  p.layerSkip = c->layerSkip ? 1 : 0;
+  p.layerSkip = (c->layerSkip && !levels_on(c)) ? 1 : 0;  // (level fluxes: every z face is a stop)
   p.layerRun = c->dLayerRun; p.layerRunT = c->dLayerRunT;
   p.fly = 0; p.flyNbx = p.flyNby = 0;  // (switched on by launch_trace where the plan allows it)
   p.flyRange = c->dFlyRange; p.bgVal = c->dBgVal;
@@ -603,7 +623,7 @@ size_t per_layer_lds(int nz, int flyCols = 0) {
 
 // clear-air flight: asked for (layerSkip 1: where the background is thin enough for it to pay; 3: regardless) and possible
 bool flight_wanted(const mcbrat_ctx *c) {
-  return c->flyBuilt && (c->layerSkip == 3 || (c->layerSkip == 1 && c->flyDepth <= c->flightMaxDepth));
+  return !levels_on(c) && c->flyBuilt && (c->layerSkip == 3 || (c->layerSkip == 1 && c->flyDepth <= c->flightMaxDepth));
 }
 
 struct LaunchPlan {
@@ -622,7 +642,7 @@ struct LaunchPlan {
 };
 
 bool blocks_worth_it(const mcbrat_ctx *c) {
-  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c)) return false;  // (the block walk has no ORD variant)
+  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c) || levels_on(c)) return false;  // (the block walk has no ORD or LVL variant)
   if (c->surfNumX > 0 && c->surfKind != 0) return false;  // (nor a BRDF one: such surfaces go face by face)
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   return (size_t)c->nBlocks * 4 <= nvox || c->blockWalk == 2;  // (2: forced, for tests of heterogeneous media)
@@ -633,7 +653,7 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.wide = false; L.blockLite = false; L.optics = 0; L.cdfTop = false;
   const size_t edges = sizeof(double) * (size_t)(c->nx + c->ny + c->nz + 3);
   const size_t tbl = sizeof(float) * (size_t)c->tblTotalFloats;
-  const size_t slab = sizeof(long long) * slabStride + 16;
+  const size_t slab = sizeof(long long) * (slabStride - level_bins(c)) + 16;  // (the level bins are never part of the LDS slab)
   L.priv = c->privMode != 0 && slab <= kPrivSlabLimit;
   L.brick = use_bricks(c);
   const size_t bg = per_layer_lds(c->nz);  // per-layer extinction (background / one-extinction layers) and the runs of such layers
@@ -649,10 +669,16 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
     L.tblLds = false;
     L.gridLds = true;
   }
+  // level fluxes: the LVL kernels are built for everything in LDS (PRIV = 2) and for global atomics (PRIV = 0); private tallies
+  // beside a grid in global memory give way to the latter
+  if (levels_on(c) && L.priv && !L.gridLds) {
+    L.priv = false;
+    L.tblLds = tbl <= kTableLdsLimit && edges + bg + tbl <= kLdsBudget;
+  }
   L.lds = edges + bg + (L.priv ? slab : 0) + (L.gridLds ? grid : 0) + (L.tblLds ? tbl : 0);
   // the wide plan: the slab did not fit beside another workgroup, but it fits a compute unit
   const size_t cuLds = c->ldsPerCU > kStaticLds ? c->ldsPerCU - kStaticLds : 0;
-  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !orders_on(c) && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
+  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !orders_on(c) && !levels_on(c) && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
     L.wide = true; L.priv = true; L.fly = false;
     size_t need = edges + bg + slab;
     L.tblLds = need + tbl <= cuLds;
@@ -677,6 +703,7 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.fly = flight_wanted(c) && !L.gridLds && !L.brick && c->nDir == 0 && L.lds + flyLds <= kLdsBudget;
   if (L.fly) L.lds += flyLds;
   L.block = c->blockSize > 0 ? c->blockSize : (L.gridLds ? 768 : ((L.tblLds || L.priv) && L.lds > 16 * 1024 ? 512 : 256));
+  if (levels_on(c) && L.block > 512) L.block = 512;  // (no 768-lane LVL kernel)
   if (blocks_worth_it(c) && L.priv && L.gridLds && c->srcKind != 0)
     L.cdfTop = block_lds_layout(c->nx, c->ny, c->nz, c->nc, slabStride, c->nBlocks, L.tblLds ? (size_t)c->tblTotalFloats : 0, 0, true).total <= kLdsBudget;
   // fill_params chose the brick arrays: private tallies give way.  Decided last, so that tblLds, block and cdfTop stay
@@ -775,6 +802,20 @@ const void *trace_ptr(bool tbl, bool emit) {
   }
   if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
   return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
+}
+
+// the LVL instantiations (level fluxes): BLOCK 256 / 512 x PRIV 0 / 2 x table x source -- 16 kernels
+template <int BLOCK, int PRIV>
+const void *trace_ptr_lvl(bool tbl, bool emit) {
+  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, true, 0, false, false, true>
+                       : (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true>;
+  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, true, 0, false, false, true>
+              : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true>;
+}
+template <int BLOCK>
+const void *trace_kernel_lvl(const mcbrat_ctx *c, const LaunchPlan &L) {
+  const bool emit = c->srcKind != 0;
+  return (L.priv && L.gridLds) ? trace_ptr_lvl<BLOCK, 2>(L.tblLds, emit) : trace_ptr_lvl<BLOCK, 0>(L.tblLds, emit);
 }
 
 // the ORD instantiations (scattering orders): BLOCK 256 / 512 x PRIV 0 / 1 / 2 x INTEN x table x source, dense grids, not instrumented
@@ -902,6 +943,9 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   if (block_walk_applies(c, L)) return launch_block(c, p, L, debug, nBatches);
   const bool tbl = L.tblLds, emit = c->srcKind != 0;
   const bool brdf = p.surfKind != 0;
+  const bool lvl = levels_on(c);
+  if (lvl && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
+    return fail(c, debug ? kLevelsCountersMsg : (brdf ? kLevelsBrdfMsg : (c->nDir > 0 ? kLevelsIntensityMsg : kLevelsOrdersMsg)));
   if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
   const void *kernel;
   int block;
@@ -910,7 +954,7 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
     block = 1024;
     if (brdf) kernel = L.gridLds ? trace_ptr<1024, 2, false, false, false, false, true>(tbl, false) : trace_ptr<1024, 1, false, false, false, false, true>(tbl, false);
     else kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
-  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0) {
+  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0 && !lvl) {
     // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
     // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
     // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
@@ -934,7 +978,8 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
       p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
       lds = base + waves * cap * 80;
     }
-    if (brdf) kernel = block == 512 ? trace_kernel_brdf<512>(c, L) : trace_kernel_brdf<256>(c, L);
+    if (lvl) kernel = block == 512 ? trace_kernel_lvl<512>(c, L) : trace_kernel_lvl<256>(c, L);
+    else if (brdf) kernel = block == 512 ? trace_kernel_brdf<512>(c, L) : trace_kernel_brdf<256>(c, L);
     else if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
       if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with scattering orders.");
       kernel = block == 512 ? trace_kernel_ord<512>(c, L) : trace_kernel_ord<256>(c, L);
@@ -952,6 +997,12 @@ int check_ready(mcbrat_ctx *c) {
   if (!c->haveSource) return fail(c, "computeRadiativeTransfer: no photon source set.");
   if (c->surfNumX > 0 && c->surfKind != 0 && c->srcKind != 0)
     return fail(c, "computeRadiativeTransfer: a BRDF surface cannot be used with the thermal source (its emissivity would be 1 - rho_dh(mu)).");
+  if (levels_on(c)) {  // (each is also refused where it is asked for, whichever call comes first)
+    if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
+    if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
+    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
+    if (level_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, kLevelsBudgetMsg);
+  }
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
 }
@@ -1086,6 +1137,7 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   for (int i = 0; i < ny; ++i) if (!(ye[i + 1] > ye[i])) return fail(c, "new_Domain: y edges must be increasing, unique.");
   for (int i = 0; i < nz; ++i) if (!(ze[i + 1] > ze[i])) return fail(c, "new_Domain: z edges must be increasing, unique.");
   if ((long long)nx * ny * nz > 0x7fffffffLL / 2) return fail(c, "new_Integrator: more than 2^30 cells are not supported.");
+  if (levels_on(c) && 2.0 * (double)nx * ny * ((double)nz + 1.0) * sizeof(long long) > (double)kSlabBudget) return fail(c, kLevelsBudgetMsg);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1327,6 +1379,7 @@ int mcbrat_get_moments(mcbrat_ctx *c, double *host) {
 
 int mcbrat_enable_counters(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
+  if (enable && levels_on(c)) return fail(c, kLevelsCountersMsg);
   c->countersOn = enable != 0;
   return 0;
 }
@@ -1372,6 +1425,7 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
     return fail(c, "specifyParameters: maxIntensityContribution must be > 0");
   if (zetaMin < 0.f) return fail(c, "specifyParameters: zetaMin must be >= 0.");
   if (limitIntensityContributions && orders_on(c)) return fail(c, kOrdersLimitMsg);
+  if (nDirections > 0 && levels_on(c)) return fail(c, kLevelsIntensityMsg);
   if (numOrdersOrigPhaseFunIntenCalcs < 0) return fail(c, "specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0");
   if (useRussianRouletteForIntensity)
     for (int i = 0; i < nDirections; ++i)
@@ -1414,6 +1468,7 @@ int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int n = numRecScatOrd < 0 ? -1 : numRecScatOrd;
   if (n >= 0 && c->limitContrib) return fail(c, kOrdersLimitMsg);
+  if (n >= 0 && levels_on(c)) return fail(c, kLevelsOrdersMsg);
   if (n >= 0) {  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
     const size_t ncol = (size_t)c->nx * c->ny;
     if ((double)(n + 1) * (2 + c->nDir) * ncol * sizeof(long long) > (double)kSlabBudget)
@@ -1453,6 +1508,50 @@ int mcbrat_report_scattering_orders(mcbrat_ctx *c, float *meanFluxUpByScatOrd, f
   take(fluxDownByScatOrd, ncol * nOrd);
   take(meanIntensityByScatOrd, nDir * nOrd);
   take(intensityByScatOrd, ncol * nDir * nOrd);
+  return 0;
+}
+
+int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
+  const int on = enable ? 1 : 0;
+  if (on) {
+    if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
+    if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
+    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
+    if (c->countersOn) return fail(c, kLevelsCountersMsg);
+    if (2.0 * (double)c->nx * c->ny * ((double)c->nz + 1.0) * sizeof(long long) > (double)kSlabBudget) return fail(c, kLevelsBudgetMsg);
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (on != c->levelFluxes) {  // the moment arrays change length: start them afresh (as mcbrat_specify_scattering_orders does)
+    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+    c->dMoments = nullptr;
+    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+    c->haveLast = false;
+    c->tuned = false;  // (another walk, other kernels: the event threshold is chosen again)
+  }
+  c->levelFluxes = on;
+  return 0;
+}
+
+int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *meanLevelFluxDown, float *levelFluxUp, float *levelFluxDown) {
+  if (!c) return 1;
+  if (!levels_on(c)) return fail(c, "reportResults: level-flux information not available");
+  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  // the tail of the last batch's results: [meanUp | meanDown | up | down], already in Fortran order (nx, ny, 0:nz)
+  const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;
+  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_len(c) - n;
+  std::vector<float> h(n);
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * n, hipMemcpyDeviceToHost));
+  const float *q = h.data();
+  const auto take = [&](float *dst, size_t m) { if (dst) std::memcpy(dst, q, sizeof(float) * m); q += m; };
+  take(meanLevelFluxUp, nLvl);
+  take(meanLevelFluxDown, nLvl);
+  take(levelFluxUp, ncol * nLvl);
+  take(levelFluxDown, ncol * nLvl);
   return 0;
 }
 
@@ -1620,6 +1719,7 @@ int mcbrat_set_surface_brdf(mcbrat_ctx *c, int32_t kind, int32_t numX, int32_t n
   if (sync_all(c)) return 1;
   if (numX <= 0 || numY <= 0) { c->surfNumX = c->surfNumY = 0; c->surfKind = 0; return 0; }  // back to the domain's albedo
   if (brdf_num_params(kind) == 0 || kind == BRDF_LAMBERTIAN) return fail(c, "new_SurfaceDescription: unknown surface BRDF model.");
+  if (levels_on(c)) return fail(c, kLevelsBrdfMsg);
   if (nParams != brdf_num_params(kind)) return fail(c, "new_SurfaceDescription: Wrong number of parameters supplied for surface BRDF.");
   if (numX < 2 || numY < 2 || !xPosition || !yPosition || !params)
     return fail(c, "new_SurfaceDescription: position vector(s) are incorrect length.");
@@ -1722,7 +1822,7 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   if (c->haveGrid && c->haveOptics) {  // what a flux launch of the loaded domain would do (the plan decides, as launch_trace does)
     // (the flux run's slab: with scattering orders its order bins too, so that private tallies give way where they no longer fit)
     const LaunchPlan L = plan_launch(c, slab_stride(c, true));
-    m = (c->layerSkip ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
+    m = ((c->layerSkip && !levels_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
   }
@@ -1756,6 +1856,8 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     return fail(c, "computeRadiativeTransfer: numRecScatOrd is too large: one batch's tallies by scattering order need more than the 4 GiB tally budget.");
   if (orders_on(c) && c->countersOn)
     return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
+  if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
+  if (levels_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, kLevelsBudgetMsg);
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
   size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
@@ -1765,7 +1867,8 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     mcbrat_ctx::Lane &L = c->lane[li];
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
     const size_t nOrdMeans = orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + c->nDir) : 0;  // (domain means by order, behind the scalars)
-    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans) * inFlight;
+    const size_t nLvlMeans = levels_on(c) ? 2 * ((size_t)c->nz + 1) : 0;  // (domain means by level, behind those)
+    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans + nLvlMeans) * inFlight;
     if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
     HIP_OK(c, hipStreamSynchronize(L.stream));
     if (L.slabCapacity < needSlab) {
@@ -1843,11 +1946,17 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.gatherOrders = (unsigned)(((size_t)(2 + c->nDir) * ncol * f.nOrd + kFinishBlock - 1) / kFinishBlock);
     f.gatherOrderMeans = (unsigned)((2 + c->nDir) * f.nOrd) * (unsigned)nb;
     f.foldOrderMeans = (unsigned)(((2 + c->nDir) * f.nOrd + kFinishBlock - 1) / kFinishBlock);
+    f.nLvl = levels_on(c) ? c->nz + 1 : 0;
+    f.lvlSlab = (long long)(slabStride - level_bins(c));
+    f.lvlVals = f.ordVals + (size_t)((2 + c->nDir) * f.nOrd) * nb;
+    f.gatherLevels = (unsigned)((2 * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
+    f.gatherLevelMeans = (unsigned)(2 * f.nLvl) * (unsigned)nb;
+    f.foldLevelMeans = (unsigned)((2 * f.nLvl + kFinishBlock - 1) / kFinishBlock);
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans),
+    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans),
                        dim3(kFinishBlock), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
+    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
     c->lastDone = c->L().evDone;
@@ -1910,6 +2019,7 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
   if (n < 1 || !fates) return fail(c, "trace_fates: nothing to trace.");
   if (sync_all(c)) return 1;
   if (c->nDir > 0) return fail(c, "trace_fates: not available together with intensity directions.");
+  if (levels_on(c)) return fail(c, kLevelsCountersMsg);
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
   const size_t slabStride = 2 * ncol + nvox;
   long long *scratch = nullptr;

@@ -30,21 +30,27 @@ def balanced_job(totalPhotons, numBatches, world):
     return ppb, nb
 
 
-def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1):
+def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False):
     """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order.
 
     With scattering orders (numRecScatOrd >= 0) the arrays end in the order tail of include/mcbrat.h, unpacked with the order
     as the LAST index, as the reference's (x, y, p) and (x, y, d, p) arrays: meanFluxUpByScatOrd[p], fluxUpByScatOrd[ix, iy, p],
     meanIntensityByScatOrd[d, p], intensityByScatOrd[ix, iy, d, p].  nDirections must then be given: the length no longer
-    tells it."""
+    tells it.
+
+    With level fluxes (levelFluxes=True) the arrays end in the level tail: meanLevelFluxUp[k], meanLevelFluxDown[k],
+    levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k], k = 0 .. nz.  The length is then checked against the layout asked for."""
     ncol, nvox = nx * ny, nx * ny * nz
     M = 3 + 3 * ncol + nz + nvox
     nOrd = int(numRecScatOrd) + 1 if numRecScatOrd is not None and int(numRecScatOrd) >= 0 else 0
+    nLvl = nz + 1 if levelFluxes else 0
     if nDirections is None:  # the length tells
         if nOrd:
             raise ValueError("unpack_moments: with numRecScatOrd >= 0 the number of directions must be given (nDirections=)")
-        nDirections = ((len(buf) - 8) // 2 - M) // ncol
-    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol)
+        nDirections = ((len(buf) - 8) // 2 - M - 2 * nLvl * (1 + ncol)) // ncol
+    if nDirections < 0:
+        raise ValueError("unpack_moments: %d doubles are too few for the layout asked for" % len(buf))
+    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol) + 2 * nLvl * (1 + ncol)
     S1, S2 = buf[8:8 + M], buf[8 + M:8 + 2 * M]
     out = {"totalPhotons": buf[0], "batches": buf[1]}
     names = [("meanFluxUp", 1, None), ("meanFluxDown", 1, None), ("meanFluxAbsorbed", 1, None),
@@ -58,7 +64,10 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1):
         if nDirections > 0:
             names += [("meanIntensityByScatOrd", nOrd * nDirections, (nOrd, nDirections)),
                       ("intensityByScatOrd", nOrd * nDirections * ncol, (nOrd, nDirections, ny, nx))]
-    if nOrd and len(buf) != 8 + 2 * M:
+    if nLvl:
+        names += [("meanLevelFluxUp", nLvl, (nLvl,)), ("meanLevelFluxDown", nLvl, (nLvl,)),
+                  ("levelFluxUp", nLvl * ncol, (nLvl, ny, nx)), ("levelFluxDown", nLvl * ncol, (nLvl, ny, nx))]
+    if (nOrd or nLvl) and len(buf) != 8 + 2 * M:
         raise ValueError("unpack_moments: %d doubles, the layout asked for has %d" % (len(buf), 8 + 2 * M))
     o = 0
     for name, n, shp in names:
@@ -167,6 +176,7 @@ def run(integrator, domain, photons, numPhotonsPerBatch, numBatches, randomNumbe
         buf = integrator.moments()
     nx, ny, nz = integrator._dims
     nOrd = getattr(integrator, "numRecScatOrd", -1)
-    if nOrd >= 0:
-        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd), solarFlux)
+    levels = bool(getattr(integrator, "recLevelFluxes", False))
+    if nOrd >= 0 or levels:
+        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels), solarFlux)
     return statistics(unpack_moments(buf, nx, ny, nz), solarFlux)

@@ -20,7 +20,8 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     "algorithms": dict(useraytracing=True, userussianroulette=True, usehybridphasefunsforintencalcs=False,
                        hybridphasefunwidth=7.0, numordersorigphasefunintencalcs=0, userussianrouletteforintensity=True,
                        zetamin=0.3, limitintensitycontributions=False, maxintensitycontribution=77.0),
-    "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False, recscatord=False, numrecscatord=0),
+    "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False, recscatord=False, numrecscatord=0,
+                   reportlevelfluxes=False),
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
 }
@@ -231,6 +232,9 @@ def main(argv=None):
         if numRecScatOrd >= 0:
             raise SystemExit("recScatOrd: fluxes and radiances by scattering order are not available for spectrally integrated "
                              "runs (numLambda > 1 or thermal emission)")
+        if cfg["reportlevelfluxes"]:
+            raise SystemExit("reportLevelFluxes: level fluxes are not available for spectrally integrated runs (numLambda > 1 "
+                             "or thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -271,6 +275,8 @@ def main(argv=None):
                                 maxIntensityContribution=cfg["maxintensitycontribution"])
     if numRecScatOrd >= 0:
         integ.specifyParameters(recScatOrd=True, numRecScatOrd=numRecScatOrd)
+    if cfg["reportlevelfluxes"]:  # (refused by specifyParameters together with intensity directions or scattering orders)
+        integ.specifyParameters(recLevelFluxes=True)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -288,6 +294,11 @@ def main(argv=None):
                 print(" order %3d mean flux up/down: %9.6f +-%9.6f  %9.6f +-%9.6f" % (
                     p, stats["meanFluxUpByScatOrd"][p], stats["meanFluxUpByScatOrd_StdErr"][p],
                     stats["meanFluxDownByScatOrd"][p], stats["meanFluxDownByScatOrd_StdErr"][p]))
+        if cfg["reportlevelfluxes"]:  # domain-mean fluxes through every level, one line per level from the top down
+            for k in range(len(dom.zPosition) - 1, -1, -1):
+                print(" level %3d z %9.4f mean flux up/down: %9.6f +-%9.6f  %9.6f +-%9.6f" % (
+                    k, dom.zPosition[k], stats["meanLevelFluxUp"][k], stats["meanLevelFluxUp_StdErr"][k],
+                    stats["meanLevelFluxDown"][k], stats["meanLevelFluxDown_StdErr"][k]))
         xe, ye, ze = dom.xPosition, dom.yPosition, dom.zPosition
         if cfg["outputfluxfile"]:
             writeResults_ASCII(cfg["outputfluxfile"], cfg, domfile, stats, xe, ye, ze, 1.0, dom.surfaceAlbedo)

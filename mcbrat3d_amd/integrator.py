@@ -75,6 +75,8 @@ class Integrator:
         # fluxes and radiances by scattering order (:1159-1171, :1293-1330): highest order recorded, -1 off
         self.recScatOrd = False
         self.numRecScatOrd = -1
+        # upward and downward flux through every level of every column
+        self.recLevelFluxes = False
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -115,7 +117,7 @@ class Integrator:
                               numOrdersOrigPhaseFunIntenCalcs=self.numOrdersOrigPhaseFunIntenCalcs,
                               limitIntensityContributions=self.limitIntensityContributions,
                               maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF,
-                              numRecScatOrd=self.numRecScatOrd)
+                              numRecScatOrd=self.numRecScatOrd, recLevelFluxes=self.recLevelFluxes)
         return new
 
     def _check(self, rc):
@@ -135,7 +137,31 @@ class Integrator:
                           useRussianRouletteForIntensity=None, zetaMin=None, useHybridPhaseFunsForIntenCalcs=None,
                           hybridPhaseFunWidth=None, numOrdersOrigPhaseFunIntenCalcs=None,
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
-                          recScatOrd=None, numRecScatOrd=None, **unsupported):
+                          recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, **unsupported):
+        # level fluxes: what they cannot be combined with is refused as the library refuses it -- here,
+        # before anything of this call is kept, so that a refused call leaves the integrator as it was
+        levels = self.recLevelFluxes if recLevelFluxes is None else bool(recLevelFluxes)
+        if levels:
+            directions = self.numIntensityDirections()
+            if intensityMus is not None:
+                directions = int(np.size(intensityMus))
+            elif computeIntensity is not None and not computeIntensity:
+                directions = 0
+            if directions > 0:
+                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with intensity directions: "
+                                  "the radiance kernels have no level tallies.")
+            wantOrders = self.numRecScatOrd >= 0
+            if numRecScatOrd is not None:
+                wantOrders = int(numRecScatOrd) >= 0
+            elif recScatOrd is not None and not recScatOrd:
+                wantOrders = False
+            if wantOrders:
+                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with scattering orders "
+                                  "(recScatOrd): no kernel tallies both.")
+            bdrf = surfaceBDRF if surfaceBDRF is not None else self.surfaceBDRF
+            if getattr(bdrf, "kind", 0) != 0:
+                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with a BRDF surface: "
+                                  "a reflected weight may exceed 1, which the level tallies do not hold.")
         # intensity keywords, :1130-1160 and :1186-1283
         if (intensityMus is None) != (intensityPhis is None):
             raise McbratError("specifyParameters: Both or neither of intensityMus, intensityPhis must be supplied")
@@ -215,6 +241,7 @@ class Integrator:
         if LW_flag is not None:
             self.LW_flag = float(LW_flag)
         self.numRecScatOrd, self.recScatOrd = orders, orders >= 0
+        self.recLevelFluxes = levels
         self._push_parameters()
 
     def _push_parameters(self):
@@ -227,7 +254,18 @@ class Integrator:
             self._param_token = token
         self._push_intensity()
 
+    def _push_levels(self):
+        if self.recLevelFluxes != getattr(self, "_levels_token", False):
+            self._check(self._lib.mcbrat_specify_level_fluxes(self._ctx, int(self.recLevelFluxes)))
+            self._levels_token = self.recLevelFluxes
+
     def _push_intensity(self):
+        if not self.recLevelFluxes:
+            self._push_levels()  # (off first: the settings below may be ones the library refuses together with level fluxes)
+        self._push_intensity_and_orders()
+        self._push_levels()
+
+    def _push_intensity_and_orders(self):
         n = int(self.intensityMus.size) if self.computeIntensity else 0
         token = (n, self.intensityMus.tobytes(), self.intensityPhis.tobytes(), self.useRussianRouletteForIntensity, self.zetaMin,
                  self.useHybridPhaseFunsForIntenCalcs, self.numOrdersOrigPhaseFunIntenCalcs, self.limitIntensityContributions,
@@ -414,6 +452,8 @@ class Integrator:
             inten = np.zeros(nd * nx * ny, np.float32)
             self._check(self._lib.mcbrat_report_intensity(self._ctx, ptr(mean_i), ptr(inten)))
             res.update(meanIntensity=mean_i, intensity=inten.reshape(nd, ny, nx).transpose(2, 1, 0))
+        if self.recLevelFluxes:
+            res.update(self.reportLevelFluxes())
         if self.numRecScatOrd >= 0:  # reportResults(...ByScatOrd) :850-864, :887-903, :1010-1040; order last, as the reference's arrays
             no = self.numRecScatOrd + 1
             mu_o, md_o = np.zeros(no, np.float32), np.zeros(no, np.float32)
@@ -429,6 +469,17 @@ class Integrator:
                 res.update(meanIntensityByScatOrd=mi_o.reshape(no, nd).T,
                            intensityByScatOrd=in_o.reshape(no, nd, ny, nx).transpose(3, 2, 1, 0))
         return res
+
+    def reportLevelFluxes(self):
+        """The last batch's upward and downward flux through every level: levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k] and
+        their domain means meanLevelFluxUp[k], meanLevelFluxDown[k]; level k = 0 .. numZ is the face zPosition[k]."""
+        nx, ny, nz = self._dims
+        nl = nz + 1
+        mu, md = np.zeros(nl, np.float32), np.zeros(nl, np.float32)
+        up, dn = np.zeros(nl * nx * ny, np.float32), np.zeros(nl * nx * ny, np.float32)
+        self._check(self._lib.mcbrat_report_level_fluxes(self._ctx, ptr(mu), ptr(md), ptr(up), ptr(dn)))
+        return dict(meanLevelFluxUp=mu, meanLevelFluxDown=md, levelFluxUp=up.reshape(nl, ny, nx).transpose(2, 1, 0),
+                    levelFluxDown=dn.reshape(nl, ny, nx).transpose(2, 1, 0))
 
     # -- batch moments (what the driver keeps in *Stats and reduces over processes) -----
     def momentsLength(self):

@@ -212,6 +212,12 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
             if intensityMus is not None and "intensityByScatOrd" in stats:
                 for name in ("intensityByScatOrd", "intensityByScatOrd_StdErr"):
                     f.createVariable(name, "f", ("numRecScatOrd", "direction", "y", "x"))[:] = np.asarray(stats[name]).transpose(3, 2, 1, 0)
+        if "levelFluxUp" in stats:  # level fluxes (reportLevelFluxes): Fortran dims (x, y, zLevel), the levels are the z edges
+            f.createDimension("zLevel", len(ze))
+            f.createVariable("zLevel", "d", ("zLevel",))[:] = ze
+            for name in ("levelFluxUp", "levelFluxDown"):
+                f.createVariable(name, "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
+                f.createVariable(name + "_StdErr", "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name + "_StdErr"]).transpose(2, 1, 0)
     finally:
         f.close()
     return outputFileName
