@@ -16,7 +16,8 @@
  * Fortran's own step-cloud outputs at 1e5 and 1e6 photons recorded in SURVEY.md section 8c / BASELINE.md, to all six
  * printed digits.  Parity unpinned (restated from the source text only, no reference output recorded): thermal
  * emission source and weighting, angle/value phase functions, irregular-grid launch, radiance by local estimation,
- * the surface description.
+ * the surface description.  Not the reference's at all: the level tallies of orc_compute_rt_levels, which restate
+ * DESIGN.md section 4.12 and are held to identities, the MT mode and transport theory by tests/test_oracle_levels.py.
  */
 #include "mcbrat_oracle.h"
 #include <float.h>
@@ -472,8 +473,23 @@ int orc_inverse_table_tabulated(int nAngles, const float *angles, const float *v
 #define IDX3(P, ix, iy, iz) ((size_t)((ix)-1) + (size_t)(P)->nx * ((size_t)((iy)-1) + (size_t)(P)->ny * (size_t)((iz)-1)))
 #define IDX4(P, ix, iy, iz, ic) (IDX3(P, ix, iy, iz) + (size_t)(P)->nx * (P)->ny * (P)->nz * (size_t)((ic)-1))
 
-float orc_accumulate_extinction(const orc_problem *P, const float dir[3], double pos[3], int32_t idx[3],
-                                int hasTarget, float extToAccumulate, int64_t *crossings) {
+/* Level tallies (not in the reference): raw sums in double, [level 0..nz][iy][ix], the number of
+ * deposits per bin, and what the walk needs to know of the photon it carries: its weight and the length of its path. */
+typedef struct {
+  double *up, *down;     /* [(nz+1)][ny][nx] */
+  int64_t *nUp, *nDown;  /* deposits per bin, same layout (may be NULL) */
+  float weight;          /* the photon's current weight */
+  double path;           /* km travelled by the photon so far */
+} level_tally;
+
+static void level_deposit(const orc_problem *P, level_tally *T, int upward, int level, int ix, int iy, float w) {
+  const size_t b = (size_t)(ix - 1) + (size_t)P->nx * ((size_t)(iy - 1) + (size_t)P->ny * (size_t)level);
+  if (upward) { T->up[b] += (double)w; if (T->nUp) T->nUp[b]++; }
+  else { T->down[b] += (double)w; if (T->nDown) T->nDown[b]++; }
+}
+
+static float accumulate_extinction(const orc_problem *P, const float dir[3], double pos[3], int32_t idx[3],
+                                   int hasTarget, float extToAccumulate, int64_t *crossings, level_tally *T) {
   const double *edge[3] = {P->xe, P->ye, P->ze};
   const int ncell[3] = {P->nx, P->ny, P->nz};
   float extAccumulated = 0.0f;
@@ -503,11 +519,14 @@ float orc_accumulate_extinction(const orc_problem *P, const float dir[3], double
         pos[1] = pos[1] + thisStep * (double)dir[1];
         pos[2] = pos[2] + thisStep * (double)dir[2];
         extAccumulated = extToAccumulate;
+        if (T) T->path += thisStep;
         break;
       }
     }
     extAccumulated = (float)((double)extAccumulated + thisStep * thisCellExt); /* :1743 */
     if (crossings) (*crossings)++;
+    const int zBefore = idx[2];
+    if (T) T->path += thisStep;
     for (int a = 0; a < 3; a++) { /* :1752-1777 */
       if (step[a] <= thisStep) {
         pos[a] = edge[a][idx[a] + side[a] - 1];
@@ -527,10 +546,19 @@ float orc_accumulate_extinction(const orc_problem *P, const float dir[3], double
         pos[a] = edge[a][0] + (double)(inc[0] * 2) * spacing_d(pos[a]);
       }
     }
+    /* section 4.12: the photon went from layer zBefore to layer idx[2] (by the step itself or by the snap of :1772) and both
+     * are inside the domain: it crossed the face between them, in the column it now holds (after any x / y change and wrap) */
+    if (T && idx[2] != zBefore && idx[2] >= 1 && idx[2] <= P->nz)
+      level_deposit(P, T, idx[2] > zBefore, idx[2] > zBefore ? zBefore : idx[2], idx[0], idx[1], T->weight);
     if (idx[2] > P->nz) { pos[2] = zMax + 2.0 * spacing_d(zMax); break; } /* :1801-1804 */
     if (idx[2] < 1) { pos[2] = z0; break; }                               /* :1809-1812 */
   }
   return extAccumulated;
+}
+
+float orc_accumulate_extinction(const orc_problem *P, const float dir[3], double pos[3], int32_t idx[3],
+                                int hasTarget, float extToAccumulate, int64_t *crossings) {
+  return accumulate_extinction(P, dir, pos, idx, hasTarget, extToAccumulate, crossings, NULL);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -923,10 +951,48 @@ int64_t orc_compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, in
                                   NULL, NULL, NULL, NULL);
 }
 
+static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
+                          float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
+                          orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
+                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace);
+
 int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
                                  float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
                                  orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
                                  float *intensityByComponent, float *intensityExcess) {
+  return compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, I, intensity,
+                    intensityByComponent, intensityExcess, NULL, NULL);
+}
+
+/* computeRT with the level tallies of DESIGN.md section 4.12 (ours, not the reference's: restated from that section's
+ * definition).  levelUp / levelDown: raw weight sums [(nz+1)][ny][nx] in double; levelUpCount / levelDownCount: deposits per
+ * bin (may be NULL); nearFace[numPhotons] (may be NULL): 1 where a collision of the photon stopped within
+ * delta = 64 * 2^-23 * (km travelled so far) of a face of its cell, or a surface arrival within delta of an edge of a
+ * surface patch -- where an implementation that differs by float rounding of the leg lengths may put the photon in another
+ * cell or on another patch. */
+int64_t orc_compute_rt_levels(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
+                              float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
+                              orc_counters *C, orc_fate *fates, double *levelUp, double *levelDown,
+                              int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace) {
+  const size_t nbins = (size_t)P->nx * P->ny * ((size_t)P->nz + 1);
+  level_tally T = {levelUp, levelDown, levelUpCount, levelDownCount, 1.0f, 0.0};
+  memset(levelUp, 0, sizeof(double) * nbins);
+  memset(levelDown, 0, sizeof(double) * nbins);
+  if (levelUpCount) memset(levelUpCount, 0, sizeof(int64_t) * nbins);
+  if (levelDownCount) memset(levelDownCount, 0, sizeof(int64_t) * nbins);
+  return compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, NULL, NULL, NULL, NULL,
+                    &T, nearFace);
+}
+
+static int near_any(double v, const double *t, int n, double delta) {
+  for (int i = 0; i < n; i++) if (fabs(v - t[i]) <= delta) return 1;
+  return 0;
+}
+
+static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
+                          float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
+                          orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
+                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace) {
   const int nx = P->nx, ny = P->ny, nz = P->nz, nc = P->nc;
   const size_t ncol = (size_t)nx * ny, nvox = ncol * nz;
   const float Pi = 3.14159265358979312f; /* :31 */
@@ -998,6 +1064,14 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
       zIndex = (int)floor(t) + 1; if (zIndex > nz) zIndex = nz;
       zPos = P->ze[zIndex - 1] + remainder * (P->ze[zIndex] - P->ze[zIndex - 1]);
     }
+    int flagged = 0;
+    if (T) { /* section 4.12: a solar launch is the downward crossing of level nz, a surface-emitted photon the upward crossing
+              * of level 0, each with weight 1 in the launch column; an atmospheric launch crosses nothing */
+      T->path = 0.0;
+      T->weight = photonWeight;
+      if (S->kind == 0) level_deposit(P, T, 0, nz, xIndex, yIndex, photonWeight);
+      else if (L.z == 0.0) level_deposit(P, T, 1, 0, xIndex, yIndex, photonWeight); /* (the surface launch of :493) */
+    }
     if (P->lwFlag > 0.0f) { /* :504-508 */
       if (zPos > 0.0) {
         size_t c2 = (size_t)(xIndex - 1) + (size_t)nx * (yIndex - 1);
@@ -1020,7 +1094,8 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
       cnt.legs++;
       double pos[3] = {xPos, yPos, zPos};
       int32_t idx[3] = {xIndex, yIndex, zIndex};
-      float tauAccumulated = orc_accumulate_extinction(P, dir, pos, idx, 1, tauToTravel, &cnt.crossings);
+      if (T) T->weight = photonWeight;
+      float tauAccumulated = accumulate_extinction(P, dir, pos, idx, 1, tauToTravel, &cnt.crossings, T);
       xPos = pos[0]; yPos = pos[1]; zPos = pos[2];
       xIndex = idx[0]; yIndex = idx[1]; zIndex = idx[2];
       if (tauAccumulated < 0.0f) { cnt.badPhotons++; fate = 3; break; } /* :562-563 */
@@ -1028,6 +1103,7 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
       if (zPos >= zMax) { /* :573-617 */
         size_t c2 = (size_t)(xIndex - 1) + (size_t)nx * (yIndex - 1);
         fluxUp[c2] = fluxUp[c2] + photonWeight;
+        if (T) level_deposit(P, T, 1, nz, xIndex, yIndex, photonWeight); /* section 4.12: beside the fluxUp deposit */
         cnt.topExits++;
         fate = 0; fateWeight = photonWeight;
         break;
@@ -1036,6 +1112,11 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
         zPos = z0 + spacing_d(z0);
         size_t c2 = (size_t)(xIndex - 1) + (size_t)nx * (yIndex - 1);
         fluxDown[c2] = fluxDown[c2] + photonWeight;
+        if (T) level_deposit(P, T, 0, 0, xIndex, yIndex, photonWeight); /* section 4.12: the weight before the albedo */
+        if (T && P->surfNumX > 0) {
+          const double delta = 64.0 * ldexp(1.0, -23) * T->path;
+          if (near_any(xPos, P->surfXPosition, P->surfNumX, delta) || near_any(yPos, P->surfYPosition, P->surfNumY, delta)) flagged = 1;
+        }
         cnt.surfaceHits++;
         scatteringOrder++;
         for (uint32_t j = 0;; j++) { /* Philox slots: mu attempt 0 = X, 1 = Z, then block 2.. ; phi = Y */
@@ -1049,6 +1130,7 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
         else
           photonWeight = (float)((double)photonWeight * albedo); /* :673 */
         if (photonWeight <= FLT_MIN) { cnt.surfaceAbsorbed++; fate = 1; fateWeight = wBefore; break; }
+        if (T) level_deposit(P, T, 1, 0, xIndex, yIndex, photonWeight); /* section 4.12: the reflected photon, the weight after the albedo */
         if (R->mode == 1) { /* Philox mode: cos / sin of 2 pi Y by the kernel's expression (sincos_2pi), as in next_direct */
           float sinTheta = sqrtf(1.0f - mu * mu), c, s;
           sincos_2pi(draw(R, 0, 2), &c, &s);
@@ -1067,6 +1149,12 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
                   R->event, xIndex, yIndex, zIndex, xPos, yPos, zPos, dir[0], dir[1], dir[2], tauToTravel, photonWeight);
         scatteringOrder++;
         cnt.collisions++;
+        if (T) { /* a stop point within delta of a face of its cell */
+          const double delta = 64.0 * ldexp(1.0, -23) * T->path;
+          if (xPos - P->xe[xIndex - 1] <= delta || P->xe[xIndex] - xPos <= delta || yPos - P->ye[yIndex - 1] <= delta ||
+              P->ye[yIndex] - yPos <= delta || zPos - P->ze[zIndex - 1] <= delta || P->ze[zIndex] - zPos <= delta)
+            flagged = 1;
+        }
         if (P->totalExt[IDX3(P, xIndex, yIndex, zIndex)] <= 0.0) { /* :728-754 */
           if (xPos - P->xe[xIndex - 1] <= 0.0 && dir[0] > 0.0f) {
             xPos = xPos - spacing_d(xPos);
@@ -1127,6 +1215,7 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
         next_direct(R, cosf(scatteringAngle), dir); /* :819 */
       }
     }
+    if (nearFace) nearFace[ip] = (uint8_t)flagged;
     if (fates) {
       fates[ip].fate = fate;
       fates[ip].ix = xIndex; fates[ip].iy = yIndex; fates[ip].iz = zIndex;

@@ -185,6 +185,15 @@ int64_t orc_compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
                        int64_t numPhotons, float *fluxUp, float *fluxDown,
                        float *fluxAbsorbed, float *volumeAbsorption,
                        orc_counters *C, orc_fate *fates);
+/* computeRT with the level tallies of DESIGN.md section 4.12 (not in the reference): raw weight sums levelUp / levelDown
+ * [(nz+1)][ny][nx] in double, deposits per bin (may be NULL), and nearFace[numPhotons] (may be NULL): 1 where a collision of
+ * the photon stopped within 64 * 2^-23 * (km travelled so far) of a face of its cell (or a surface arrival that close to
+ * an edge of a surface patch).  The other results are orc_compute_rt's. */
+int64_t orc_compute_rt_levels(const orc_problem *P, const orc_source *S, orc_rng *R,
+                              int64_t numPhotons, float *fluxUp, float *fluxDown,
+                              float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C,
+                              orc_fate *fates, double *levelUp, double *levelDown,
+                              int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace);
 /* normalisation of computeRadiativeTransfer (:328-364), in place. */
 void orc_normalize(const orc_problem *P, int64_t numPhotonsProcessed, float *fluxUp,
                    float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption);

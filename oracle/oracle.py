@@ -102,6 +102,8 @@ def lib():
         L.orc_compute_rt.restype = C.c_int64
         L.orc_compute_rt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         L.orc_normalize.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        L.orc_compute_rt_levels.restype = C.c_int64
+        L.orc_compute_rt_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 11
         L.orc_find_index_double.argtypes = [C.c_double, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_real.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_mixed.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
@@ -369,6 +371,50 @@ def compute_rt(problem, source, rng, n_photons, want_fates=False):
     if want_fates:
         res["fates"] = fates
     return res
+
+
+def compute_rt_levels(problem, source, rng, n_photons, want_fates=False):
+    """computeRT with the level tallies of DESIGN.md section 4.12 (not in the reference): compute_rt()'s raw results plus
+    levelUp / levelDown[nz + 1, ny, nx] (raw weight sums, float64), levelUpCount / levelDownCount (deposits per bin) and
+    nearFace[n_photons] (bool: a stop point of the photon lay within 64 * 2^-23 * its path length of a face)."""
+    ncol = problem.nx * problem.ny
+    nvox = ncol * problem.nz
+    shape = (problem.nz + 1, problem.ny, problem.nx)
+    up, dn, ab = (np.zeros(ncol, np.float32) for _ in range(3))
+    vol = np.zeros(nvox, np.float32)
+    lup, ldn = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
+    nup, ndn = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+    near = np.zeros(max(int(n_photons), 1), np.uint8)
+    cnt = OrcCounters()
+    fates = np.zeros(n_photons, FATE_DTYPE) if want_fates else None
+    src = source.c if hasattr(source, "c") else source
+    n = lib().orc_compute_rt_levels(C.addressof(problem.c), C.addressof(src), C.addressof(rng), int(n_photons),
+                                    _p(up), _p(dn), _p(ab), _p(vol), C.addressof(cnt), _p(fates) if want_fates else None,
+                                    _p(lup), _p(ldn), _p(nup), _p(ndn), _p(near))
+    res = {"n": int(n), "fluxUp": up, "fluxDown": dn, "fluxAbsorbed": ab, "volumeAbsorption": vol, "counters": cnt.as_dict(),
+           "levelUp": lup, "levelDown": ldn, "levelUpCount": nup, "levelDownCount": ndn,
+           "nearFace": near[:int(n_photons)].astype(bool)}
+    if want_fates:
+        res["fates"] = fates
+    return res
+
+
+def normalize_levels(problem, n_done, res):
+    """levelFluxUp / levelFluxDown [nz + 1, ny, nx] and their domain means [nz + 1] (float64) from compute_rt_levels():
+    the raw sums over the photons per column, by the expression used for fluxUp (:331-342, :347-349)."""
+    nppc = _nppc(problem, n_done)
+    up, dn = res["levelUp"] / nppc[None], res["levelDown"] / nppc[None]
+    return dict(levelFluxUp=up, levelFluxDown=dn, meanLevelFluxUp=up.mean(axis=(1, 2)), meanLevelFluxDown=dn.mean(axis=(1, 2)))
+
+
+def _nppc(problem, n_done):
+    """numPhotonsPerColumn [ny, nx] as the float32 the reference forms (:331 regular x/y, :334-342 by relative area)."""
+    xy_regular = problem.grid_flags()[0]
+    if xy_regular:
+        return np.full((problem.ny, problem.nx), np.float32(n_done) / np.float32(problem.nx * problem.ny), np.float32).astype(np.float64)
+    xe, ye = problem.xe, problem.ye
+    rel = (np.diff(ye)[:, None] * np.diff(xe)[None, :]) / ((xe[-1] - xe[0]) * (ye[-1] - ye[0]))
+    return (rel.astype(np.float32) * np.float32(n_done)).astype(np.float64)
 
 
 def intensity_directions(mus, phis_deg):

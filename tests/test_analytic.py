@@ -460,6 +460,159 @@ def test_the_two_deterministic_solvers_agree_on_isotropic_scattering():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# flux profiles: upward and downward flux at optical depths inside the slab (for the level fluxes)
+# ---------------------------------------------------------------------------------------------------------------------
+def _profile_from_source(edges, src, taus, direct_mu0, leaving_surface):
+    """(up, down) at the optical depths `taus` (from the top) of a slab whose isotropic source function is `src` on the cells
+    between `edges`: down = the direct beam + 2 pi sum src dE3 over (the parts of) the cells above, up = the same over the
+    cells below + 2 (flux leaving the surface) E3(b - tau)."""
+    b = edges[-1]
+    up, down = [], []
+    for tau in np.atleast_1d(np.asarray(taus, np.float64)):
+        lo, hi = np.minimum(edges[:-1], tau), np.minimum(edges[1:], tau)     # the part of each cell above tau
+        d = 2.0 * np.pi * float(np.sum(src * (expn(3, tau - hi) - expn(3, tau - lo))))
+        lo, hi = np.maximum(edges[:-1], tau), np.maximum(edges[1:], tau)     # ... and below
+        u = 2.0 * np.pi * float(np.sum(src * (expn(3, lo - tau) - expn(3, hi - tau))))
+        down.append(d + (float(np.exp(-tau / direct_mu0)) if direct_mu0 else 0.0))
+        up.append(u + 2.0 * leaving_surface * float(expn(3, max(b - tau, 0.0))))
+    return np.array(up), np.array(down)
+
+
+def _layered_solution(dtaus, omegas, mu0, albedo, cells_per_layer):
+    """The linear system of `layered_isotropic_slab`, solved: (cell edges, cell widths, omega per cell, source per cell, flux
+    onto the surface, mean intensity J per cell)."""
+    dtaus, omegas = np.asarray(dtaus, np.float64), np.asarray(omegas, np.float64)
+    h = np.repeat(dtaus / cells_per_layer, cells_per_layer)
+    om = np.repeat(omegas, cells_per_layer)
+    edges = np.concatenate([[0.0], np.cumsum(h)])
+    b = edges[-1]
+    tc = 0.5 * (edges[:-1] + edges[1:])
+    cells = len(h)
+    kern = 0.5 * np.abs(expn(2, np.abs(tc[:, None] - edges[None, :-1])) - expn(2, np.abs(tc[:, None] - edges[None, 1:])))
+    kern[np.arange(cells), np.arange(cells)] = 1.0 - expn(2, 0.5 * h)
+    direct = (np.exp(-edges[:-1] / mu0) - np.exp(-edges[1:] / mu0)) / (4.0 * np.pi * h)
+    lamb = 0.5 * (expn(3, b - edges[1:]) - expn(3, b - edges[:-1])) / h / np.pi
+    to_sfc = 2.0 * np.pi * (expn(3, b - edges[1:]) - expn(3, b - edges[:-1]))
+    a = np.zeros((cells + 1, cells + 1))
+    a[:cells, :cells] = np.eye(cells) - om[:, None] * kern
+    a[:cells, cells] = -om * albedo * lamb
+    a[cells, :cells] = -to_sfc
+    a[cells, cells] = 1.0
+    sol = np.linalg.solve(a, np.concatenate([om * direct, [np.exp(-b / mu0)]]))
+    src, onto = sol[:cells], float(sol[cells])
+    return edges, h, om, src, onto, kern @ src + direct + albedo * onto * lamb
+
+
+def layered_isotropic_profile(dtaus, omegas, mu0, taus, albedo=0.0, cells_per_layer=150):
+    """(upward, downward) flux at the optical depths `taus` (from the top) inside `layered_isotropic_slab`'s slab, per unit
+    incident flux, from the source function it solves for; the downward flux holds the direct beam, as the integrator's
+    does.  At tau = 0 the upward one is that function's first result, at tau = b the downward one its second."""
+    edges, _, _, src, onto, _ = _layered_solution(dtaus, omegas, mu0, albedo, cells_per_layer)
+    return _profile_from_source(edges, src, taus, mu0, albedo * onto)
+
+
+def layered_isotropic_absorption(dtaus, omegas, mu0, albedo=0.0, cells_per_layer=150):
+    """What each layer absorbs, per unit incident flux: 4 pi (1 - omega) J dtau summed over its cells, J the mean intensity
+    (scattered, direct and from the surface) that the integral equation is written in."""
+    _, h, om, _, _, j = _layered_solution(dtaus, omegas, mu0, albedo, cells_per_layer)
+    return (4.0 * np.pi * (1.0 - om) * j * h).reshape(len(dtaus), cells_per_layer).sum(axis=1)
+
+
+def _thermal_solution(b, omega, planck_layers, planck_sfc, cells_per_layer):
+    planck_layers = np.asarray(planck_layers, np.float64)
+    cells = cells_per_layer * len(planck_layers)
+    h = b / cells
+    edges = np.arange(cells + 1) * h
+    tc = edges[:-1] + 0.5 * h
+    kern = 0.5 * np.abs(expn(2, np.abs(tc[:, None] - edges[None, :-1])) - expn(2, np.abs(tc[:, None] - edges[None, 1:])))
+    kern[np.arange(cells), np.arange(cells)] = 1.0 - expn(2, 0.5 * h)
+    bb = np.repeat(planck_layers, cells_per_layer)
+    from_surface = 0.5 * planck_sfc * (expn(3, b - edges[1:]) - expn(3, b - edges[:-1])) / h
+    src = np.linalg.solve(np.eye(cells) - omega * kern, (1.0 - omega) * bb + omega * from_surface)
+    total = 4.0 * np.pi * (1.0 - omega) * float(np.sum(bb)) * h + np.pi * planck_sfc
+    return edges, h, bb, src, total, kern @ src + from_surface
+
+
+def thermal_profile(b, omega, planck_layers, planck_sfc, taus, cells_per_layer=150):
+    """(upward, downward) flux at the optical depths `taus` (from the top) inside `thermal_slab`'s slab, as shares of the
+    emitted power; the black surface sends pi B_s upward: 2 pi B_s E3(b - tau) of it reaches tau."""
+    edges, _, _, src, total, _ = _thermal_solution(b, omega, planck_layers, planck_sfc, cells_per_layer)
+    up, down = _profile_from_source(edges, src, taus, None, np.pi * planck_sfc)
+    return up / total, down / total
+
+
+def thermal_absorption(b, omega, planck_layers, planck_sfc, cells_per_layer=150):
+    """Net absorption (absorbed minus emitted) of each layer as a share of the emitted power: 4 pi (1 - omega) (J - B) dtau."""
+    _, h, bb, _, total, j = _thermal_solution(b, omega, planck_layers, planck_sfc, cells_per_layer)
+    return (4.0 * np.pi * (1.0 - omega) * (j - bb) * h).reshape(len(planck_layers), cells_per_layer).sum(axis=1) / total
+
+
+def doubling_profile(b, omega, chi, node, taus, streams=33, halvings=24):
+    """(mu0, upward, downward incl. direct) flux at the optical depths `taus` inside `doubling_slab`'s slab: the slab above tau
+    (r_a, t_a) added to the slab below (r_b) -- the field between them is D = (E - r_a r_b)^-1 t_a inc downward and
+    U = r_b D upward (a homogeneous slab reflects alike from both sides); fluxes as in `doubling_slab`."""
+    up, down = [], []
+    mu0 = None
+    for tau in np.atleast_1d(np.asarray(taus, np.float64)):
+        mu, c, ra, ta = doubling_matrices(float(tau), omega, chi, streams, halvings)
+        _, _, rb, _ = doubling_matrices(float(b - tau), omega, chi, streams, halvings)
+        inc = np.zeros(streams)
+        inc[node] = 1.0 / (2.0 * np.pi * mu[node] * c[node])
+        d = np.linalg.solve(np.eye(streams) - ra @ rb, ta @ inc)
+        mu0 = float(mu[node])
+        down.append(float(2.0 * np.pi * np.sum(mu * c * d)))
+        up.append(float(2.0 * np.pi * np.sum(mu * c * (rb @ d))))
+    return mu0, np.array(up), np.array(down)
+
+
+def test_the_profiles_end_in_what_the_solvers_return():
+    dt, om = LAYERED["dtaus"], LAYERED["omegas"]
+    up, onto = layered_isotropic_slab(dt, om, 0.35, albedo=0.5)
+    u, d = layered_isotropic_profile(dt, om, 0.35, [0.0, float(np.sum(dt))], albedo=0.5)
+    assert abs(u[0] - up) < 1e-12 and abs(d[1] - onto) < 1e-12 and d[0] == 1.0 and abs(u[1] - 0.5 * onto) < 1e-12
+    tau, omega, temps, sfc = THERMAL_SLABS[1]
+    pl, ps = planck(10.0, np.asarray(temps)[::-1]), float(planck(10.0, sfc))
+    _, up, down = thermal_slab(tau, omega, pl, ps)
+    u, d = thermal_profile(tau, omega, pl, ps, [0.0, tau])
+    assert abs(u[0] - up) < 1e-12 and abs(d[1] - down) < 1e-12 and d[0] == 0.0
+    chi = sampled_moments(hg_slab(4.0, 0.9, 0.85, 64)[1], table=9001)
+    mu0, up, down = doubling_slab(4.0, 0.9, chi, 20, streams=HG_STREAMS)
+    m, u, d = doubling_profile(4.0, 0.9, chi, 20, [0.0, 4.0], streams=HG_STREAMS)
+    assert m == mu0 and abs(u[0] - up) < 1e-12 and abs(d[1] - down) < 1e-12 and abs(d[0] - 1.0) < 1e-12 and abs(u[1]) < 1e-12
+
+
+def test_the_two_deterministic_solvers_agree_on_isotropic_scattering_at_inner_levels():
+    for b, omega, node in ((1.0, 1.0, 16), (2.0, 0.9, 5), (0.5, 1.0, 31)):
+        taus = b * np.array([0.1, 0.25, 0.5, 0.8])
+        mu0, u1, d1 = doubling_profile(b, omega, [1.0], node, taus)
+        # (1500 cells as isotropic_slab has, half of them in the top 15 %: under the low sun of the second case, mu0 = 0.07, the
+        # source function falls off within 0.1 of the top, and equal cells leave 3 x 10^-6 there -- 9 x 10^-7 at 3000)
+        u2, d2 = layered_isotropic_profile([0.15 * b, 0.85 * b], [omega, omega], mu0, taus, cells_per_layer=750)
+        print("b", b, "omega", omega, "mu0 %.4f" % mu0, "up", np.abs(u1 - u2).max(), "down", np.abs(d1 - d2).max())
+        assert np.all(np.abs(u1 - u2) < 1e-6) and np.all(np.abs(d1 - d2) < 1e-6)
+
+
+def test_the_net_flux_of_the_profiles_diverges_by_what_each_layer_absorbs():
+    """Net downward flux into a layer minus net downward flux out of it = what the layer absorbs (thermal: minus what it
+    emits).  The fluxes come from the source function through E3, the absorption from the mean intensity through the E1
+    kernel of the integral equation: equal up to the midpoint rule of the latter, which the file holds to 3 x 10^-5 at these
+    cell counts (test_the_layered_solver_reduces_to_the_homogeneous_one_and_conserves_energy)."""
+    dt, om = np.asarray(LAYERED["dtaus"]), LAYERED["omegas"]
+    levels = np.concatenate([[0.0], np.cumsum(dt)])
+    for albedo, mu0 in ((0.0, 0.8), (0.5, 0.35)):
+        u, d = layered_isotropic_profile(dt, om, mu0, levels, albedo=albedo)
+        worst = np.abs(-np.diff(d - u) - layered_isotropic_absorption(dt, om, mu0, albedo=albedo)).max()
+        print("layered, albedo", albedo, "worst", worst)
+        assert worst < 3e-5
+    for tau, omega, temps, sfc in THERMAL_SLABS:
+        pl, ps = planck(10.0, np.asarray(temps)[::-1]), float(planck(10.0, sfc))
+        u, d = thermal_profile(tau, omega, pl, ps, np.linspace(0.0, tau, len(temps) + 1))
+        worst = np.abs(-np.diff(d - u) - thermal_absorption(tau, omega, pl, ps)).max()
+        print("thermal", tau, omega, "worst", worst)
+        assert worst < 3e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the oracle (CPU)
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("b,omega,g,nleg,node", HG_SLABS)

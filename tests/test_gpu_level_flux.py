@@ -1,8 +1,9 @@
 """Upward and downward flux through every level of every column (recLevelFluxes) on the GPU.
 
-The oracle has no level tallies; the checks are exact identities (the boundary levels are fluxUp / fluxDown bit for bit, nothing
-else moves, the schedule does not show, the flux divergence of a layer is what it absorbed), closed forms (Beer-Lambert over a
-grey surface) and a direct-beam ray-cast written here."""
+The checks of this file need no oracle: exact identities (the boundary levels are fluxUp / fluxDown bit for bit, nothing else
+moves, the schedule does not show, the flux divergence of a layer is what it absorbed), closed forms (Beer-Lambert over a grey
+surface) and a direct-beam ray-cast written here.  The oracle's own level tallies, and transport theory at the inner levels of
+scattering media, are what tests/test_gpu_level_flux_oracle.py holds the same kernels to."""
 import ctypes as C
 
 import numpy as np
