@@ -11,7 +11,8 @@
 ! (Domain-Files/i3rcStepCloud.f95, planeParallel.f95) or a flat binary written by
 ! mcbrat3d_amd.flatdomain.write_flat_domain (any domain the Python host layer can build).
 program mcbrat_driver
-  use mcbrat_hip_integrator, lastBatchLevelFluxes => reportLevelFluxes   ! (the /output/ namelist has a variable of that name)
+  use mcbrat_hip_integrator, lastBatchLevelFluxes => reportLevelFluxes, &   ! (the /output/ namelist has variables of these names)
+                             lastBatchDirectLevelFluxes => reportDirectLevelFluxes
   implicit none
   ! --- namelist variables (names and defaults of the reference driver) ---
   real     :: solarMu = 1., solarAzimuth = 0., LW_flag = -1.
@@ -34,7 +35,7 @@ program mcbrat_driver
   logical  :: reportVolumeAbsorption = .false., reportAbsorptionProfile = .false.
   logical  :: recScatOrd = .false.
   integer  :: numRecScatOrd = 0
-  logical  :: reportLevelFluxes = .false.
+  logical  :: reportLevelFluxes = .false., reportDirectLevelFluxes = .false.
   character(len=256) :: auxhist01_radFile = "", auxhist01_fluxFile = ""
   character(len=256) :: solarSourceFile = "", instrResponseFile = "", physDomainFile = ""
   character(len=256), dimension(4) :: SSPfilename = ""
@@ -48,7 +49,7 @@ program mcbrat_driver
                                useRussianRouletteForIntensity, zetaMin, limitIntensityContributions, &
                                maxIntensityContribution
   namelist /output/            reportVolumeAbsorption, reportAbsorptionProfile, recScatOrd, numRecScatOrd, &
-                               reportLevelFluxes, auxhist01_fluxFile, auxhist01_radFile
+                               reportLevelFluxes, reportDirectLevelFluxes, auxhist01_fluxFile, auxhist01_radFile
   namelist /fileNames/         solarSourceFile, instrResponseFile, SSPfilename, physDomainFile, &
                                outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, &
                                outputNetcdfFile
@@ -66,7 +67,7 @@ program mcbrat_driver
                           absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:), &
                           meanLevelStats(:,:,:)
   real,    allocatable :: forwardTable(:,:), legendreCoefficients(:)
-  integer :: numRadDir, off
+  integer :: numRadDir, off, nLevelStats
   logical :: computeIntensity
   real :: t0, t1
 
@@ -80,6 +81,8 @@ program mcbrat_driver
   read (1, nml = fileNames); close (1)
   if (numPhotonsPerBatch <= 0) stop "must specify numPhotonsPerBatch"
   if (len_trim(physDomainFile) == 0) stop "must specify physDomainFile"
+  if (reportDirectLevelFluxes .and. (numLambda > 1 .or. LW_flag >= 0.)) &
+    stop "reportDirectLevelFluxes: direct level fluxes are not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
   solarFlux = 1.0_8
 
   call cpu_time(t0)
@@ -115,6 +118,10 @@ program mcbrat_driver
   ! flux through every level of every column (refused together with intensity directions and scattering orders)
   if (reportLevelFluxes) then
     call specifyLevelFluxes(mcIntegrator, .true., ierr); call check("specifyParameters")
+  end if
+  ! their direct / diffuse separation (refused without reportLevelFluxes)
+  if (reportDirectLevelFluxes) then
+    call specifyDirectLevelFluxes(mcIntegrator, .true., ierr); call check("specifyParameters")
   end if
   call setSolarSource(mcIntegrator, solarMu, solarAzimuth, ierr); call check("setSolarSource")
   call resetMoments(mcIntegrator, ierr); call check("resetMoments")
@@ -166,20 +173,30 @@ program mcbrat_driver
             meanByScatOrdStats(i, 1, 2), meanByScatOrdStats(i, 2, 1), " +-", meanByScatOrdStats(i, 2, 2)
     end do
   end if
-  if (reportLevelFluxes) then   ! domain-mean fluxes through every level: the moment tail's first 2 (nz+1) entries
-    allocate(meanLevelStats(0:nz, 2, 2))
-    off = int(M) - 2*(nz+1)*(1+ncol)
+  if (reportLevelFluxes) then   ! domain-mean fluxes through every level: the first 2 (nz+1) entries of the level tail, and with
+    ! reportDirectLevelFluxes the first 2 (nz+1) of the direct / diffuse tail behind it (meanStats 3, 4: direct, diffuse)
+    nLevelStats = merge(4, 2, reportDirectLevelFluxes)
+    allocate(meanLevelStats(0:nz, nLevelStats, 2))
+    off = int(M) - nLevelStats*(nz+1)*(1+ncol)
     do k = 1, 2
-      do j = 1, 2
-        meanLevelStats(:, j, k) = moments(8 + (k-1)*M + off + (j-1)*(nz+1) + 1 : 8 + (k-1)*M + off + j*(nz+1))
+      do j = 1, nLevelStats
+        i = off + merge(2*(nz+1)*(1+ncol), 0, j > 2) + (j - merge(3, 1, j > 2))*(nz+1)
+        meanLevelStats(:, j, k) = moments(8 + (k-1)*M + i + 1 : 8 + (k-1)*M + i + nz + 1)
       end do
     end do
-    do j = 1, 2
+    do j = 1, nLevelStats
       call momentsToStats1(meanLevelStats(:, j, :))
     end do
     do i = nz, 0, -1
-      print '(A,I3,A,F9.4,A,2(2X,F9.6,A,F9.6))', " level ", i, " z ", zPosition(i+1), " mean flux up/down:", &
-            meanLevelStats(i, 1, 1), " +-", meanLevelStats(i, 1, 2), meanLevelStats(i, 2, 1), " +-", meanLevelStats(i, 2, 2)
+      if (reportDirectLevelFluxes) then
+        print '(A,I3,A,F9.4,A,2(2X,F9.6,A,F9.6),A,2(2X,F9.6,A,F9.6))', " level ", i, " z ", zPosition(i+1), " mean flux up/down:", &
+              meanLevelStats(i, 1, 1), " +-", meanLevelStats(i, 1, 2), meanLevelStats(i, 2, 1), " +-", meanLevelStats(i, 2, 2), &
+              "  direct/diffuse:", meanLevelStats(i, 3, 1), " +-", meanLevelStats(i, 3, 2), meanLevelStats(i, 4, 1), " +-", &
+              meanLevelStats(i, 4, 2)
+      else
+        print '(A,I3,A,F9.4,A,2(2X,F9.6,A,F9.6))', " level ", i, " z ", zPosition(i+1), " mean flux up/down:", &
+              meanLevelStats(i, 1, 1), " +-", meanLevelStats(i, 1, 2), meanLevelStats(i, 2, 1), " +-", meanLevelStats(i, 2, 2)
+      end if
     end do
   end if
   if (len_trim(outputFluxFile) > 0) call writeFluxASCII()

@@ -30,7 +30,8 @@ module mcbrat_hip_integrator
             inverseTableLegendre, lastTraceMilliseconds, setAsynchronous, synchronize, &
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
             setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
-            specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes
+            specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes, &
+            specifyDirectLevelFluxes, reportDirectLevelFluxes
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -208,6 +209,18 @@ module mcbrat_hip_integrator
     function mcbrat_report_level_fluxes(ctx, mUp, mDown, fUp, fDown) bind(C, name="mcbrat_report_level_fluxes") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, mUp, mDown, fUp, fDown   ! (c_null_ptr: not wanted)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_specify_direct_level_fluxes(ctx, enable) bind(C, name="mcbrat_specify_direct_level_fluxes") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: enable
+      integer(c_int) :: rc
+    end function
+    function mcbrat_report_direct_level_fluxes(ctx, mDirect, mDiffuse, fDirect, fDiffuse) &
+        bind(C, name="mcbrat_report_direct_level_fluxes") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, mDirect, mDiffuse, fDirect, fDiffuse   ! (c_null_ptr: not wanted)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -668,6 +681,46 @@ contains
     end if
     ierr = mcbrat_report_level_fluxes(this%ctx, mUp, mDown, fUp, fDown)
   end subroutine reportLevelFluxes
+
+  ! specifyParameters(recDirectLevelFluxes): the direct beam apart from the diffuse light in the downward level flux.  Needs
+  ! level fluxes (specifyLevelFluxes first) and a solar source.  Changes momentsLength().
+  subroutine specifyDirectLevelFluxes(this, enable, ierr)
+    type(integrator), intent(inout) :: this
+    logical,          intent(in)    :: enable
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_specify_direct_level_fluxes(this%ctx, merge(1_c_int32_t, 0_c_int32_t, enable))
+  end subroutine specifyDirectLevelFluxes
+
+  ! the last batch's direct and diffuse parts of levelFluxDown: mean*(0:numZ), levelFluxDown*(numX, numY, 0:numZ)
+  subroutine reportDirectLevelFluxes(this, meanLevelFluxDownDirect, meanLevelFluxDownDiffuse, levelFluxDownDirect, &
+                                     levelFluxDownDiffuse, ierr)
+    type(integrator), intent(inout) :: this
+    real, dimension(0:),       contiguous, optional, target, intent(out) :: meanLevelFluxDownDirect, meanLevelFluxDownDiffuse
+    real, dimension(:, :, 0:), contiguous, optional, target, intent(out) :: levelFluxDownDirect, levelFluxDownDiffuse
+    integer,                   intent(out) :: ierr
+    type(c_ptr) :: mDirect, mDiffuse, fDirect, fDiffuse
+    integer :: n
+    n = this%numZ + 1
+    mDirect = c_null_ptr; mDiffuse = c_null_ptr; fDirect = c_null_ptr; fDiffuse = c_null_ptr
+    ierr = 2   ! "reportResults: levelFluxDown... is the wrong size"
+    if (present(meanLevelFluxDownDirect)) then
+      if (size(meanLevelFluxDownDirect) /= n) return
+      mDirect = c_loc(meanLevelFluxDownDirect)
+    end if
+    if (present(meanLevelFluxDownDiffuse)) then
+      if (size(meanLevelFluxDownDiffuse) /= n) return
+      mDiffuse = c_loc(meanLevelFluxDownDiffuse)
+    end if
+    if (present(levelFluxDownDirect)) then
+      if (any(shape(levelFluxDownDirect) /= (/ this%numX, this%numY, n /))) return
+      fDirect = c_loc(levelFluxDownDirect)
+    end if
+    if (present(levelFluxDownDiffuse)) then
+      if (any(shape(levelFluxDownDiffuse) /= (/ this%numX, this%numY, n /))) return
+      fDiffuse = c_loc(levelFluxDownDiffuse)
+    end if
+    ierr = mcbrat_report_direct_level_fluxes(this%ctx, mDirect, mDiffuse, fDirect, fDiffuse)
+  end subroutine reportDirectLevelFluxes
 
   integer(8) function numBadPhotons(this)
     type(integrator), intent(in) :: this

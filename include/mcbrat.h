@@ -201,6 +201,22 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *ctx, int32_t enable);
 int mcbrat_report_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxUp, float *meanLevelFluxDown, float *levelFluxUp,
                                float *levelFluxDown);
 
+/* The direct beam apart from the diffuse light in the downward level flux (specifyParameters(recDirectLevelFluxes); an addition
+ * under ABI version 3).  A photon is direct from its launch until its first collision or its first
+ * surface arrival, whichever comes first: any collision ends it, whatever the single-scattering albedo; periodic wrapping does
+ * not; the surface arrival itself (the downward crossing of level 0) still counts, the reflection ends it.
+ * levelFluxDownDirect(x, y, k) is the part of levelFluxDown(x, y, k) carried by direct photons, levelFluxDownDiffuse the rest:
+ * the kernel tallies every downward crossing to ONE of the two and the total is the integer sum of the raw bins, so levelFluxUp
+ * and levelFluxDown keep their bits.  Level nz is all direct (the launch is the crossing); there is no upward direct flux.
+ * Needs level fluxes (fails without them, and mcbrat_specify_level_fluxes(0) fails while it is on) and a solar source
+ * (mcbrat_compute_radiative_transfer fails with the thermal one); fails where one batch's three level parts would not fit the
+ * tally budget.  Changes mcbrat_moments_length(): a caller-bound moment buffer must be bound again. */
+int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *ctx, int32_t enable);
+/* The LAST batch, as mcbrat_report_level_fluxes: meanLevelFluxDownDirect / Diffuse(0:nz), levelFluxDownDirect / Diffuse(nx, ny, 0:nz).
+ * Any pointer may be NULL. */
+int mcbrat_report_direct_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxDownDirect, float *meanLevelFluxDownDiffuse,
+                                      float *levelFluxDownDirect, float *levelFluxDownDiffuse);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:
@@ -213,7 +229,9 @@ int mcbrat_report_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxUp, float *m
  *   fluxUpByScatOrd[(N+1)*nx*ny], fluxDownByScatOrd[(N+1)*nx*ny], meanIntensityByScatOrd[(N+1)*nDirections],
  *   intensityByScatOrd[(N+1)*nDirections*nx*ny] (order slowest, x fastest),
  *   and with level fluxes, after everything else: meanLevelFluxUp[nz+1], meanLevelFluxDown[nz+1],
- *   levelFluxUp[(nz+1)*nx*ny], levelFluxDown[(nz+1)*nx*ny] (level slowest, x fastest).
+ *   levelFluxUp[(nz+1)*nx*ny], levelFluxDown[(nz+1)*nx*ny] (level slowest, x fastest),
+ *   and with direct level fluxes, behind those: meanLevelFluxDownDirect[nz+1], meanLevelFluxDownDiffuse[nz+1],
+ *   levelFluxDownDirect[(nz+1)*nx*ny], levelFluxDownDiffuse[(nz+1)*nx*ny].
  * Total doubles = 8 + 2*length.  The buffer is device memory; a caller that
  * wants to all-reduce it with RCCL binds its own device buffer. */
 int64_t mcbrat_moments_length(const mcbrat_ctx *ctx);

@@ -123,6 +123,8 @@ struct mcbrat_ctx {
   int numRecScatOrd = -1;
   // upward and downward flux through every level of every column (mcbrat_specify_level_fluxes)
   int levelFluxes = 0;
+  // the direct beam apart from the diffuse light in the downward level flux (mcbrat_specify_direct_level_fluxes)
+  int directLevelFluxes = 0;
   // parameters
   float albedo = 0.f;
   int useRR = 1;
@@ -252,21 +254,36 @@ int upload(mcbrat_ctx *c, T **dst, const T *src, size_t n) {
 bool orders_on(const mcbrat_ctx *c) { return c->numRecScatOrd >= 0; }
 
 bool levels_on(const mcbrat_ctx *c) { return c->levelFluxes != 0; }
-// bins of one batch's level fluxes: [levelUp ncol (nz+1) | levelDown ncol (nz+1)], level slowest
-size_t level_bins(const mcbrat_ctx *c) { return levels_on(c) ? 2 * (size_t)c->nx * c->ny * ((size_t)c->nz + 1) : 0; }
+bool direct_on(const mcbrat_ctx *c) { return c->levelFluxes != 0 && c->directLevelFluxes != 0; }
+// level parts of one batch's slab and level quantities in the moments: [up | down], with the direct tally [up | diffuse | direct]
+// and (up, down, direct, diffuse)
+size_t level_parts(const mcbrat_ctx *c) { return levels_on(c) ? (direct_on(c) ? 3 : 2) : 0; }
+size_t level_quantities(const mcbrat_ctx *c) { return levels_on(c) ? (direct_on(c) ? 4 : 2) : 0; }
+// bins of one batch's level fluxes: [levelUp ncol (nz+1) | levelDown ncol (nz+1) (| levelDirect ncol (nz+1))], level slowest
+size_t level_bins(const mcbrat_ctx *c) { return level_parts(c) * (size_t)c->nx * c->ny * ((size_t)c->nz + 1); }
+// whether the level bins of one batch of an nx x ny x nz grid fit the tally budget (in double: the product may pass 2^64)
+bool level_bins_fit(double parts, double nx, double ny, double nz);
 
 // [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest,
 // then the level fluxes: [meanLevelUp (nz+1) | meanLevelDown (nz+1) | levelUp ncol (nz+1) | levelDown ncol (nz+1)]
+// then their direct / diffuse separation: [meanDirect (nz+1) | meanDiffuse (nz+1) | direct ncol (nz+1) | diffuse ncol (nz+1)]
 long long moments_len(const mcbrat_ctx *c) {
   const long long ncol = (long long)c->nx * c->ny;
   return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol +
          (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0) +
-         (levels_on(c) ? 2LL * (c->nz + 1) * (1 + ncol) : 0);
+         (long long)level_quantities(c) * (c->nz + 1) * (1 + ncol);
+}
+// where the level tail starts in the moments (behind the orders' tail) and where the direct / diffuse tail does
+long long moments_levels_at(const mcbrat_ctx *c) {
+  return moments_len(c) - (long long)level_quantities(c) * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
+}
+long long moments_direct_at(const mcbrat_ctx *c) {
+  return moments_levels_at(c) + 2LL * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
 }
 
 // Elements of one batch's tally slab: [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:)
 // intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1) |
-// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1)]
+// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1) | (their direct tally:) levelDirect ncol (nz+1)]
 // fluxRun: the slab of a flux launch of the loaded domain (no intensity parts), what mcbrat_get_walk_mode reports on.
 size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz, nDir = fluxRun ? 0 : (size_t)c->nDir;
@@ -287,6 +304,13 @@ const char *const kLevelsCountersMsg =
     "specifyParameters: level fluxes (recLevelFluxes) are not available together with event counters / photon fates: the instrumented kernels have no level tallies.";
 const char *const kLevelsBudgetMsg =
     "specifyParameters: level fluxes (recLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
+const char *const kDirectNeedsLevelsMsg =
+    "specifyParameters: direct level fluxes (recDirectLevelFluxes) need level fluxes (recLevelFluxes): they separate the downward level flux.";
+const char *const kDirectThermalMsg =
+    "computeRadiativeTransfer: direct level fluxes (recDirectLevelFluxes) are not available with the thermal source: there is no direct beam.";
+const char *const kDirectBudgetMsg =
+    "specifyParameters: direct level fluxes (recDirectLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
+bool level_bins_fit(double parts, double nx, double ny, double nz) { return parts * nx * ny * (nz + 1.0) * sizeof(long long) <= (double)kSlabBudget; }
 const char *const kOrdersLimitMsg =
     "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
     "redistribution adds each direction's clipped excess to every order, which would count it numRecScatOrd + 1 times.";
@@ -812,9 +836,16 @@ const void *trace_ptr_lvl(bool tbl, bool emit) {
   return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, true, 0, false, false, true>
               : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true>;
 }
+// their DIRECT variants, solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table -- 8 kernels
+template <int BLOCK, int PRIV>
+const void *trace_ptr_lvl_direct(bool tbl) {
+  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true, true>
+             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true, true>;
+}
 template <int BLOCK>
 const void *trace_kernel_lvl(const mcbrat_ctx *c, const LaunchPlan &L) {
   const bool emit = c->srcKind != 0;
+  if (direct_on(c)) return (L.priv && L.gridLds) ? trace_ptr_lvl_direct<BLOCK, 2>(L.tblLds) : trace_ptr_lvl_direct<BLOCK, 0>(L.tblLds);  // (emit: refused, check_ready)
   return (L.priv && L.gridLds) ? trace_ptr_lvl<BLOCK, 2>(L.tblLds, emit) : trace_ptr_lvl<BLOCK, 0>(L.tblLds, emit);
 }
 
@@ -946,6 +977,7 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   const bool lvl = levels_on(c);
   if (lvl && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
     return fail(c, debug ? kLevelsCountersMsg : (brdf ? kLevelsBrdfMsg : (c->nDir > 0 ? kLevelsIntensityMsg : kLevelsOrdersMsg)));
+  if (direct_on(c) && emit) return fail(c, kDirectThermalMsg);  // (check_ready refuses it; a second line of defence: no thermal DIRECT kernel)
   if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
   const void *kernel;
   int block;
@@ -1001,7 +1033,8 @@ int check_ready(mcbrat_ctx *c) {
     if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
     if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
-    if (level_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, kLevelsBudgetMsg);
+    if (level_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+    if (direct_on(c) && c->srcKind != 0) return fail(c, kDirectThermalMsg);
   }
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
@@ -1137,7 +1170,7 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   for (int i = 0; i < ny; ++i) if (!(ye[i + 1] > ye[i])) return fail(c, "new_Domain: y edges must be increasing, unique.");
   for (int i = 0; i < nz; ++i) if (!(ze[i + 1] > ze[i])) return fail(c, "new_Domain: z edges must be increasing, unique.");
   if ((long long)nx * ny * nz > 0x7fffffffLL / 2) return fail(c, "new_Integrator: more than 2^30 cells are not supported.");
-  if (levels_on(c) && 2.0 * (double)nx * ny * ((double)nz + 1.0) * sizeof(long long) > (double)kSlabBudget) return fail(c, kLevelsBudgetMsg);
+  if (levels_on(c) && !level_bins_fit((double)level_parts(c), nx, ny, nz)) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1520,8 +1553,9 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
     if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
     if (c->countersOn) return fail(c, kLevelsCountersMsg);
-    if (2.0 * (double)c->nx * c->ny * ((double)c->nz + 1.0) * sizeof(long long) > (double)kSlabBudget) return fail(c, kLevelsBudgetMsg);
-  }
+    if (!level_bins_fit(2.0, c->nx, c->ny, c->nz)) return fail(c, kLevelsBudgetMsg);
+    if (c->directLevelFluxes && !level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
+  } else if (c->directLevelFluxes) return fail(c, kDirectNeedsLevelsMsg);  // (switch the direct tally off first)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (on != c->levelFluxes) {  // the moment arrays change length: start them afresh (as mcbrat_specify_scattering_orders does)
@@ -1541,9 +1575,9 @@ int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *mea
   if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  // the tail of the last batch's results: [meanUp | meanDown | up | down], already in Fortran order (nx, ny, 0:nz)
+  // the level tail of the last batch's results: [meanUp | meanDown | up | down], already in Fortran order (nx, ny, 0:nz)
   const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;
-  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_len(c) - n;
+  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_levels_at(c);
   std::vector<float> h(n);
   HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * n, hipMemcpyDeviceToHost));
   const float *q = h.data();
@@ -1552,6 +1586,48 @@ int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *mea
   take(meanLevelFluxDown, nLvl);
   take(levelFluxUp, ncol * nLvl);
   take(levelFluxDown, ncol * nLvl);
+  return 0;
+}
+
+int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
+  const int on = enable ? 1 : 0;
+  if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
+    if (!levels_on(c)) return fail(c, kDirectNeedsLevelsMsg);
+    if (!level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (direct_on(c) != (levels_on(c) && on)) {  // the moment arrays change length: start them afresh (as mcbrat_specify_level_fluxes does)
+    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+    c->dMoments = nullptr;
+    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+    c->haveLast = false;
+    c->tuned = false;  // (other kernels: the event threshold is chosen again)
+  }
+  c->directLevelFluxes = on;
+  return 0;
+}
+
+int mcbrat_report_direct_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxDownDirect, float *meanLevelFluxDownDiffuse, float *levelFluxDownDirect,
+                                      float *levelFluxDownDiffuse) {
+  if (!c) return 1;
+  if (!direct_on(c)) return fail(c, "reportResults: direct level-flux information not available");
+  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  // the direct / diffuse tail of the last batch's results: [meanDirect | meanDiffuse | direct | diffuse], in Fortran order (nx, ny, 0:nz)
+  const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;
+  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_direct_at(c);
+  std::vector<float> h(n);
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * n, hipMemcpyDeviceToHost));
+  const float *q = h.data();
+  const auto take = [&](float *dst, size_t m) { if (dst) std::memcpy(dst, q, sizeof(float) * m); q += m; };
+  take(meanLevelFluxDownDirect, nLvl);
+  take(meanLevelFluxDownDiffuse, nLvl);
+  take(levelFluxDownDirect, ncol * nLvl);
+  take(levelFluxDownDiffuse, ncol * nLvl);
   return 0;
 }
 
@@ -1857,7 +1933,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   if (orders_on(c) && c->countersOn)
     return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
   if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
-  if (levels_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, kLevelsBudgetMsg);
+  if (levels_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
   size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
@@ -1867,7 +1943,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     mcbrat_ctx::Lane &L = c->lane[li];
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
     const size_t nOrdMeans = orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + c->nDir) : 0;  // (domain means by order, behind the scalars)
-    const size_t nLvlMeans = levels_on(c) ? 2 * ((size_t)c->nz + 1) : 0;  // (domain means by level, behind those)
+    const size_t nLvlMeans = level_quantities(c) * ((size_t)c->nz + 1);  // (domain means by level, behind those)
     const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans + nLvlMeans) * inFlight;
     if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
     HIP_OK(c, hipStreamSynchronize(L.stream));
@@ -1949,9 +2025,11 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.nLvl = levels_on(c) ? c->nz + 1 : 0;
     f.lvlSlab = (long long)(slabStride - level_bins(c));
     f.lvlVals = f.ordVals + (size_t)((2 + c->nDir) * f.nOrd) * nb;
-    f.gatherLevels = (unsigned)((2 * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
-    f.gatherLevelMeans = (unsigned)(2 * f.nLvl) * (unsigned)nb;
-    f.foldLevelMeans = (unsigned)((2 * f.nLvl + kFinishBlock - 1) / kFinishBlock);
+    f.lvlDirect = direct_on(c) ? 1 : 0;
+    const size_t nLvlQ = level_quantities(c);  // (up, down; with the direct tally direct and diffuse too)
+    f.gatherLevels = (unsigned)((nLvlQ * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
+    f.gatherLevelMeans = (unsigned)(nLvlQ * f.nLvl) * (unsigned)nb;
+    f.foldLevelMeans = (unsigned)((nLvlQ * f.nLvl + kFinishBlock - 1) / kFinishBlock);
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
     hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans),

@@ -30,7 +30,7 @@ def balanced_job(totalPhotons, numBatches, world):
     return ppb, nb
 
 
-def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False):
+def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False, directLevelFluxes=False):
     """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order.
 
     With scattering orders (numRecScatOrd >= 0) the arrays end in the order tail of include/mcbrat.h, unpacked with the order
@@ -39,18 +39,24 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
     tells it.
 
     With level fluxes (levelFluxes=True) the arrays end in the level tail: meanLevelFluxUp[k], meanLevelFluxDown[k],
-    levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k], k = 0 .. nz.  The length is then checked against the layout asked for."""
+    levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k], k = 0 .. nz.  The length is then checked against the layout asked for.
+
+    With their direct / diffuse separation (directLevelFluxes=True, which needs levelFluxes=True) the direct tail follows the level
+    tail: meanLevelFluxDownDirect[k], meanLevelFluxDownDiffuse[k], levelFluxDownDirect[ix, iy, k], levelFluxDownDiffuse[ix, iy, k]."""
+    if directLevelFluxes and not levelFluxes:
+        raise ValueError("unpack_moments: directLevelFluxes needs levelFluxes")
     ncol, nvox = nx * ny, nx * ny * nz
     M = 3 + 3 * ncol + nz + nvox
     nOrd = int(numRecScatOrd) + 1 if numRecScatOrd is not None and int(numRecScatOrd) >= 0 else 0
     nLvl = nz + 1 if levelFluxes else 0
+    nLvlQ = 4 if directLevelFluxes else 2  # level quantities: up, down (, direct, diffuse)
     if nDirections is None:  # the length tells
         if nOrd:
             raise ValueError("unpack_moments: with numRecScatOrd >= 0 the number of directions must be given (nDirections=)")
-        nDirections = ((len(buf) - 8) // 2 - M - 2 * nLvl * (1 + ncol)) // ncol
+        nDirections = ((len(buf) - 8) // 2 - M - nLvlQ * nLvl * (1 + ncol)) // ncol
     if nDirections < 0:
         raise ValueError("unpack_moments: %d doubles are too few for the layout asked for" % len(buf))
-    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol) + 2 * nLvl * (1 + ncol)
+    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol) + nLvlQ * nLvl * (1 + ncol)
     S1, S2 = buf[8:8 + M], buf[8 + M:8 + 2 * M]
     out = {"totalPhotons": buf[0], "batches": buf[1]}
     names = [("meanFluxUp", 1, None), ("meanFluxDown", 1, None), ("meanFluxAbsorbed", 1, None),
@@ -67,6 +73,9 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
     if nLvl:
         names += [("meanLevelFluxUp", nLvl, (nLvl,)), ("meanLevelFluxDown", nLvl, (nLvl,)),
                   ("levelFluxUp", nLvl * ncol, (nLvl, ny, nx)), ("levelFluxDown", nLvl * ncol, (nLvl, ny, nx))]
+        if directLevelFluxes:
+            names += [("meanLevelFluxDownDirect", nLvl, (nLvl,)), ("meanLevelFluxDownDiffuse", nLvl, (nLvl,)),
+                      ("levelFluxDownDirect", nLvl * ncol, (nLvl, ny, nx)), ("levelFluxDownDiffuse", nLvl * ncol, (nLvl, ny, nx))]
     if (nOrd or nLvl) and len(buf) != 8 + 2 * M:
         raise ValueError("unpack_moments: %d doubles, the layout asked for has %d" % (len(buf), 8 + 2 * M))
     o = 0
@@ -177,6 +186,8 @@ def run(integrator, domain, photons, numPhotonsPerBatch, numBatches, randomNumbe
     nx, ny, nz = integrator._dims
     nOrd = getattr(integrator, "numRecScatOrd", -1)
     levels = bool(getattr(integrator, "recLevelFluxes", False))
+    direct = levels and bool(getattr(integrator, "recDirectLevelFluxes", False))
     if nOrd >= 0 or levels:
-        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels), solarFlux)
+        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels,
+                                         directLevelFluxes=direct), solarFlux)
     return statistics(unpack_moments(buf, nx, ny, nz), solarFlux)

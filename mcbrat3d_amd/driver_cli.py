@@ -21,7 +21,7 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
                        hybridphasefunwidth=7.0, numordersorigphasefunintencalcs=0, userussianrouletteforintensity=True,
                        zetamin=0.3, limitintensitycontributions=False, maxintensitycontribution=77.0),
     "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False, recscatord=False, numrecscatord=0,
-                   reportlevelfluxes=False),
+                   reportlevelfluxes=False, reportdirectlevelfluxes=False),
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
 }
@@ -235,6 +235,9 @@ def main(argv=None):
         if cfg["reportlevelfluxes"]:
             raise SystemExit("reportLevelFluxes: level fluxes are not available for spectrally integrated runs (numLambda > 1 "
                              "or thermal emission)")
+        if cfg["reportdirectlevelfluxes"]:
+            raise SystemExit("reportDirectLevelFluxes: direct level fluxes are not available for spectrally integrated runs "
+                             "(numLambda > 1 or thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -277,6 +280,8 @@ def main(argv=None):
         integ.specifyParameters(recScatOrd=True, numRecScatOrd=numRecScatOrd)
     if cfg["reportlevelfluxes"]:  # (refused by specifyParameters together with intensity directions or scattering orders)
         integ.specifyParameters(recLevelFluxes=True)
+    if cfg["reportdirectlevelfluxes"]:  # (refused by specifyParameters without reportLevelFluxes)
+        integ.specifyParameters(recDirectLevelFluxes=True)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -298,7 +303,11 @@ def main(argv=None):
             for k in range(len(dom.zPosition) - 1, -1, -1):
                 print(" level %3d z %9.4f mean flux up/down: %9.6f +-%9.6f  %9.6f +-%9.6f" % (
                     k, dom.zPosition[k], stats["meanLevelFluxUp"][k], stats["meanLevelFluxUp_StdErr"][k],
-                    stats["meanLevelFluxDown"][k], stats["meanLevelFluxDown_StdErr"][k]))
+                    stats["meanLevelFluxDown"][k], stats["meanLevelFluxDown_StdErr"][k]) + (
+                    "  direct/diffuse: %9.6f +-%9.6f  %9.6f +-%9.6f" % (
+                        stats["meanLevelFluxDownDirect"][k], stats["meanLevelFluxDownDirect_StdErr"][k],
+                        stats["meanLevelFluxDownDiffuse"][k], stats["meanLevelFluxDownDiffuse_StdErr"][k])
+                    if cfg["reportdirectlevelfluxes"] else ""))
         xe, ye, ze = dom.xPosition, dom.yPosition, dom.zPosition
         if cfg["outputfluxfile"]:
             writeResults_ASCII(cfg["outputfluxfile"], cfg, domfile, stats, xe, ye, ze, 1.0, dom.surfaceAlbedo)

@@ -77,6 +77,8 @@ class Integrator:
         self.numRecScatOrd = -1
         # upward and downward flux through every level of every column
         self.recLevelFluxes = False
+        # the direct beam apart from the diffuse light in the downward level flux; needs recLevelFluxes
+        self.recDirectLevelFluxes = False
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -117,7 +119,8 @@ class Integrator:
                               numOrdersOrigPhaseFunIntenCalcs=self.numOrdersOrigPhaseFunIntenCalcs,
                               limitIntensityContributions=self.limitIntensityContributions,
                               maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF,
-                              numRecScatOrd=self.numRecScatOrd, recLevelFluxes=self.recLevelFluxes)
+                              numRecScatOrd=self.numRecScatOrd, recLevelFluxes=self.recLevelFluxes,
+                              recDirectLevelFluxes=self.recDirectLevelFluxes)
         return new
 
     def _check(self, rc):
@@ -137,10 +140,19 @@ class Integrator:
                           useRussianRouletteForIntensity=None, zetaMin=None, useHybridPhaseFunsForIntenCalcs=None,
                           hybridPhaseFunWidth=None, numOrdersOrigPhaseFunIntenCalcs=None,
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
-                          recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, **unsupported):
+                          recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, recDirectLevelFluxes=None, **unsupported):
         # level fluxes: what they cannot be combined with is refused as the library refuses it -- here,
         # before anything of this call is kept, so that a refused call leaves the integrator as it was
         levels = self.recLevelFluxes if recLevelFluxes is None else bool(recLevelFluxes)
+        direct = self.recDirectLevelFluxes if recDirectLevelFluxes is None else bool(recDirectLevelFluxes)
+        if direct:  # (with level fluxes only, and refused with everything they are refused with, below)
+            if not levels:
+                raise McbratError("specifyParameters: direct level fluxes (recDirectLevelFluxes) need level fluxes (recLevelFluxes): "
+                                  "they separate the downward level flux.")
+            nx, ny, nz = self._dims
+            if 3 * nx * ny * (nz + 1) * 8 > 4 << 30:
+                raise McbratError("specifyParameters: direct level fluxes (recDirectLevelFluxes): the level bins of one batch would "
+                                  "not fit the 4 GiB tally budget.")
         if levels:
             directions = self.numIntensityDirections()
             if intensityMus is not None:
@@ -242,6 +254,7 @@ class Integrator:
             self.LW_flag = float(LW_flag)
         self.numRecScatOrd, self.recScatOrd = orders, orders >= 0
         self.recLevelFluxes = levels
+        self.recDirectLevelFluxes = direct
         self._push_parameters()
 
     def _push_parameters(self):
@@ -255,9 +268,18 @@ class Integrator:
         self._push_intensity()
 
     def _push_levels(self):
+        # (the direct tally needs level fluxes: off before them, on after them)
+        if not self.recDirectLevelFluxes:
+            self._push_direct_levels()
         if self.recLevelFluxes != getattr(self, "_levels_token", False):
             self._check(self._lib.mcbrat_specify_level_fluxes(self._ctx, int(self.recLevelFluxes)))
             self._levels_token = self.recLevelFluxes
+        self._push_direct_levels()
+
+    def _push_direct_levels(self):
+        if self.recDirectLevelFluxes != getattr(self, "_direct_levels_token", False):
+            self._check(self._lib.mcbrat_specify_direct_level_fluxes(self._ctx, int(self.recDirectLevelFluxes)))
+            self._direct_levels_token = self.recDirectLevelFluxes
 
     def _push_intensity(self):
         if not self.recLevelFluxes:
@@ -472,14 +494,24 @@ class Integrator:
 
     def reportLevelFluxes(self):
         """The last batch's upward and downward flux through every level: levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k] and
-        their domain means meanLevelFluxUp[k], meanLevelFluxDown[k]; level k = 0 .. numZ is the face zPosition[k]."""
+        their domain means meanLevelFluxUp[k], meanLevelFluxDown[k]; level k = 0 .. numZ is the face zPosition[k].  With
+        recDirectLevelFluxes also levelFluxDownDirect / levelFluxDownDiffuse[ix, iy, k] -- the parts of levelFluxDown carried by
+        photons that have not yet collided or reached the surface, and by the others -- and their domain means."""
         nx, ny, nz = self._dims
         nl = nz + 1
         mu, md = np.zeros(nl, np.float32), np.zeros(nl, np.float32)
         up, dn = np.zeros(nl * nx * ny, np.float32), np.zeros(nl * nx * ny, np.float32)
         self._check(self._lib.mcbrat_report_level_fluxes(self._ctx, ptr(mu), ptr(md), ptr(up), ptr(dn)))
-        return dict(meanLevelFluxUp=mu, meanLevelFluxDown=md, levelFluxUp=up.reshape(nl, ny, nx).transpose(2, 1, 0),
-                    levelFluxDown=dn.reshape(nl, ny, nx).transpose(2, 1, 0))
+        res = dict(meanLevelFluxUp=mu, meanLevelFluxDown=md, levelFluxUp=up.reshape(nl, ny, nx).transpose(2, 1, 0),
+                   levelFluxDown=dn.reshape(nl, ny, nx).transpose(2, 1, 0))
+        if self.recDirectLevelFluxes:
+            mdir, mdif = np.zeros(nl, np.float32), np.zeros(nl, np.float32)
+            dirc, dif = np.zeros(nl * nx * ny, np.float32), np.zeros(nl * nx * ny, np.float32)
+            self._check(self._lib.mcbrat_report_direct_level_fluxes(self._ctx, ptr(mdir), ptr(mdif), ptr(dirc), ptr(dif)))
+            res.update(meanLevelFluxDownDirect=mdir, meanLevelFluxDownDiffuse=mdif,
+                       levelFluxDownDirect=dirc.reshape(nl, ny, nx).transpose(2, 1, 0),
+                       levelFluxDownDiffuse=dif.reshape(nl, ny, nx).transpose(2, 1, 0))
+        return res
 
     # -- batch moments (what the driver keeps in *Stats and reduces over processes) -----
     def momentsLength(self):

@@ -215,7 +215,10 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
         if "levelFluxUp" in stats:  # level fluxes (reportLevelFluxes): Fortran dims (x, y, zLevel), the levels are the z edges
             f.createDimension("zLevel", len(ze))
             f.createVariable("zLevel", "d", ("zLevel",))[:] = ze
-            for name in ("levelFluxUp", "levelFluxDown"):
+            names = ("levelFluxUp", "levelFluxDown")
+            if "levelFluxDownDirect" in stats:  # their direct / diffuse separation (reportDirectLevelFluxes)
+                names += ("levelFluxDownDirect", "levelFluxDownDiffuse")
+            for name in names:
                 f.createVariable(name, "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
                 f.createVariable(name + "_StdErr", "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name + "_StdErr"]).transpose(2, 1, 0)
     finally:
