@@ -12,7 +12,8 @@
 ! mcbrat3d_amd.flatdomain.write_flat_domain (any domain the Python host layer can build).
 program mcbrat_driver
   use mcbrat_hip_integrator, lastBatchLevelFluxes => reportLevelFluxes, &   ! (the /output/ namelist has variables of these names)
-                             lastBatchDirectLevelFluxes => reportDirectLevelFluxes
+                             lastBatchDirectLevelFluxes => reportDirectLevelFluxes, &
+                             lastBatchActinicFlux => reportActinicFlux
   implicit none
   ! --- namelist variables (names and defaults of the reference driver) ---
   real     :: solarMu = 1., solarAzimuth = 0., LW_flag = -1.
@@ -35,7 +36,7 @@ program mcbrat_driver
   logical  :: reportVolumeAbsorption = .false., reportAbsorptionProfile = .false.
   logical  :: recScatOrd = .false.
   integer  :: numRecScatOrd = 0
-  logical  :: reportLevelFluxes = .false., reportDirectLevelFluxes = .false.
+  logical  :: reportLevelFluxes = .false., reportDirectLevelFluxes = .false., reportActinicFlux = .false.
   character(len=256) :: auxhist01_radFile = "", auxhist01_fluxFile = ""
   character(len=256) :: solarSourceFile = "", instrResponseFile = "", physDomainFile = ""
   character(len=256), dimension(4) :: SSPfilename = ""
@@ -49,7 +50,8 @@ program mcbrat_driver
                                useRussianRouletteForIntensity, zetaMin, limitIntensityContributions, &
                                maxIntensityContribution
   namelist /output/            reportVolumeAbsorption, reportAbsorptionProfile, recScatOrd, numRecScatOrd, &
-                               reportLevelFluxes, reportDirectLevelFluxes, auxhist01_fluxFile, auxhist01_radFile
+                               reportLevelFluxes, reportDirectLevelFluxes, reportActinicFlux, auxhist01_fluxFile, &
+                               auxhist01_radFile
   namelist /fileNames/         solarSourceFile, instrResponseFile, SSPfilename, physDomainFile, &
                                outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, &
                                outputNetcdfFile
@@ -65,7 +67,7 @@ program mcbrat_driver
   real(8), allocatable :: moments(:)
   real(8), allocatable :: meanStats(:,:), fluxUpStats(:,:,:), fluxDownStats(:,:,:), fluxAbsorbedStats(:,:,:), &
                           absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:), &
-                          meanLevelStats(:,:,:)
+                          meanLevelStats(:,:,:), meanActinicStats(:,:)
   real,    allocatable :: forwardTable(:,:), legendreCoefficients(:)
   integer :: numRadDir, off, nLevelStats
   logical :: computeIntensity
@@ -83,6 +85,8 @@ program mcbrat_driver
   if (len_trim(physDomainFile) == 0) stop "must specify physDomainFile"
   if (reportDirectLevelFluxes .and. (numLambda > 1 .or. LW_flag >= 0.)) &
     stop "reportDirectLevelFluxes: direct level fluxes are not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
+  if (reportActinicFlux .and. (numLambda > 1 .or. LW_flag >= 0.)) &
+    stop "reportActinicFlux: the actinic flux is not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
   solarFlux = 1.0_8
 
   call cpu_time(t0)
@@ -122,6 +126,10 @@ program mcbrat_driver
   ! their direct / diffuse separation (refused without reportLevelFluxes)
   if (reportDirectLevelFluxes) then
     call specifyDirectLevelFluxes(mcIntegrator, .true., ierr); call check("specifyParameters")
+  end if
+  ! the actinic flux of every cell by track length (refused together with directions, orders and the direct level tally)
+  if (reportActinicFlux) then
+    call specifyActinicFlux(mcIntegrator, .true., ierr); call check("specifyParameters")
   end if
   call setSolarSource(mcIntegrator, solarMu, solarAzimuth, ierr); call check("setSolarSource")
   call resetMoments(mcIntegrator, ierr); call check("resetMoments")
@@ -177,7 +185,7 @@ program mcbrat_driver
     ! reportDirectLevelFluxes the first 2 (nz+1) of the direct / diffuse tail behind it (meanStats 3, 4: direct, diffuse)
     nLevelStats = merge(4, 2, reportDirectLevelFluxes)
     allocate(meanLevelStats(0:nz, nLevelStats, 2))
-    off = int(M) - nLevelStats*(nz+1)*(1+ncol)
+    off = int(M) - nLevelStats*(nz+1)*(1+ncol) - merge(nz*(1+ncol), 0, reportActinicFlux)   ! (the actinic tail lies behind)
     do k = 1, 2
       do j = 1, nLevelStats
         i = off + merge(2*(nz+1)*(1+ncol), 0, j > 2) + (j - merge(3, 1, j > 2))*(nz+1)
@@ -197,6 +205,18 @@ program mcbrat_driver
         print '(A,I3,A,F9.4,A,2(2X,F9.6,A,F9.6))', " level ", i, " z ", zPosition(i+1), " mean flux up/down:", &
               meanLevelStats(i, 1, 1), " +-", meanLevelStats(i, 1, 2), meanLevelStats(i, 2, 1), " +-", meanLevelStats(i, 2, 2)
       end if
+    end do
+  end if
+  if (reportActinicFlux) then   ! layer means of the actinic flux: the first nz entries of the actinic tail, the last of all
+    allocate(meanActinicStats(nz, 2))
+    off = int(M) - nz*(1+ncol)
+    do k = 1, 2
+      meanActinicStats(:, k) = moments(8 + (k-1)*M + off + 1 : 8 + (k-1)*M + off + nz)
+    end do
+    call momentsToStats1(meanActinicStats)
+    do i = nz, 1, -1
+      print '(A,I3,A,F9.4,A,F9.4,A,2X,F9.6,A,F9.6)', " layer ", i - 1, " z ", zPosition(i), " -", zPosition(i+1), &
+            " mean actinic flux:", meanActinicStats(i, 1), " +-", meanActinicStats(i, 2)
     end do
   end if
   if (len_trim(outputFluxFile) > 0) call writeFluxASCII()

@@ -31,7 +31,7 @@ module mcbrat_hip_integrator
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
             setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
             specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes, &
-            specifyDirectLevelFluxes, reportDirectLevelFluxes
+            specifyDirectLevelFluxes, reportDirectLevelFluxes, specifyActinicFlux, reportActinicFlux
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -221,6 +221,17 @@ module mcbrat_hip_integrator
         bind(C, name="mcbrat_report_direct_level_fluxes") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, mDirect, mDiffuse, fDirect, fDiffuse   ! (c_null_ptr: not wanted)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_specify_actinic_flux(ctx, enable) bind(C, name="mcbrat_specify_actinic_flux") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: enable
+      integer(c_int) :: rc
+    end function
+    function mcbrat_report_actinic_flux(ctx, mActinic, fActinic) bind(C, name="mcbrat_report_actinic_flux") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, mActinic, fActinic   ! (c_null_ptr: not wanted)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -721,6 +732,35 @@ contains
     end if
     ierr = mcbrat_report_direct_level_fluxes(this%ctx, mDirect, mDiffuse, fDirect, fDiffuse)
   end subroutine reportDirectLevelFluxes
+
+  ! specifyParameters(recActinicFlux): the actinic flux of every cell by track length.  Solar sources only; may be combined with
+  ! level fluxes, not with their direct tally.  Changes momentsLength().
+  subroutine specifyActinicFlux(this, enable, ierr)
+    type(integrator), intent(inout) :: this
+    logical,          intent(in)    :: enable
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_specify_actinic_flux(this%ctx, merge(1_c_int32_t, 0_c_int32_t, enable))
+  end subroutine specifyActinicFlux
+
+  ! the last batch's actinic flux: meanActinicFlux(numZ), actinicFlux(numX, numY, numZ)
+  subroutine reportActinicFlux(this, meanActinicFlux, actinicFlux, ierr)
+    type(integrator), intent(inout) :: this
+    real, dimension(:),       contiguous, optional, target, intent(out) :: meanActinicFlux
+    real, dimension(:, :, :), contiguous, optional, target, intent(out) :: actinicFlux
+    integer,                  intent(out) :: ierr
+    type(c_ptr) :: mActinic, fActinic
+    mActinic = c_null_ptr; fActinic = c_null_ptr
+    ierr = 2   ! "reportResults: actinicFlux is the wrong size"
+    if (present(meanActinicFlux)) then
+      if (size(meanActinicFlux) /= this%numZ) return
+      mActinic = c_loc(meanActinicFlux)
+    end if
+    if (present(actinicFlux)) then
+      if (any(shape(actinicFlux) /= (/ this%numX, this%numY, this%numZ /))) return
+      fActinic = c_loc(actinicFlux)
+    end if
+    ierr = mcbrat_report_actinic_flux(this%ctx, mActinic, fActinic)
+  end subroutine reportActinicFlux
 
   integer(8) function numBadPhotons(this)
     type(integrator), intent(in) :: this

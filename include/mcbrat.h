@@ -217,6 +217,21 @@ int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *ctx, int32_t enable);
 int mcbrat_report_direct_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxDownDirect, float *meanLevelFluxDownDiffuse,
                                       float *levelFluxDownDirect, float *levelFluxDownDiffuse);
 
+/* The actinic flux of every cell by track length (specifyParameters(recActinicFlux); an addition under ABI version 3; DESIGN.md
+ * section 4.14).  The raw tally of cell (x, y, k) is the sum of w l over every piece of a photon's path inside the cell: w the
+ * weight carried on that leg, l the piece's length in km -- the launch leg and the legs after a Lambertian reflection (with the
+ * weight after the albedo) included.  actinicFlux(x, y, k) = sum / (photons per column * dz_k): dimensionless, per unit flux
+ * through a horizontal unit area at the top (a vacuum under an overhead sun gives 1 in every cell, under mu0 the layer mean is
+ * 1 / mu0).  The expectation of volumeAbsorption is sigma_abs * actinicFlux / 1000 (sigma_abs in 1/km).  meanActinicFlux(k) is
+ * the sum over the columns of layer k divided by their number.  Such runs use the face-by-face walk, as level fluxes do, and
+ * may be combined with them.  Solar sources only (mcbrat_compute_radiative_transfer fails with the thermal one); fails together
+ * with intensity directions, scattering orders, a BRDF surface, event counters / photon fates, direct level fluxes, and where
+ * one batch's level and actinic bins would not fit the tally budget -- whichever call comes first.  Changes
+ * mcbrat_moments_length(): a caller-bound moment buffer must be bound again. */
+int mcbrat_specify_actinic_flux(mcbrat_ctx *ctx, int32_t enable);
+/* The LAST batch, Fortran order with the layer slowest: meanActinicFlux(nz), actinicFlux(nx, ny, nz).  Any pointer may be NULL. */
+int mcbrat_report_actinic_flux(mcbrat_ctx *ctx, float *meanActinicFlux, float *actinicFlux);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:
@@ -231,7 +246,8 @@ int mcbrat_report_direct_level_fluxes(mcbrat_ctx *ctx, float *meanLevelFluxDownD
  *   and with level fluxes, after everything else: meanLevelFluxUp[nz+1], meanLevelFluxDown[nz+1],
  *   levelFluxUp[(nz+1)*nx*ny], levelFluxDown[(nz+1)*nx*ny] (level slowest, x fastest),
  *   and with direct level fluxes, behind those: meanLevelFluxDownDirect[nz+1], meanLevelFluxDownDiffuse[nz+1],
- *   levelFluxDownDirect[(nz+1)*nx*ny], levelFluxDownDiffuse[(nz+1)*nx*ny].
+ *   levelFluxDownDirect[(nz+1)*nx*ny], levelFluxDownDiffuse[(nz+1)*nx*ny],
+ *   and with the actinic flux, behind every other tail: meanActinicFlux[nz], actinicFlux[nz*nx*ny] (layer slowest, x fastest).
  * Total doubles = 8 + 2*length.  The buffer is device memory; a caller that
  * wants to all-reduce it with RCCL binds its own device buffer. */
 int64_t mcbrat_moments_length(const mcbrat_ctx *ctx);

@@ -125,6 +125,8 @@ struct mcbrat_ctx {
   int levelFluxes = 0;
   // the direct beam apart from the diffuse light in the downward level flux (mcbrat_specify_direct_level_fluxes)
   int directLevelFluxes = 0;
+  // the actinic flux of every cell by track length (mcbrat_specify_actinic_flux)
+  int actinicFlux = 0;
   // parameters
   float albedo = 0.f;
   int useRR = 1;
@@ -263,19 +265,31 @@ size_t level_quantities(const mcbrat_ctx *c) { return levels_on(c) ? (direct_on(
 size_t level_bins(const mcbrat_ctx *c) { return level_parts(c) * (size_t)c->nx * c->ny * ((size_t)c->nz + 1); }
 // whether the level bins of one batch of an nx x ny x nz grid fit the tally budget (in double: the product may pass 2^64)
 bool level_bins_fit(double parts, double nx, double ny, double nz);
+// the actinic flux of every cell: one bin per cell behind the level parts of a batch's slab, layer slowest
+bool actinic_on(const mcbrat_ctx *c) { return c->actinicFlux != 0; }
+size_t actinic_bins(const mcbrat_ctx *c) { return actinic_on(c) ? (size_t)c->nx * c->ny * (size_t)c->nz : 0; }
+// the tallies that make every cell face a stop: the plan then walks face by face (no layer skipping, flight, block walk, wide
+// plan, bricks or 768-lane kernel), and their bins stay in global memory
+bool facewalk_on(const mcbrat_ctx *c) { return levels_on(c) || actinic_on(c); }
+size_t global_bins(const mcbrat_ctx *c) { return level_bins(c) + actinic_bins(c); }
+// whether the level parts and the actinic part of one batch of an nx x ny x nz grid fit the tally budget together
+bool global_bins_fit(double levelParts, bool actinic, double nx, double ny, double nz);
 
 // [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest,
 // then the level fluxes: [meanLevelUp (nz+1) | meanLevelDown (nz+1) | levelUp ncol (nz+1) | levelDown ncol (nz+1)]
 // then their direct / diffuse separation: [meanDirect (nz+1) | meanDiffuse (nz+1) | direct ncol (nz+1) | diffuse ncol (nz+1)]
+// then, behind every other tail, the actinic flux: [meanActinic nz | actinic ncol nz]
+long long moments_actinic_len(const mcbrat_ctx *c) { return actinic_on(c) ? (long long)c->nz * (1 + (long long)c->nx * c->ny) : 0; }
 long long moments_len(const mcbrat_ctx *c) {
   const long long ncol = (long long)c->nx * c->ny;
   return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol +
          (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0) +
-         (long long)level_quantities(c) * (c->nz + 1) * (1 + ncol);
+         (long long)level_quantities(c) * (c->nz + 1) * (1 + ncol) + moments_actinic_len(c);
 }
+long long moments_actinic_at(const mcbrat_ctx *c) { return moments_len(c) - moments_actinic_len(c); }
 // where the level tail starts in the moments (behind the orders' tail) and where the direct / diffuse tail does
 long long moments_levels_at(const mcbrat_ctx *c) {
-  return moments_len(c) - (long long)level_quantities(c) * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
+  return moments_actinic_at(c) - (long long)level_quantities(c) * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
 }
 long long moments_direct_at(const mcbrat_ctx *c) {
   return moments_levels_at(c) + 2LL * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
@@ -283,12 +297,13 @@ long long moments_direct_at(const mcbrat_ctx *c) {
 
 // Elements of one batch's tally slab: [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:)
 // intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1) |
-// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1) | (their direct tally:) levelDirect ncol (nz+1)]
+// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1) | (their direct tally:) levelDirect ncol (nz+1) |
+// (actinic flux:) actinic ncol nz]
 // fluxRun: the slab of a flux launch of the loaded domain (no intensity parts), what mcbrat_get_walk_mode reports on.
 size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz, nDir = fluxRun ? 0 : (size_t)c->nDir;
   return 2 * ncol + nvox + nDir * ncol + (c->limitContrib && !fluxRun ? (size_t)(c->nc + 1) * nDir * (ncol + 1) : 0) +
-         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0) + level_bins(c);
+         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0) + global_bins(c);
 }
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
 constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
@@ -310,6 +325,40 @@ const char *const kDirectThermalMsg =
     "computeRadiativeTransfer: direct level fluxes (recDirectLevelFluxes) are not available with the thermal source: there is no direct beam.";
 const char *const kDirectBudgetMsg =
     "specifyParameters: direct level fluxes (recDirectLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
+// The actinic flux is tallied by solar flux kernels on the face-by-face walk only: what it is refused with
+const char *const kActinicIntensityMsg =
+    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with intensity directions: the radiance kernels have no track-length tally.";
+const char *const kActinicOrdersMsg =
+    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with scattering orders (recScatOrd): no kernel tallies both.";
+const char *const kActinicBrdfMsg =
+    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with a BRDF surface: a reflected weight may exceed 1, which the track-length tally does not hold.";
+const char *const kActinicCountersMsg =
+    "specifyParameters: the actinic flux (recActinicFlux) is not available together with event counters / photon fates: the instrumented kernels have no track-length tally.";
+const char *const kActinicDirectMsg =
+    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with direct level fluxes (recDirectLevelFluxes): no kernel tallies both.";
+const char *const kActinicBudgetMsg =
+    "specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch would not fit the 4 GiB tally budget.";
+const char *const kActinicThermalMsg =
+    "computeRadiativeTransfer: the actinic flux (recActinicFlux) is not available with the thermal source: the track-length tally is built for solar sources only.";
+// The fixed point of an actinic deposit: 2^e km, e the smallest integer that keeps the longest possible step of the walk below
+// 2^e -- the diagonal of the largest spacings of the three axes, times 1 + 2^-10 for the float rounding of tmin - tcur (a few
+// ulp of the distance along the leg, which may be many steps long).  The kernel deposits w l 2^-e, the epilogue multiplies
+// 2^e back in double: a power of two, so the scaling itself is exact.  Chosen once per grid.
+double actinic_unit(const mcbrat_ctx *c) {
+  const auto widest = [](const std::vector<double> &e) {
+    double m = 0.0;
+    for (size_t i = 0; i + 1 < e.size(); ++i) m = std::max(m, e[i + 1] - e[i]);
+    return m;
+  };
+  const double wx = widest(c->xe), wy = widest(c->ye), wz = widest(c->ze);
+  const double longest = std::sqrt(wx * wx + wy * wy + wz * wz) * (1.0 + 1.0 / 1024.0);
+  int e = 0;
+  (void)std::frexp(longest, &e);  // longest = m 2^e with m in [0.5, 1)
+  return std::ldexp(1.0, e);
+}
+bool global_bins_fit(double levelParts, bool actinic, double nx, double ny, double nz) {
+  return (levelParts * nx * ny * (nz + 1.0) + (actinic ? nx * ny * nz : 0.0)) * sizeof(long long) <= (double)kSlabBudget;
+}
 bool level_bins_fit(double parts, double nx, double ny, double nz) { return parts * nx * ny * (nz + 1.0) * sizeof(long long) <= (double)kSlabBudget; }
 const char *const kOrdersLimitMsg =
     "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
@@ -537,7 +586,7 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
 // dense grid is as fast or 1-3 % faster, so the automatic rule only switches
 // for grids of 64 MiB and more.
 bool use_bricks(const mcbrat_ctx *c) {
-  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0 || orders_on(c) || levels_on(c)) return false;  // (radiance rays read the dense grid; no ORD or LVL kernel reads bricks)
+  if (!c->bricksBuilt || c->brickMode == 0 || c->nDir > 0 || orders_on(c) || facewalk_on(c)) return false;  // (radiance rays read the dense grid; no ORD, LVL or ACT kernel reads bricks)
   if (c->brickMode == 1) return true;
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   // automatic: the dense layout is the faster one wherever measured (128x128x64: equal; 512x512x128: 83 vs 105 ms per
@@ -562,7 +611,8 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.xyRegularWalk = (c->xyRegular && c->regularWalk) ? 1 : 0;
   p.zRegularWalk = (c->zRegular && c->regularWalk) ? 1 : 0;
   p.dXf = (float)((p.xMax - p.x0) / c->nx); p.dYf = (float)((p.yMax - p.y0) / c->ny); p.dZf = (float)((p.zMax - p.z0) / c->nz);
-  p.layerSkip = (c->layerSkip && !levels_on(c)) ? 1 : 0;  // (level fluxes: every z face is a stop)
+  p.layerSkip = (c->layerSkip && !facewalk_on(c)) ? 1 : 0;  // (level fluxes: every z face is a stop; actinic flux: every face)
+  p.actScale = actinic_on(c) ? (float)(1.0 / actinic_unit(c)) : 0.0f;
   p.layerRun = c->dLayerRun; p.layerRunT = c->dLayerRunT;
   p.fly = 0; p.flyNbx = p.flyNby = 0;  // (switched on by launch_trace where the plan allows it)
   p.flyRange = c->dFlyRange; p.bgVal = c->dBgVal;
@@ -647,7 +697,7 @@ size_t per_layer_lds(int nz, int flyCols = 0) {
 
 // clear-air flight: asked for (layerSkip 1: where the background is thin enough for it to pay; 3: regardless) and possible
 bool flight_wanted(const mcbrat_ctx *c) {
-  return !levels_on(c) && c->flyBuilt && (c->layerSkip == 3 || (c->layerSkip == 1 && c->flyDepth <= c->flightMaxDepth));
+  return !facewalk_on(c) && c->flyBuilt && (c->layerSkip == 3 || (c->layerSkip == 1 && c->flyDepth <= c->flightMaxDepth));
 }
 
 struct LaunchPlan {
@@ -666,7 +716,7 @@ struct LaunchPlan {
 };
 
 bool blocks_worth_it(const mcbrat_ctx *c) {
-  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c) || levels_on(c)) return false;  // (the block walk has no ORD or LVL variant)
+  if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c) || facewalk_on(c)) return false;  // (the block walk has no ORD, LVL or ACT variant)
   if (c->surfNumX > 0 && c->surfKind != 0) return false;  // (nor a BRDF one: such surfaces go face by face)
   const size_t nvox = (size_t)c->nx * c->ny * c->nz;
   return (size_t)c->nBlocks * 4 <= nvox || c->blockWalk == 2;  // (2: forced, for tests of heterogeneous media)
@@ -677,7 +727,7 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.wide = false; L.blockLite = false; L.optics = 0; L.cdfTop = false;
   const size_t edges = sizeof(double) * (size_t)(c->nx + c->ny + c->nz + 3);
   const size_t tbl = sizeof(float) * (size_t)c->tblTotalFloats;
-  const size_t slab = sizeof(long long) * (slabStride - level_bins(c)) + 16;  // (the level bins are never part of the LDS slab)
+  const size_t slab = sizeof(long long) * (slabStride - global_bins(c)) + 16;  // (the level and actinic bins are never part of the LDS slab)
   L.priv = c->privMode != 0 && slab <= kPrivSlabLimit;
   L.brick = use_bricks(c);
   const size_t bg = per_layer_lds(c->nz);  // per-layer extinction (background / one-extinction layers) and the runs of such layers
@@ -693,16 +743,16 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
     L.tblLds = false;
     L.gridLds = true;
   }
-  // level fluxes: the LVL kernels are built for everything in LDS (PRIV = 2) and for global atomics (PRIV = 0); private tallies
-  // beside a grid in global memory give way to the latter
-  if (levels_on(c) && L.priv && !L.gridLds) {
+  // level fluxes, actinic flux: the LVL and ACT kernels are built for everything in LDS (PRIV = 2) and for global atomics (PRIV = 0);
+  // private tallies beside a grid in global memory give way to the latter
+  if (facewalk_on(c) && L.priv && !L.gridLds) {
     L.priv = false;
     L.tblLds = tbl <= kTableLdsLimit && edges + bg + tbl <= kLdsBudget;
   }
   L.lds = edges + bg + (L.priv ? slab : 0) + (L.gridLds ? grid : 0) + (L.tblLds ? tbl : 0);
   // the wide plan: the slab did not fit beside another workgroup, but it fits a compute unit
   const size_t cuLds = c->ldsPerCU > kStaticLds ? c->ldsPerCU - kStaticLds : 0;
-  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !orders_on(c) && !levels_on(c) && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
+  if ((!L.priv || c->wideMode == 2) && c->privMode != 0 && c->wideMode != 0 && c->nDir == 0 && !orders_on(c) && !facewalk_on(c) && !L.brick && c->blockSize == 0 && edges + bg + slab <= cuLds) {
     L.wide = true; L.priv = true; L.fly = false;
     size_t need = edges + bg + slab;
     L.tblLds = need + tbl <= cuLds;
@@ -727,7 +777,7 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.fly = flight_wanted(c) && !L.gridLds && !L.brick && c->nDir == 0 && L.lds + flyLds <= kLdsBudget;
   if (L.fly) L.lds += flyLds;
   L.block = c->blockSize > 0 ? c->blockSize : (L.gridLds ? 768 : ((L.tblLds || L.priv) && L.lds > 16 * 1024 ? 512 : 256));
-  if (levels_on(c) && L.block > 512) L.block = 512;  // (no 768-lane LVL kernel)
+  if (facewalk_on(c) && L.block > 512) L.block = 512;  // (no 768-lane LVL or ACT kernel)
   if (blocks_worth_it(c) && L.priv && L.gridLds && c->srcKind != 0)
     L.cdfTop = block_lds_layout(c->nx, c->ny, c->nz, c->nc, slabStride, c->nBlocks, L.tblLds ? (size_t)c->tblTotalFloats : 0, 0, true).total <= kLdsBudget;
   // fill_params chose the brick arrays: private tallies give way.  Decided last, so that tblLds, block and cdfTop stay
@@ -841,6 +891,17 @@ template <int BLOCK, int PRIV>
 const void *trace_ptr_lvl_direct(bool tbl) {
   return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true, true>
              : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true, true>;
+}
+// the ACT instantiations (actinic flux), solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table x LVL -- 16 kernels
+template <int BLOCK, int PRIV, bool LVL>
+const void *trace_ptr_act(bool tbl) {
+  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, LVL, false, true>
+             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, LVL, false, true>;
+}
+template <int BLOCK>
+const void *trace_kernel_act(const mcbrat_ctx *c, const LaunchPlan &L) {  // (thermal source, direct tally: refused, check_ready)
+  if (levels_on(c)) return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, true>(L.tblLds) : trace_ptr_act<BLOCK, 0, true>(L.tblLds);
+  return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, false>(L.tblLds) : trace_ptr_act<BLOCK, 0, false>(L.tblLds);
 }
 template <int BLOCK>
 const void *trace_kernel_lvl(const mcbrat_ctx *c, const LaunchPlan &L) {
@@ -978,6 +1039,10 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   if (lvl && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
     return fail(c, debug ? kLevelsCountersMsg : (brdf ? kLevelsBrdfMsg : (c->nDir > 0 ? kLevelsIntensityMsg : kLevelsOrdersMsg)));
   if (direct_on(c) && emit) return fail(c, kDirectThermalMsg);  // (check_ready refuses it; a second line of defence: no thermal DIRECT kernel)
+  const bool act = actinic_on(c);
+  if (act && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
+    return fail(c, debug ? kActinicCountersMsg : (brdf ? kActinicBrdfMsg : (c->nDir > 0 ? kActinicIntensityMsg : kActinicOrdersMsg)));
+  if (act && (emit || direct_on(c))) return fail(c, emit ? kActinicThermalMsg : kActinicDirectMsg);  // (no thermal ACT kernel, none with DIRECT)
   if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
   const void *kernel;
   int block;
@@ -986,7 +1051,7 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
     block = 1024;
     if (brdf) kernel = L.gridLds ? trace_ptr<1024, 2, false, false, false, false, true>(tbl, false) : trace_ptr<1024, 1, false, false, false, false, true>(tbl, false);
     else kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
-  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0 && !lvl) {
+  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0 && !lvl && !act) {
     // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
     // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
     // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
@@ -1010,7 +1075,8 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
       p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
       lds = base + waves * cap * 80;
     }
-    if (lvl) kernel = block == 512 ? trace_kernel_lvl<512>(c, L) : trace_kernel_lvl<256>(c, L);
+    if (act) kernel = block == 512 ? trace_kernel_act<512>(c, L) : trace_kernel_act<256>(c, L);
+    else if (lvl) kernel = block == 512 ? trace_kernel_lvl<512>(c, L) : trace_kernel_lvl<256>(c, L);
     else if (brdf) kernel = block == 512 ? trace_kernel_brdf<512>(c, L) : trace_kernel_brdf<256>(c, L);
     else if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
       if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with scattering orders.");
@@ -1035,6 +1101,14 @@ int check_ready(mcbrat_ctx *c) {
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
     if (level_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
     if (direct_on(c) && c->srcKind != 0) return fail(c, kDirectThermalMsg);
+  }
+  if (actinic_on(c)) {  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
+    if (c->nDir > 0) return fail(c, kActinicIntensityMsg);
+    if (orders_on(c)) return fail(c, kActinicOrdersMsg);
+    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
+    if (direct_on(c)) return fail(c, kActinicDirectMsg);
+    if (global_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, kActinicBudgetMsg);
+    if (c->srcKind != 0) return fail(c, kActinicThermalMsg);
   }
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
@@ -1171,6 +1245,7 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   for (int i = 0; i < nz; ++i) if (!(ze[i + 1] > ze[i])) return fail(c, "new_Domain: z edges must be increasing, unique.");
   if ((long long)nx * ny * nz > 0x7fffffffLL / 2) return fail(c, "new_Integrator: more than 2^30 cells are not supported.");
   if (levels_on(c) && !level_bins_fit((double)level_parts(c), nx, ny, nz)) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+  if (actinic_on(c) && !global_bins_fit((double)level_parts(c), true, nx, ny, nz)) return fail(c, kActinicBudgetMsg);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1413,6 +1488,7 @@ int mcbrat_get_moments(mcbrat_ctx *c, double *host) {
 int mcbrat_enable_counters(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
   if (enable && levels_on(c)) return fail(c, kLevelsCountersMsg);
+  if (enable && actinic_on(c)) return fail(c, kActinicCountersMsg);
   c->countersOn = enable != 0;
   return 0;
 }
@@ -1459,6 +1535,7 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   if (zetaMin < 0.f) return fail(c, "specifyParameters: zetaMin must be >= 0.");
   if (limitIntensityContributions && orders_on(c)) return fail(c, kOrdersLimitMsg);
   if (nDirections > 0 && levels_on(c)) return fail(c, kLevelsIntensityMsg);
+  if (nDirections > 0 && actinic_on(c)) return fail(c, kActinicIntensityMsg);
   if (numOrdersOrigPhaseFunIntenCalcs < 0) return fail(c, "specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0");
   if (useRussianRouletteForIntensity)
     for (int i = 0; i < nDirections; ++i)
@@ -1502,6 +1579,7 @@ int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
   const int n = numRecScatOrd < 0 ? -1 : numRecScatOrd;
   if (n >= 0 && c->limitContrib) return fail(c, kOrdersLimitMsg);
   if (n >= 0 && levels_on(c)) return fail(c, kLevelsOrdersMsg);
+  if (n >= 0 && actinic_on(c)) return fail(c, kActinicOrdersMsg);
   if (n >= 0) {  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
     const size_t ncol = (size_t)c->nx * c->ny;
     if ((double)(n + 1) * (2 + c->nDir) * ncol * sizeof(long long) > (double)kSlabBudget)
@@ -1555,6 +1633,7 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
     if (c->countersOn) return fail(c, kLevelsCountersMsg);
     if (!level_bins_fit(2.0, c->nx, c->ny, c->nz)) return fail(c, kLevelsBudgetMsg);
     if (c->directLevelFluxes && !level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
+    if (actinic_on(c) && !global_bins_fit(2.0, true, c->nx, c->ny, c->nz)) return fail(c, kActinicBudgetMsg);
   } else if (c->directLevelFluxes) return fail(c, kDirectNeedsLevelsMsg);  // (switch the direct tally off first)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
@@ -1595,6 +1674,7 @@ int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
   const int on = enable ? 1 : 0;
   if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
     if (!levels_on(c)) return fail(c, kDirectNeedsLevelsMsg);
+    if (actinic_on(c)) return fail(c, kActinicDirectMsg);
     if (!level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
   }
   (void)hipSetDevice(c->device);
@@ -1628,6 +1708,46 @@ int mcbrat_report_direct_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxDownDir
   take(meanLevelFluxDownDiffuse, nLvl);
   take(levelFluxDownDirect, ncol * nLvl);
   take(levelFluxDownDiffuse, ncol * nLvl);
+  return 0;
+}
+
+int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
+  const int on = enable ? 1 : 0;
+  if (on) {  // (level fluxes may be on together with it; their direct tally may not: no kernel has both flags)
+    if (c->nDir > 0) return fail(c, kActinicIntensityMsg);
+    if (orders_on(c)) return fail(c, kActinicOrdersMsg);
+    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
+    if (c->countersOn) return fail(c, kActinicCountersMsg);
+    if (direct_on(c)) return fail(c, kActinicDirectMsg);
+    if (!global_bins_fit((double)level_parts(c), true, c->nx, c->ny, c->nz)) return fail(c, kActinicBudgetMsg);
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (on != c->actinicFlux) {  // the moment arrays change length: start them afresh (as mcbrat_specify_level_fluxes does)
+    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+    c->dMoments = nullptr;
+    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+    c->haveLast = false;
+    c->tuned = false;  // (another walk, other kernels: the event threshold is chosen again)
+  }
+  c->actinicFlux = on;
+  return 0;
+}
+
+int mcbrat_report_actinic_flux(mcbrat_ctx *c, float *meanActinicFlux, float *actinicFlux) {
+  if (!c) return 1;
+  if (!actinic_on(c)) return fail(c, "reportResults: actinic-flux information not available");
+  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  // the actinic tail of the last batch's results: [meanActinic | actinic], already in Fortran order (nx, ny, nz)
+  const size_t nvox = (size_t)c->nx * c->ny * (size_t)c->nz, n = (size_t)c->nz + nvox;
+  std::vector<float> h(n);
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast + (size_t)moments_actinic_at(c), sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (meanActinicFlux) std::memcpy(meanActinicFlux, h.data(), sizeof(float) * (size_t)c->nz);
+  if (actinicFlux) std::memcpy(actinicFlux, h.data() + c->nz, sizeof(float) * nvox);
   return 0;
 }
 
@@ -1796,6 +1916,7 @@ int mcbrat_set_surface_brdf(mcbrat_ctx *c, int32_t kind, int32_t numX, int32_t n
   if (numX <= 0 || numY <= 0) { c->surfNumX = c->surfNumY = 0; c->surfKind = 0; return 0; }  // back to the domain's albedo
   if (brdf_num_params(kind) == 0 || kind == BRDF_LAMBERTIAN) return fail(c, "new_SurfaceDescription: unknown surface BRDF model.");
   if (levels_on(c)) return fail(c, kLevelsBrdfMsg);
+  if (actinic_on(c)) return fail(c, kActinicBrdfMsg);
   if (nParams != brdf_num_params(kind)) return fail(c, "new_SurfaceDescription: Wrong number of parameters supplied for surface BRDF.");
   if (numX < 2 || numY < 2 || !xPosition || !yPosition || !params)
     return fail(c, "new_SurfaceDescription: position vector(s) are incorrect length.");
@@ -1898,7 +2019,7 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   if (c->haveGrid && c->haveOptics) {  // what a flux launch of the loaded domain would do (the plan decides, as launch_trace does)
     // (the flux run's slab: with scattering orders its order bins too, so that private tallies give way where they no longer fit)
     const LaunchPlan L = plan_launch(c, slab_stride(c, true));
-    m = ((c->layerSkip && !levels_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
+    m = ((c->layerSkip && !facewalk_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
   }
@@ -1933,7 +2054,9 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   if (orders_on(c) && c->countersOn)
     return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
   if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
-  if (levels_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+  if (levels_on(c) && !actinic_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+  if (actinic_on(c) && c->countersOn) return fail(c, kActinicCountersMsg);
+  if (actinic_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, kActinicBudgetMsg);
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
   size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
@@ -1944,7 +2067,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
     const size_t nOrdMeans = orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + c->nDir) : 0;  // (domain means by order, behind the scalars)
     const size_t nLvlMeans = level_quantities(c) * ((size_t)c->nz + 1);  // (domain means by level, behind those)
-    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans + nLvlMeans) * inFlight;
+    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans + nLvlMeans + (actinic_on(c) ? c->nz : 0)) * inFlight;  // (and the actinic layer means)
     if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
     HIP_OK(c, hipStreamSynchronize(L.stream));
     if (L.slabCapacity < needSlab) {
@@ -2023,18 +2146,25 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.gatherOrderMeans = (unsigned)((2 + c->nDir) * f.nOrd) * (unsigned)nb;
     f.foldOrderMeans = (unsigned)(((2 + c->nDir) * f.nOrd + kFinishBlock - 1) / kFinishBlock);
     f.nLvl = levels_on(c) ? c->nz + 1 : 0;
-    f.lvlSlab = (long long)(slabStride - level_bins(c));
+    f.lvlSlab = (long long)(slabStride - global_bins(c));
     f.lvlVals = f.ordVals + (size_t)((2 + c->nDir) * f.nOrd) * nb;
     f.lvlDirect = direct_on(c) ? 1 : 0;
     const size_t nLvlQ = level_quantities(c);  // (up, down; with the direct tally direct and diffuse too)
     f.gatherLevels = (unsigned)((nLvlQ * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
     f.gatherLevelMeans = (unsigned)(nLvlQ * f.nLvl) * (unsigned)nb;
     f.foldLevelMeans = (unsigned)((nLvlQ * f.nLvl + kFinishBlock - 1) / kFinishBlock);
+    f.act = actinic_on(c) ? 1 : 0;
+    f.actSlab = (long long)(slabStride - actinic_bins(c));
+    f.actUnit = actinic_unit(c);
+    f.actVals = f.lvlVals + nLvlQ * (size_t)f.nLvl * nb;
+    f.gatherActinic = f.act ? (unsigned)((nvox + kVolVox - 1) / kVolVox) : 0u;
+    f.gatherActinicMeans = f.act ? (unsigned)c->nz * (unsigned)nb : 0u;
+    f.foldActinicMeans = f.act ? (unsigned)((c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans),
+    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans + f.gatherActinic + f.gatherActinicMeans),
                        dim3(kFinishBlock), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
+    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans + f.foldActinicMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
     c->lastDone = c->L().evDone;
@@ -2098,6 +2228,7 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
   if (sync_all(c)) return 1;
   if (c->nDir > 0) return fail(c, "trace_fates: not available together with intensity directions.");
   if (levels_on(c)) return fail(c, kLevelsCountersMsg);
+  if (actinic_on(c)) return fail(c, kActinicCountersMsg);
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
   const size_t slabStride = 2 * ncol + nvox;
   long long *scratch = nullptr;

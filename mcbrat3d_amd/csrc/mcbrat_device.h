@@ -162,6 +162,10 @@ struct DevParams {
   int launchThreshold;            // idle lanes queued before new photons are launched
   int surfaceThreshold;           // lanes queued before exits (top / surface) are served
   int jumpThreshold;              // lanes queued before transitions of the layer-skipping walk are served
+  // actinic flux (ACT instantiations of trace_kernel): 2^-e, the power of two that keeps w l 2^-e of the
+  // longest possible step below 1.  (In the padding behind jumpThreshold: the parameter block keeps its size and every other
+  // member its offset.)
+  float actScale;
   // Termination guarantees.  The reference's walk marches by cell INDEX and drops a photon whose step
   // is not positive (opticalProperties.f95:1719-1722, counted in nBad, monteCarloRadiativeTransfer.f95:562-563); the kernels
   // here find cells from positions in places (block walk, clear-air flight, layer skipping), keep face distances in float,

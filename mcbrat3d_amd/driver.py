@@ -30,7 +30,8 @@ def balanced_job(totalPhotons, numBatches, world):
     return ppb, nb
 
 
-def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False, directLevelFluxes=False):
+def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False, directLevelFluxes=False,
+                   actinicFlux=False):
     """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order.
 
     With scattering orders (numRecScatOrd >= 0) the arrays end in the order tail of include/mcbrat.h, unpacked with the order
@@ -42,7 +43,10 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
     levelFluxUp[ix, iy, k], levelFluxDown[ix, iy, k], k = 0 .. nz.  The length is then checked against the layout asked for.
 
     With their direct / diffuse separation (directLevelFluxes=True, which needs levelFluxes=True) the direct tail follows the level
-    tail: meanLevelFluxDownDirect[k], meanLevelFluxDownDiffuse[k], levelFluxDownDirect[ix, iy, k], levelFluxDownDiffuse[ix, iy, k]."""
+    tail: meanLevelFluxDownDirect[k], meanLevelFluxDownDiffuse[k], levelFluxDownDirect[ix, iy, k], levelFluxDownDiffuse[ix, iy, k].
+
+    With the actinic flux (actinicFlux=True) the actinic tail follows every other tail: meanActinicFlux[iz], actinicFlux[ix, iy, iz].
+    The length is then checked against the layout asked for."""
     if directLevelFluxes and not levelFluxes:
         raise ValueError("unpack_moments: directLevelFluxes needs levelFluxes")
     ncol, nvox = nx * ny, nx * ny * nz
@@ -50,13 +54,14 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
     nOrd = int(numRecScatOrd) + 1 if numRecScatOrd is not None and int(numRecScatOrd) >= 0 else 0
     nLvl = nz + 1 if levelFluxes else 0
     nLvlQ = 4 if directLevelFluxes else 2  # level quantities: up, down (, direct, diffuse)
+    nAct = nz * (1 + ncol) if actinicFlux else 0
     if nDirections is None:  # the length tells
         if nOrd:
             raise ValueError("unpack_moments: with numRecScatOrd >= 0 the number of directions must be given (nDirections=)")
-        nDirections = ((len(buf) - 8) // 2 - M - nLvlQ * nLvl * (1 + ncol)) // ncol
+        nDirections = ((len(buf) - 8) // 2 - M - nLvlQ * nLvl * (1 + ncol) - nAct) // ncol
     if nDirections < 0:
         raise ValueError("unpack_moments: %d doubles are too few for the layout asked for" % len(buf))
-    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol) + nLvlQ * nLvl * (1 + ncol)
+    M += nDirections * ncol + nOrd * (2 + nDirections) * (1 + ncol) + nLvlQ * nLvl * (1 + ncol) + nAct
     S1, S2 = buf[8:8 + M], buf[8 + M:8 + 2 * M]
     out = {"totalPhotons": buf[0], "batches": buf[1]}
     names = [("meanFluxUp", 1, None), ("meanFluxDown", 1, None), ("meanFluxAbsorbed", 1, None),
@@ -76,7 +81,9 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
         if directLevelFluxes:
             names += [("meanLevelFluxDownDirect", nLvl, (nLvl,)), ("meanLevelFluxDownDiffuse", nLvl, (nLvl,)),
                       ("levelFluxDownDirect", nLvl * ncol, (nLvl, ny, nx)), ("levelFluxDownDiffuse", nLvl * ncol, (nLvl, ny, nx))]
-    if (nOrd or nLvl) and len(buf) != 8 + 2 * M:
+    if actinicFlux:
+        names += [("meanActinicFlux", nz, (nz,)), ("actinicFlux", nvox, (nz, ny, nx))]
+    if (nOrd or nLvl or nAct) and len(buf) != 8 + 2 * M:
         raise ValueError("unpack_moments: %d doubles, the layout asked for has %d" % (len(buf), 8 + 2 * M))
     o = 0
     for name, n, shp in names:
@@ -187,7 +194,8 @@ def run(integrator, domain, photons, numPhotonsPerBatch, numBatches, randomNumbe
     nOrd = getattr(integrator, "numRecScatOrd", -1)
     levels = bool(getattr(integrator, "recLevelFluxes", False))
     direct = levels and bool(getattr(integrator, "recDirectLevelFluxes", False))
-    if nOrd >= 0 or levels:
+    actinic = bool(getattr(integrator, "recActinicFlux", False))
+    if nOrd >= 0 or levels or actinic:
         return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels,
-                                         directLevelFluxes=direct), solarFlux)
+                                         directLevelFluxes=direct, actinicFlux=actinic), solarFlux)
     return statistics(unpack_moments(buf, nx, ny, nz), solarFlux)

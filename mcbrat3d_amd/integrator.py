@@ -79,6 +79,8 @@ class Integrator:
         self.recLevelFluxes = False
         # the direct beam apart from the diffuse light in the downward level flux; needs recLevelFluxes
         self.recDirectLevelFluxes = False
+        # the actinic flux of every cell by track length; solar sources, with or without recLevelFluxes
+        self.recActinicFlux = False
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -120,7 +122,7 @@ class Integrator:
                               limitIntensityContributions=self.limitIntensityContributions,
                               maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF,
                               numRecScatOrd=self.numRecScatOrd, recLevelFluxes=self.recLevelFluxes,
-                              recDirectLevelFluxes=self.recDirectLevelFluxes)
+                              recDirectLevelFluxes=self.recDirectLevelFluxes, recActinicFlux=self.recActinicFlux)
         return new
 
     def _check(self, rc):
@@ -140,7 +142,8 @@ class Integrator:
                           useRussianRouletteForIntensity=None, zetaMin=None, useHybridPhaseFunsForIntenCalcs=None,
                           hybridPhaseFunWidth=None, numOrdersOrigPhaseFunIntenCalcs=None,
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
-                          recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, recDirectLevelFluxes=None, **unsupported):
+                          recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, recDirectLevelFluxes=None, recActinicFlux=None,
+                          **unsupported):
         # level fluxes: what they cannot be combined with is refused as the library refuses it -- here,
         # before anything of this call is kept, so that a refused call leaves the integrator as it was
         levels = self.recLevelFluxes if recLevelFluxes is None else bool(recLevelFluxes)
@@ -174,6 +177,36 @@ class Integrator:
             if getattr(bdrf, "kind", 0) != 0:
                 raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with a BRDF surface: "
                                   "a reflected weight may exceed 1, which the level tallies do not hold.")
+        # the actinic flux: refused as the library refuses it, before anything of this call is kept
+        actinic = self.recActinicFlux if recActinicFlux is None else bool(recActinicFlux)
+        if actinic:
+            directions = self.numIntensityDirections()
+            if intensityMus is not None:
+                directions = int(np.size(intensityMus))
+            elif computeIntensity is not None and not computeIntensity:
+                directions = 0
+            if directions > 0:
+                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with intensity "
+                                  "directions: the radiance kernels have no track-length tally.")
+            wantOrders = self.numRecScatOrd >= 0
+            if numRecScatOrd is not None:
+                wantOrders = int(numRecScatOrd) >= 0
+            elif recScatOrd is not None and not recScatOrd:
+                wantOrders = False
+            if wantOrders:
+                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with scattering orders "
+                                  "(recScatOrd): no kernel tallies both.")
+            bdrf = surfaceBDRF if surfaceBDRF is not None else self.surfaceBDRF
+            if getattr(bdrf, "kind", 0) != 0:
+                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with a BRDF surface: "
+                                  "a reflected weight may exceed 1, which the track-length tally does not hold.")
+            if direct:
+                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with direct level fluxes "
+                                  "(recDirectLevelFluxes): no kernel tallies both.")
+            nx, ny, nz = self._dims
+            if ((2 * nx * ny * (nz + 1) if levels else 0) + nx * ny * nz) * 8 > 4 << 30:
+                raise McbratError("specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch "
+                                  "would not fit the 4 GiB tally budget.")
         # intensity keywords, :1130-1160 and :1186-1283
         if (intensityMus is None) != (intensityPhis is None):
             raise McbratError("specifyParameters: Both or neither of intensityMus, intensityPhis must be supplied")
@@ -255,6 +288,7 @@ class Integrator:
         self.numRecScatOrd, self.recScatOrd = orders, orders >= 0
         self.recLevelFluxes = levels
         self.recDirectLevelFluxes = direct
+        self.recActinicFlux = actinic
         self._push_parameters()
 
     def _push_parameters(self):
@@ -281,11 +315,19 @@ class Integrator:
             self._check(self._lib.mcbrat_specify_direct_level_fluxes(self._ctx, int(self.recDirectLevelFluxes)))
             self._direct_levels_token = self.recDirectLevelFluxes
 
+    def _push_actinic(self):
+        if self.recActinicFlux != getattr(self, "_actinic_token", False):
+            self._check(self._lib.mcbrat_specify_actinic_flux(self._ctx, int(self.recActinicFlux)))
+            self._actinic_token = self.recActinicFlux
+
     def _push_intensity(self):
+        if not self.recActinicFlux:
+            self._push_actinic()  # (off first, as level fluxes: what follows may be refused together with it -- the direct tally too)
         if not self.recLevelFluxes:
             self._push_levels()  # (off first: the settings below may be ones the library refuses together with level fluxes)
         self._push_intensity_and_orders()
         self._push_levels()
+        self._push_actinic()
 
     def _push_intensity_and_orders(self):
         n = int(self.intensityMus.size) if self.computeIntensity else 0
@@ -476,6 +518,8 @@ class Integrator:
             res.update(meanIntensity=mean_i, intensity=inten.reshape(nd, ny, nx).transpose(2, 1, 0))
         if self.recLevelFluxes:
             res.update(self.reportLevelFluxes())
+        if self.recActinicFlux:
+            res.update(self.reportActinicFlux())
         if self.numRecScatOrd >= 0:  # reportResults(...ByScatOrd) :850-864, :887-903, :1010-1040; order last, as the reference's arrays
             no = self.numRecScatOrd + 1
             mu_o, md_o = np.zeros(no, np.float32), np.zeros(no, np.float32)
@@ -512,6 +556,15 @@ class Integrator:
                        levelFluxDownDirect=dirc.reshape(nl, ny, nx).transpose(2, 1, 0),
                        levelFluxDownDiffuse=dif.reshape(nl, ny, nx).transpose(2, 1, 0))
         return res
+
+    def reportActinicFlux(self):
+        """The last batch's actinic flux by track length: actinicFlux[ix, iy, iz], the weighted path length inside the cell per
+        photon of its column and per km of its depth (dimensionless: 1 in a vacuum under an overhead sun), and the layer means
+        meanActinicFlux[iz] (the sum over the columns divided by their number)."""
+        nx, ny, nz = self._dims
+        mean, act = np.zeros(nz, np.float32), np.zeros(nx * ny * nz, np.float32)
+        self._check(self._lib.mcbrat_report_actinic_flux(self._ctx, ptr(mean), ptr(act)))
+        return dict(meanActinicFlux=mean, actinicFlux=act.reshape(nz, ny, nx).transpose(2, 1, 0))
 
     # -- batch moments (what the driver keeps in *Stats and reduces over processes) -----
     def momentsLength(self):

@@ -221,6 +221,14 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
             for name in names:
                 f.createVariable(name, "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
                 f.createVariable(name + "_StdErr", "f", ("zLevel", "y", "x"))[:] = np.asarray(stats[name + "_StdErr"]).transpose(2, 1, 0)
+        if "actinicFlux" in stats:  # the actinic flux of every cell (reportActinicFlux): Fortran dims (x, y, z) and its layer means (z)
+            if not withZ:
+                f.createDimension("z", len(ze) - 1)
+                f.createVariable("z", "d", ("z",))[:] = 0.5 * (ze[1:] + ze[:-1])
+            for name in ("actinicFlux", "actinicFlux_StdErr"):
+                f.createVariable(name, "f", ("z", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
+            for name in ("meanActinicFlux", "meanActinicFlux_StdErr"):
+                f.createVariable(name, "f", ("z",))[:] = np.asarray(stats[name])
     finally:
         f.close()
     return outputFileName
