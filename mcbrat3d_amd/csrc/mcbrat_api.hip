@@ -257,55 +257,25 @@ bool orders_on(const mcbrat_ctx *c) { return c->numRecScatOrd >= 0; }
 
 bool levels_on(const mcbrat_ctx *c) { return c->levelFluxes != 0; }
 bool direct_on(const mcbrat_ctx *c) { return c->levelFluxes != 0 && c->directLevelFluxes != 0; }
-// level parts of one batch's slab and level quantities in the moments: [up | down], with the direct tally [up | diffuse | direct]
-// and (up, down, direct, diffuse)
-size_t level_parts(const mcbrat_ctx *c) { return levels_on(c) ? (direct_on(c) ? 3 : 2) : 0; }
-size_t level_quantities(const mcbrat_ctx *c) { return levels_on(c) ? (direct_on(c) ? 4 : 2) : 0; }
-// bins of one batch's level fluxes: [levelUp ncol (nz+1) | levelDown ncol (nz+1) (| levelDirect ncol (nz+1))], level slowest
-size_t level_bins(const mcbrat_ctx *c) { return level_parts(c) * (size_t)c->nx * c->ny * ((size_t)c->nz + 1); }
-// whether the level bins of one batch of an nx x ny x nz grid fit the tally budget (in double: the product may pass 2^64)
-bool level_bins_fit(double parts, double nx, double ny, double nz);
-// the actinic flux of every cell: one bin per cell behind the level parts of a batch's slab, layer slowest
+// the actinic flux of every cell
 bool actinic_on(const mcbrat_ctx *c) { return c->actinicFlux != 0; }
-size_t actinic_bins(const mcbrat_ctx *c) { return actinic_on(c) ? (size_t)c->nx * c->ny * (size_t)c->nz : 0; }
 // the tallies that make every cell face a stop: the plan then walks face by face (no layer skipping, flight, block walk, wide
 // plan, bricks or 768-lane kernel), and their bins stay in global memory
 bool facewalk_on(const mcbrat_ctx *c) { return levels_on(c) || actinic_on(c); }
-size_t global_bins(const mcbrat_ctx *c) { return level_bins(c) + actinic_bins(c); }
-// whether the level parts and the actinic part of one batch of an nx x ny x nz grid fit the tally budget together
-bool global_bins_fit(double levelParts, bool actinic, double nx, double ny, double nz);
 
-// [meanUp (N+1) | meanDown (N+1) | up ncol (N+1) | down ncol (N+1) | meanIntensity nDir (N+1) | intensity ncol nDir (N+1)] behind the rest,
-// then the level fluxes: [meanLevelUp (nz+1) | meanLevelDown (nz+1) | levelUp ncol (nz+1) | levelDown ncol (nz+1)]
-// then their direct / diffuse separation: [meanDirect (nz+1) | meanDiffuse (nz+1) | direct ncol (nz+1) | diffuse ncol (nz+1)]
-// then, behind every other tail, the actinic flux: [meanActinic nz | actinic ncol nz]
-long long moments_actinic_len(const mcbrat_ctx *c) { return actinic_on(c) ? (long long)c->nz * (1 + (long long)c->nx * c->ny) : 0; }
-long long moments_len(const mcbrat_ctx *c) {
-  const long long ncol = (long long)c->nx * c->ny;
-  return 3 + 3 * ncol + c->nz + ncol * c->nz + (long long)c->nDir * ncol +
-         (orders_on(c) ? (long long)(c->numRecScatOrd + 1) * (2 + c->nDir) * (1 + ncol) : 0) +
-         (long long)level_quantities(c) * (c->nz + 1) * (1 + ncol) + moments_actinic_len(c);
+// Where every tally lies -- in one batch's slab, in the moments and the last batch's results, in the finish kernels' scalar
+// scratch -- is defined by mcbrat_layout.h; nothing here derives an offset of its own.
+int32_t order_count(int32_t numRecScatOrd) { return numRecScatOrd < 0 ? 0 : (numRecScatOrd < INT32_MAX ? numRecScatOrd + 1 : INT32_MAX); }
+TallyShape tally_shape(const mcbrat_ctx *c) {
+  return TallyShape{c->nx, c->ny, c->nz, c->nc, c->nDir, c->limitContrib, order_count(c->numRecScatOrd), levels_on(c), direct_on(c), actinic_on(c)};
 }
-long long moments_actinic_at(const mcbrat_ctx *c) { return moments_len(c) - moments_actinic_len(c); }
-// where the level tail starts in the moments (behind the orders' tail) and where the direct / diffuse tail does
-long long moments_levels_at(const mcbrat_ctx *c) {
-  return moments_actinic_at(c) - (long long)level_quantities(c) * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
-}
-long long moments_direct_at(const mcbrat_ctx *c) {
-  return moments_levels_at(c) + 2LL * (c->nz + 1) * (1 + (long long)c->nx * c->ny);
-}
-
-// Elements of one batch's tally slab: [fluxUp | fluxDown | volume | intensity per direction | (limitIntensityContributions:)
-// intensity by component, excess | (scattering orders:) upByOrd ncol (N+1) | downByOrd ncol (N+1) | intensityByOrd ncol nDir (N+1) |
-// (level fluxes:) levelUp ncol (nz+1) | levelDown ncol (nz+1) | (their direct tally:) levelDirect ncol (nz+1) |
-// (actinic flux:) actinic ncol nz]
-// fluxRun: the slab of a flux launch of the loaded domain (no intensity parts), what mcbrat_get_walk_mode reports on.
-size_t slab_stride(const mcbrat_ctx *c, bool fluxRun = false) {
-  const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz, nDir = fluxRun ? 0 : (size_t)c->nDir;
-  return 2 * ncol + nvox + nDir * ncol + (c->limitContrib && !fluxRun ? (size_t)(c->nc + 1) * nDir * (ncol + 1) : 0) +
-         (orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + nDir) * ncol : 0) + global_bins(c);
-}
+TallyLayout tally_layout(const mcbrat_ctx *c) { return tally_layout(tally_shape(c)); }
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
+// whether the bins of one batch of a (candidate) shape fit that budget: its order part, its level and actinic bins, all of it
+TallyFit budget_fit(const TallyShape &s) { return tally_fit(s, kSlabBudget); }
+// (candidate shapes: the context's with other level and actinic settings; without the actinic flux a refusal is the level tallies')
+TallyShape with_tallies(TallyShape s, int levels, int direct, int actinic) { s.levels = levels; s.direct = levels && direct; s.actinic = actinic; return s; }
+TallyShape without_actinic(const TallyShape &s) { return with_tallies(s, s.levels, s.direct, 0); }
 constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
 // The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
 // Level fluxes are tallied by the general flux kernels on the face-by-face walk only: what they are refused with
@@ -356,17 +326,44 @@ double actinic_unit(const mcbrat_ctx *c) {
   (void)std::frexp(longest, &e);  // longest = m 2^e with m in [0.5, 1)
   return std::ldexp(1.0, e);
 }
-bool global_bins_fit(double levelParts, bool actinic, double nx, double ny, double nz) {
-  return (levelParts * nx * ny * (nz + 1.0) + (actinic ? nx * ny * nz : 0.0)) * sizeof(long long) <= (double)kSlabBudget;
-}
-bool level_bins_fit(double parts, double nx, double ny, double nz) { return parts * nx * ny * (nz + 1.0) * sizeof(long long) <= (double)kSlabBudget; }
 const char *const kOrdersLimitMsg =
     "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
     "redistribution adds each direction's clipped excess to every order, which would count it numRecScatOrd + 1 times.";
 
+// The last batch's results from element `base` on (they are laid out as one sum of the moments), once everything enqueued is done
+int read_last(mcbrat_ctx *c, size_t base, std::vector<float> &h) {
+  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+  return 0;
+}
+// ... dealt out to the caller's arrays in the order the parts lie in, already in Fortran order (a null array is skipped)
+using LastPart = std::pair<float *, size_t>;
+int deal_last(mcbrat_ctx *c, size_t base, std::initializer_list<LastPart> parts) {
+  size_t n = 0;
+  for (const LastPart &p : parts) n += p.second;
+  std::vector<float> h(n);
+  if (read_last(c, base, h)) return 1;
+  const float *q = h.data();
+  for (const LastPart &p : parts) { if (p.first) std::memcpy(p.first, q, sizeof(float) * p.second); q += p.second; }
+  return 0;
+}
+
+// A setting changed the length of the moments: the moment arrays and the last batch's results (both laid out by the old length)
+// go, to be made afresh by the next call.  retune: the setting also changes the walk or the kernels, so the event threshold is
+// chosen again.
+void drop_results(mcbrat_ctx *c, bool retune) {
+  if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+  c->dMoments = nullptr;
+  if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+  c->haveLast = false;
+  if (retune) c->tuned = false;
+}
+
 int ensure_moments(mcbrat_ctx *c) {
   if (c->dMoments) return 0;
-  const size_t n = 8 + 2 * (size_t)moments_len(c);
+  const size_t n = 8 + 2 * (size_t)tally_layout(c).momentsLen;
   HIP_OK(c, dev_malloc((void **)&c->dMomentsOwned, sizeof(double) * n));
   // (on the stream the finish kernels run on: hipMemset on the null stream is asynchronous for device memory and the
   // context's streams are non-blocking, so nothing would order a null-stream memset before the first finish kernels)
@@ -727,7 +724,8 @@ LaunchPlan plan_launch(const mcbrat_ctx *c, size_t slabStride) {
   L.wide = false; L.blockLite = false; L.optics = 0; L.cdfTop = false;
   const size_t edges = sizeof(double) * (size_t)(c->nx + c->ny + c->nz + 3);
   const size_t tbl = sizeof(float) * (size_t)c->tblTotalFloats;
-  const size_t slab = sizeof(long long) * (slabStride - global_bins(c)) + 16;  // (the level and actinic bins are never part of the LDS slab)
+  // (the level and actinic bins, which lie behind slabLds in every slab of this context, are never part of the LDS slab)
+  const size_t slab = sizeof(long long) * std::min(slabStride, (size_t)tally_layout(c).slabLds) + 16;
   L.priv = c->privMode != 0 && slab <= kPrivSlabLimit;
   L.brick = use_bricks(c);
   const size_t bg = per_layer_lds(c->nz);  // per-layer extinction (background / one-extinction layers) and the runs of such layers
@@ -1099,7 +1097,7 @@ int check_ready(mcbrat_ctx *c) {
     if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
     if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
-    if (level_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+    if (!budget_fit(without_actinic(tally_shape(c))).globalBins) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
     if (direct_on(c) && c->srcKind != 0) return fail(c, kDirectThermalMsg);
   }
   if (actinic_on(c)) {  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
@@ -1107,13 +1105,12 @@ int check_ready(mcbrat_ctx *c) {
     if (orders_on(c)) return fail(c, kActinicOrdersMsg);
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
     if (direct_on(c)) return fail(c, kActinicDirectMsg);
-    if (global_bins(c) * sizeof(long long) > kSlabBudget) return fail(c, kActinicBudgetMsg);
+    if (!budget_fit(tally_shape(c)).globalBins) return fail(c, kActinicBudgetMsg);
     if (c->srcKind != 0) return fail(c, kActinicThermalMsg);
   }
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
 }
-
 
 // Times short trial launches at a few event thresholds and keeps the fastest.  The best value
 // depends on how many voxel faces a leg crosses (step cloud ~3, 128x128x64 cloud field ~14).
@@ -1244,8 +1241,10 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   for (int i = 0; i < ny; ++i) if (!(ye[i + 1] > ye[i])) return fail(c, "new_Domain: y edges must be increasing, unique.");
   for (int i = 0; i < nz; ++i) if (!(ze[i + 1] > ze[i])) return fail(c, "new_Domain: z edges must be increasing, unique.");
   if ((long long)nx * ny * nz > 0x7fffffffLL / 2) return fail(c, "new_Integrator: more than 2^30 cells are not supported.");
-  if (levels_on(c) && !level_bins_fit((double)level_parts(c), nx, ny, nz)) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
-  if (actinic_on(c) && !global_bins_fit((double)level_parts(c), true, nx, ny, nz)) return fail(c, kActinicBudgetMsg);
+  TallyShape asked = tally_shape(c);
+  asked.nx = nx; asked.ny = ny; asked.nz = nz;
+  if (levels_on(c) && !budget_fit(without_actinic(asked)).globalBins) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+  if (actinic_on(c) && !budget_fit(asked).globalBins) return fail(c, kActinicBudgetMsg);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1269,13 +1268,10 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
     for (int i = 0; i < nx; ++i)
       rel[(size_t)i + (size_t)nx * j] = (float)(((ye[j + 1] - ye[j]) * (xe[i + 1] - xe[i])) / ((xe[nx] - xe[0]) * (ye[ny] - ye[0])));
   if (upload(c, &c->dRelArea, rel.data(), rel.size())) return 1;
-  c->haveGrid = true; c->haveOptics = false; c->haveSource = false; c->haveLast = false; c->tuned = false;
-  // everything sized by the old grid goes: the moment arrays, the last batch's results (the finish kernels write
-  // moments_len() elements of it), and the per-lane buffers are re-sized by the next call (their capacities are
-  // kept in elements and compared with what that call needs)
-  if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-  c->dMoments = nullptr;
-  if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+  c->haveGrid = true; c->haveOptics = false; c->haveSource = false;
+  // everything sized by the old grid goes: the moment arrays and the last batch's results; the per-lane buffers are re-sized by
+  // the next call (their capacities are kept in elements and compared with what that call needs)
+  drop_results(c, true);
   return 0;
 }
 
@@ -1446,7 +1442,7 @@ int mcbrat_set_source_emission(mcbrat_ctx *c, const double *voxelWeights, double
   return 0;
 }
 
-int64_t mcbrat_moments_length(const mcbrat_ctx *c) { return c && c->haveGrid ? moments_len(c) : 0; }
+int64_t mcbrat_moments_length(const mcbrat_ctx *c) { return c && c->haveGrid ? tally_layout(c).momentsLen : 0; }
 
 int mcbrat_bind_moments(mcbrat_ctx *c, double *deviceBuffer) {
   if (!c) return 1;
@@ -1469,7 +1465,7 @@ int mcbrat_reset_moments(mcbrat_ctx *c) {
     if (c->chainSnapshot) HIP_OK(c, hipStreamWaitEvent(c->L().stream, c->chainSnapshot, 0));
     c->chainAfter = false; c->chainSnapshot = nullptr;
   }
-  HIP_OK(c, hipMemsetAsync(c->dMoments, 0, sizeof(double) * (8 + 2 * (size_t)moments_len(c)), c->L().stream));
+  HIP_OK(c, hipMemsetAsync(c->dMoments, 0, sizeof(double) * (8 + 2 * (size_t)tally_layout(c).momentsLen), c->L().stream));
   // stream-ordered before whatever the context enqueues next; readers synchronise (get_moments, report_results)
   HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
   c->lastDone = c->L().evDone;
@@ -1481,7 +1477,7 @@ int mcbrat_get_moments(mcbrat_ctx *c, double *host) {
   (void)hipSetDevice(c->device);
   if (ensure_moments(c)) return 1;
   if (sync_all(c)) return 1;
-  HIP_OK(c, hipMemcpy(host, c->dMoments, sizeof(double) * (8 + 2 * (size_t)moments_len(c)), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(host, c->dMoments, sizeof(double) * (8 + 2 * (size_t)tally_layout(c).momentsLen), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1557,13 +1553,7 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   const int limit = (limitIntensityContributions && maxIntensityContribution < FLT_MAX) ? 1 : 0;
   c->limitContrib = limit;  // (the batch slabs change length: the next call compares element counts)
   c->maxContrib = maxIntensityContribution;
-  if (nDirections != c->nDir) {  // the moment arrays change length: start them afresh
-    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-    c->dMoments = nullptr;
-    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
-    c->haveLast = false;
-    c->tuned = false;
-  }
+  if (nDirections != c->nDir) drop_results(c, true);  // the moment arrays change length: start them afresh
   c->nDir = nDirections;
   c->useRRIntensity = useRussianRouletteForIntensity ? 1 : 0;
   c->zetaMin = zetaMin;
@@ -1581,18 +1571,14 @@ int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
   if (n >= 0 && levels_on(c)) return fail(c, kLevelsOrdersMsg);
   if (n >= 0 && actinic_on(c)) return fail(c, kActinicOrdersMsg);
   if (n >= 0) {  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
-    const size_t ncol = (size_t)c->nx * c->ny;
-    if ((double)(n + 1) * (2 + c->nDir) * ncol * sizeof(long long) > (double)kSlabBudget)
+    TallyShape asked = tally_shape(c);
+    asked.nOrd = order_count(n);
+    if (!budget_fit(asked).orders)
       return fail(c, "specifyParameters: numRecScatOrd is too large: the tallies of one batch by scattering order would not fit the 4 GiB tally budget.");
   }
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  if (n != c->numRecScatOrd) {  // the moment arrays change length: start them afresh (as mcbrat_specify_intensity does)
-    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-    c->dMoments = nullptr;
-    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
-    c->haveLast = false;
-  }
+  if (n != c->numRecScatOrd) drop_results(c, false);  // the moment arrays change length: start them afresh
   c->numRecScatOrd = n;
   return 0;
 }
@@ -1603,23 +1589,9 @@ int mcbrat_report_scattering_orders(mcbrat_ctx *c, float *meanFluxUpByScatOrd, f
   if (!orders_on(c)) return fail(c, "reportResults: scattering-order information not available");
   if ((meanIntensityByScatOrd || intensityByScatOrd) && c->nDir == 0)
     return fail(c, "reportResults: intensityByScatOrd information not available");
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  // the tail of the last batch's results: [meanUp | meanDown | up | down | meanIntensity | intensity], already in Fortran order
   const size_t ncol = (size_t)c->nx * c->ny, nOrd = (size_t)c->numRecScatOrd + 1, nDir = (size_t)c->nDir;
-  const size_t base = 3 + 3 * ncol + c->nz + ncol * c->nz + nDir * ncol;
-  std::vector<float> h((size_t)moments_len(c) - base);
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
-  const float *q = h.data();
-  const auto take = [&](float *dst, size_t n) { if (dst) std::memcpy(dst, q, sizeof(float) * n); q += n; };
-  take(meanFluxUpByScatOrd, nOrd);
-  take(meanFluxDownByScatOrd, nOrd);
-  take(fluxUpByScatOrd, ncol * nOrd);
-  take(fluxDownByScatOrd, ncol * nOrd);
-  take(meanIntensityByScatOrd, nDir * nOrd);
-  take(intensityByScatOrd, ncol * nDir * nOrd);
-  return 0;
+  return deal_last(c, (size_t)tally_layout(c).momOrders, {{meanFluxUpByScatOrd, nOrd}, {meanFluxDownByScatOrd, nOrd}, {fluxUpByScatOrd, ncol * nOrd},
+                   {fluxDownByScatOrd, ncol * nOrd}, {meanIntensityByScatOrd, nDir * nOrd}, {intensityByScatOrd, ncol * nDir * nOrd}});
 }
 
 int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
@@ -1631,19 +1603,14 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
     if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
     if (c->countersOn) return fail(c, kLevelsCountersMsg);
-    if (!level_bins_fit(2.0, c->nx, c->ny, c->nz)) return fail(c, kLevelsBudgetMsg);
-    if (c->directLevelFluxes && !level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
-    if (actinic_on(c) && !global_bins_fit(2.0, true, c->nx, c->ny, c->nz)) return fail(c, kActinicBudgetMsg);
+    const TallyShape now = tally_shape(c);
+    if (!budget_fit(with_tallies(now, 1, 0, 0)).globalBins) return fail(c, kLevelsBudgetMsg);
+    if (c->directLevelFluxes && !budget_fit(with_tallies(now, 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
+    if (actinic_on(c) && !budget_fit(with_tallies(now, 1, 0, 1)).globalBins) return fail(c, kActinicBudgetMsg);
   } else if (c->directLevelFluxes) return fail(c, kDirectNeedsLevelsMsg);  // (switch the direct tally off first)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  if (on != c->levelFluxes) {  // the moment arrays change length: start them afresh (as mcbrat_specify_scattering_orders does)
-    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-    c->dMoments = nullptr;
-    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
-    c->haveLast = false;
-    c->tuned = false;  // (another walk, other kernels: the event threshold is chosen again)
-  }
+  if (on != c->levelFluxes) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
   c->levelFluxes = on;
   return 0;
 }
@@ -1651,21 +1618,8 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
 int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *meanLevelFluxDown, float *levelFluxUp, float *levelFluxDown) {
   if (!c) return 1;
   if (!levels_on(c)) return fail(c, "reportResults: level-flux information not available");
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  // the level tail of the last batch's results: [meanUp | meanDown | up | down], already in Fortran order (nx, ny, 0:nz)
-  const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;
-  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_levels_at(c);
-  std::vector<float> h(n);
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * n, hipMemcpyDeviceToHost));
-  const float *q = h.data();
-  const auto take = [&](float *dst, size_t m) { if (dst) std::memcpy(dst, q, sizeof(float) * m); q += m; };
-  take(meanLevelFluxUp, nLvl);
-  take(meanLevelFluxDown, nLvl);
-  take(levelFluxUp, ncol * nLvl);
-  take(levelFluxDown, ncol * nLvl);
-  return 0;
+  const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;  // (the arrays are (nx, ny, 0:nz))
+  return deal_last(c, (size_t)tally_layout(c).momLevels, {{meanLevelFluxUp, nLvl}, {meanLevelFluxDown, nLvl}, {levelFluxUp, ncol * nLvl}, {levelFluxDown, ncol * nLvl}});
 }
 
 int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
@@ -1675,17 +1629,11 @@ int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
   if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
     if (!levels_on(c)) return fail(c, kDirectNeedsLevelsMsg);
     if (actinic_on(c)) return fail(c, kActinicDirectMsg);
-    if (!level_bins_fit(3.0, c->nx, c->ny, c->nz)) return fail(c, kDirectBudgetMsg);
+    if (!budget_fit(with_tallies(tally_shape(c), 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
   }
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  if (direct_on(c) != (levels_on(c) && on)) {  // the moment arrays change length: start them afresh (as mcbrat_specify_level_fluxes does)
-    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-    c->dMoments = nullptr;
-    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
-    c->haveLast = false;
-    c->tuned = false;  // (other kernels: the event threshold is chosen again)
-  }
+  if (direct_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
   c->directLevelFluxes = on;
   return 0;
 }
@@ -1694,21 +1642,9 @@ int mcbrat_report_direct_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxDownDir
                                       float *levelFluxDownDiffuse) {
   if (!c) return 1;
   if (!direct_on(c)) return fail(c, "reportResults: direct level-flux information not available");
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  // the direct / diffuse tail of the last batch's results: [meanDirect | meanDiffuse | direct | diffuse], in Fortran order (nx, ny, 0:nz)
   const size_t ncol = (size_t)c->nx * c->ny, nLvl = (size_t)c->nz + 1;
-  const size_t n = 2 * nLvl * (1 + ncol), base = (size_t)moments_direct_at(c);
-  std::vector<float> h(n);
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * n, hipMemcpyDeviceToHost));
-  const float *q = h.data();
-  const auto take = [&](float *dst, size_t m) { if (dst) std::memcpy(dst, q, sizeof(float) * m); q += m; };
-  take(meanLevelFluxDownDirect, nLvl);
-  take(meanLevelFluxDownDiffuse, nLvl);
-  take(levelFluxDownDirect, ncol * nLvl);
-  take(levelFluxDownDiffuse, ncol * nLvl);
-  return 0;
+  return deal_last(c, (size_t)tally_layout(c).momDirect, {{meanLevelFluxDownDirect, nLvl}, {meanLevelFluxDownDiffuse, nLvl}, {levelFluxDownDirect, ncol * nLvl},
+                   {levelFluxDownDiffuse, ncol * nLvl}});
 }
 
 int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
@@ -1721,17 +1657,11 @@ int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
     if (c->countersOn) return fail(c, kActinicCountersMsg);
     if (direct_on(c)) return fail(c, kActinicDirectMsg);
-    if (!global_bins_fit((double)level_parts(c), true, c->nx, c->ny, c->nz)) return fail(c, kActinicBudgetMsg);
+    if (!budget_fit(with_tallies(tally_shape(c), levels_on(c), direct_on(c), 1)).globalBins) return fail(c, kActinicBudgetMsg);
   }
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  if (on != c->actinicFlux) {  // the moment arrays change length: start them afresh (as mcbrat_specify_level_fluxes does)
-    if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
-    c->dMoments = nullptr;
-    if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
-    c->haveLast = false;
-    c->tuned = false;  // (another walk, other kernels: the event threshold is chosen again)
-  }
+  if (on != c->actinicFlux) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
   c->actinicFlux = on;
   return 0;
 }
@@ -1739,27 +1669,15 @@ int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
 int mcbrat_report_actinic_flux(mcbrat_ctx *c, float *meanActinicFlux, float *actinicFlux) {
   if (!c) return 1;
   if (!actinic_on(c)) return fail(c, "reportResults: actinic-flux information not available");
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  // the actinic tail of the last batch's results: [meanActinic | actinic], already in Fortran order (nx, ny, nz)
-  const size_t nvox = (size_t)c->nx * c->ny * (size_t)c->nz, n = (size_t)c->nz + nvox;
-  std::vector<float> h(n);
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + (size_t)moments_actinic_at(c), sizeof(float) * n, hipMemcpyDeviceToHost));
-  if (meanActinicFlux) std::memcpy(meanActinicFlux, h.data(), sizeof(float) * (size_t)c->nz);
-  if (actinicFlux) std::memcpy(actinicFlux, h.data() + c->nz, sizeof(float) * nvox);
-  return 0;
+  return deal_last(c, (size_t)tally_layout(c).momActinic, {{meanActinicFlux, (size_t)c->nz}, {actinicFlux, (size_t)c->nx * c->ny * (size_t)c->nz}});
 }
 
 int mcbrat_report_intensity(mcbrat_ctx *c, float *meanIntensity, float *intensity) {
   if (!c) return 1;
   if (c->nDir == 0) return fail(c, "reportResults: intensity information not available");
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  const size_t ncol = (size_t)c->nx * c->ny, base = 3 + 3 * ncol + c->nz + ncol * c->nz;
+  const size_t ncol = (size_t)c->nx * c->ny;
   std::vector<float> h(ncol * c->nDir);
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+  if (read_last(c, (size_t)tally_layout(c).momIntensity, h)) return 1;
   if (intensity) std::memcpy(intensity, h.data(), sizeof(float) * h.size());
   if (meanIntensity)
     for (int d = 0; d < c->nDir; ++d) {  // reportResults :980-992
@@ -2018,7 +1936,7 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   int m = (c->layerSkip ? 1 : 0) | (c->blockWalk ? 2 : 0);
   if (c->haveGrid && c->haveOptics) {  // what a flux launch of the loaded domain would do (the plan decides, as launch_trace does)
     // (the flux run's slab: with scattering orders its order bins too, so that private tallies give way where they no longer fit)
-    const LaunchPlan L = plan_launch(c, slab_stride(c, true));
+    const LaunchPlan L = plan_launch(c, (size_t)tally_layout(flux_run(tally_shape(c))).slabStride);
     m = ((c->layerSkip && !facewalk_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
@@ -2048,15 +1966,17 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     c->cur = 0;
   }
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
-  const size_t slabStride = slab_stride(c);
-  if (orders_on(c) && slabStride * sizeof(long long) > kSlabBudget)
+  const TallyLayout lay = tally_layout(c);
+  const size_t slabStride = (size_t)lay.slabStride;
+  const bool strideFits = budget_fit(tally_shape(c)).stride;
+  if (orders_on(c) && !strideFits)
     return fail(c, "computeRadiativeTransfer: numRecScatOrd is too large: one batch's tallies by scattering order need more than the 4 GiB tally budget.");
   if (orders_on(c) && c->countersOn)
     return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
   if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
-  if (levels_on(c) && !actinic_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
+  if (levels_on(c) && !actinic_on(c) && !strideFits) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
   if (actinic_on(c) && c->countersOn) return fail(c, kActinicCountersMsg);
-  if (actinic_on(c) && slabStride * sizeof(long long) > kSlabBudget) return fail(c, kActinicBudgetMsg);
+  if (actinic_on(c) && !strideFits) return fail(c, kActinicBudgetMsg);
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
   size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
@@ -2065,9 +1985,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   for (int li = 0; li < mcbrat_ctx::kLanes; ++li) {
     mcbrat_ctx::Lane &L = c->lane[li];
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
-    const size_t nOrdMeans = orders_on(c) ? (size_t)(c->numRecScatOrd + 1) * (2 + c->nDir) : 0;  // (domain means by order, behind the scalars)
-    const size_t nLvlMeans = level_quantities(c) * ((size_t)c->nz + 1);  // (domain means by level, behind those)
-    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)(3 + c->nz + nOrdMeans + nLvlMeans + (actinic_on(c) ? c->nz : 0)) * inFlight;  // (and the actinic layer means)
+    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)lay.scalPerBatch * inFlight;
     if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
     HIP_OK(c, hipStreamSynchronize(L.stream));
     if (L.slabCapacity < needSlab) {
@@ -2089,7 +2007,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
       L.scalCapacity = needScal;
     }
   }
-  if (!c->dLast) HIP_OK(c, dev_malloc((void **)&c->dLast, sizeof(float) * (size_t)moments_len(c)));
+  if (!c->dLast) HIP_OK(c, dev_malloc((void **)&c->dLast, sizeof(float) * (size_t)tally_layout(c).momentsLen));
 
   DevParams p;
   fill_params(c, p);
@@ -2130,7 +2048,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     }
     FinishParams f;
     f.nx = c->nx; f.ny = c->ny; f.nz = c->nz; f.nBatches = nb; f.xyRegular = c->xyRegular; f.nDir = c->nDir; f.nc = c->nc; f.limitContrib = c->limitContrib;
-    f.ppb = p.ppb; f.total = p.total; f.slabStride = slabStride;
+    f.ppb = p.ppb; f.total = p.total; f.lay = lay;
     f.slabs = c->L().dSlabs; f.relArea = c->dRelArea; f.ze = c->dEdges + (c->nx + 1) + (c->ny + 1);
     f.colVals = c->L().dColVals; f.scalVals = c->L().dScalVals; f.moments = c->dMoments; f.last = c->dLast;
     f.bad = c->dBad; f.badHost = c->hBadDev;
@@ -2141,22 +2059,20 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.foldColumns = (unsigned)((3 * ncol + kFinishBlock - 1) / kFinishBlock);
     f.foldScalars = (unsigned)((3 + c->nz + kFinishBlock - 1) / kFinishBlock);
     f.nOrd = orders_on(c) ? c->numRecScatOrd + 1 : 0;
-    f.ordVals = f.scalVals + (size_t)(3 + c->nz) * nb;
+    f.ordVals = f.scalVals + (size_t)lay.scalOrders * nb;
     f.gatherOrders = (unsigned)(((size_t)(2 + c->nDir) * ncol * f.nOrd + kFinishBlock - 1) / kFinishBlock);
     f.gatherOrderMeans = (unsigned)((2 + c->nDir) * f.nOrd) * (unsigned)nb;
     f.foldOrderMeans = (unsigned)(((2 + c->nDir) * f.nOrd + kFinishBlock - 1) / kFinishBlock);
     f.nLvl = levels_on(c) ? c->nz + 1 : 0;
-    f.lvlSlab = (long long)(slabStride - global_bins(c));
-    f.lvlVals = f.ordVals + (size_t)((2 + c->nDir) * f.nOrd) * nb;
+    f.lvlVals = f.scalVals + (size_t)lay.scalLevels * nb;
     f.lvlDirect = direct_on(c) ? 1 : 0;
-    const size_t nLvlQ = level_quantities(c);  // (up, down; with the direct tally direct and diffuse too)
+    const size_t nLvlQ = levels_on(c) ? (direct_on(c) ? 4 : 2) : 0;  // (up, down; with the direct tally direct and diffuse too)
     f.gatherLevels = (unsigned)((nLvlQ * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
     f.gatherLevelMeans = (unsigned)(nLvlQ * f.nLvl) * (unsigned)nb;
     f.foldLevelMeans = (unsigned)((nLvlQ * f.nLvl + kFinishBlock - 1) / kFinishBlock);
     f.act = actinic_on(c) ? 1 : 0;
-    f.actSlab = (long long)(slabStride - actinic_bins(c));
     f.actUnit = actinic_unit(c);
-    f.actVals = f.lvlVals + nLvlQ * (size_t)f.nLvl * nb;
+    f.actVals = f.scalVals + (size_t)lay.scalActinic * nb;
     f.gatherActinic = f.act ? (unsigned)((nvox + kVolVox - 1) / kVolVox) : 0u;
     f.gatherActinicMeans = f.act ? (unsigned)c->nz * (unsigned)nb : 0u;
     f.foldActinicMeans = f.act ? (unsigned)((c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
@@ -2203,20 +2119,18 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
 int mcbrat_report_results(mcbrat_ctx *c, float *meanUp, float *meanDown, float *meanAbs, float *fluxUp, float *fluxDown,
                           float *fluxAbs, float *absorbedProfile, float *volumeAbsorption) {
   if (!c) return 1;
-  if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
-  std::vector<float> h((size_t)moments_len(c));
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
-  if (meanUp) *meanUp = h[0];
-  if (meanDown) *meanDown = h[1];
-  if (meanAbs) *meanAbs = h[2];
-  if (fluxUp) std::memcpy(fluxUp, &h[3], sizeof(float) * ncol);
-  if (fluxDown) std::memcpy(fluxDown, &h[3 + ncol], sizeof(float) * ncol);
-  if (fluxAbs) std::memcpy(fluxAbs, &h[3 + 2 * ncol], sizeof(float) * ncol);
-  if (absorbedProfile) std::memcpy(absorbedProfile, &h[3 + 3 * ncol], sizeof(float) * c->nz);
-  if (volumeAbsorption) std::memcpy(volumeAbsorption, &h[3 + 3 * ncol + c->nz], sizeof(float) * nvox);
+  const TallyLayout lay = tally_layout(c);
+  std::vector<float> h((size_t)lay.momentsLen);
+  if (read_last(c, 0, h)) return 1;
+  if (meanUp) *meanUp = h[lay.momMeans];
+  if (meanDown) *meanDown = h[lay.momMeans + 1];
+  if (meanAbs) *meanAbs = h[lay.momMeans + 2];
+  if (fluxUp) std::memcpy(fluxUp, &h[lay.momColumns], sizeof(float) * ncol);
+  if (fluxDown) std::memcpy(fluxDown, &h[lay.momColumns + ncol], sizeof(float) * ncol);
+  if (fluxAbs) std::memcpy(fluxAbs, &h[lay.momColumns + 2 * ncol], sizeof(float) * ncol);
+  if (absorbedProfile) std::memcpy(absorbedProfile, &h[lay.momProfile], sizeof(float) * c->nz);
+  if (volumeAbsorption) std::memcpy(volumeAbsorption, &h[lay.momVolume], sizeof(float) * nvox);
   return 0;
 }
 
@@ -2229,8 +2143,9 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
   if (c->nDir > 0) return fail(c, "trace_fates: not available together with intensity directions.");
   if (levels_on(c)) return fail(c, kLevelsCountersMsg);
   if (actinic_on(c)) return fail(c, kActinicCountersMsg);
-  const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
-  const size_t slabStride = 2 * ncol + nvox;
+  TallyShape fluxes = flux_run(tally_shape(c));  // the slab of the instrumented kernels: the fluxes and the volume only
+  fluxes.nOrd = 0;
+  const size_t slabStride = (size_t)tally_layout(fluxes).slabStride;
   long long *scratch = nullptr;
   mcbrat_fate *dF = nullptr;
   HIP_OK(c, dev_malloc((void **)&scratch, sizeof(long long) * slabStride));
