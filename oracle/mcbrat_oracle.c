@@ -17,7 +17,9 @@
  * printed digits.  Parity unpinned (restated from the source text only, no reference output recorded): thermal
  * emission source and weighting, angle/value phase functions, irregular-grid launch, radiance by local estimation,
  * the surface description.  Not the reference's at all: the level tallies of orc_compute_rt_levels, which restate
- * DESIGN.md section 4.12 and are held to identities, the MT mode and transport theory by tests/test_oracle_levels.py.
+ * DESIGN.md section 4.12 and are held to identities, the MT mode and transport theory by tests/test_oracle_levels.py, and the
+ * track-length tally of orc_compute_rt_actinic, which restates DESIGN.md section 4.14 and is held the same way by
+ * tests/test_oracle_actinic.py.
  */
 #include "mcbrat_oracle.h"
 #include <float.h>
@@ -480,7 +482,21 @@ typedef struct {
   int64_t *nUp, *nDown;  /* deposits per bin, same layout (may be NULL) */
   float weight;          /* the photon's current weight */
   double path;           /* km travelled by the photon so far */
+  /* the track-length tally of DESIGN.md section 4.14 (orc_compute_rt_actinic only; act == NULL otherwise) */
+  double *act;           /* [nz][ny][nx]: sum of w l (km) over every piece of path inside the cell */
+  int64_t *nAct;         /* deposits per bin (may be NULL) */
+  double *actSlack;      /* sum of w 2 delta per bin, delta = 64 * 2^-23 * (km travelled up to the end of the piece) (may be NULL) */
+  int edge;              /* set where a full step of the photon had two finite face distances within delta of each other */
+  double legSum;         /* sum over photons and legs of w * (leg length), the length from the leg's two end positions */
 } level_tally;
+
+/* section 4.14: the piece of length len (km) inside cell idx, at the weight the leg carries; T->path already holds the piece */
+static void actinic_deposit(const orc_problem *P, level_tally *T, const int32_t idx[3], double len) {
+  const size_t b = IDX3(P, idx[0], idx[1], idx[2]);
+  T->act[b] += (double)T->weight * len;
+  if (T->nAct) T->nAct[b]++;
+  if (T->actSlack) T->actSlack[b] += (double)T->weight * 2.0 * (64.0 * ldexp(1.0, -23) * T->path);
+}
 
 static void level_deposit(const orc_problem *P, level_tally *T, int upward, int level, int ix, int iy, float w) {
   const size_t b = (size_t)(ix - 1) + (size_t)P->nx * ((size_t)(iy - 1) + (size_t)P->ny * (size_t)level);
@@ -520,6 +536,7 @@ static float accumulate_extinction(const orc_problem *P, const float dir[3], dou
         pos[2] = pos[2] + thisStep * (double)dir[2];
         extAccumulated = extToAccumulate;
         if (T) T->path += thisStep;
+        if (T && T->act) actinic_deposit(P, T, idx, thisStep); /* section 4.14: the piece up to the collision */
         break;
       }
     }
@@ -527,6 +544,17 @@ static float accumulate_extinction(const orc_problem *P, const float dir[3], dou
     if (crossings) (*crossings)++;
     const int zBefore = idx[2];
     if (T) T->path += thisStep;
+    if (T && T->act) { /* section 4.14: the whole step belongs to the cell being left (a step out of the top or the surface too),
+                        * credited before idx moves and before the periodic wrap */
+      actinic_deposit(P, T, idx, thisStep);
+      /* two faces of the cell reached within delta of each other: the walk passes an edge or a corner, and two correct walks
+       * may visit different sliver cells there (a direction cosine of zero has no face distance) */
+      const double delta = 64.0 * ldexp(1.0, -23) * T->path;
+      for (int a = 0; a < 3; a++) {
+        const int b = (a + 1) % 3;
+        if (step[a] < DBL_MAX && step[b] < DBL_MAX && fabs(step[a] - step[b]) <= delta) T->edge = 1;
+      }
+    }
     for (int a = 0; a < 3; a++) { /* :1752-1777 */
       if (step[a] <= thisStep) {
         pos[a] = edge[a][idx[a] + side[a] - 1];
@@ -955,6 +983,7 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
                           float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
                           orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
                           float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace);
+static double leg_length(const orc_problem *P, const float dir[3], const double before[3], const double after[3]);
 
 int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
                                  float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
@@ -982,6 +1011,46 @@ int64_t orc_compute_rt_levels(const orc_problem *P, const orc_source *S, orc_rng
   if (levelDownCount) memset(levelDownCount, 0, sizeof(int64_t) * nbins);
   return compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, NULL, NULL, NULL, NULL,
                     &T, nearFace);
+}
+
+/* computeRT with the level tallies and the track-length tally of DESIGN.md section 4.14 (ours, restated from that section's
+ * definition): actinic [nz][ny][nx] = sum of w l in km, in double, over every piece of path inside the cell at the weight the
+ * leg carries; actinicCount the deposits per bin; actinicSlack the sum per bin of w 2 delta, delta = 64 * 2^-23 * (km travelled
+ * up to the end of the piece) -- what a walk whose positions differ by delta at both ends of a piece may tally differently;
+ * legSum (may be NULL) the sum over photons and legs of w * (leg length), the length taken from the positions before and after
+ * the leg and not from the walk's steps.  nearFace is orc_compute_rt_levels' flag, and also set where a full step of the
+ * photon had two of its face distances within delta of each other. */
+int64_t orc_compute_rt_actinic(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
+                               float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
+                               orc_counters *C, orc_fate *fates, double *levelUp, double *levelDown,
+                               int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace, double *actinic,
+                               int64_t *actinicCount, double *actinicSlack, double *legSum) {
+  const size_t ncol = (size_t)P->nx * P->ny, nbins = ncol * ((size_t)P->nz + 1), nvox = ncol * (size_t)P->nz;
+  level_tally T = {levelUp, levelDown, levelUpCount, levelDownCount, 1.0f, 0.0, actinic, actinicCount, actinicSlack, 0, 0.0};
+  memset(levelUp, 0, sizeof(double) * nbins);
+  memset(levelDown, 0, sizeof(double) * nbins);
+  if (levelUpCount) memset(levelUpCount, 0, sizeof(int64_t) * nbins);
+  if (levelDownCount) memset(levelDownCount, 0, sizeof(int64_t) * nbins);
+  memset(actinic, 0, sizeof(double) * nvox);
+  if (actinicCount) memset(actinicCount, 0, sizeof(int64_t) * nvox);
+  if (actinicSlack) memset(actinicSlack, 0, sizeof(double) * nvox);
+  const int64_t n = compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, NULL, NULL, NULL,
+                               NULL, &T, nearFace);
+  if (legSum) *legSum = T.legSum;
+  return n;
+}
+
+/* length of the leg from `before` to `after` along dir, from the positions alone: by z (which does not wrap), refined along the
+ * axis of the largest direction cosine once the whole periods of x / y that the leg wrapped through are put back */
+static double leg_length(const orc_problem *P, const float dir[3], const double before[3], const double after[3]) {
+  int a = 2;
+  if (fabsf(dir[0]) > fabsf(dir[a])) a = 0;
+  if (fabsf(dir[1]) > fabsf(dir[a])) a = 1;
+  if (a == 2) return (after[2] - before[2]) / (double)dir[2];
+  const double estimate = (after[2] - before[2]) / (double)dir[2];
+  const double period = a == 0 ? P->xe[P->nx] - P->xe[0] : P->ye[P->ny] - P->ye[0];
+  const double wraps = rint((before[a] + estimate * (double)dir[a] - after[a]) / period);
+  return (after[a] + wraps * period - before[a]) / (double)dir[a];
 }
 
 static int near_any(double v, const double *t, int n, double delta) {
@@ -1069,6 +1138,7 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
               * of level 0, each with weight 1 in the launch column; an atmospheric launch crosses nothing */
       T->path = 0.0;
       T->weight = photonWeight;
+      T->edge = 0;
       if (S->kind == 0) level_deposit(P, T, 0, nz, xIndex, yIndex, photonWeight);
       else if (L.z == 0.0) level_deposit(P, T, 1, 0, xIndex, yIndex, photonWeight); /* (the surface launch of :493) */
     }
@@ -1096,6 +1166,10 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
       int32_t idx[3] = {xIndex, yIndex, zIndex};
       if (T) T->weight = photonWeight;
       float tauAccumulated = accumulate_extinction(P, dir, pos, idx, 1, tauToTravel, &cnt.crossings, T);
+      if (T && T->act && tauAccumulated >= 0.0f) {
+        const double before[3] = {xPos, yPos, zPos};
+        T->legSum += (double)photonWeight * leg_length(P, dir, before, pos);
+      }
       xPos = pos[0]; yPos = pos[1]; zPos = pos[2];
       xIndex = idx[0]; yIndex = idx[1]; zIndex = idx[2];
       if (tauAccumulated < 0.0f) { cnt.badPhotons++; fate = 3; break; } /* :562-563 */
@@ -1215,6 +1289,7 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
         next_direct(R, cosf(scatteringAngle), dir); /* :819 */
       }
     }
+    if (T && T->act && T->edge) flagged = 1;
     if (nearFace) nearFace[ip] = (uint8_t)flagged;
     if (fates) {
       fates[ip].fate = fate;

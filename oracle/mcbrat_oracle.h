@@ -194,6 +194,18 @@ int64_t orc_compute_rt_levels(const orc_problem *P, const orc_source *S, orc_rng
                               float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C,
                               orc_fate *fates, double *levelUp, double *levelDown,
                               int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace);
+/* orc_compute_rt_levels with the track-length tally of DESIGN.md section 4.14 beside it (not in the reference): actinic
+ * [nz][ny][nx], the sum of w l (km) in double over every piece of path inside the cell at the weight the leg carries (steps that
+ * leave through the top or the surface count); actinicCount, the deposits per bin; actinicSlack, the sum per bin of w 2 delta
+ * with delta = 64 * 2^-23 * (km travelled up to the end of the piece); legSum, the sum over photons and legs of w * (leg length)
+ * from the leg's two end positions (the last three may be NULL).  nearFace is also set where a full step of the photon had two
+ * of its face distances within delta of each other (the walk passes an edge or a corner of the cell). */
+int64_t orc_compute_rt_actinic(const orc_problem *P, const orc_source *S, orc_rng *R,
+                               int64_t numPhotons, float *fluxUp, float *fluxDown,
+                               float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C,
+                               orc_fate *fates, double *levelUp, double *levelDown,
+                               int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace,
+                               double *actinic, int64_t *actinicCount, double *actinicSlack, double *legSum);
 /* normalisation of computeRadiativeTransfer (:328-364), in place. */
 void orc_normalize(const orc_problem *P, int64_t numPhotonsProcessed, float *fluxUp,
                    float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption);

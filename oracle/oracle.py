@@ -104,6 +104,8 @@ def lib():
         L.orc_normalize.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
         L.orc_compute_rt_levels.restype = C.c_int64
         L.orc_compute_rt_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 11
+        L.orc_compute_rt_actinic.restype = C.c_int64
+        L.orc_compute_rt_actinic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 15
         L.orc_find_index_double.argtypes = [C.c_double, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_real.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_mixed.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
@@ -405,6 +407,41 @@ def normalize_levels(problem, n_done, res):
     nppc = _nppc(problem, n_done)
     up, dn = res["levelUp"] / nppc[None], res["levelDown"] / nppc[None]
     return dict(levelFluxUp=up, levelFluxDown=dn, meanLevelFluxUp=up.mean(axis=(1, 2)), meanLevelFluxDown=dn.mean(axis=(1, 2)))
+
+
+def compute_rt_actinic(problem, source, rng, n_photons):
+    """compute_rt_levels() with the track-length tally of DESIGN.md section 4.14 beside it (not in the reference): also
+    actinic [nz, ny, nx] (sum of w l in km over every piece of path inside the cell, float64), actinicCount (deposits per bin),
+    actinicSlack (sum per bin of w 2 delta, delta = 64 * 2^-23 * the path length up to the end of the piece) and legSum (sum over
+    photons and legs of w * leg length, from the legs' end positions).  nearFace is also set where the photon's walk passed an
+    edge or a corner of a cell (two face distances of a full step within delta of each other)."""
+    ncol = problem.nx * problem.ny
+    nvox = ncol * problem.nz
+    shape, cells = (problem.nz + 1, problem.ny, problem.nx), (problem.nz, problem.ny, problem.nx)
+    up, dn, ab = (np.zeros(ncol, np.float32) for _ in range(3))
+    vol = np.zeros(nvox, np.float32)
+    lup, ldn = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
+    nup, ndn = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+    act, slack, nact = np.zeros(cells, np.float64), np.zeros(cells, np.float64), np.zeros(cells, np.int64)
+    legs = C.c_double(0.0)
+    near = np.zeros(max(int(n_photons), 1), np.uint8)
+    cnt = OrcCounters()
+    src = source.c if hasattr(source, "c") else source
+    n = lib().orc_compute_rt_actinic(C.addressof(problem.c), C.addressof(src), C.addressof(rng), int(n_photons),
+                                     _p(up), _p(dn), _p(ab), _p(vol), C.addressof(cnt), None,
+                                     _p(lup), _p(ldn), _p(nup), _p(ndn), _p(near), _p(act), _p(nact), _p(slack), C.addressof(legs))
+    return {"n": int(n), "fluxUp": up, "fluxDown": dn, "fluxAbsorbed": ab, "volumeAbsorption": vol, "counters": cnt.as_dict(),
+            "levelUp": lup, "levelDown": ldn, "levelUpCount": nup, "levelDownCount": ndn,
+            "nearFace": near[:int(n_photons)].astype(bool), "actinic": act, "actinicCount": nact, "actinicSlack": slack,
+            "legSum": legs.value}
+
+
+def normalize_actinic(problem, n_done, res):
+    """actinicFlux [nz, ny, nx] = sum of w l / (nppc dz_k) and meanActinicFlux [nz], the plain mean over the columns of a layer
+    (float64), from compute_rt_actinic()."""
+    nppc = _nppc(problem, n_done)
+    act = res["actinic"] / (nppc[None] * np.diff(problem.ze)[:, None, None])
+    return dict(actinicFlux=act, meanActinicFlux=act.mean(axis=(1, 2)))
 
 
 def _nppc(problem, n_done):

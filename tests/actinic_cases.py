@@ -148,3 +148,107 @@ def sigma_abs(case):
             ext, ssa = ext[None, None, :], ssa[None, None, :]
         s = s + np.broadcast_to(ext * (1.0 - ssa), shape)
     return s
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the product against the oracle's track-length tally (oracle.compute_rt_actinic): tests/test_oracle_actinic.py (CPU) and
+# tests/test_gpu_actinic_oracle.py
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_IDS = 128  # photon ids per product call of the exact tier
+SOLAR_EXACT = [n for n, v in LC.EXACT.items() if v[1] is not None]
+
+
+def split_runs(runs, most=MAX_IDS):
+    """[(first id, count)] of the calls that trace the runs of clean ids, none longer than `most`."""
+    return [(first + lo, min(most, count - lo)) for first, count in runs for lo in range(0, count, most)]
+
+
+def actinic_bracket(res, xe, ye, ze, n):
+    """[lo, hi] for every float reportActinicFlux() may return for the photons whose oracle sums are `res`
+    (oracle.compute_rt_actinic): dict(actinicFlux=(lo, hi) [nz, ny, nx], meanActinicFlux=(lo, hi) [nz]), float32.
+
+    Per bin the oracle holds S = sum of w l (km, double), the deposits c and actinicSlack = sum of w 2 delta.  The product's
+    integer tally R (units of 2^-32 2^e km, 2^e = actinic_unit) is the sum over the same pieces of
+    rint(fl(fl(w l') 2^-e) 2^32), l' its own float length of the piece.  Term by term, |R 2^-32 2^e - S| is at most
+
+    * sum of w |l' - l| <= sum of w 2 delta = actinicSlack: the two walks place each end of a piece (a face, a collision point)
+      within delta = 64 x 2^-23 x (the path so far) of each other -- the margin by which a photon is called clean, so an end that
+      could fall on the other side of a face is not among the ids compared;
+    * the float roundings of l' = tmin - tcur and of w l', 2^-24 relative each (the scaling by 2^-e and by 2^32 is exact):
+      (1 + 2^-24)^2 - 1 < 3 x 2^-24 of the product's own sum, itself at most S + actinicSlack;
+    * half a fixed-point unit per deposit, c 2^-33 2^e (a value rounded to zero, or a negative length converted to zero, which
+      only moves it towards the oracle's non-negative piece, included);
+    * the rounding of the oracle's own double sum of c non-negative terms, c 2^-53 S.
+
+    R is an integer: it lies between the floor and the ceiling of the two ends in its unit.  The epilogue then forms
+    (float)(((R 2^-32) 2^e) / (nppc dz)) per cell and the fixed float tree over the columns of a layer (actinic_values): every
+    step is a correctly rounded operation, monotone in its non-negative inputs, so pushing the two ends through the written-out
+    epilogue brackets the floats.  No measured slack."""
+    g = EM.Grid(xe, ye, ze)
+    unit = actinic_unit(xe, ye, ze)
+    s, c, slack = res["actinic"].reshape(-1), res["actinicCount"].reshape(-1).astype(F64), res["actinicSlack"].reshape(-1)
+    half = slack + 3.0 * 2.0 ** -24 * (s + slack) + c * 2.0 ** -33 * unit + c * 2.0 ** -53 * s
+    to_raw = 4294967296.0 / unit
+    ends = [np.floor(np.maximum(s - half, 0.0) * to_raw).astype(np.int64), np.ceil((s + half) * to_raw).astype(np.int64)]
+    (mlo, clo), (mhi, chi) = (actinic_values(g, raw, n, unit) for raw in ends)
+    shape = res["actinic"].shape
+    return dict(actinicFlux=(clo.reshape(shape), chi.reshape(shape)), meanActinicFlux=(mlo, mhi))
+
+
+def _actinic_worker(args):
+    name, mode, seed, proc, first_batch, n_batches, ppb = args
+    from oracle import oracle as O
+    make, mu0, phi0 = LC.STATISTICAL[name]
+    P = cases.oracle_problem(make(), use_russian_roulette=True)
+    rng = O.mt_rng([seed, proc, 0]) if mode == "mt" else None
+    out = []
+    for b in range(first_batch, first_batch + n_batches):
+        if mode == "philox":
+            rng = O.philox_rng(seed, b * ppb)
+        r = O.compute_rt_actinic(P, O.solar_source(mu0, phi0), rng, ppb)
+        v = O.normalize_actinic(P, r["n"], r)
+        out.append((ppb, v["meanActinicFlux"], v["actinicFlux"].reshape(-1)))
+    return out
+
+
+def oracle_actinic_run(name, mode, n_batches, ppb, seed=10, procs=None):
+    """-> {"means": (mean, stderr) of meanActinicFlux [nz], "bins": the same of actinicFlux [nz ny nx], layer slowest, x fastest}
+    of a case of level_cases.STATISTICAL from the batch variance, the oracle spread over processes as
+    level_cases.oracle_level_run spreads it."""
+    import multiprocessing as mp
+    import os
+    from oracle import oracle as O
+    O.build()
+    procs = procs or max(1, min(8, len(os.sched_getaffinity(0)), n_batches))
+    base, extra = divmod(n_batches, procs)
+    jobs, lo = [], 0
+    for p in range(procs):
+        nb = base + (1 if p < extra else 0)
+        if nb:
+            jobs.append((name, mode, seed, p + 1, lo, nb, ppb))
+        lo += nb
+    if len(jobs) == 1:
+        parts = [_actinic_worker(jobs[0])]
+    else:
+        with mp.get_context("spawn").Pool(len(jobs)) as pool:
+            parts = pool.map(_actinic_worker, jobs)
+    rows = [r for part in parts for r in part]
+    return {"means": O.batch_statistics([(n, m) for n, m, _ in rows]), "bins": O.batch_statistics([(n, b) for n, _, b in rows])}
+
+
+SOLAR_THEORY = ("isotropic layers over albedo 0.5", "HG g = 0.85, tau = 4, regular z", "homogeneous on a stretched 7 x 5 x 12 grid")
+
+
+def actinic_theory(name):
+    """level_cases.theory(name) with the layer means of the actinic flux that its level fluxes imply.  In a plane-parallel medium
+    what layer k absorbs is the difference of the net flux (down - up) between its two levels, and it is sigma_abs dz times the
+    layer's actinic flux: actinic[k] = (net[k + 1] - net[k]) / ((1 - omega_k) dtau_k), (1 - omega_k) dtau_k = sigma_abs_k dz_k, wherever
+    that is positive (`layers`).  floor[k] = 4e-6 / ((1 - omega_k) dtau_k): 1e-6 on each of the four fluxes, through the quotient."""
+    t = LC.theory(name)
+    sig = sigma_abs(t["case"])
+    assert np.all(sig == sig[:1, :1, :])  # plane parallel
+    absorbing = sig[0, 0] * np.diff(np.asarray(t["case"]["ze"], F64))
+    layers = absorbing > 0
+    net = np.asarray(t["down"], F64) - np.asarray(t["up"], F64)
+    safe = np.where(layers, absorbing, 1.0)
+    return dict(t, layers=layers, actinic=np.where(layers, (net[1:] - net[:-1]) / safe, np.nan), floor=np.where(layers, 4e-6 / safe, np.nan))
