@@ -13,7 +13,8 @@
 program mcbrat_driver
   use mcbrat_hip_integrator, lastBatchLevelFluxes => reportLevelFluxes, &   ! (the /output/ namelist has variables of these names)
                              lastBatchDirectLevelFluxes => reportDirectLevelFluxes, &
-                             lastBatchActinicFlux => reportActinicFlux
+                             lastBatchActinicFlux => reportActinicFlux, &
+                             lastBatchSideFluxes => reportSideFluxes
   implicit none
   ! --- namelist variables (names and defaults of the reference driver) ---
   real     :: solarMu = 1., solarAzimuth = 0., LW_flag = -1.
@@ -37,6 +38,7 @@ program mcbrat_driver
   logical  :: recScatOrd = .false.
   integer  :: numRecScatOrd = 0
   logical  :: reportLevelFluxes = .false., reportDirectLevelFluxes = .false., reportActinicFlux = .false.
+  logical  :: reportSideFluxes = .false.
   character(len=256) :: auxhist01_radFile = "", auxhist01_fluxFile = ""
   character(len=256) :: solarSourceFile = "", instrResponseFile = "", physDomainFile = ""
   character(len=256), dimension(4) :: SSPfilename = ""
@@ -50,7 +52,7 @@ program mcbrat_driver
                                useRussianRouletteForIntensity, zetaMin, limitIntensityContributions, &
                                maxIntensityContribution
   namelist /output/            reportVolumeAbsorption, reportAbsorptionProfile, recScatOrd, numRecScatOrd, &
-                               reportLevelFluxes, reportDirectLevelFluxes, reportActinicFlux, auxhist01_fluxFile, &
+                               reportLevelFluxes, reportDirectLevelFluxes, reportActinicFlux, reportSideFluxes, auxhist01_fluxFile, &
                                auxhist01_radFile
   namelist /fileNames/         solarSourceFile, instrResponseFile, SSPfilename, physDomainFile, &
                                outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, &
@@ -67,7 +69,7 @@ program mcbrat_driver
   real(8), allocatable :: moments(:)
   real(8), allocatable :: meanStats(:,:), fluxUpStats(:,:,:), fluxDownStats(:,:,:), fluxAbsorbedStats(:,:,:), &
                           absorbedProfileStats(:,:), RadianceStats(:,:,:,:), meanByScatOrdStats(:,:,:), &
-                          meanLevelStats(:,:,:), meanActinicStats(:,:)
+                          meanLevelStats(:,:,:), meanActinicStats(:,:), meanSideStats(:,:,:)
   real,    allocatable :: forwardTable(:,:), legendreCoefficients(:)
   integer :: numRadDir, off, nLevelStats
   logical :: computeIntensity
@@ -87,6 +89,8 @@ program mcbrat_driver
     stop "reportDirectLevelFluxes: direct level fluxes are not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
   if (reportActinicFlux .and. (numLambda > 1 .or. LW_flag >= 0.)) &
     stop "reportActinicFlux: the actinic flux is not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
+  if (reportSideFluxes .and. (numLambda > 1 .or. LW_flag >= 0.)) &
+    stop "reportSideFluxes: side fluxes are not available for spectrally integrated runs (numLambda > 1 or thermal emission)"
   solarFlux = 1.0_8
 
   call cpu_time(t0)
@@ -130,6 +134,10 @@ program mcbrat_driver
   ! the actinic flux of every cell by track length (refused together with directions, orders and the direct level tally)
   if (reportActinicFlux) then
     call specifyActinicFlux(mcIntegrator, .true., ierr); call check("specifyParameters")
+  end if
+  ! the flux through the vertical faces of every cell (refused without reportLevelFluxes, with the direct tally and the actinic flux)
+  if (reportSideFluxes) then
+    call specifySideFluxes(mcIntegrator, .true., ierr); call check("specifyParameters")
   end if
   call setSolarSource(mcIntegrator, solarMu, solarAzimuth, ierr); call check("setSolarSource")
   call resetMoments(mcIntegrator, ierr); call check("resetMoments")
@@ -185,7 +193,8 @@ program mcbrat_driver
     ! reportDirectLevelFluxes the first 2 (nz+1) of the direct / diffuse tail behind it (meanStats 3, 4: direct, diffuse)
     nLevelStats = merge(4, 2, reportDirectLevelFluxes)
     allocate(meanLevelStats(0:nz, nLevelStats, 2))
-    off = int(M) - nLevelStats*(nz+1)*(1+ncol) - merge(nz*(1+ncol), 0, reportActinicFlux)   ! (the actinic tail lies behind)
+    off = int(M) - nLevelStats*(nz+1)*(1+ncol) - merge(nz*(1+ncol), 0, reportActinicFlux) &
+          - merge(4*nz*(1+ncol), 0, reportSideFluxes)   ! (the actinic tail or the side tail lies behind)
     do k = 1, 2
       do j = 1, nLevelStats
         i = off + merge(2*(nz+1)*(1+ncol), 0, j > 2) + (j - merge(3, 1, j > 2))*(nz+1)
@@ -217,6 +226,23 @@ program mcbrat_driver
     do i = nz, 1, -1
       print '(A,I3,A,F9.4,A,F9.4,A,2X,F9.6,A,F9.6)', " layer ", i - 1, " z ", zPosition(i), " -", zPosition(i+1), &
             " mean actinic flux:", meanActinicStats(i, 1), " +-", meanActinicStats(i, 2)
+    end do
+  end if
+  if (reportSideFluxes) then   ! layer means of the four side fluxes: the first 4 nz entries of the side tail, the last of all
+    allocate(meanSideStats(nz, 4, 2))
+    off = int(M) - 4*nz*(1+ncol)
+    do k = 1, 2
+      do j = 1, 4
+        meanSideStats(:, j, k) = moments(8 + (k-1)*M + off + (j-1)*nz + 1 : 8 + (k-1)*M + off + j*nz)
+      end do
+    end do
+    do j = 1, 4
+      call momentsToStats1(meanSideStats(:, j, :))
+    end do
+    do i = nz, 1, -1
+      print '(A,I3,A,F9.4,A,F9.4,A,4(1X,F9.6))', " layer ", i - 1, " z ", zPosition(i), " -", zPosition(i+1), &
+            " mean side flux x+ x- y+ y-:", meanSideStats(i, 1, 1), meanSideStats(i, 2, 1), meanSideStats(i, 3, 1), &
+            meanSideStats(i, 4, 1)
     end do
   end if
   if (len_trim(outputFluxFile) > 0) call writeFluxASCII()

@@ -31,7 +31,8 @@ module mcbrat_hip_integrator
             specifyIntensity, setForwardTable, reportIntensity, forwardTableLegendre, &
             setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
             specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes, &
-            specifyDirectLevelFluxes, reportDirectLevelFluxes, specifyActinicFlux, reportActinicFlux
+            specifyDirectLevelFluxes, reportDirectLevelFluxes, specifyActinicFlux, reportActinicFlux, &
+            specifySideFluxes, reportSideFluxes
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -232,6 +233,17 @@ module mcbrat_hip_integrator
     function mcbrat_report_actinic_flux(ctx, mActinic, fActinic) bind(C, name="mcbrat_report_actinic_flux") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, mActinic, fActinic   ! (c_null_ptr: not wanted)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_specify_side_fluxes(ctx, enable) bind(C, name="mcbrat_specify_side_fluxes") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: enable
+      integer(c_int) :: rc
+    end function
+    function mcbrat_report_side_fluxes(ctx, mSide, fSide) bind(C, name="mcbrat_report_side_fluxes") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, mSide, fSide   ! (c_null_ptr: not wanted)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -761,6 +773,36 @@ contains
     end if
     ierr = mcbrat_report_actinic_flux(this%ctx, mActinic, fActinic)
   end subroutine reportActinicFlux
+
+  ! specifyParameters(recSideFluxes): the flux through the vertical faces of every cell.  Solar sources only; needs level fluxes
+  ! (specifyLevelFluxes first), not together with their direct tally or the actinic flux.  Changes momentsLength().
+  subroutine specifySideFluxes(this, enable, ierr)
+    type(integrator), intent(inout) :: this
+    logical,          intent(in)    :: enable
+    integer,          intent(out)   :: ierr
+    ierr = mcbrat_specify_side_fluxes(this%ctx, merge(1_c_int32_t, 0_c_int32_t, enable))
+  end subroutine specifySideFluxes
+
+  ! the last batch's side fluxes, the last index 1 .. 4: x plus, x minus, y plus, y minus --
+  ! meanSideFluxes(numZ, 4), sideFluxes(numX, numY, numZ, 4)
+  subroutine reportSideFluxes(this, meanSideFluxes, sideFluxes, ierr)
+    type(integrator), intent(inout) :: this
+    real, dimension(:, :),       contiguous, optional, target, intent(out) :: meanSideFluxes
+    real, dimension(:, :, :, :), contiguous, optional, target, intent(out) :: sideFluxes
+    integer,                     intent(out) :: ierr
+    type(c_ptr) :: mSide, fSide
+    mSide = c_null_ptr; fSide = c_null_ptr
+    ierr = 2   ! "reportResults: sideFluxes is the wrong size"
+    if (present(meanSideFluxes)) then
+      if (any(shape(meanSideFluxes) /= (/ this%numZ, 4 /))) return
+      mSide = c_loc(meanSideFluxes)
+    end if
+    if (present(sideFluxes)) then
+      if (any(shape(sideFluxes) /= (/ this%numX, this%numY, this%numZ, 4 /))) return
+      fSide = c_loc(sideFluxes)
+    end if
+    ierr = mcbrat_report_side_fluxes(this%ctx, mSide, fSide)
+  end subroutine reportSideFluxes
 
   integer(8) function numBadPhotons(this)
     type(integrator), intent(in) :: this

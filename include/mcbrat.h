@@ -232,6 +232,24 @@ int mcbrat_specify_actinic_flux(mcbrat_ctx *ctx, int32_t enable);
 /* The LAST batch, Fortran order with the layer slowest: meanActinicFlux(nz), actinicFlux(nx, ny, nz).  Any pointer may be NULL. */
 int mcbrat_report_actinic_flux(mcbrat_ctx *ctx, float *meanActinicFlux, float *actinicFlux);
 
+/* The flux through the vertical faces of every cell (specifyParameters(recSideFluxes); an addition under ABI version 3; DESIGN.md
+ * section 4.15).  Four quantities per cell, each (nx, ny, nz): sideFluxXPlus(x, y, k) is the weight that crossed the face
+ * x = xPosition[x+1] of the patch (row y, layer k) -- the high-x face of cell (x, y, k); for x = nx-1 the periodic boundary --
+ * towards +x, sideFluxXMinus the weight that crossed it towards -x; sideFluxYPlus / sideFluxYMinus the same for the face
+ * y = yPosition[y+1].  A crossing adds the weight the photon carries on that leg, a periodic wrap is a crossing like any other,
+ * and the patch of a crossing is that of the cell being left.  F_x = sum * dx_x / (photons per column * dz_k), F_y = sum * dy_y /
+ * (photons per column * dz_k): the flux density through the vertical face per unit flux through a horizontal unit area at the
+ * top (a vacuum under a sun at (mu0, phi0) gives F_x+ - F_x- = sqrt(1 - mu0^2) cos(phi0) / mu0 in every face).  The layer means
+ * are the sum over the columns of layer k divided by their number.  A tally of the solar level-flux kernels: fails without
+ * level fluxes (which cannot be switched off under it), with everything level fluxes fail with, with direct level fluxes and
+ * the actinic flux, with the thermal source (mcbrat_compute_radiative_transfer), and where one batch's level and side bins
+ * would not fit the tally budget -- whichever call comes first.  Changes mcbrat_moments_length(): a caller-bound moment buffer
+ * must be bound again. */
+int mcbrat_specify_side_fluxes(mcbrat_ctx *ctx, int32_t enable);
+/* The LAST batch, Fortran order with the layer slowest, the four quantities in the order x plus, x minus, y plus, y minus:
+ * meanSideFluxes(nz, 4), sideFluxes(nx, ny, nz, 4).  Either pointer may be NULL. */
+int mcbrat_report_side_fluxes(mcbrat_ctx *ctx, float *meanSideFluxes, float *sideFluxes);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:
@@ -247,7 +265,9 @@ int mcbrat_report_actinic_flux(mcbrat_ctx *ctx, float *meanActinicFlux, float *a
  *   levelFluxUp[(nz+1)*nx*ny], levelFluxDown[(nz+1)*nx*ny] (level slowest, x fastest),
  *   and with direct level fluxes, behind those: meanLevelFluxDownDirect[nz+1], meanLevelFluxDownDiffuse[nz+1],
  *   levelFluxDownDirect[(nz+1)*nx*ny], levelFluxDownDiffuse[(nz+1)*nx*ny],
- *   and with the actinic flux, behind every other tail: meanActinicFlux[nz], actinicFlux[nz*nx*ny] (layer slowest, x fastest).
+ *   and with the actinic flux, behind every other tail: meanActinicFlux[nz], actinicFlux[nz*nx*ny] (layer slowest, x fastest),
+ *   and with side fluxes, behind every other tail: meanSideFluxXPlus[nz], meanSideFluxXMinus[nz], meanSideFluxYPlus[nz],
+ *   meanSideFluxYMinus[nz], then sideFluxXPlus, sideFluxXMinus, sideFluxYPlus, sideFluxYMinus, [nz*nx*ny] each (layer slowest).
  * Total doubles = 8 + 2*length.  The buffer is device memory; a caller that
  * wants to all-reduce it with RCCL binds its own device buffer. */
 int64_t mcbrat_moments_length(const mcbrat_ctx *ctx);

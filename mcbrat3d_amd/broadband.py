@@ -101,6 +101,8 @@ class SpectralRun:
             raise McbratError("SpectralRun: direct level fluxes (recDirectLevelFluxes) are not available for spectrally integrated runs")
         if parameters.get("recActinicFlux"):
             raise McbratError("SpectralRun: the actinic flux (recActinicFlux) is not available for spectrally integrated runs")
+        if parameters.get("recSideFluxes"):
+            raise McbratError("SpectralRun: side fluxes (recSideFluxes) are not available for spectrally integrated runs")
         if getattr(parameters.get("surfaceBDRF"), "kind", 0) != 0:
             raise McbratError("SpectralRun: BRDF surfaces (RPV, Ross-Li) are not available for spectrally integrated runs: "
                               "their parameters do not vary with wavelength and the thermal source cannot use them")

@@ -127,6 +127,8 @@ struct mcbrat_ctx {
   int directLevelFluxes = 0;
   // the actinic flux of every cell by track length (mcbrat_specify_actinic_flux)
   int actinicFlux = 0;
+  // the flux through the vertical faces of every cell (mcbrat_specify_side_fluxes); needs levelFluxes
+  int sideFluxes = 0;
   // parameters
   float albedo = 0.f;
   int useRR = 1;
@@ -262,19 +264,25 @@ bool actinic_on(const mcbrat_ctx *c) { return c->actinicFlux != 0; }
 // the tallies that make every cell face a stop: the plan then walks face by face (no layer skipping, flight, block walk, wide
 // plan, bricks or 768-lane kernel), and their bins stay in global memory
 bool facewalk_on(const mcbrat_ctx *c) { return levels_on(c) || actinic_on(c); }
+// the flux through the vertical faces of every cell: a tally of the level-flux kernels, on their walk
+bool side_on(const mcbrat_ctx *c) { return c->levelFluxes != 0 && c->sideFluxes != 0; }
 
 // Where every tally lies -- in one batch's slab, in the moments and the last batch's results, in the finish kernels' scalar
 // scratch -- is defined by mcbrat_layout.h; nothing here derives an offset of its own.
 int32_t order_count(int32_t numRecScatOrd) { return numRecScatOrd < 0 ? 0 : (numRecScatOrd < INT32_MAX ? numRecScatOrd + 1 : INT32_MAX); }
 TallyShape tally_shape(const mcbrat_ctx *c) {
-  return TallyShape{c->nx, c->ny, c->nz, c->nc, c->nDir, c->limitContrib, order_count(c->numRecScatOrd), levels_on(c), direct_on(c), actinic_on(c)};
+  return TallyShape{c->nx, c->ny, c->nz, c->nc, c->nDir, c->limitContrib, order_count(c->numRecScatOrd), levels_on(c), direct_on(c), actinic_on(c), side_on(c)};
 }
 TallyLayout tally_layout(const mcbrat_ctx *c) { return tally_layout(tally_shape(c)); }
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
 // whether the bins of one batch of a (candidate) shape fit that budget: its order part, its level and actinic bins, all of it
 TallyFit budget_fit(const TallyShape &s) { return tally_fit(s, kSlabBudget); }
-// (candidate shapes: the context's with other level and actinic settings; without the actinic flux a refusal is the level tallies')
-TallyShape with_tallies(TallyShape s, int levels, int direct, int actinic) { s.levels = levels; s.direct = levels && direct; s.actinic = actinic; return s; }
+// (candidate shapes: the context's with other level and actinic settings and, unless asked for, without the side part; without
+// the actinic flux and the side fluxes a refusal is the level tallies')
+TallyShape with_tallies(TallyShape s, int levels, int direct, int actinic, int side = 0) {
+  s.levels = levels; s.direct = levels && direct; s.actinic = actinic; s.side = levels && side;
+  return s;
+}
 TallyShape without_actinic(const TallyShape &s) { return with_tallies(s, s.levels, s.direct, 0); }
 constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
 // The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
@@ -310,6 +318,18 @@ const char *const kActinicBudgetMsg =
     "specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch would not fit the 4 GiB tally budget.";
 const char *const kActinicThermalMsg =
     "computeRadiativeTransfer: the actinic flux (recActinicFlux) is not available with the thermal source: the track-length tally is built for solar sources only.";
+// Side fluxes are a tally of the solar level-flux kernels: what they are refused with (and with everything
+// level fluxes are refused with, by those messages: the setting needs them)
+const char *const kSideNeedsLevelsMsg =
+    "specifyParameters: side fluxes (recSideFluxes) need level fluxes (recLevelFluxes): the kernels that stop at every face tally both.";
+const char *const kSideDirectMsg =
+    "specifyParameters: side fluxes (recSideFluxes) cannot be combined with direct level fluxes (recDirectLevelFluxes): no kernel tallies both.";
+const char *const kSideActinicMsg =
+    "specifyParameters: side fluxes (recSideFluxes) cannot be combined with the actinic flux (recActinicFlux): no kernel tallies both.";
+const char *const kSideBudgetMsg =
+    "specifyParameters: side fluxes (recSideFluxes): the level and side bins of one batch would not fit the 4 GiB tally budget.";
+const char *const kSideThermalMsg =
+    "computeRadiativeTransfer: side fluxes (recSideFluxes) are not available with the thermal source: the side tally is built for solar sources only.";
 // The fixed point of an actinic deposit: 2^e km, e the smallest integer that keeps the longest possible step of the walk below
 // 2^e -- the diagonal of the largest spacings of the three axes, times 1 + 2^-10 for the float rounding of tmin - tcur (a few
 // ulp of the distance along the leg, which may be many steps long).  The kernel deposits w l 2^-e, the epilogue multiplies
@@ -901,9 +921,16 @@ const void *trace_kernel_act(const mcbrat_ctx *c, const LaunchPlan &L) {  // (th
   if (levels_on(c)) return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, true>(L.tblLds) : trace_ptr_act<BLOCK, 0, true>(L.tblLds);
   return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, false>(L.tblLds) : trace_ptr_act<BLOCK, 0, false>(L.tblLds);
 }
+// the SIDE instantiations (side fluxes), solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table -- 8 kernels
+template <int BLOCK, int PRIV>
+const void *trace_ptr_lvl_side(bool tbl) {
+  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true, false, false, true>
+             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true, false, false, true>;
+}
 template <int BLOCK>
 const void *trace_kernel_lvl(const mcbrat_ctx *c, const LaunchPlan &L) {
   const bool emit = c->srcKind != 0;
+  if (side_on(c)) return (L.priv && L.gridLds) ? trace_ptr_lvl_side<BLOCK, 2>(L.tblLds) : trace_ptr_lvl_side<BLOCK, 0>(L.tblLds);  // (emit, direct, actinic: refused, check_ready)
   if (direct_on(c)) return (L.priv && L.gridLds) ? trace_ptr_lvl_direct<BLOCK, 2>(L.tblLds) : trace_ptr_lvl_direct<BLOCK, 0>(L.tblLds);  // (emit: refused, check_ready)
   return (L.priv && L.gridLds) ? trace_ptr_lvl<BLOCK, 2>(L.tblLds, emit) : trace_ptr_lvl<BLOCK, 0>(L.tblLds, emit);
 }
@@ -1041,6 +1068,8 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   if (act && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
     return fail(c, debug ? kActinicCountersMsg : (brdf ? kActinicBrdfMsg : (c->nDir > 0 ? kActinicIntensityMsg : kActinicOrdersMsg)));
   if (act && (emit || direct_on(c))) return fail(c, emit ? kActinicThermalMsg : kActinicDirectMsg);  // (no thermal ACT kernel, none with DIRECT)
+  if (side_on(c) && (emit || direct_on(c) || act))  // (check_ready refuses them; a second line of defence: no such SIDE kernel)
+    return fail(c, emit ? kSideThermalMsg : (act ? kSideActinicMsg : kSideDirectMsg));
   if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
   const void *kernel;
   int block;
@@ -1107,6 +1136,13 @@ int check_ready(mcbrat_ctx *c) {
     if (direct_on(c)) return fail(c, kActinicDirectMsg);
     if (!budget_fit(tally_shape(c)).globalBins) return fail(c, kActinicBudgetMsg);
     if (c->srcKind != 0) return fail(c, kActinicThermalMsg);
+  }
+  if (c->sideFluxes) {  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
+    if (!levels_on(c)) return fail(c, kSideNeedsLevelsMsg);
+    if (direct_on(c)) return fail(c, kSideDirectMsg);
+    if (actinic_on(c)) return fail(c, kSideActinicMsg);
+    if (!budget_fit(tally_shape(c)).globalBins) return fail(c, kSideBudgetMsg);
+    if (c->srcKind != 0) return fail(c, kSideThermalMsg);
   }
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
@@ -1245,6 +1281,7 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   asked.nx = nx; asked.ny = ny; asked.nz = nz;
   if (levels_on(c) && !budget_fit(without_actinic(asked)).globalBins) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
   if (actinic_on(c) && !budget_fit(asked).globalBins) return fail(c, kActinicBudgetMsg);
+  if (side_on(c) && !budget_fit(asked).globalBins) return fail(c, kSideBudgetMsg);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1608,6 +1645,7 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
     if (c->directLevelFluxes && !budget_fit(with_tallies(now, 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
     if (actinic_on(c) && !budget_fit(with_tallies(now, 1, 0, 1)).globalBins) return fail(c, kActinicBudgetMsg);
   } else if (c->directLevelFluxes) return fail(c, kDirectNeedsLevelsMsg);  // (switch the direct tally off first)
+  else if (c->sideFluxes) return fail(c, kSideNeedsLevelsMsg);  // (switch the side tally off first)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (on != c->levelFluxes) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
@@ -1629,6 +1667,7 @@ int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
   if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
     if (!levels_on(c)) return fail(c, kDirectNeedsLevelsMsg);
     if (actinic_on(c)) return fail(c, kActinicDirectMsg);
+    if (side_on(c)) return fail(c, kSideDirectMsg);
     if (!budget_fit(with_tallies(tally_shape(c), 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
   }
   (void)hipSetDevice(c->device);
@@ -1657,6 +1696,7 @@ int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
     if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
     if (c->countersOn) return fail(c, kActinicCountersMsg);
     if (direct_on(c)) return fail(c, kActinicDirectMsg);
+    if (side_on(c)) return fail(c, kSideActinicMsg);
     if (!budget_fit(with_tallies(tally_shape(c), levels_on(c), direct_on(c), 1)).globalBins) return fail(c, kActinicBudgetMsg);
   }
   (void)hipSetDevice(c->device);
@@ -1670,6 +1710,29 @@ int mcbrat_report_actinic_flux(mcbrat_ctx *c, float *meanActinicFlux, float *act
   if (!c) return 1;
   if (!actinic_on(c)) return fail(c, "reportResults: actinic-flux information not available");
   return deal_last(c, (size_t)tally_layout(c).momActinic, {{meanActinicFlux, (size_t)c->nz}, {actinicFlux, (size_t)c->nx * c->ny * (size_t)c->nz}});
+}
+
+int mcbrat_specify_side_fluxes(mcbrat_ctx *c, int32_t enable) {
+  if (!c) return 1;
+  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
+  const int on = enable ? 1 : 0;
+  if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
+    if (!levels_on(c)) return fail(c, kSideNeedsLevelsMsg);
+    if (direct_on(c)) return fail(c, kSideDirectMsg);
+    if (actinic_on(c)) return fail(c, kSideActinicMsg);
+    if (!budget_fit(with_tallies(tally_shape(c), 1, 0, 0, 1)).globalBins) return fail(c, kSideBudgetMsg);
+  }
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  if (side_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
+  c->sideFluxes = on;
+  return 0;
+}
+
+int mcbrat_report_side_fluxes(mcbrat_ctx *c, float *meanSideFluxes, float *sideFluxes) {
+  if (!c) return 1;
+  if (!side_on(c)) return fail(c, "reportResults: side-flux information not available");
+  return deal_last(c, (size_t)tally_layout(c).momSide, {{meanSideFluxes, 4 * (size_t)c->nz}, {sideFluxes, 4 * (size_t)c->nx * c->ny * (size_t)c->nz}});
 }
 
 int mcbrat_report_intensity(mcbrat_ctx *c, float *meanIntensity, float *intensity) {
@@ -1974,6 +2037,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   if (orders_on(c) && c->countersOn)
     return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
   if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
+  if (side_on(c) && !strideFits) return fail(c, kSideBudgetMsg);
   if (levels_on(c) && !actinic_on(c) && !strideFits) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
   if (actinic_on(c) && c->countersOn) return fail(c, kActinicCountersMsg);
   if (actinic_on(c) && !strideFits) return fail(c, kActinicBudgetMsg);
@@ -2076,11 +2140,17 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.gatherActinic = f.act ? (unsigned)((nvox + kVolVox - 1) / kVolVox) : 0u;
     f.gatherActinicMeans = f.act ? (unsigned)c->nz * (unsigned)nb : 0u;
     f.foldActinicMeans = f.act ? (unsigned)((c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
+    f.side = side_on(c) ? 1 : 0;
+    f.xe = c->dEdges; f.ye = c->dEdges + (c->nx + 1);
+    f.sideVals = f.scalVals + (size_t)lay.scalSide * nb;
+    f.gatherSide = f.side ? (unsigned)((4 * nvox + kVolVox - 1) / kVolVox) : 0u;
+    f.gatherSideMeans = f.side ? 4u * (unsigned)c->nz * (unsigned)nb : 0u;
+    f.foldSideMeans = f.side ? (unsigned)((4 * c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans + f.gatherActinic + f.gatherActinicMeans),
+    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans + f.gatherActinic + f.gatherActinicMeans + f.gatherSide + f.gatherSideMeans),
                        dim3(kFinishBlock), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans + f.foldActinicMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
+    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans + f.foldActinicMeans + f.foldSideMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
     c->lastDone = c->L().evDone;

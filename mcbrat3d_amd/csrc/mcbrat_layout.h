@@ -9,11 +9,13 @@
 //    (limitIntensityContributions:) intensity by component ncol nDir (nc+1) | excess nDir (nc+1) |
 //    (scattering orders:) upByOrd ncol nOrd | downByOrd ncol nOrd | intensityByOrd ncol nDir nOrd |
 //    (level fluxes:) levelUp ncol nLvl | levelDown ncol nLvl (with the direct tally: diffuse) | (direct tally:) levelDirect ncol nLvl |
-//    (actinic flux:) actinic ncol nz]
-// The level and actinic bins always stay in global memory; what lies in front of them may live in LDS (slabLds elements).
+//    (actinic flux:) actinic ncol nz |
+//    (side fluxes:) sideXPlus ncol nz | sideXMinus ncol nz | sideYPlus ncol nz | sideYMinus ncol nz]
+// The level, actinic and side bins always stay in global memory; what lies in front of them may live in LDS (slabLds elements).
 // One sum of the moments (the array is header(8) + S1 + S2; the caller's view is in include/mcbrat.h): the means, column fluxes,
-// profile, volume and intensity, then a tail per tally, each [domain means | column or cell bins]: orders, levels, direct, actinic.
-// The scalar scratch of a launch round of nb batches: [nb][3 + nz], then the order, level and actinic means: part X at scalX * nb.
+// profile, volume and intensity, then a tail per tally, each [domain means | column or cell bins]: orders, levels, direct, actinic, side
+// (side: [means 4 nz | bins 4 ncol nz], both in the order x plus, x minus, y plus, y minus).
+// The scalar scratch of a launch round of nb batches: [nb][3 + nz], then the order, level, actinic and side means: part X at scalX * nb.
 #pragma once
 #include <cstdint>
 
@@ -23,6 +25,7 @@ struct TallyShape {
   int32_t nx, ny, nz, nc, nDir, limitContrib;
   int32_t nOrd;  // numRecScatOrd + 1, 0 when off
   int32_t levels, direct, actinic;
+  int32_t side = 0;  // the flux through the vertical faces of every cell (needs levels)
 };
 
 // Starts in elements: slab* within one batch's slab, mom* within one sum of the moments (and within the last batch's results), scal*
@@ -36,6 +39,7 @@ struct TallyLayout {
   int64_t slabOrders, momOrders, scalOrders;
   int64_t slabLevels, momLevels, momDirect, scalLevels;
   int64_t slabActinic, momActinic, scalActinic;
+  int64_t slabSide, momSide, scalSide;
 };
 
 // Products and sums of counts that saturate: numRecScatOrd and the number of directions arrive unchecked, and a part's length
@@ -58,6 +62,7 @@ inline TallyLayout tally_layout(const TallyShape &s) {
   const int64_t nDir = s.nDir, nOrd = s.nOrd, nComp = s.limitContrib ? (int64_t)s.nc + 1 : 0;
   const bool direct = s.levels && s.direct;
   const int64_t nAct = s.actinic ? nz : 0;
+  const int64_t nSide = s.side ? times(4, nz) : 0;  // (layers of the four side parts)
   TallyLayout l{};
   l.slabFluxUp = take(ncol);
   l.slabFluxDown = take(ncol);
@@ -69,6 +74,7 @@ inline TallyLayout tally_layout(const TallyShape &s) {
   l.slabLds = at;
   l.slabLevels = take(times(ncol, nLvl, direct ? 3 : 2));
   l.slabActinic = take(times(ncol, nAct));
+  l.slabSide = take(times(ncol, nSide));
   l.slabStride = at;
   at = 0;
   l.momMeans = take(3);
@@ -80,12 +86,14 @@ inline TallyLayout tally_layout(const TallyShape &s) {
   l.momLevels = take(times(1 + ncol, 2, nLvl));
   l.momDirect = take(direct ? times(1 + ncol, 2, nLvl) : 0);
   l.momActinic = take(times(1 + ncol, nAct));
+  l.momSide = take(times(1 + ncol, nSide));
   l.momentsLen = at;
   at = 0;
   take(3 + nz);
   l.scalOrders = take(times(2 + nDir, nOrd));
   l.scalLevels = take(times(direct ? 4 : 2, nLvl));
   l.scalActinic = take(nAct);
+  l.scalSide = take(nSide);
   l.scalPerBatch = at;
   return l;
 }
@@ -93,7 +101,7 @@ inline TallyLayout tally_layout(const TallyShape &s) {
 // The slab of a flux launch of the same domain: no intensity parts.
 inline TallyShape flux_run(TallyShape s) { s.nDir = 0; s.limitContrib = 0; return s; }
 
-// Whether one batch's bins fit a budget in bytes: the order part alone, the level and actinic bins alone, the whole stride.
+// Whether one batch's bins fit a budget in bytes: the order part alone, the level, actinic and side bins alone, the whole stride.
 struct TallyFit { bool orders, globalBins, stride; };
 inline TallyFit tally_fit(const TallyShape &s, uint64_t budgetBytes) {
   const TallyLayout l = tally_layout(s);

@@ -31,7 +31,7 @@ def balanced_job(totalPhotons, numBatches, world):
 
 
 def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFluxes=False, directLevelFluxes=False,
-                   actinicFlux=False):
+                   actinicFlux=False, sideFluxes=False):
     """header(8) + S1[M] + S2[M] -> dict name -> (S1, S2) in [ix, iy(, iz | direction)] index order.
 
     With scattering orders (numRecScatOrd >= 0) the arrays end in the order tail of include/mcbrat.h, unpacked with the order
@@ -46,15 +46,21 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
     tail: meanLevelFluxDownDirect[k], meanLevelFluxDownDiffuse[k], levelFluxDownDirect[ix, iy, k], levelFluxDownDiffuse[ix, iy, k].
 
     With the actinic flux (actinicFlux=True) the actinic tail follows every other tail: meanActinicFlux[iz], actinicFlux[ix, iy, iz].
-    The length is then checked against the layout asked for."""
+    The length is then checked against the layout asked for.
+
+    With side fluxes (sideFluxes=True, which needs levelFluxes=True) the side tail follows every other tail: meanSideFluxXPlus[iz],
+    meanSideFluxXMinus[iz], meanSideFluxYPlus[iz], meanSideFluxYMinus[iz], then sideFluxXPlus[ix, iy, iz] ... sideFluxYMinus[ix, iy, iz]."""
     if directLevelFluxes and not levelFluxes:
         raise ValueError("unpack_moments: directLevelFluxes needs levelFluxes")
+    if sideFluxes and not levelFluxes:
+        raise ValueError("unpack_moments: sideFluxes needs levelFluxes")
     ncol, nvox = nx * ny, nx * ny * nz
     M = 3 + 3 * ncol + nz + nvox
     nOrd = int(numRecScatOrd) + 1 if numRecScatOrd is not None and int(numRecScatOrd) >= 0 else 0
     nLvl = nz + 1 if levelFluxes else 0
     nLvlQ = 4 if directLevelFluxes else 2  # level quantities: up, down (, direct, diffuse)
     nAct = nz * (1 + ncol) if actinicFlux else 0
+    nAct += 4 * nz * (1 + ncol) if sideFluxes else 0  # (the side tail lies behind the actinic one)
     if nDirections is None:  # the length tells
         if nOrd:
             raise ValueError("unpack_moments: with numRecScatOrd >= 0 the number of directions must be given (nDirections=)")
@@ -83,6 +89,9 @@ def unpack_moments(buf, nx, ny, nz, nDirections=None, numRecScatOrd=-1, levelFlu
                       ("levelFluxDownDirect", nLvl * ncol, (nLvl, ny, nx)), ("levelFluxDownDiffuse", nLvl * ncol, (nLvl, ny, nx))]
     if actinicFlux:
         names += [("meanActinicFlux", nz, (nz,)), ("actinicFlux", nvox, (nz, ny, nx))]
+    if sideFluxes:
+        sideNames = ("sideFluxXPlus", "sideFluxXMinus", "sideFluxYPlus", "sideFluxYMinus")
+        names += [("mean" + s[0].upper() + s[1:], nz, (nz,)) for s in sideNames] + [(s, nvox, (nz, ny, nx)) for s in sideNames]
     if (nOrd or nLvl or nAct) and len(buf) != 8 + 2 * M:
         raise ValueError("unpack_moments: %d doubles, the layout asked for has %d" % (len(buf), 8 + 2 * M))
     o = 0
@@ -195,6 +204,10 @@ def run(integrator, domain, photons, numPhotonsPerBatch, numBatches, randomNumbe
     levels = bool(getattr(integrator, "recLevelFluxes", False))
     direct = levels and bool(getattr(integrator, "recDirectLevelFluxes", False))
     actinic = bool(getattr(integrator, "recActinicFlux", False))
+    side = levels and bool(getattr(integrator, "recSideFluxes", False))
+    if side:
+        return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels,
+                                         directLevelFluxes=direct, actinicFlux=actinic, sideFluxes=True), solarFlux)
     if nOrd >= 0 or levels or actinic:
         return statistics(unpack_moments(buf, nx, ny, nz, integrator.numIntensityDirections(), nOrd, levelFluxes=levels,
                                          directLevelFluxes=direct, actinicFlux=actinic), solarFlux)

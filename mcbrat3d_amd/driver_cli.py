@@ -21,7 +21,7 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
                        hybridphasefunwidth=7.0, numordersorigphasefunintencalcs=0, userussianrouletteforintensity=True,
                        zetamin=0.3, limitintensitycontributions=False, maxintensitycontribution=77.0),
     "output": dict(reportvolumeabsorption=False, reportabsorptionprofile=False, recscatord=False, numrecscatord=0,
-                   reportlevelfluxes=False, reportdirectlevelfluxes=False, reportactinicflux=False),
+                   reportlevelfluxes=False, reportdirectlevelfluxes=False, reportactinicflux=False, reportsidefluxes=False),
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
 }
@@ -241,6 +241,9 @@ def main(argv=None):
         if cfg["reportactinicflux"]:
             raise SystemExit("reportActinicFlux: the actinic flux is not available for spectrally integrated runs (numLambda > 1 "
                              "or thermal emission)")
+        if cfg["reportsidefluxes"]:
+            raise SystemExit("reportSideFluxes: side fluxes are not available for spectrally integrated runs (numLambda > 1 or "
+                             "thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -287,6 +290,8 @@ def main(argv=None):
         integ.specifyParameters(recDirectLevelFluxes=True)
     if cfg["reportactinicflux"]:  # (refused by specifyParameters together with directions, orders or the direct level tally)
         integ.specifyParameters(recActinicFlux=True)
+    if cfg["reportsidefluxes"]:  # (refused by specifyParameters without reportLevelFluxes, with the direct tally or the actinic flux)
+        integ.specifyParameters(recSideFluxes=True)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -317,6 +322,11 @@ def main(argv=None):
             for k in range(len(dom.zPosition) - 2, -1, -1):
                 print(" layer %3d z %9.4f - %9.4f mean actinic flux: %9.6f +-%9.6f" % (
                     k, dom.zPosition[k], dom.zPosition[k + 1], stats["meanActinicFlux"][k], stats["meanActinicFlux_StdErr"][k]))
+        if cfg["reportsidefluxes"]:  # layer means of the four side fluxes, one line per layer from the top down
+            for k in range(len(dom.zPosition) - 2, -1, -1):
+                print(" layer %3d z %9.4f - %9.4f mean side flux x+ x- y+ y-: %9.6f %9.6f %9.6f %9.6f" % (
+                    k, dom.zPosition[k], dom.zPosition[k + 1], stats["meanSideFluxXPlus"][k], stats["meanSideFluxXMinus"][k],
+                    stats["meanSideFluxYPlus"][k], stats["meanSideFluxYMinus"][k]))
         xe, ye, ze = dom.xPosition, dom.yPosition, dom.zPosition
         if cfg["outputfluxfile"]:
             writeResults_ASCII(cfg["outputfluxfile"], cfg, domfile, stats, xe, ye, ze, 1.0, dom.surfaceAlbedo)

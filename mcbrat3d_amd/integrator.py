@@ -37,6 +37,10 @@ class RandomNumberSequence:
         self.nextPhotonId = int(firstPhotonId)
 
 
+# the four side-flux quantities in the order of the library's parts
+SIDE_FLUX_NAMES = ("sideFluxXPlus", "sideFluxXMinus", "sideFluxYPlus", "sideFluxYMinus")
+
+
 def new_RandomNumberSequence(seed=10, firstPhotonId=0):
     if not np.isscalar(seed):  # (/ iseed, thisProc, thisThread /), monteCarloDriver.f95:901
         s = [int(x) & 0xFFFFFFFF for x in seed]
@@ -81,6 +85,8 @@ class Integrator:
         self.recDirectLevelFluxes = False
         # the actinic flux of every cell by track length; solar sources, with or without recLevelFluxes
         self.recActinicFlux = False
+        # the flux through the vertical faces of every cell; solar sources, needs recLevelFluxes
+        self.recSideFluxes = False
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -122,7 +128,8 @@ class Integrator:
                               limitIntensityContributions=self.limitIntensityContributions,
                               maxIntensityContribution=self.maxIntensityContribution, surfaceBDRF=self.surfaceBDRF,
                               numRecScatOrd=self.numRecScatOrd, recLevelFluxes=self.recLevelFluxes,
-                              recDirectLevelFluxes=self.recDirectLevelFluxes, recActinicFlux=self.recActinicFlux)
+                              recDirectLevelFluxes=self.recDirectLevelFluxes, recActinicFlux=self.recActinicFlux,
+                              recSideFluxes=self.recSideFluxes)
         return new
 
     def _check(self, rc):
@@ -143,7 +150,7 @@ class Integrator:
                           hybridPhaseFunWidth=None, numOrdersOrigPhaseFunIntenCalcs=None,
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
                           recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, recDirectLevelFluxes=None, recActinicFlux=None,
-                          **unsupported):
+                          recSideFluxes=None, **unsupported):
         # level fluxes: what they cannot be combined with is refused as the library refuses it -- here,
         # before anything of this call is kept, so that a refused call leaves the integrator as it was
         levels = self.recLevelFluxes if recLevelFluxes is None else bool(recLevelFluxes)
@@ -207,6 +214,23 @@ class Integrator:
             if ((2 * nx * ny * (nz + 1) if levels else 0) + nx * ny * nz) * 8 > 4 << 30:
                 raise McbratError("specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch "
                                   "would not fit the 4 GiB tally budget.")
+        # side fluxes: with level fluxes only -- and so refused with everything they are refused with,
+        # above -- and refused as the library refuses them, before anything of this call is kept
+        side = self.recSideFluxes if recSideFluxes is None else bool(recSideFluxes)
+        if side:
+            if not levels:
+                raise McbratError("specifyParameters: side fluxes (recSideFluxes) need level fluxes (recLevelFluxes): the kernels "
+                                  "that stop at every face tally both.")
+            if direct:
+                raise McbratError("specifyParameters: side fluxes (recSideFluxes) cannot be combined with direct level fluxes "
+                                  "(recDirectLevelFluxes): no kernel tallies both.")
+            if actinic:
+                raise McbratError("specifyParameters: side fluxes (recSideFluxes) cannot be combined with the actinic flux "
+                                  "(recActinicFlux): no kernel tallies both.")
+            nx, ny, nz = self._dims
+            if (2 * nx * ny * (nz + 1) + 4 * nx * ny * nz) * 8 > 4 << 30:
+                raise McbratError("specifyParameters: side fluxes (recSideFluxes): the level and side bins of one batch would not "
+                                  "fit the 4 GiB tally budget.")
         # intensity keywords, :1130-1160 and :1186-1283
         if (intensityMus is None) != (intensityPhis is None):
             raise McbratError("specifyParameters: Both or neither of intensityMus, intensityPhis must be supplied")
@@ -289,6 +313,7 @@ class Integrator:
         self.recLevelFluxes = levels
         self.recDirectLevelFluxes = direct
         self.recActinicFlux = actinic
+        self.recSideFluxes = side
         self._push_parameters()
 
     def _push_parameters(self):
@@ -320,7 +345,14 @@ class Integrator:
             self._check(self._lib.mcbrat_specify_actinic_flux(self._ctx, int(self.recActinicFlux)))
             self._actinic_token = self.recActinicFlux
 
+    def _push_side(self):
+        if self.recSideFluxes != getattr(self, "_side_token", False):
+            self._check(self._lib.mcbrat_specify_side_fluxes(self._ctx, int(self.recSideFluxes)))
+            self._side_token = self.recSideFluxes
+
     def _push_intensity(self):
+        if not self.recSideFluxes:
+            self._push_side()  # (off first: level fluxes cannot be switched off under it, the direct and actinic tallies not on)
         if not self.recActinicFlux:
             self._push_actinic()  # (off first, as level fluxes: what follows may be refused together with it -- the direct tally too)
         if not self.recLevelFluxes:
@@ -328,6 +360,7 @@ class Integrator:
         self._push_intensity_and_orders()
         self._push_levels()
         self._push_actinic()
+        self._push_side()
 
     def _push_intensity_and_orders(self):
         n = int(self.intensityMus.size) if self.computeIntensity else 0
@@ -520,6 +553,8 @@ class Integrator:
             res.update(self.reportLevelFluxes())
         if self.recActinicFlux:
             res.update(self.reportActinicFlux())
+        if self.recSideFluxes:
+            res.update(self.reportSideFluxes())
         if self.numRecScatOrd >= 0:  # reportResults(...ByScatOrd) :850-864, :887-903, :1010-1040; order last, as the reference's arrays
             no = self.numRecScatOrd + 1
             mu_o, md_o = np.zeros(no, np.float32), np.zeros(no, np.float32)
@@ -565,6 +600,21 @@ class Integrator:
         mean, act = np.zeros(nz, np.float32), np.zeros(nx * ny * nz, np.float32)
         self._check(self._lib.mcbrat_report_actinic_flux(self._ctx, ptr(mean), ptr(act)))
         return dict(meanActinicFlux=mean, actinicFlux=act.reshape(nz, ny, nx).transpose(2, 1, 0))
+
+    def reportSideFluxes(self):
+        """The last batch's flux through the vertical faces of every cell: sideFluxXPlus[ix, iy, iz] and sideFluxXMinus[ix, iy, iz],
+        the weight that crossed the face x = xPosition[ix+1] of the patch (iy, iz) towards +x and towards -x, per photon of the
+        column and scaled by dx / dz to a flux density per unit flux through a horizontal unit area at the top; sideFluxYPlus and
+        sideFluxYMinus likewise for the face y = yPosition[iy+1]; and their layer means meanSideFluxXPlus[iz] ... (the sum over
+        the columns divided by their number)."""
+        nx, ny, nz = self._dims
+        mean, bins = np.zeros(4 * nz, np.float32), np.zeros(4 * nx * ny * nz, np.float32)
+        self._check(self._lib.mcbrat_report_side_fluxes(self._ctx, ptr(mean), ptr(bins)))
+        res = {}
+        for q, name in enumerate(SIDE_FLUX_NAMES):
+            res["mean" + name[0].upper() + name[1:]] = mean[q * nz:(q + 1) * nz].copy()
+            res[name] = bins[q * nx * ny * nz:(q + 1) * nx * ny * nz].reshape(nz, ny, nx).transpose(2, 1, 0)
+        return res
 
     # -- batch moments (what the driver keeps in *Stats and reduces over processes) -----
     def momentsLength(self):

@@ -229,6 +229,16 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
                 f.createVariable(name, "f", ("z", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
             for name in ("meanActinicFlux", "meanActinicFlux_StdErr"):
                 f.createVariable(name, "f", ("z",))[:] = np.asarray(stats[name])
+        if "sideFluxXPlus" in stats:  # the flux through the vertical faces of every cell (reportSideFluxes) and its layer means
+            if not withZ and "actinicFlux" not in stats:
+                f.createDimension("z", len(ze) - 1)
+                f.createVariable("z", "d", ("z",))[:] = 0.5 * (ze[1:] + ze[:-1])
+            for side in ("sideFluxXPlus", "sideFluxXMinus", "sideFluxYPlus", "sideFluxYMinus"):
+                for name in (side, side + "_StdErr"):
+                    f.createVariable(name, "f", ("z", "y", "x"))[:] = np.asarray(stats[name]).transpose(2, 1, 0)
+                mean = "mean" + side[0].upper() + side[1:]
+                for name in (mean, mean + "_StdErr"):
+                    f.createVariable(name, "f", ("z",))[:] = np.asarray(stats[name])
     finally:
         f.close()
     return outputFileName
