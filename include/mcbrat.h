@@ -350,6 +350,8 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
  *   "jumpThreshold", "crossThreshold"  lanes queued before transitions of the layer-skipping walk / block crossings are served
  *   "batchUnits"  1: the block walk cuts its workgroups' work units inside batches, as the flat walk does (default 0: units
  *                 across the launch, two batches' tallies per workgroup where they fit; environment MCBRAT_BATCH_UNITS)
+ *   "blockSpanKernel"  1: the block walk keeps its general instantiation where the one without periodic folds inside blocks
+ *                 would do (default 0: automatic; both trace every photon bit for bit alike -- tests/test_gpu_blockwalk_nospan.py)
  * The reference has no counterpart (its loop is one photon at a time, monteCarloRadiativeTransfer.f95:463-466). */
 int mcbrat_set_option(mcbrat_ctx *ctx, const char *name, int32_t value);
 
@@ -414,7 +416,9 @@ int mcbrat_set_walk_options(mcbrat_ctx *ctx, int32_t layerSkip, int32_t blockWal
  * bit 4 the wide plan (a tally slab too large to share a compute unit's LDS: one workgroup of 1024 lanes per compute unit
  * owns up to its whole 160 KB), bit 5 the block walk with the per-cell optics left in global memory (extinction per block
  * in LDS), bit 7 the block walk with the optics per BLOCK in LDS (every block uniform in them), bit 8 the thermal source's level
- * and row sums of the emission CDF staged in LDS.  Before grid and optics are loaded: the options. */
+ * and row sums of the emission CDF staged in LDS, bit 9 (512) the block walk's instantiation with the periodic folds inside blocks
+ * compiled out (no block of the medium spans a whole periodic axis, solar source, equally spaced axes, one component, the
+ * domain's albedo, 768-lane workgroups, option "blockSpanKernel" not set).  Before grid and optics are loaded: the options. */
 int mcbrat_get_walk_mode(const mcbrat_ctx *ctx);
 
 /* The event threshold in use (after the first call of a domain: the one chosen by the trial launches). */

@@ -83,6 +83,9 @@ struct mcbrat_ctx {
   int crossThreshold = 8;      // MCBRAT_CROSS_THRESHOLD
   int batchUnits = 0;          // MCBRAT_BATCH_UNITS / option "batchUnits": 1 cuts the block walk's work units inside batches (launch_kernel)
   int jumpThreshold = 8;       // MCBRAT_JUMP_THRESHOLD
+  // no record of the block decomposition has bit 0 / bit 1 of w: no block spans the whole periodic x / y axis (build_blocks)
+  bool blockSpansX = true, blockSpansY = true;
+  int blockSpanKernel = 0;     // option "blockSpanKernel": 1 keeps the general block-walk instantiation where NOSPAN would do (tests)
   bool noSimple3 = false;      // MCBRAT_NO_SIMPLE3 (tests): the block walk's near-uniform grids run the general kernel, not SIMPLE = 3
   float *dExtB = nullptr, *dCumB = nullptr, *dSsaB = nullptr, *dBgExt = nullptr, *dBgCum = nullptr, *dBgSsa = nullptr;
   uint16_t *dPfiB = nullptr, *dBgPfi = nullptr;
@@ -564,6 +567,7 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
   if (c->dBlockCum) { (void)hipFree(c->dBlockCum); c->dBlockCum = nullptr; }
   if (c->dBlockPfi) { (void)hipFree(c->dBlockPfi); c->dBlockPfi = nullptr; }
   c->blockOpticsUniform = false;
+  c->blockSpansX = c->blockSpansY = true;
   // only grids that can live in LDS are walked this way (plan_launch decides); bounds are packed in 16 bits
   if (nvox > 65536 || nx > 65535 || ny > 65535 || nz > 65535) return 0;
   std::vector<uint16_t> of(nvox);
@@ -594,6 +598,9 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
         upload(c, &c->dBlockPfi, bPfi.data(), bPfi.size())) return 1;
     c->blockOpticsUniform = true;
   }
+  bool sx = false, sy = false;  // (mcbrat_block_decomposition sets bit 0 / 1 of w where a block covers the whole x / y axis)
+  for (int32_t b = 0; b < nb; ++b) { sx = sx || (rec[4 * (size_t)b + 3] & 1u); sy = sy || (rec[4 * (size_t)b + 3] & 2u); }
+  c->blockSpansX = sx; c->blockSpansY = sy;
   c->nBlocks = nb;
   return 0;
 }
@@ -1001,11 +1008,25 @@ const void *block_ptr(bool tbl, bool emit) {
   return emit ? (const void *)trace_block_kernel<BLOCK, false, DBG, true, SIMPLE, OPT> : (const void *)trace_block_kernel<BLOCK, false, DBG, false, SIMPLE, OPT>;
 }
 
+// The NOSPAN instantiations (mcbrat_blockwalk.hip): solar SIMPLE = 1 and 2 kernels of 768 lanes, the library's own plan for a
+// grid in LDS, for media none of whose blocks spans a periodic axis the kernel looks at (an x-z problem has no y to look at).
+bool nospan_kernel(const mcbrat_ctx *c) {
+  const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
+  if (!simple || c->srcKind != 0 || c->blockSpanKernel != 0) return false;
+  return !c->blockSpansX && (c->ny == 1 || !c->blockSpansY);
+}
+
 template <int BLOCK, bool DBG, int OPT = 0>
 const void *block_kernel_for(const mcbrat_ctx *c, const DevParams &p, bool tbl) {
   const bool emit = c->srcKind != 0;
   // equally spaced axes, one component, no surface description: the instantiation with those decided at compile time
   const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
+  if constexpr (OPT == 0 && BLOCK == 768 && !DBG) {
+    if (nospan_kernel(c)) {
+      if (c->ny == 1) return tbl ? (const void *)trace_block_kernel<768, true, false, false, 2, 0, true> : (const void *)trace_block_kernel<768, false, false, false, 2, 0, true>;
+      return tbl ? (const void *)trace_block_kernel<768, true, false, false, 1, 0, true> : (const void *)trace_block_kernel<768, false, false, false, 1, 0, true>;
+    }
+  }
   if constexpr (OPT == 0 && BLOCK != 1024) {
     if (simple && c->ny == 1 && !DBG) return block_ptr<BLOCK, DBG, 2, OPT>(tbl, emit);  // an x-z problem
   }
@@ -1860,6 +1881,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   if (n == "jumpThreshold") c->jumpThreshold = std::max(1, std::min(64, (int)value));
   else if (n == "crossThreshold") c->crossThreshold = std::max(1, std::min(64, (int)value));
   else if (n == "batchUnits") c->batchUnits = value != 0;
+  else if (n == "blockSpanKernel") c->blockSpanKernel = value != 0;
   else return fail(c, "set_option: unknown option '" + n + "'");
   return 0;
 }
@@ -2003,6 +2025,8 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
     m = ((c->layerSkip && !facewalk_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
+    // (the 768-lane block walk of launch_block, the only one with NOSPAN instantiations)
+    if (block_walk_applies(c, L) && !L.wide && (c->blockSize == 0 || c->blockSize == 768) && nospan_kernel(c)) m |= 512;
   }
   return m;
 }

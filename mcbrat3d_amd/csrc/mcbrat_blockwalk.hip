@@ -52,7 +52,7 @@ __device__ __forceinline__ long long unwrapped_index(const double *e, int n, dou
 
 // LDS layout of trace_block_kernel (byte offsets), computed the same way by the host (plan_launch) and the kernel
 struct BlockLds {
-  size_t slab, cursor, rec, cdf, ext, ssa, cum, pfi, blockOf, tbl, total;
+  size_t slab, cursor, rec, invExt, cdf, ext, ssa, cum, pfi, blockOf, tbl, total;
 };
 // optics: where a collision finds single-scattering albedo, cumulative fractions and phase-function index of its cell (OPT below)
 //   0  per cell in LDS, beside the extinction per cell (the small domains: step cloud, plane parallel);
@@ -72,6 +72,7 @@ __host__ __device__ inline BlockLds block_lds_layout(int nx, int ny, int nz, int
   L.cursor = o; o += 16;
   o = (o + 15) & ~(size_t)15;
   L.rec = o; o += 16 * (size_t)nBlocks;
+  L.invExt = o; o += 4 * nB4;  // 1 / extinction of each block (the collision's step), beside the records: nB4 floats keep the alignment
   L.cdf = o; o += cdfTop ? sizeof(double) * ((size_t)nz + (size_t)ny * nz) : 0;
   L.ext = o; o += optics == 0 ? 4 * nvox : 4 * nB4;
   L.ssa = o; o += optics == 0 ? 4 * nvox * nc : (optics == 2 ? 4 * nB4 * nc : 0);
@@ -101,10 +102,19 @@ __host__ __device__ inline BlockLds block_lds_layout(int nx, int ny, int nz, int
 // instantiation keeps y, it counts the periodic y faces a leg crosses as the reference does).
 // OPT: where a collision finds the optics of its cell (0 per cell in LDS, 1 per cell in global memory, 2 per block in LDS), see
 // block_lds_layout.  Workgroups of 1024 lanes are ONE per compute unit (they own most of its 160 KB of LDS): 4 waves per SIMD.
-template <int BLOCK, bool TBL_LDS, bool DEBUG, bool EMIT, int SIMPLE, int OPT = 0>
+// NOSPAN: no block of the medium spans a whole periodic axis that this instantiation looks at (x; y too unless SIMPLE = 2) -- the
+// host has seen every record (build_blocks) and picks the instantiation (block_kernel_for).  A lane then never leaves the
+// principal image inside a block: the `spans` bits do not exist, the periodic folds that depend on them (collision, block
+// crossing) and the tests of rec.w are compiled out.  The forced fold of an exit and the wrap through the domain boundary of a
+// crossing stay.  Any medium with horizontal structure is of this kind; plane-parallel and homogeneous media are not.
+template <int BLOCK, bool TBL_LDS, bool DEBUG, bool EMIT, int SIMPLE, int OPT = 0, bool NOSPAN = false>
 __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK > 512 ? BLOCK / 128 : MCBRAT_MIN_WAVES_PER_SIMD))
 trace_block_kernel(const DevParams p) {
   constexpr bool NOY = SIMPLE == 2 && !DEBUG;
+  // HOIST: what is constant per photon (Philox) and per block (1 / extinction) is kept in the lane instead of being formed in every
+  // leg and collision.  Two lane registers: taken where the budget has them -- the kernels of 128 registers and, of the 768-lane
+  // ones (80 registers), the solar x-z instantiation; the others and the instrumented ones would pay with scratch.
+  constexpr bool HOIST = !DEBUG && (BLOCK != 768 || (SIMPLE == 2 && !EMIT));
   constexpr bool NEAR = SIMPLE == 3;  // every axis: not regular by the reference's test, equally spaced to 1e-6 of a cell
   const bool xyRegular = NEAR ? false : (SIMPLE != 0 ? true : p.xyRegular != 0);
   const bool zRegular = NEAR ? false : (SIMPLE != 0 ? true : p.zRegular != 0);
@@ -128,6 +138,7 @@ trace_block_kernel(const DevParams p) {
   long long *s_slab = reinterpret_cast<long long *>(smem_raw + lay.slab);
   unsigned *s_cursor = reinterpret_cast<unsigned *>(smem_raw + lay.cursor);
   uint4 *s_blockRec = reinterpret_cast<uint4 *>(smem_raw + lay.rec);
+  float *s_invExt = reinterpret_cast<float *>(smem_raw + lay.invExt);   // [nBlocks] rcp_fast of the blocks' extinction
   float *s_ext = reinterpret_cast<float *>(smem_raw + lay.ext);         // [nvox]; OPT != 0: [nBlocks], the blocks' extinction
   double *s_cdfLevel = reinterpret_cast<double *>(smem_raw + lay.cdf);  // [nz] level sums of the emission CDF, then [nz][ny] row sums (cdfTop)
   double *s_cdfRow = s_cdfLevel + p.nz;
@@ -148,7 +159,7 @@ trace_block_kernel(const DevParams p) {
     for (int i = threadIdx.x; i < p.tblTotalFloats; i += BLOCK) s_tbl[i] = p.tables[i];
   for (int i = threadIdx.x; i < slabsLen; i += BLOCK) s_slab[i] = 0;
   if (threadIdx.x == 0) s_cursor[0] = 0;
-  for (int i = threadIdx.x; i < p.nBlocks; i += BLOCK) s_blockRec[i] = p.blockRec[i];
+  for (int i = threadIdx.x; i < p.nBlocks; i += BLOCK) { s_blockRec[i] = p.blockRec[i]; s_invExt[i] = rcp_fast(p.blockExt[i]); }
   for (int i = threadIdx.x; i < nvox; i += BLOCK) s_blockOf[i] = p.blockOf[i];
   if (OPT == 0) {
     for (int i = threadIdx.x; i < nvox; i += BLOCK) s_ext[i] = p.ext[i];
@@ -194,12 +205,17 @@ trace_block_kernel(const DevParams p) {
   unsigned long long moreMask = ~0ull;
   int slabOff = 0;                     // the LDS slab of the lane's photon: 0, or slabLen for the second batch of a launch-wide unit
   uint32_t idLo = 0, idHi = 0, event = 0;
-  unsigned long long idP1 = 0;         // philox_p1(idLo): the first round's product shared by every block of the photon's stream
+  // what every leg block (event, 0, idLo, idHi) of the photon shares: the second round's product q0 and the low word of the
+  // first round's p1 (philox4x32_10_leg; the rare blocks with another second counter word recompute philox_p1(idLo))
+  unsigned long long legQ0 = 0;
+  uint32_t legD1 = 0;
+  unsigned long long idP1 = 0;         // !HOIST: philox_p1(idLo), the first round's product shared by every block of the photon's stream
+  auto photonP1 = [&]() { if constexpr (HOIST) return philox_p1(idLo); else return idP1; };
   double px = 0, py = 0, pz = 0;      // leg origin (in the periodic image the leg is currently in)
   float dx = 0, dy = 0, dz = 1;       // direction cosines
   float ivx = 0, ivy = 0, ivz = 0;    // 1/direction
   float tnx = 0, tny = 0, tnz = 0, tcur = 0;  // distance along the leg to the x/y/z face of the current BLOCK
-  float acc = 0, tau = 0, w = 0, extCur = 0, uX = 0, uY = 0, uZ = 0;
+  float acc = 0, tau = 0, w = 0, extCur = 0, invExtCur = 0, uX = 0, uY = 0, uZ = 0;
   // cell range of the current block per axis, lo | hi << 16 (the face ahead of the lane is hi or lo by its direction).
   // Kept whole, not just the face ahead: the cell a lane enters on the far side of a face comes from its POSITION on the
   // two other axes, and a position that lies on a second face of the block (a leg through an edge of the block: float
@@ -208,7 +224,9 @@ trace_block_kernel(const DevParams p) {
   // look-ups that both round backwards hand the lane to and fro between two blocks for ever (found by the soak run of
   // test_random_box_media_against_face_by_face_kernel).
   unsigned rx = 0, ry = 0, rz = 0;
-  unsigned spans = 0;                  // bit 0 / 1: the current block spans the whole periodic x / y axis
+  unsigned spans = 0;                  // bit 0 / 1: the current block spans the whole periodic x / y axis (NOSPAN: never set, never read)
+  auto spanX = [&]() { return !NOSPAN && (spans & 1u) != 0; };
+  auto spanY = [&]() { return !NOSPAN && (spans & 2u) != 0; };
   int nScat = 0, nLegs = 0;
   long long dbgX = 0, dbgY = 0;        // DEBUG: cell of the leg's start counted through the periodic images
   int dbgZ = 0;
@@ -270,17 +288,18 @@ trace_block_kernel(const DevParams p) {
     const unsigned blk = s_blockOf[cell];
     const uint4 rec = s_blockRec[blk];
     if constexpr (OPT == 0) extCur = s_ext[cell]; else extCur = s_ext[blk];
+    if constexpr (HOIST) invExtCur = s_invExt[blk];
     rx = rec.x; rz = rec.z;
     if (!NOY) ry = rec.y;
     const int fx = dx >= 0.0f ? (int)(rx >> 16) : (int)(rx & 0xffffu);
     const int fy = NOY ? 0 : (dy >= 0.0f ? (int)(ry >> 16) : (int)(ry & 0xffffu));
     const int fz = dz >= 0.0f ? (int)(rz >> 16) : (int)(rz & 0xffffu);
     // a block that spans a whole periodic axis has no face on it (the lane's position runs through the images)
-    spans |= rec.w;  // (in such a block the lane may leave the principal image: folded when it leaves the block)
+    if constexpr (!NOSPAN) spans |= rec.w;  // (in such a block the lane may leave the principal image: folded when it leaves the block)
     // (the edges are read whether or not the select keeps them -- every face index is in the table: selects, no branches)
     const float ex = (float)(s_edge[fx] - px), ez = (float)(s_edge[offZ + fz] - pz);
-    tnx = ((rec.w & 1u) || ivx == 0.0f) ? FLT_MAX : ex * ivx;
-    tny = (NOY || (rec.w & 2u) || ivy == 0.0f) ? FLT_MAX : (float)(s_edge[offY + fy] - py) * ivy;
+    tnx = ((!NOSPAN && (rec.w & 1u)) || ivx == 0.0f) ? FLT_MAX : ex * ivx;
+    tny = (NOY || (!NOSPAN && (rec.w & 2u)) || ivy == 0.0f) ? FLT_MAX : (float)(s_edge[offY + fy] - py) * ivy;
     tnz = ivz == 0.0f ? FLT_MAX : ez * ivz;
   };
 
@@ -342,7 +361,7 @@ trace_block_kernel(const DevParams p) {
       if ((state == BW_SURFACE || state == BW_TOP) && doSurface) {
         const bool top = state == BW_TOP;
         {
-          const double xw = px + (double)tcur * (double)dx, yw = py + (double)tcur * (double)dy;  // where the leg met the face (:1801-1812)
+          const double xw = __fma_rn((double)tcur, (double)dx, px), yw = __fma_rn((double)tcur, (double)dy, py);  // where the leg met the face (:1801-1812); exact product, see the collision
           if (DEBUG) countCrossings(xw, yw, top ? p.nz : -1);
           px = xw;
           if (!NOY) py = yw;
@@ -384,7 +403,7 @@ trace_block_kernel(const DevParams p) {
             mu = sqrtf(uZ);
             uint32_t r[4];
             for (uint32_t j = 0; !(fabsf(mu) > 2.0f * FLT_MIN); j++) {
-              if ((j & 3u) == 0) philox4x32_10_p1(event, 2u + (j >> 2), idP1, idHi, p.seedLo, p.seedHi, r);
+              if ((j & 3u) == 0) philox4x32_10_p1(event, 2u + (j >> 2), photonP1(), idHi, p.seedLo, p.seedHi, r);
               mu = sqrtf(u01(pick4(r, j & 3u)));
             }
           }
@@ -430,6 +449,7 @@ trace_block_kernel(const DevParams p) {
             const unsigned long long id = p.firstPhoton + myIdx;
             idLo = (uint32_t)id; idHi = (uint32_t)(id >> 32);
             idP1 = philox_p1(idLo);
+            if constexpr (HOIST) { legQ0 = philox_leg_q0(idP1, p.seedLo); legD1 = (uint32_t)idP1; }
             event = 0; nScat = 0; nLegs = 0;
             slabOff = k < unitSplit ? 0 : slabLen;
             uint32_t r[4];
@@ -530,17 +550,26 @@ trace_block_kernel(const DevParams p) {
         // photon goes on colliding in the CELL it is in until its weight is gone; here the cell comes from the position, so
         // the position must stay where it is -- moved along a NaN it would never die: found by the soak run against the oracle.)
         if (dz == dz || legacyMoveNaN) {
+#ifdef MCBRAT_PRECISE_MATH
           const double s = (double)(tcur + div_fast(tau - acc, extCur));
-          px = px + s * (double)dx;
-          if (!NOY) py = py + s * (double)dy;
-          pz = pz + s * (double)dz;
+#else
+          // (HOIST: invExtCur = rcp_fast(extCur), formed once per launch -- div_fast's own instruction on the same input, the same float)
+          const double s = (double)(tcur + (HOIST ? (tau - acc) * invExtCur : div_fast(tau - acc, extCur)));
+#endif
+          // p + s * d as ONE f64 fma.  s and d are floats widened to double: their product has at most 48 significant bits and an
+          // exponent far inside double's range, so it is exact -- the multiply of `p + s * d` rounds nothing, and the sum rounds
+          // once, as the fma does.  Bit for bit the same (NaN and infinities included); the library is built with
+          // -ffp-contract=off, hence the explicit call.
+          px = __fma_rn(s, (double)dx, px);
+          if (!NOY) py = __fma_rn(s, (double)dy, py);
+          pz = __fma_rn(s, (double)dz, pz);
         }
         // its cell, from the position (the periodic fold moves the position into the domain)
         {
           const double xw = px, yw = py;
           iz = NEAR ? locate_near_uniform(s_edge + offZ, p.nz, p.z0, invDz, pz) : locate_z(s_edge + offZ, p.nz, zRegular, p.z0, invDz, pz);
-          ix = locX(xw, (spans & 1u) != 0);
-          iy = locY(yw, (spans & 2u) != 0);
+          ix = locX(xw, spanX());
+          iy = locY(yw, spanY());
         }
         int cell = cellOf(ix, iy, iz);
         nScat++;
@@ -579,7 +608,7 @@ trace_block_kernel(const DevParams p) {
           float uR = uZ;  // one component: Z decides nothing at the component pick and serves here (no second block; mcbrat_kernels.hip)
           if (nc != 1) {  // (wave-uniform; compile time in the SIMPLE instantiations)
             uint32_t r1[4];
-            philox4x32_10_p1(event, 1u, idP1, idHi, p.seedLo, p.seedHi, r1);
+            philox4x32_10_p1(event, 1u, photonP1(), idHi, p.seedLo, p.seedHi, r1);
             uR = u01(r1[1]);
           }
           if (uR >= w) { w = 0.0f; if (DEBUG) cKill++; }
@@ -648,7 +677,8 @@ trace_block_kernel(const DevParams p) {
           dbgZ = iz;
         }
         uint32_t r[4];
-        philox4x32_10_p1(event, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
+        if constexpr (HOIST) philox4x32_10_leg(event, legQ0, legD1, idHi, p.seedLo, p.seedHi, r);
+        else philox4x32_10_p1(event, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
 #ifdef MCBRAT_PRECISE_MATH
         tau = -logf(fmaxf(FLT_MIN, u01(r[0])));
 #else
@@ -660,7 +690,7 @@ trace_block_kernel(const DevParams p) {
         ivx = fabsf(dx) >= 2.0f * FLT_MIN ? rcp_fast(dx) : 0.0f;
         ivy = (!NOY && fabsf(dy) >= 2.0f * FLT_MIN) ? rcp_fast(dy) : 0.0f;
         ivz = fabsf(dz) >= 2.0f * FLT_MIN ? rcp_fast(dz) : 0.0f;
-        spans = 0;  // (the leg starts inside the domain: its origin was folded where it was located)
+        if constexpr (!NOSPAN) spans = 0;  // (the leg starts inside the domain: its origin was folded where it was located)
         nCrossLeg = 0u;
         enterBlock(ix, iy, iz);
         state = BW_MOVE;
@@ -671,25 +701,25 @@ trace_block_kernel(const DevParams p) {
         const bool yLtX = !NOY && tny < tnx;
         const float m2 = yLtX ? tny : tnx;
         const bool isZ = tnz < m2;  // (the axis whose face was reached: the same comparison the move made)
-        const double xw = px + (double)tcur * (double)dx, yw = py + (double)tcur * (double)dy, zw = pz + (double)tcur * (double)dz;
+        const double xw = __fma_rn((double)tcur, (double)dx, px), yw = __fma_rn((double)tcur, (double)dy, py), zw = __fma_rn((double)tcur, (double)dz, pz);  // (exact products: see the collision)
         // (the face crossed gives its axis' index exactly; the two others come from the position, clamped to the
         // range of the block the lane is leaving -- see rx, ry, rz above)
         int jx, jy, jz;
         if (isZ) {
           jz = dz >= 0.0f ? (int)(rz >> 16) : (int)(rz & 0xffffu) - 1;  // (0 <= jz < nz: leaving the domain was decided when the face was reached)
-          jx = inRangeX(locX(xw, (spans & 1u) != 0), rx);
-          jy = NOY ? 0 : inRangeX(locY(yw, (spans & 2u) != 0), ry);
+          jx = inRangeX(locX(xw, spanX()), rx);
+          jy = NOY ? 0 : inRangeX(locY(yw, spanY()), ry);
         } else if (yLtX) {
           jy = dy >= 0.0f ? (int)(ry >> 16) : (int)(ry & 0xffffu) - 1;
           if (jy >= p.ny) { jy = 0; py -= p.Ly; if (DEBUG) dbgY -= p.ny; }            // periodic y :1790-1796: continue in the next image
           else if (jy < 0) { jy = p.ny - 1; py += p.Ly; if (DEBUG) dbgY += p.ny; }
-          jx = inRangeX(locX(xw, (spans & 1u) != 0), rx);
+          jx = inRangeX(locX(xw, spanX()), rx);
           jz = inRangeX(NEAR ? locate_near_uniform(s_edge + offZ, p.nz, p.z0, invDz, zw) : locate_z(s_edge + offZ, p.nz, zRegular, p.z0, invDz, zw), rz);
         } else {
           jx = dx >= 0.0f ? (int)(rx >> 16) : (int)(rx & 0xffffu) - 1;
           if (jx >= p.nx) { jx = 0; px -= p.Lx; if (DEBUG) dbgX -= p.nx; }            // periodic x :1782-1788
           else if (jx < 0) { jx = p.nx - 1; px += p.Lx; if (DEBUG) dbgX += p.nx; }
-          jy = NOY ? 0 : inRangeX(locY(yw, (spans & 2u) != 0), ry);
+          jy = NOY ? 0 : inRangeX(locY(yw, spanY()), ry);
           jz = inRangeX(NEAR ? locate_near_uniform(s_edge + offZ, p.nz, p.z0, invDz, zw) : locate_z(s_edge + offZ, p.nz, zRegular, p.z0, invDz, zw), rz);
         }
         // (every axis the block left spans has just been folded -- it cannot be the axis crossed, a spanning block has no
@@ -697,7 +727,7 @@ trace_block_kernel(const DevParams p) {
         // a second fold by floor() may take the image on the far side of it while the clamp keeps the cell on this side;
         // the next face then lies behind the lane, tcur steps back, and the lane goes round a corner of four blocks for
         // ever -- the third hang the soak runs found, test_random_domains_against_the_oracle seed 763, a grazing sun.)
-        if (!legacyKeepSpans) spans = 0;
+        if (!NOSPAN && !legacyKeepSpans) spans = 0;
         enterBlock(jx, jy, jz);
         state = BW_MOVE;
         if (++nCrossLeg > watchdog) MCBRAT_BW_DROP(DROP_CROSSINGS);  // (a leg that has crossed 2^20 blocks is going round in circles)

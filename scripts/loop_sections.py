@@ -2,7 +2,7 @@
 """Static instruction counts of the block walk's collision loop, section by section (no GPU needed).
 
 Compiles the device code with -DMCBRAT_MARKS (each STAMP(i) of mcbrat_blockwalk.hip becomes an `@@mark i` comment in the
-assembly), takes the step cloud's instantiation trace_block_kernel<768, true, false, false, 2, 0>, keeps the basic blocks of its
+assembly), takes the step cloud's instantiation trace_block_kernel<768, true, false, false, 2, 0, true>, keeps the basic blocks of its
 inner loop and counts, per section between two marks, vector / scalar / LDS instructions, s_nop / s_waitcnt, and the classes
 worth watching (moves, 64-bit address and multiply-add ops, SGPR spills into VGPR lanes, f32 <-> f64 conversions, kernel-argument
 reloads, exec-mask saves).  Sections follow the layout of the code, so a section holds the rare branch that follows its mark.
@@ -16,7 +16,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_ZN6mcbrat18trace_block_kernelILi768ELb1ELb0ELb0ELi2ELi0EEEvNS_9DevParamsE"
+KERNEL = "_ZN6mcbrat18trace_block_kernelILi768ELb1ELb0ELb0ELi2ELi0ELb1EEEvNS_9DevParamsE"
 SECTIONS = {"7": "loop head + exits", "5": "launch", "0": "collision", "2": "scattering angle",
             "3": "next_direct", "4": "next_direct + drop test + leg set-up", "6": "crossings + exit test", "1": "move (loop end)"}
 ORDER = ["loop head + exits", "launch", "collision", "scattering angle", "next_direct + drop test + leg set-up",

@@ -101,6 +101,25 @@ KERNEL_S(k_v_swap, FOUR_SWAP)
 KERNEL_S(k_v_cndmask, EIGHT_CND)
 KERNEL_S(k_v_accvgpr, FOUR_ACC)
 
+// ---- round 5: what a vector instruction costs when it issues with an EMPTY exec mask (a predicated block none of whose lanes
+// is in: the f64 periodic fold of the block walk's collision).  One asm block saves exec, clears it, issues 32 instructions and
+// restores it: two scalar instructions per 32 vector ones, counted as 32.
+#define REP2(x) x x
+#define KERNEL_E(name, body)                                                             \
+  __global__ void __launch_bounds__(256) name(float *out, int iters) {                   \
+    float a0 = threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7; \
+    double d0 = a0, d1 = a1, d2 = a2, d3 = a3, d4 = a4, d5 = a5, d6 = a6, d7 = a7;       \
+    unsigned long long m;                                                                \
+    for (int i = 0; i < iters; i++) { REP2(body) }                                        \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (float)(d0 + d1 + d2 + d3 + d4 + d5 + d6 + d7); \
+  }
+#define OPS8(op) op " %0, %0, %0\n\t" op " %1, %1, %1\n\t" op " %2, %2, %2\n\t" op " %3, %3, %3\n\t" op " %4, %4, %4\n\t" op " %5, %5, %5\n\t" op " %6, %6, %6\n\t" op " %7, %7, %7\n\t"
+#define EXEC0_32(op, r0, r1, r2, r3, r4, r5, r6, r7)                                                                  \
+  asm volatile("s_mov_b64 %8, exec\n\ts_mov_b64 exec, 0\n\t" OPS8(op) OPS8(op) OPS8(op) OPS8(op) "s_mov_b64 exec, %8" \
+               : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "=&s"(m));
+KERNEL_E(k_add_f64_exec0, EXEC0_32("v_add_f64", d0, d1, d2, d3, d4, d5, d6, d7))
+KERNEL_E(k_fmac_f32_exec0, EXEC0_32("v_fmac_f32", a0, a1, a2, a3, a4, a5, a6, a7))
+
 template <typename K>
 void run(const char *name, K kernel, float *out, int wavesPerSimd) {
   const int iters = 2000;
@@ -141,6 +160,7 @@ int main() {
     run("v_rcp_f32", k_rcp, out, w); run("v_log_f32", k_log, out, w); run("v_sqrt_f32", k_sqrt, out, w); run("v_sin_f32", k_sin, out, w);
     run("v_add_f64", k_add_f64, out, w); run("v_mul_f64", k_mul_f64, out, w); run("v_fma_f64", k_fma_f64, out, w);
     run("v_cvt_f64_f32", k_cvt_f64_f32, out, w); run("v_cvt_f32_f64", k_cvt_f32_f64, out, w);
+    run("v_add_f64, exec = 0", k_add_f64_exec0, out, w); run("v_fmac_f32, exec = 0", k_fmac_f32_exec0, out, w);
   }
   return 0;
 }
