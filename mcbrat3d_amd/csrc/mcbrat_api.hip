@@ -10,10 +10,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mcbrat_kernels.hip"
 #include "mcbrat_blockwalk.hip"
+#include "mcbrat_variants.h"
 
 using namespace mcbrat;
 
@@ -280,59 +282,24 @@ TallyLayout tally_layout(const mcbrat_ctx *c) { return tally_layout(tally_shape(
 constexpr size_t kSlabBudget = (size_t)4 << 30;  // bytes of batch slabs in flight at most (one batch's slab must fit it)
 // whether the bins of one batch of a (candidate) shape fit that budget: its order part, its level and actinic bins, all of it
 TallyFit budget_fit(const TallyShape &s) { return tally_fit(s, kSlabBudget); }
-// (candidate shapes: the context's with other level and actinic settings and, unless asked for, without the side part; without
-// the actinic flux and the side fluxes a refusal is the level tallies')
-TallyShape with_tallies(TallyShape s, int levels, int direct, int actinic, int side = 0) {
-  s.levels = levels; s.direct = levels && direct; s.actinic = actinic; s.side = levels && side;
-  return s;
+// What a call asks refusal() (mcbrat_variants.h) about: the context's settings -- a setter first changes the one field it is about
+struct Asked { int nx, ny, nz, nDir, limitContrib, numRecScatOrd, levels, direct, actinic, side; bool brdf, debug; };
+Asked asked(const mcbrat_ctx *c) {
+  return Asked{c->nx, c->ny, c->nz, c->nDir, c->limitContrib, c->numRecScatOrd, c->levelFluxes, c->directLevelFluxes, c->actinicFlux, c->sideFluxes,
+               c->surfNumX > 0 && c->surfKind != 0, c->countersOn};
 }
-TallyShape without_actinic(const TallyShape &s) { return with_tallies(s, s.levels, s.direct, 0); }
+Settings settings_of(const mcbrat_ctx *c, const Asked &a) {
+  const TallyShape s{a.nx, a.ny, a.nz, c->nc, a.nDir, a.limitContrib, order_count(a.numRecScatOrd), a.levels != 0, a.levels && a.direct, a.actinic != 0, a.levels && a.side};
+  TallyShape l = s;  // (without the actinic flux and the side fluxes a refusal is the level tallies')
+  l.actinic = l.side = 0;
+  const TallyFit all = budget_fit(s), levels = budget_fit(l);
+  return Settings{a.nDir > 0, a.numRecScatOrd >= 0, a.limitContrib != 0, a.levels != 0, a.direct != 0, a.actinic != 0, a.side != 0, a.brdf, a.debug, c->srcKind != 0,
+                  all.orders, levels.globalBins, all.globalBins, all.stride};
+}
+// (a refused call leaves the context as it was, but for its error text)
+#define REFUSE(c, a, stage) \
+  do { if (const char *m_ = refusal(settings_of(c, a), stage)) return fail(c, m_); } while (0)
 constexpr int64_t kMaxPhotonsPerBatch = 0x7fffffffLL;  // a unit weight per photon in one bin stays below 2^63 (2^-32 units)
-// The reference's commented redistribution (computeRadiativeTransfer :307-313) adds each direction's clipped excess to EVERY order.
-// Level fluxes are tallied by the general flux kernels on the face-by-face walk only: what they are refused with
-const char *const kLevelsIntensityMsg =
-    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with intensity directions: the radiance kernels have no level tallies.";
-const char *const kLevelsOrdersMsg =
-    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with scattering orders (recScatOrd): no kernel tallies both.";
-const char *const kLevelsBrdfMsg =
-    "specifyParameters: level fluxes (recLevelFluxes) cannot be combined with a BRDF surface: a reflected weight may exceed 1, which the level tallies do not hold.";
-const char *const kLevelsCountersMsg =
-    "specifyParameters: level fluxes (recLevelFluxes) are not available together with event counters / photon fates: the instrumented kernels have no level tallies.";
-const char *const kLevelsBudgetMsg =
-    "specifyParameters: level fluxes (recLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
-const char *const kDirectNeedsLevelsMsg =
-    "specifyParameters: direct level fluxes (recDirectLevelFluxes) need level fluxes (recLevelFluxes): they separate the downward level flux.";
-const char *const kDirectThermalMsg =
-    "computeRadiativeTransfer: direct level fluxes (recDirectLevelFluxes) are not available with the thermal source: there is no direct beam.";
-const char *const kDirectBudgetMsg =
-    "specifyParameters: direct level fluxes (recDirectLevelFluxes): the level bins of one batch would not fit the 4 GiB tally budget.";
-// The actinic flux is tallied by solar flux kernels on the face-by-face walk only: what it is refused with
-const char *const kActinicIntensityMsg =
-    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with intensity directions: the radiance kernels have no track-length tally.";
-const char *const kActinicOrdersMsg =
-    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with scattering orders (recScatOrd): no kernel tallies both.";
-const char *const kActinicBrdfMsg =
-    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with a BRDF surface: a reflected weight may exceed 1, which the track-length tally does not hold.";
-const char *const kActinicCountersMsg =
-    "specifyParameters: the actinic flux (recActinicFlux) is not available together with event counters / photon fates: the instrumented kernels have no track-length tally.";
-const char *const kActinicDirectMsg =
-    "specifyParameters: the actinic flux (recActinicFlux) cannot be combined with direct level fluxes (recDirectLevelFluxes): no kernel tallies both.";
-const char *const kActinicBudgetMsg =
-    "specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch would not fit the 4 GiB tally budget.";
-const char *const kActinicThermalMsg =
-    "computeRadiativeTransfer: the actinic flux (recActinicFlux) is not available with the thermal source: the track-length tally is built for solar sources only.";
-// Side fluxes are a tally of the solar level-flux kernels: what they are refused with (and with everything
-// level fluxes are refused with, by those messages: the setting needs them)
-const char *const kSideNeedsLevelsMsg =
-    "specifyParameters: side fluxes (recSideFluxes) need level fluxes (recLevelFluxes): the kernels that stop at every face tally both.";
-const char *const kSideDirectMsg =
-    "specifyParameters: side fluxes (recSideFluxes) cannot be combined with direct level fluxes (recDirectLevelFluxes): no kernel tallies both.";
-const char *const kSideActinicMsg =
-    "specifyParameters: side fluxes (recSideFluxes) cannot be combined with the actinic flux (recActinicFlux): no kernel tallies both.";
-const char *const kSideBudgetMsg =
-    "specifyParameters: side fluxes (recSideFluxes): the level and side bins of one batch would not fit the 4 GiB tally budget.";
-const char *const kSideThermalMsg =
-    "computeRadiativeTransfer: side fluxes (recSideFluxes) are not available with the thermal source: the side tally is built for solar sources only.";
 // The fixed point of an actinic deposit: 2^e km, e the smallest integer that keeps the longest possible step of the walk below
 // 2^e -- the diagonal of the largest spacings of the three axes, times 1 + 2^-10 for the float rounding of tmin - tcur (a few
 // ulp of the distance along the leg, which may be many steps long).  The kernel deposits w l 2^-e, the epilogue multiplies
@@ -349,10 +316,6 @@ double actinic_unit(const mcbrat_ctx *c) {
   (void)std::frexp(longest, &e);  // longest = m 2^e with m in [0.5, 1)
   return std::ldexp(1.0, e);
 }
-const char *const kOrdersLimitMsg =
-    "specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): the reference's "
-    "redistribution adds each direction's clipped excess to every order, which would count it numRecScatOrd + 1 times.";
-
 // The last batch's results from element `base` on (they are laid out as one sum of the moments), once everything enqueued is done
 int read_last(mcbrat_ctx *c, size_t base, std::vector<float> &h) {
   if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
@@ -724,21 +687,6 @@ bool flight_wanted(const mcbrat_ctx *c) {
   return !facewalk_on(c) && c->flyBuilt && (c->layerSkip == 3 || (c->layerSkip == 1 && c->flyDepth <= c->flightMaxDepth));
 }
 
-struct LaunchPlan {
-  bool tblLds, priv, brick, gridLds;
-  bool fly;  // clear-air flight: dense grid in global memory, flux run, tables built, room in LDS
-  // Wide plan (MI355X: 160 KB of LDS per compute unit): a tally slab too large to share a compute unit's LDS with a second
-  // workgroup -- the broadband 20 x 20 x 20 domain's is 70 KB -- gets the compute unit to itself: ONE workgroup of 1024 lanes
-  // (16 waves, 4 per SIMD) with up to the whole LDS, tallies in LDS as for the small domains instead of one memory-side
-  // atomic per deposit (config 4 waited 57 % of its wave time behind them).  Flux runs only.
-  bool wide;
-  bool blockLite;  // wide plan, block walk without the per-cell optics in LDS (trace_block_kernel<..., OPT = 1 or 2>)
-  int optics;      // block walk: where a collision finds its cell's optics: 0 per cell in LDS, 1 per cell in global memory, 2 per block in LDS
-  bool cdfTop;     // block walk, thermal source: level and row sums of the emission CDF staged in LDS
-  int block;
-  size_t lds;
-};
-
 bool blocks_worth_it(const mcbrat_ctx *c) {
   if (!c->blockWalk || c->nDir > 0 || c->nBlocks <= 0 || orders_on(c) || facewalk_on(c)) return false;  // (the block walk has no ORD, LVL or ACT variant)
   if (c->surfNumX > 0 && c->surfKind != 0) return false;  // (nor a BRDF one: such surfaces go face by face)
@@ -889,154 +837,33 @@ int launch_kernel(mcbrat_ctx *c, DevParams &p, const void *kernel, int block, si
   return 0;
 }
 
-// trace_kernel with the table and source flags picked at run time (every value of both is built).  (The source kind is a
-// template parameter: the emission launch code costs the solar instantiations registers.)
-template <int BLOCK, int PRIV, bool BRICK, bool DBG, bool INTEN = false, bool ORD = false, bool BRDF = false>
-const void *trace_ptr(bool tbl, bool emit) {
-  if constexpr (BRDF) {  // (solar sources only: a BRDF surface is refused with the thermal one, check_ready)
-    static_assert(!DBG, "no instrumented BRDF instantiation");
-    (void)emit;
-    return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, false, INTEN, false, 0, ORD, true>
-               : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, false, INTEN, false, 0, ORD, true>;
-  }
-  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, true, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
-  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, true, 0, ORD> : (const void *)trace_kernel<BLOCK, false, PRIV, BRICK, DBG, INTEN, false, 0, ORD>;
+// One table of kernel pointers per kernel, built from the lists of mcbrat_variants.h: entry I is the instantiation that entry I of
+// the list names.  These two templates are the only places where the kernels' positional template arguments are written out.
+constexpr auto kTraceList = trace_variants();
+constexpr auto kBlockList = block_variants();
+static_assert(kTraceList.n == kTraceVariants && kBlockList.n == kBlockVariants, "the lists are as long as they say");
+template <int I>
+const void *trace_entry() {
+  constexpr TraceVariant v = kTraceList.v[I];
+  return (const void *)trace_kernel<v.block, v.tblLds, v.priv, v.brick, v.debug, v.inten, v.emit, v.spec, v.ord, v.brdf, v.lvl, v.direct, v.act, v.side>;
 }
+template <int I>
+const void *block_entry() {
+  constexpr BlockVariant v = kBlockList.v[I];
+  return (const void *)trace_block_kernel<v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan>;
+}
+template <int... I>
+std::array<const void *, sizeof...(I)> trace_table(std::integer_sequence<int, I...>) { return {{trace_entry<I>()...}}; }
+template <int... I>
+std::array<const void *, sizeof...(I)> block_table(std::integer_sequence<int, I...>) { return {{block_entry<I>()...}}; }
+const std::array<const void *, kTraceVariants> kTraceKernels = trace_table(std::make_integer_sequence<int, kTraceVariants>{});
+const std::array<const void *, kBlockVariants> kBlockKernels = block_table(std::make_integer_sequence<int, kBlockVariants>{});
+const char *const kNoKernelMsg = "computeRadiativeTransfer: no kernel is built for this combination of settings.";
 
-// the LVL instantiations (level fluxes): BLOCK 256 / 512 x PRIV 0 / 2 x table x source -- 16 kernels
-template <int BLOCK, int PRIV>
-const void *trace_ptr_lvl(bool tbl, bool emit) {
-  if (tbl) return emit ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, true, 0, false, false, true>
-                       : (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true>;
-  return emit ? (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, true, 0, false, false, true>
-              : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true>;
-}
-// their DIRECT variants, solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table -- 8 kernels
-template <int BLOCK, int PRIV>
-const void *trace_ptr_lvl_direct(bool tbl) {
-  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true, true>
-             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true, true>;
-}
-// the ACT instantiations (actinic flux), solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table x LVL -- 16 kernels
-template <int BLOCK, int PRIV, bool LVL>
-const void *trace_ptr_act(bool tbl) {
-  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, LVL, false, true>
-             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, LVL, false, true>;
-}
-template <int BLOCK>
-const void *trace_kernel_act(const mcbrat_ctx *c, const LaunchPlan &L) {  // (thermal source, direct tally: refused, check_ready)
-  if (levels_on(c)) return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, true>(L.tblLds) : trace_ptr_act<BLOCK, 0, true>(L.tblLds);
-  return (L.priv && L.gridLds) ? trace_ptr_act<BLOCK, 2, false>(L.tblLds) : trace_ptr_act<BLOCK, 0, false>(L.tblLds);
-}
-// the SIDE instantiations (side fluxes), solar sources only: BLOCK 256 / 512 x PRIV 0 / 2 x table -- 8 kernels
-template <int BLOCK, int PRIV>
-const void *trace_ptr_lvl_side(bool tbl) {
-  return tbl ? (const void *)trace_kernel<BLOCK, true, PRIV, false, false, false, false, 0, false, false, true, false, false, true>
-             : (const void *)trace_kernel<BLOCK, false, PRIV, false, false, false, false, 0, false, false, true, false, false, true>;
-}
-template <int BLOCK>
-const void *trace_kernel_lvl(const mcbrat_ctx *c, const LaunchPlan &L) {
-  const bool emit = c->srcKind != 0;
-  if (side_on(c)) return (L.priv && L.gridLds) ? trace_ptr_lvl_side<BLOCK, 2>(L.tblLds) : trace_ptr_lvl_side<BLOCK, 0>(L.tblLds);  // (emit, direct, actinic: refused, check_ready)
-  if (direct_on(c)) return (L.priv && L.gridLds) ? trace_ptr_lvl_direct<BLOCK, 2>(L.tblLds) : trace_ptr_lvl_direct<BLOCK, 0>(L.tblLds);  // (emit: refused, check_ready)
-  return (L.priv && L.gridLds) ? trace_ptr_lvl<BLOCK, 2>(L.tblLds, emit) : trace_ptr_lvl<BLOCK, 0>(L.tblLds, emit);
-}
-
-// the ORD instantiations (scattering orders): BLOCK 256 / 512 x PRIV 0 / 1 / 2 x INTEN x table x source, dense grids, not instrumented
-template <int BLOCK, bool BRDF = false>
-const void *trace_kernel_ord(const mcbrat_ctx *c, const LaunchPlan &L) {
-  const bool tbl = L.tblLds, emit = c->srcKind != 0;
-  if (c->nDir > 0) {
-    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, true, BRDF>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true, true, BRDF>(tbl, emit);
-    return trace_ptr<BLOCK, 0, false, false, true, true, BRDF>(tbl, emit);
-  }
-  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, true, BRDF>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, false, true, BRDF>(tbl, emit);
-  return trace_ptr<BLOCK, 0, false, false, false, true, BRDF>(tbl, emit);
-}
-
-// BRDF surfaces: the kernels the face-by-face plan picks for a surface description, from a solar source,
-// not instrumented -- BLOCK 256 / 512 x PRIV 0 / 1 / 2 / bricks x INTEN x ORD, the wide plan's 1024 and the 768-lane kernel, x table
-template <int BLOCK>
-const void *trace_kernel_brdf(const mcbrat_ctx *c, const LaunchPlan &L) {
-  const bool tbl = L.tblLds;
-  if (orders_on(c)) return trace_kernel_ord<BLOCK, true>(c, L);
-  if (c->nDir > 0) {
-    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true, false, true>(tbl, false) : trace_ptr<BLOCK, 1, false, false, true, false, true>(tbl, false);
-    return trace_ptr<BLOCK, 0, false, false, true, false, true>(tbl, false);
-  }
-  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, false, false, true>(tbl, false) : trace_ptr<BLOCK, 1, false, false, false, false, true>(tbl, false);
-  if (L.brick) return trace_ptr<BLOCK, 0, true, false, false, false, true>(tbl, false);
-  return trace_ptr<BLOCK, 0, false, false, false, false, true>(tbl, false);
-}
-
-// trace_kernel of 256 or 512 lanes.  Instantiated combinations: private tallies (small domains) and bricks (large ones) never
-// coincide; radiance runs read dense grids and are not instrumented.
-template <int BLOCK, bool DBG>
-const void *trace_kernel_for(const mcbrat_ctx *c, const DevParams &p, const LaunchPlan &L) {
-  const bool tbl = L.tblLds, emit = c->srcKind != 0;
-  if (c->nDir > 0) {
-    if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, false, true>(tbl, emit) : trace_ptr<BLOCK, 1, false, false, true>(tbl, emit);
-    return trace_ptr<BLOCK, 0, false, false, true>(tbl, emit);
-  }
-  if (L.priv) return L.gridLds ? trace_ptr<BLOCK, 2, false, DBG>(tbl, emit) : trace_ptr<BLOCK, 1, false, DBG>(tbl, emit);
-  if (L.brick) return trace_ptr<BLOCK, 0, true, DBG>(tbl, emit);
-  if constexpr (BLOCK == 256 && !DBG) {
-    // the large flux runs: dense grid in global memory, collision records (nc <= 2), layer-skipping walk, albedo
-    // surface -- with the walk's spacing flags decided at compile time too (SPEC, mcbrat_kernels.hip)
-    // A solar run with roulette (every bench workload) also has its component count and the roulette decided at compile
-    // time (SPEC bits 2-3 and 4); without roulette it runs the general kernel.  (Each SPEC is built for one source: EMIT = SPEC < 16.)
-    // The solar SPEC kernels launch the Directional source only: the other solar kinds run the general kernel.
-    if (p.rec != nullptr && p.layerSkip && p.fly && p.surfNumX == 0 && (p.xyRegularWalk || !p.zRegularWalk)) {
-      const int walk = p.xyRegularWalk ? (p.zRegularWalk ? 2 : 3) : 1;
-      switch (emit ? walk : (p.useRR && (p.nc == 1 || p.nc == 2) && p.solarKind == 0 ? walk | p.nc << 2 | 16 : 0)) {
-#define MCBRAT_SPEC_CASE(S) \
-  case S: return tbl ? (const void *)trace_kernel<256, true, 0, false, false, false, ((S) < 16), (S)> : (const void *)trace_kernel<256, false, 0, false, false, false, ((S) < 16), (S)>
-        MCBRAT_SPEC_CASE(1); MCBRAT_SPEC_CASE(2); MCBRAT_SPEC_CASE(3);
-        MCBRAT_SPEC_CASE(1 | 1 << 2 | 16); MCBRAT_SPEC_CASE(2 | 1 << 2 | 16); MCBRAT_SPEC_CASE(3 | 1 << 2 | 16);
-        MCBRAT_SPEC_CASE(1 | 2 << 2 | 16); MCBRAT_SPEC_CASE(2 | 2 << 2 | 16); MCBRAT_SPEC_CASE(3 | 2 << 2 | 16);
-#undef MCBRAT_SPEC_CASE
-      }
-    }
-  }
-  return trace_ptr<BLOCK, 0, false, DBG>(tbl, emit);
-}
-
-// trace_block_kernel with the table and source flags picked at run time (every value of both is built)
-template <int BLOCK, bool DBG, int SIMPLE, int OPT>
-const void *block_ptr(bool tbl, bool emit) {
-  if (tbl) return emit ? (const void *)trace_block_kernel<BLOCK, true, DBG, true, SIMPLE, OPT> : (const void *)trace_block_kernel<BLOCK, true, DBG, false, SIMPLE, OPT>;
-  return emit ? (const void *)trace_block_kernel<BLOCK, false, DBG, true, SIMPLE, OPT> : (const void *)trace_block_kernel<BLOCK, false, DBG, false, SIMPLE, OPT>;
-}
-
-// The NOSPAN instantiations (mcbrat_blockwalk.hip): solar SIMPLE = 1 and 2 kernels of 768 lanes, the library's own plan for a
-// grid in LDS, for media none of whose blocks spans a periodic axis the kernel looks at (an x-z problem has no y to look at).
-bool nospan_kernel(const mcbrat_ctx *c) {
-  const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
-  if (!simple || c->srcKind != 0 || c->blockSpanKernel != 0) return false;
-  return !c->blockSpansX && (c->ny == 1 || !c->blockSpansY);
-}
-
-template <int BLOCK, bool DBG, int OPT = 0>
-const void *block_kernel_for(const mcbrat_ctx *c, const DevParams &p, bool tbl) {
-  const bool emit = c->srcKind != 0;
-  // equally spaced axes, one component, no surface description: the instantiation with those decided at compile time
-  const bool simple = c->xyRegular && c->zRegular && c->nc == 1 && c->surfNumX == 0;
-  if constexpr (OPT == 0 && BLOCK == 768 && !DBG) {
-    if (nospan_kernel(c)) {
-      if (c->ny == 1) return tbl ? (const void *)trace_block_kernel<768, true, false, false, 2, 0, true> : (const void *)trace_block_kernel<768, false, false, false, 2, 0, true>;
-      return tbl ? (const void *)trace_block_kernel<768, true, false, false, 1, 0, true> : (const void *)trace_block_kernel<768, false, false, false, 1, 0, true>;
-    }
-  }
-  if constexpr (OPT == 0 && BLOCK != 1024) {
-    if (simple && c->ny == 1 && !DBG) return block_ptr<BLOCK, DBG, 2, OPT>(tbl, emit);  // an x-z problem
-  }
-  if constexpr (!DBG && (BLOCK == 1024 || BLOCK == 768)) {
-    // no axis equally spaced by the reference's single-precision test, every axis equally spaced to 1e-6 of a cell (0.1 km cells):
-    // the same cells as the general instantiation finds, with nothing left to decide at run time (SIMPLE = 3)
-    if (!c->xyRegular && !c->zRegular && p.xyNearUniform && p.zNearUniform && c->nc == 1 && c->surfNumX == 0 && !c->noSimple3)
-      return block_ptr<BLOCK, DBG, 3, OPT>(tbl, emit);
-  }
-  return simple ? block_ptr<BLOCK, DBG, 1, OPT>(tbl, emit) : block_ptr<BLOCK, DBG, 0, OPT>(tbl, emit);
+// What the block walk's instantiations decide at compile time, of this context (the near-uniform flags: fill_params)
+BlockWalk block_walk_of(const mcbrat_ctx *c, bool xyNearUniform, bool zNearUniform) {
+  return BlockWalk{c->xyRegular != 0, c->zRegular != 0, c->nc == 1, c->surfNumX != 0, c->ny == 1, xyNearUniform, zNearUniform, c->noSimple3,
+                   c->blockSpansX, c->blockSpansY, c->blockSpanKernel != 0, c->blockSize};
 }
 
 // The block walk applies where the face-by-face plan already keeps grid, tallies (and tables) in LDS -- or, in the wide
@@ -1044,6 +871,17 @@ const void *block_kernel_for(const mcbrat_ctx *c, const DevParams &p, bool tbl) 
 // per block on average (a medium that differs from cell to cell would pay a position look-up at every face for nothing).
 bool block_walk_applies(const mcbrat_ctx *c, const LaunchPlan &L) {
   return blocks_worth_it(c) && ((L.priv && L.gridLds) || L.blockLite);
+}
+
+// What a launch runs: one instantiation, its workgroup size and its dynamic LDS.  kernel == nullptr: refused, the context's error says why.
+struct KernelChoice { const void *kernel; int block; size_t lds; };
+
+// (lds: the layout of launch_block, which knows the slabs)
+KernelChoice choose_block(mcbrat_ctx *c, const DevParams &p, const LaunchPlan &L, bool debug) {
+  const BlockVariant v = pick_block(L, debug, c->srcKind != 0, block_walk_of(c, p.xyNearUniform != 0, p.zNearUniform != 0));
+  const int i = find_variant(kBlockList, v);
+  if (i < 0) { fail(c, kNoKernelMsg); return {nullptr, 0, 0}; }
+  return {kBlockKernels[(size_t)i], v.block, 0};
 }
 
 int launch_block(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool debug, int nBatches) {
@@ -1054,22 +892,43 @@ int launch_block(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool debug, i
                             opt, L.cdfTop).total;
   };
   if (lds(1) + 512 > c->ldsPerCU) return fail(c, "computeRadiativeTransfer: the block-walk tables do not fit the LDS of a compute unit.");
-  const void *kernel;
-  int block;
-  if (L.wide) {  // one workgroup per compute unit: 1024 lanes (the instrumented instantiation: 512)
-    block = debug ? 512 : 1024;
-    if (opt == 2) kernel = debug ? block_kernel_for<512, true, 2>(c, p, L.tblLds) : block_kernel_for<1024, false, 2>(c, p, L.tblLds);
-    else if (opt == 1) kernel = debug ? block_kernel_for<512, true, 1>(c, p, L.tblLds) : block_kernel_for<1024, false, 1>(c, p, L.tblLds);
-    else kernel = debug ? block_kernel_for<512, true>(c, p, L.tblLds) : block_kernel_for<1024, false>(c, p, L.tblLds);
-  } else {
-    const int want = c->blockSize > 0 ? c->blockSize : 768;
-    block = debug ? 512 : (want == 768 || want == 256 ? want : 512);
-    if (debug) kernel = block_kernel_for<512, true>(c, p, L.tblLds);
-    else if (block == 768) kernel = block_kernel_for<768, false>(c, p, L.tblLds);
-    else if (block == 256) kernel = block_kernel_for<256, false>(c, p, L.tblLds);
-    else kernel = block_kernel_for<512, false>(c, p, L.tblLds);
+  const KernelChoice k = choose_block(c, p, L, debug);
+  if (!k.kernel) return 1;
+  return launch_kernel(c, p, k.kernel, k.block, lds(1), Units::BlockWalk, nBatches, lds(2));
+}
+
+// The settings of a launch: the order tallies are the parameter block's (an instrumented trace has none), debug the launch's
+Asked launch_asked(const mcbrat_ctx *c, const DevParams &p, bool debug) {
+  Asked a = asked(c);
+  a.numRecScatOrd = p.numRecScatOrd; a.debug = debug;
+  return a;
+}
+
+// The choosing part of launch_trace: the instantiation for a plan and the context's settings, after launch_trace's refusals (each
+// but the instrumented radiance and order runs is refused where it is asked for and by check_ready: a second line of defence);
+// sets the ray fields of the parameter block on radiance runs.
+KernelChoice choose_trace(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool debug) {
+  const Settings s = settings_of(c, launch_asked(c, p, debug));
+  const TraceWalk w{p.rec != nullptr, p.layerSkip != 0, p.fly != 0, p.surfNumX != 0, p.xyRegularWalk != 0, p.zRegularWalk != 0, p.useRR != 0, p.nc, p.solarKind};
+  const TraceVariant v = pick_trace(L, s, w);
+  const int i = find_variant(kTraceList, v);
+  const char *why = refusal(s, Launch);
+  if (why || i < 0) {  // (never a null pointer to launch)
+    fail(c, why ? why : kNoKernelMsg);
+    return {nullptr, 0, 0};
   }
-  return launch_kernel(c, p, kernel, block, lds(1), Units::BlockWalk, nBatches, lds(2));
+  size_t lds = L.lds;
+  if (v.inten) {  // radiance runs: the waves' buffers of unfinished long rays (ray_cap, mcbrat_variants.h)
+    const int cap = ray_cap(v.block, L.priv, L.lds, c->ldsPerCU, c->rayDefer != 0, c->nx + c->ny + c->nz + 3 <= 0xffff && c->nDir <= 0xffff);
+    p.rayCap = cap;
+    // measured on the 128x128x64 cloud field, 4 directions: with roulette most rays end within a few cells and the long
+    // ones are best served in short, dense passes; without it every ray runs to the boundary and long passes pay
+    p.rayShort = c->rayShort > 0 ? c->rayShort : (c->useRRIntensity ? 4 : 8);
+    p.rayPassIters = c->rayPassIters > 0 ? c->rayPassIters : (c->useRRIntensity ? 16 : 64);
+    p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), cap);
+    lds = ray_lds(v.block, L.lds, cap);
+  }
+  return {kTraceKernels[(size_t)i], v.block, lds};
 }
 
 int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
@@ -1079,92 +938,18 @@ int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
     p.flyInvBrickX = (float)(c->flyNbx / p.Lx); p.flyInvBrickY = (float)(c->flyNby / p.Ly);
   }
   if (block_walk_applies(c, L)) return launch_block(c, p, L, debug, nBatches);
-  const bool tbl = L.tblLds, emit = c->srcKind != 0;
-  const bool brdf = p.surfKind != 0;
-  const bool lvl = levels_on(c);
-  if (lvl && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
-    return fail(c, debug ? kLevelsCountersMsg : (brdf ? kLevelsBrdfMsg : (c->nDir > 0 ? kLevelsIntensityMsg : kLevelsOrdersMsg)));
-  if (direct_on(c) && emit) return fail(c, kDirectThermalMsg);  // (check_ready refuses it; a second line of defence: no thermal DIRECT kernel)
-  const bool act = actinic_on(c);
-  if (act && (debug || brdf || c->nDir > 0 || p.numRecScatOrd >= 0))  // (refused where they are asked for; a second line of defence)
-    return fail(c, debug ? kActinicCountersMsg : (brdf ? kActinicBrdfMsg : (c->nDir > 0 ? kActinicIntensityMsg : kActinicOrdersMsg)));
-  if (act && (emit || direct_on(c))) return fail(c, emit ? kActinicThermalMsg : kActinicDirectMsg);  // (no thermal ACT kernel, none with DIRECT)
-  if (side_on(c) && (emit || direct_on(c) || act))  // (check_ready refuses them; a second line of defence: no such SIDE kernel)
-    return fail(c, emit ? kSideThermalMsg : (act ? kSideActinicMsg : kSideDirectMsg));
-  if (brdf && debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with a BRDF surface.");
-  const void *kernel;
-  int block;
-  size_t lds = L.lds;
-  if (L.wide && !debug) {  // one workgroup of 1024 lanes per compute unit, tallies (and what else fits) in its LDS; instrumented: 512 lanes
-    block = 1024;
-    if (brdf) kernel = L.gridLds ? trace_ptr<1024, 2, false, false, false, false, true>(tbl, false) : trace_ptr<1024, 1, false, false, false, false, true>(tbl, false);
-    else kernel = L.gridLds ? trace_ptr<1024, 2, false, false>(tbl, emit) : trace_ptr<1024, 1, false, false>(tbl, emit);
-  } else if (L.block == 768 && L.priv && L.gridLds && c->nDir == 0 && !debug && p.numRecScatOrd < 0 && !lvl && !act) {
-    // small domains (grid, tables and tallies in LDS): LDS holds two workgroups per CU, and two workgroups of 12 waves
-    // (6 per SIMD, 80 VGPRs) beat two of 8 (4 per SIMD, no spills) by 10 % on the step cloud (640 and 896 lanes lose)
-    // (radiance on LDS-resident domains keeps 512 lanes: 768 lanes at 80 VGPRs lose 20 % there)
-    block = 768;
-    kernel = brdf ? trace_ptr<768, 2, false, false, false, false, true>(tbl, false) : trace_ptr<768, 2, false, false>(tbl, emit);
-  } else {
-    block = L.block >= 512 ? 512 : 256;
-    if (c->nDir > 0) {  // radiance runs
-      if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with intensity directions.");
-      // the waves' buffers of unfinished long rays (80 B per ray) take what LDS is left at the residency the kernel is built
-      // for: 4 workgroups of 256 lanes per CU on grids in global memory, 2 workgroups otherwise
-      const size_t waves = block / 64, base = (L.lds + 15) & ~(size_t)15;
-      const size_t budget = c->ldsPerCU / (L.priv ? 2 : (block == 256 ? 4 : 2));
-      size_t cap = (c->rayDefer && budget > base + 64) ? std::min<size_t>(64, (budget - base - 64) / (waves * 80)) : 0;
-      if (cap < 24 || c->nx + c->ny + c->nz + 3 > 0xffff || c->nDir > 0xffff) cap = 0;  // (a ray record packs edge-table indices and the direction in 16 bits)
-      p.rayCap = (int)cap;
-      // measured on the 128x128x64 cloud field, 4 directions: with roulette most rays end within a few cells and the long
-      // ones are best served in short, dense passes; without it every ray runs to the boundary and long passes pay
-      p.rayShort = c->rayShort > 0 ? c->rayShort : (c->useRRIntensity ? 4 : 8);
-      p.rayPassIters = c->rayPassIters > 0 ? c->rayPassIters : (c->useRRIntensity ? 16 : 64);
-      p.rayPassAt = std::min<int>(c->rayPassAt > 0 ? c->rayPassAt : (c->useRRIntensity ? 56 : 40), (int)cap);
-      lds = base + waves * cap * 80;
-    }
-    if (act) kernel = block == 512 ? trace_kernel_act<512>(c, L) : trace_kernel_act<256>(c, L);
-    else if (lvl) kernel = block == 512 ? trace_kernel_lvl<512>(c, L) : trace_kernel_lvl<256>(c, L);
-    else if (brdf) kernel = block == 512 ? trace_kernel_brdf<512>(c, L) : trace_kernel_brdf<256>(c, L);
-    else if (p.numRecScatOrd >= 0) {  // scattering orders: never instrumented, never bricks (use_bricks)
-      if (debug) return fail(c, "computeRadiativeTransfer: event counters / photon fates are not available together with scattering orders.");
-      kernel = block == 512 ? trace_kernel_ord<512>(c, L) : trace_kernel_ord<256>(c, L);
-    } else if (block == 512) kernel = debug ? trace_kernel_for<512, true>(c, p, L) : trace_kernel_for<512, false>(c, p, L);
-    else kernel = debug ? trace_kernel_for<256, true>(c, p, L) : trace_kernel_for<256, false>(c, p, L);
-  }
+  const KernelChoice k = choose_trace(c, p, L, debug);
+  if (!k.kernel) return 1;
   // (very tall grids: the per-layer tables alone can pass the default limit of a workgroup)
-  if (lds + kStaticLds > c->ldsPerCU && lds > kLdsBudget) return fail(c, "computeRadiativeTransfer: the grid's edge and layer tables do not fit the LDS of a compute unit.");
-  return launch_kernel(c, p, kernel, block, lds, L.priv ? Units::PerBatch : Units::PerBlock, nBatches);
+  if (k.lds + kStaticLds > c->ldsPerCU && k.lds > kLdsBudget) return fail(c, "computeRadiativeTransfer: the grid's edge and layer tables do not fit the LDS of a compute unit.");
+  return launch_kernel(c, p, k.kernel, k.block, k.lds, L.priv ? Units::PerBatch : Units::PerBlock, nBatches);
 }
 
 int check_ready(mcbrat_ctx *c) {
   if (!c) return 1;
   if (!c->haveGrid || !c->haveOptics) return fail(c, "computeRadiativeTransfer: problem not completely specified.");
   if (!c->haveSource) return fail(c, "computeRadiativeTransfer: no photon source set.");
-  if (c->surfNumX > 0 && c->surfKind != 0 && c->srcKind != 0)
-    return fail(c, "computeRadiativeTransfer: a BRDF surface cannot be used with the thermal source (its emissivity would be 1 - rho_dh(mu)).");
-  if (levels_on(c)) {  // (each is also refused where it is asked for, whichever call comes first)
-    if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
-    if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
-    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
-    if (!budget_fit(without_actinic(tally_shape(c))).globalBins) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
-    if (direct_on(c) && c->srcKind != 0) return fail(c, kDirectThermalMsg);
-  }
-  if (actinic_on(c)) {  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
-    if (c->nDir > 0) return fail(c, kActinicIntensityMsg);
-    if (orders_on(c)) return fail(c, kActinicOrdersMsg);
-    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
-    if (direct_on(c)) return fail(c, kActinicDirectMsg);
-    if (!budget_fit(tally_shape(c)).globalBins) return fail(c, kActinicBudgetMsg);
-    if (c->srcKind != 0) return fail(c, kActinicThermalMsg);
-  }
-  if (c->sideFluxes) {  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
-    if (!levels_on(c)) return fail(c, kSideNeedsLevelsMsg);
-    if (direct_on(c)) return fail(c, kSideDirectMsg);
-    if (actinic_on(c)) return fail(c, kSideActinicMsg);
-    if (!budget_fit(tally_shape(c)).globalBins) return fail(c, kSideBudgetMsg);
-    if (c->srcKind != 0) return fail(c, kSideThermalMsg);
-  }
+  REFUSE(c, asked(c), Ready);  // (each is also refused where it is asked for, whichever call comes first; the thermal source only here)
   if (sync_tables(c)) return 1;
   return sync_forward_tables(c);
 }
@@ -1298,11 +1083,9 @@ int mcbrat_set_grid(mcbrat_ctx *c, int32_t nx, int32_t ny, int32_t nz, const dou
   for (int i = 0; i < ny; ++i) if (!(ye[i + 1] > ye[i])) return fail(c, "new_Domain: y edges must be increasing, unique.");
   for (int i = 0; i < nz; ++i) if (!(ze[i + 1] > ze[i])) return fail(c, "new_Domain: z edges must be increasing, unique.");
   if ((long long)nx * ny * nz > 0x7fffffffLL / 2) return fail(c, "new_Integrator: more than 2^30 cells are not supported.");
-  TallyShape asked = tally_shape(c);
-  asked.nx = nx; asked.ny = ny; asked.nz = nz;
-  if (levels_on(c) && !budget_fit(without_actinic(asked)).globalBins) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
-  if (actinic_on(c) && !budget_fit(asked).globalBins) return fail(c, kActinicBudgetMsg);
-  if (side_on(c) && !budget_fit(asked).globalBins) return fail(c, kSideBudgetMsg);
+  Asked a = asked(c);
+  a.nx = nx; a.ny = ny; a.nz = nz;
+  REFUSE(c, a, SetGrid);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   c->nx = nx; c->ny = ny; c->nz = nz;
@@ -1541,8 +1324,9 @@ int mcbrat_get_moments(mcbrat_ctx *c, double *host) {
 
 int mcbrat_enable_counters(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
-  if (enable && levels_on(c)) return fail(c, kLevelsCountersMsg);
-  if (enable && actinic_on(c)) return fail(c, kActinicCountersMsg);
+  Asked a = asked(c);
+  a.debug = enable != 0;
+  REFUSE(c, a, SetCounters);
   c->countersOn = enable != 0;
   return 0;
 }
@@ -1587,9 +1371,9 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   if (limitIntensityContributions && !(maxIntensityContribution > 0.f))
     return fail(c, "specifyParameters: maxIntensityContribution must be > 0");
   if (zetaMin < 0.f) return fail(c, "specifyParameters: zetaMin must be >= 0.");
-  if (limitIntensityContributions && orders_on(c)) return fail(c, kOrdersLimitMsg);
-  if (nDirections > 0 && levels_on(c)) return fail(c, kLevelsIntensityMsg);
-  if (nDirections > 0 && actinic_on(c)) return fail(c, kActinicIntensityMsg);
+  Asked a = asked(c);
+  a.nDir = nDirections; a.limitContrib = limitIntensityContributions != 0;
+  REFUSE(c, a, SetIntensity);
   if (numOrdersOrigPhaseFunIntenCalcs < 0) return fail(c, "specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0");
   if (useRussianRouletteForIntensity)
     for (int i = 0; i < nDirections; ++i)
@@ -1625,15 +1409,10 @@ int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int n = numRecScatOrd < 0 ? -1 : numRecScatOrd;
-  if (n >= 0 && c->limitContrib) return fail(c, kOrdersLimitMsg);
-  if (n >= 0 && levels_on(c)) return fail(c, kLevelsOrdersMsg);
-  if (n >= 0 && actinic_on(c)) return fail(c, kActinicOrdersMsg);
-  if (n >= 0) {  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
-    TallyShape asked = tally_shape(c);
-    asked.nOrd = order_count(n);
-    if (!budget_fit(asked).orders)
-      return fail(c, "specifyParameters: numRecScatOrd is too large: the tallies of one batch by scattering order would not fit the 4 GiB tally budget.");
-  }
+  Asked a = asked(c);
+  a.numRecScatOrd = n;
+  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
+  if (n >= 0) REFUSE(c, a, SetOrders);
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (n != c->numRecScatOrd) drop_results(c, false);  // the moment arrays change length: start them afresh
@@ -1656,17 +1435,9 @@ int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int on = enable ? 1 : 0;
-  if (on) {
-    if (c->nDir > 0) return fail(c, kLevelsIntensityMsg);
-    if (orders_on(c)) return fail(c, kLevelsOrdersMsg);
-    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kLevelsBrdfMsg);
-    if (c->countersOn) return fail(c, kLevelsCountersMsg);
-    const TallyShape now = tally_shape(c);
-    if (!budget_fit(with_tallies(now, 1, 0, 0)).globalBins) return fail(c, kLevelsBudgetMsg);
-    if (c->directLevelFluxes && !budget_fit(with_tallies(now, 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
-    if (actinic_on(c) && !budget_fit(with_tallies(now, 1, 0, 1)).globalBins) return fail(c, kActinicBudgetMsg);
-  } else if (c->directLevelFluxes) return fail(c, kDirectNeedsLevelsMsg);  // (switch the direct tally off first)
-  else if (c->sideFluxes) return fail(c, kSideNeedsLevelsMsg);  // (switch the side tally off first)
+  Asked a = asked(c);
+  a.levels = on;
+  REFUSE(c, a, on ? SetLevels : LevelsOff);  // (off: switch the direct and the side tally off first)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (on != c->levelFluxes) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
@@ -1685,12 +1456,9 @@ int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int on = enable ? 1 : 0;
-  if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
-    if (!levels_on(c)) return fail(c, kDirectNeedsLevelsMsg);
-    if (actinic_on(c)) return fail(c, kActinicDirectMsg);
-    if (side_on(c)) return fail(c, kSideDirectMsg);
-    if (!budget_fit(with_tallies(tally_shape(c), 1, 1, 0)).globalBins) return fail(c, kDirectBudgetMsg);
-  }
+  Asked a = asked(c);
+  a.direct = on;
+  if (on) REFUSE(c, a, SetDirect);  // (what level fluxes are refused with is refused with them: the setting needs them)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (direct_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
@@ -1711,15 +1479,9 @@ int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int on = enable ? 1 : 0;
-  if (on) {  // (level fluxes may be on together with it; their direct tally may not: no kernel has both flags)
-    if (c->nDir > 0) return fail(c, kActinicIntensityMsg);
-    if (orders_on(c)) return fail(c, kActinicOrdersMsg);
-    if (c->surfNumX > 0 && c->surfKind != 0) return fail(c, kActinicBrdfMsg);
-    if (c->countersOn) return fail(c, kActinicCountersMsg);
-    if (direct_on(c)) return fail(c, kActinicDirectMsg);
-    if (side_on(c)) return fail(c, kSideActinicMsg);
-    if (!budget_fit(with_tallies(tally_shape(c), levels_on(c), direct_on(c), 1)).globalBins) return fail(c, kActinicBudgetMsg);
-  }
+  Asked a = asked(c);
+  a.actinic = on;
+  if (on) REFUSE(c, a, SetActinic);  // (level fluxes may be on together with it; their direct tally may not: no kernel has both flags)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (on != c->actinicFlux) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
@@ -1737,12 +1499,9 @@ int mcbrat_specify_side_fluxes(mcbrat_ctx *c, int32_t enable) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
   const int on = enable ? 1 : 0;
-  if (on) {  // (what level fluxes are refused with is refused with them: the setting needs them)
-    if (!levels_on(c)) return fail(c, kSideNeedsLevelsMsg);
-    if (direct_on(c)) return fail(c, kSideDirectMsg);
-    if (actinic_on(c)) return fail(c, kSideActinicMsg);
-    if (!budget_fit(with_tallies(tally_shape(c), 1, 0, 0, 1)).globalBins) return fail(c, kSideBudgetMsg);
-  }
+  Asked a = asked(c);
+  a.side = on;
+  if (on) REFUSE(c, a, SetSide);  // (what level fluxes are refused with is refused with them: the setting needs them)
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (side_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
@@ -1918,8 +1677,9 @@ int mcbrat_set_surface_brdf(mcbrat_ctx *c, int32_t kind, int32_t numX, int32_t n
   if (sync_all(c)) return 1;
   if (numX <= 0 || numY <= 0) { c->surfNumX = c->surfNumY = 0; c->surfKind = 0; return 0; }  // back to the domain's albedo
   if (brdf_num_params(kind) == 0 || kind == BRDF_LAMBERTIAN) return fail(c, "new_SurfaceDescription: unknown surface BRDF model.");
-  if (levels_on(c)) return fail(c, kLevelsBrdfMsg);
-  if (actinic_on(c)) return fail(c, kActinicBrdfMsg);
+  Asked a = asked(c);
+  a.brdf = true;
+  REFUSE(c, a, SetBrdf);
   if (nParams != brdf_num_params(kind)) return fail(c, "new_SurfaceDescription: Wrong number of parameters supplied for surface BRDF.");
   if (numX < 2 || numY < 2 || !xPosition || !yPosition || !params)
     return fail(c, "new_SurfaceDescription: position vector(s) are incorrect length.");
@@ -2025,8 +1785,8 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
     m = ((c->layerSkip && !facewalk_on(c)) ? 1 : 0) | (block_walk_applies(c, L) ? 2 : 0) | (L.fly ? 4 : 0) | (c->blockWalk ? 8 : 0) |
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
-    // (the 768-lane block walk of launch_block, the only one with NOSPAN instantiations)
-    if (block_walk_applies(c, L) && !L.wide && (c->blockSize == 0 || c->blockSize == 768) && nospan_kernel(c)) m |= 512;
+    // (a NOSPAN instantiation: the near-uniform flags have no say in that)
+    if (block_walk_applies(c, L) && pick_block(L, false, c->srcKind != 0, block_walk_of(c, false, false)).nospan) m |= 512;
   }
   return m;
 }
@@ -2055,16 +1815,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
   const TallyLayout lay = tally_layout(c);
   const size_t slabStride = (size_t)lay.slabStride;
-  const bool strideFits = budget_fit(tally_shape(c)).stride;
-  if (orders_on(c) && !strideFits)
-    return fail(c, "computeRadiativeTransfer: numRecScatOrd is too large: one batch's tallies by scattering order need more than the 4 GiB tally budget.");
-  if (orders_on(c) && c->countersOn)
-    return fail(c, "computeRadiativeTransfer: event counters are not available together with scattering orders.");
-  if (levels_on(c) && c->countersOn) return fail(c, kLevelsCountersMsg);
-  if (side_on(c) && !strideFits) return fail(c, kSideBudgetMsg);
-  if (levels_on(c) && !actinic_on(c) && !strideFits) return fail(c, direct_on(c) ? kDirectBudgetMsg : kLevelsBudgetMsg);
-  if (actinic_on(c) && c->countersOn) return fail(c, kActinicCountersMsg);
-  if (actinic_on(c) && !strideFits) return fail(c, kActinicBudgetMsg);
+  REFUSE(c, asked(c), Trace);
   // batches in flight: bounded by a memory budget (slabs are 8 B per tally bin per batch)
   size_t inFlight = std::max<size_t>(1, kSlabBudget / (slabStride * sizeof(long long)));
   if (c->maxBatchesInFlight > 0) inFlight = std::min<size_t>(inFlight, (size_t)c->maxBatchesInFlight);
@@ -2234,9 +1985,9 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
   if (check_ready(c)) return 1;
   if (n < 1 || !fates) return fail(c, "trace_fates: nothing to trace.");
   if (sync_all(c)) return 1;
-  if (c->nDir > 0) return fail(c, "trace_fates: not available together with intensity directions.");
-  if (levels_on(c)) return fail(c, kLevelsCountersMsg);
-  if (actinic_on(c)) return fail(c, kActinicCountersMsg);
+  Asked a = asked(c);
+  a.debug = true;
+  REFUSE(c, a, Fates);
   TallyShape fluxes = flux_run(tally_shape(c));  // the slab of the instrumented kernels: the fluxes and the volume only
   fluxes.nOrd = 0;
   const size_t slabStride = (size_t)tally_layout(fluxes).slabStride;
