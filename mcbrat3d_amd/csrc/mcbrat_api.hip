@@ -1812,7 +1812,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   } else {
     c->cur = 0;
   }
-  const size_t ncol = (size_t)c->nx * c->ny, nvox = ncol * c->nz;
+  const size_t ncol = (size_t)c->nx * c->ny;
   const TallyLayout lay = tally_layout(c);
   const size_t slabStride = (size_t)lay.slabStride;
   REFUSE(c, asked(c), Trace);
@@ -1886,46 +1886,18 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
       c->chainAfter = false; c->chainSnapshot = nullptr;
     }
     FinishParams f;
-    f.nx = c->nx; f.ny = c->ny; f.nz = c->nz; f.nBatches = nb; f.xyRegular = c->xyRegular; f.nDir = c->nDir; f.nc = c->nc; f.limitContrib = c->limitContrib;
+    f.shape = tally_shape(c); f.nBatches = nb; f.xyRegular = c->xyRegular;
     f.ppb = p.ppb; f.total = p.total; f.lay = lay;
-    f.slabs = c->L().dSlabs; f.relArea = c->dRelArea; f.ze = c->dEdges + (c->nx + 1) + (c->ny + 1);
+    f.parts = finish_parts(f.shape, nb);
+    f.slabs = c->L().dSlabs; f.relArea = c->dRelArea;
+    f.xe = c->dEdges; f.ye = c->dEdges + (c->nx + 1); f.ze = c->dEdges + (c->nx + 1) + (c->ny + 1);
     f.colVals = c->L().dColVals; f.scalVals = c->L().dScalVals; f.moments = c->dMoments; f.last = c->dLast;
     f.bad = c->dBad; f.badHost = c->hBadDev;
-    f.gatherColumns = (unsigned)((ncol * (size_t)nb + kFinishBlock - 1) / kFinishBlock);
-    f.gatherVolume = (unsigned)((nvox + kVolVox - 1) / kVolVox);
-    f.gatherReduce = (unsigned)(3 + c->nz) * (unsigned)nb;
-    f.gatherIntensity = (unsigned)((ncol * (size_t)c->nDir + kFinishBlock - 1) / kFinishBlock);
-    f.foldColumns = (unsigned)((3 * ncol + kFinishBlock - 1) / kFinishBlock);
-    f.foldScalars = (unsigned)((3 + c->nz + kFinishBlock - 1) / kFinishBlock);
-    f.nOrd = orders_on(c) ? c->numRecScatOrd + 1 : 0;
-    f.ordVals = f.scalVals + (size_t)lay.scalOrders * nb;
-    f.gatherOrders = (unsigned)(((size_t)(2 + c->nDir) * ncol * f.nOrd + kFinishBlock - 1) / kFinishBlock);
-    f.gatherOrderMeans = (unsigned)((2 + c->nDir) * f.nOrd) * (unsigned)nb;
-    f.foldOrderMeans = (unsigned)(((2 + c->nDir) * f.nOrd + kFinishBlock - 1) / kFinishBlock);
-    f.nLvl = levels_on(c) ? c->nz + 1 : 0;
-    f.lvlVals = f.scalVals + (size_t)lay.scalLevels * nb;
-    f.lvlDirect = direct_on(c) ? 1 : 0;
-    const size_t nLvlQ = levels_on(c) ? (direct_on(c) ? 4 : 2) : 0;  // (up, down; with the direct tally direct and diffuse too)
-    f.gatherLevels = (unsigned)((nLvlQ * ncol * (size_t)f.nLvl + kFinishBlock - 1) / kFinishBlock);
-    f.gatherLevelMeans = (unsigned)(nLvlQ * f.nLvl) * (unsigned)nb;
-    f.foldLevelMeans = (unsigned)((nLvlQ * f.nLvl + kFinishBlock - 1) / kFinishBlock);
-    f.act = actinic_on(c) ? 1 : 0;
     f.actUnit = actinic_unit(c);
-    f.actVals = f.scalVals + (size_t)lay.scalActinic * nb;
-    f.gatherActinic = f.act ? (unsigned)((nvox + kVolVox - 1) / kVolVox) : 0u;
-    f.gatherActinicMeans = f.act ? (unsigned)c->nz * (unsigned)nb : 0u;
-    f.foldActinicMeans = f.act ? (unsigned)((c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
-    f.side = side_on(c) ? 1 : 0;
-    f.xe = c->dEdges; f.ye = c->dEdges + (c->nx + 1);
-    f.sideVals = f.scalVals + (size_t)lay.scalSide * nb;
-    f.gatherSide = f.side ? (unsigned)((4 * nvox + kVolVox - 1) / kVolVox) : 0u;
-    f.gatherSideMeans = f.side ? 4u * (unsigned)c->nz * (unsigned)nb : 0u;
-    f.foldSideMeans = f.side ? (unsigned)((4 * c->nz + kFinishBlock - 1) / kFinishBlock) : 0u;
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_gather, dim3(f.gatherColumns + f.gatherVolume + f.gatherReduce + f.gatherIntensity + f.gatherOrders + f.gatherOrderMeans + f.gatherLevels + f.gatherLevelMeans + f.gatherActinic + f.gatherActinicMeans + f.gatherSide + f.gatherSideMeans),
-                       dim3(kFinishBlock), 0, c->L().stream, f);
-    hipLaunchKernelGGL(finish_fold, dim3(f.foldColumns + f.foldScalars + f.foldOrderMeans + f.foldLevelMeans + f.foldActinicMeans + f.foldSideMeans), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
+    hipLaunchKernelGGL(finish_gather, dim3(f.parts.gatherGrid()), dim3(kFinishBlock), 0, c->L().stream, f);
+    hipLaunchKernelGGL(finish_fold, dim3(f.parts.foldGrid()), dim3(kFinishBlock), 0, c->L().stream, f);  // (also hands the dropped-photon count to the host)
     HIP_OK(c, hipGetLastError());
     HIP_OK(c, hipEventRecord(c->L().evDone, c->L().stream));
     c->lastDone = c->L().evDone;

@@ -110,4 +110,67 @@ inline TallyFit tally_fit(const TallyShape &s, uint64_t budgetBytes) {
   return TallyFit{fits(l.slabOrders, l.slabLds), fits(l.slabLds, l.slabStride), fits(0, l.slabStride)};
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The parts of the two finish kernels (mcbrat_kernels.hip), in the order their workgroups are dealt out -- the order decides which
+// workgroups start first.  finish_parts() is the one statement of that order and of every part's size: the host sizes both launches by
+// it, FinishParams carries its result, and both kernels find a workgroup's part by walking the same arrays.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int kFinishBlock = 256;                                                  // lanes of a finish workgroup
+constexpr int kVolVox = 32, kVolGroups = kFinishBlock / kVolVox, kVolChunk = 64;  // the cell fold: bins / batch groups per workgroup, batches per pass
+
+enum GatherPart { kGatherColumns, kGatherVolume, kGatherReduce, kGatherIntensity, kGatherOrders, kGatherOrderMeans, kGatherLevels,
+                  kGatherLevelMeans, kGatherActinic, kGatherActinicMeans, kGatherSide, kGatherSideMeans, kGatherParts };
+enum FoldPart { kFoldColumns, kFoldScalars, kFoldOrderMeans, kFoldLevelMeans, kFoldActinicMeans, kFoldSideMeans, kFoldParts };
+
+// The means per batch of every tally with a scratch behind scalVals (0 when the tally is off), and the level quantities
+// (up, down; with the direct tally direct and diffuse too).
+constexpr int64_t level_quantities(const TallyShape &s) { return s.levels ? (s.direct ? 4 : 2) : 0; }
+constexpr int64_t order_means(const TallyShape &s) { return (2 + (int64_t)s.nDir) * s.nOrd; }
+constexpr int64_t level_means(const TallyShape &s) { return level_quantities(s) * ((int64_t)s.nz + 1); }
+constexpr int64_t actinic_means(const TallyShape &s) { return s.actinic ? (int64_t)s.nz : 0; }
+constexpr int64_t side_means(const TallyShape &s) { return s.side ? 4 * (int64_t)s.nz : 0; }
+
+// Where every part's workgroups end in its launch: the running sums of the parts' workgroup counts, in the enums' order.
+struct FinishParts {
+  uint32_t gatherEnd[kGatherParts], foldEnd[kFoldParts];
+  constexpr uint32_t gatherGrid() const { return gatherEnd[kGatherParts - 1]; }  // the launches' grid sizes
+  constexpr uint32_t foldGrid() const { return foldEnd[kFoldParts - 1]; }
+  constexpr uint32_t gather(int part) const { return gatherEnd[part] - (part > 0 ? gatherEnd[part - 1] : 0); }  // a part's workgroups
+  constexpr uint32_t fold(int part) const { return foldEnd[part] - (part > 0 ? foldEnd[part - 1] : 0); }
+};
+
+// nb: the batches of the launch round.  Three sizes of part: one thread per element (a bin, or a mean to fold), one workgroup per
+// (batch, mean), kVolVox cells per workgroup.
+inline FinishParts finish_parts(const TallyShape &s, int nb) {
+  const auto threads = [](int64_t n) { return (uint32_t)((n + kFinishBlock - 1) / kFinishBlock); };
+  const auto cells = [](int64_t n) { return (uint32_t)((n + kVolVox - 1) / kVolVox); };
+  const auto perBatch = [nb](int64_t nMeans) { return (uint32_t)(nMeans * nb); };
+  const int64_t ncol = (int64_t)s.nx * s.ny, nvox = ncol * s.nz;
+  uint32_t gather[kGatherParts], fold[kFoldParts];
+  gather[kGatherColumns] = threads(ncol * nb);
+  gather[kGatherVolume] = cells(nvox);
+  gather[kGatherReduce] = perBatch(3 + s.nz);
+  gather[kGatherIntensity] = threads(ncol * s.nDir);
+  gather[kGatherOrders] = threads(order_means(s) * ncol);
+  gather[kGatherOrderMeans] = perBatch(order_means(s));
+  gather[kGatherLevels] = threads(level_means(s) * ncol);
+  gather[kGatherLevelMeans] = perBatch(level_means(s));
+  gather[kGatherActinic] = s.actinic ? cells(nvox) : 0;
+  gather[kGatherActinicMeans] = perBatch(actinic_means(s));
+  gather[kGatherSide] = s.side ? cells(4 * nvox) : 0;
+  gather[kGatherSideMeans] = perBatch(side_means(s));
+  fold[kFoldColumns] = threads(3 * ncol);
+  fold[kFoldScalars] = threads(3 + s.nz);
+  fold[kFoldOrderMeans] = threads(order_means(s));
+  fold[kFoldLevelMeans] = threads(level_means(s));
+  fold[kFoldActinicMeans] = threads(actinic_means(s));
+  fold[kFoldSideMeans] = threads(side_means(s));
+  FinishParts p{};
+  uint32_t at = 0;
+  for (int i = 0; i < kGatherParts; ++i) p.gatherEnd[i] = at += gather[i];
+  at = 0;
+  for (int i = 0; i < kFoldParts; ++i) p.foldEnd[i] = at += fold[i];
+  return p;
+}
+
 }  // namespace mcbrat

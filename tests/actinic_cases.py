@@ -15,8 +15,8 @@ CALLS = ((8000, 2), (4000, 1))  # 20 000 photons in 3 batches: two of 8000 in on
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the fixed point (mcbrat_api.hip: actinic_unit) and the epilogue (mcbrat_kernels.hip: gather_actinic, gather_actinic_means,
-# fold_actinic_means) written out
+# the fixed point (mcbrat_api.hip: actinic_unit) and the epilogue (mcbrat_kernels.hip: the actinic parts -- cell_fold with
+# actinic_value, their batch_mean and mean_fold) written out
 # ---------------------------------------------------------------------------------------------------------------------
 def actinic_unit(xe, ye, ze):
     """2^e km: e the smallest integer with (diagonal of the largest spacings of the three axes) (1 + 2^-10) < 2^e."""

@@ -51,7 +51,7 @@ def slab_len(ncol, nz, nDir, nOrd):
 
 
 def tree_mean(values):
-    """gather_reduce / gather_order_means: lane t sums values[t], values[t + 256], ... in float; a fixed tree of 256 lanes
+    """batch_mean and its tree_sum (the flux means, the profile, every tally's means): lane t sums values[t], values[t + 256], ... in float; a fixed tree of 256 lanes
     (red[t] += red[t + o], o = 128 .. 1); red[0] / (float)ncol.  `values`: [..., ncol] float32, reduced over the last axis."""
     v = np.asarray(values, F32)
     ncol = v.shape[-1]
@@ -166,18 +166,18 @@ def epilogue(g, slabs, ppb, round_size, moments=None, last=None):
         per = [batch_values(g, slabs[b0 + b], ns[b]) for b in range(nb)]
         parts = []
         # (moment offset, values [nb, len]) of every part, each folded in batch order
-        parts.append((0, np.stack([p[1][:3] for p in per])))                          # domain means (fold_scalars)
-        parts.append((3, np.stack([p[0].reshape(-1) for p in per])))                  # column fluxes (fold_columns)
+        parts.append((0, np.stack([p[1][:3] for p in per])))                          # domain means (mean_fold: kFoldScalars)
+        parts.append((3, np.stack([p[0].reshape(-1) for p in per])))                  # column fluxes (mean_fold: kFoldColumns)
         parts.append((3 + 3 * ncol, np.stack([p[1][3:] for p in per])))               # absorption profile
-        parts.append((3 + 3 * ncol + nz, np.stack([p[2] for p in per])))               # volume (gather_volume)
+        parts.append((3 + 3 * ncol + nz, np.stack([p[2] for p in per])))               # volume (cell_fold, volume_value)
         if g.nDir:
-            parts.append((3 + 3 * ncol + nz + nvox, np.stack([p[3] for p in per])))   # intensity (gather_intensity)
+            parts.append((3 + 3 * ncol + nz + nvox, np.stack([p[3] for p in per])))   # intensity (bin_fold)
         if g.nOrd:
             no, nd = g.nOrd, g.nDir
             om = np.stack([p[5] for p in per])
             ob = np.stack([p[4] for p in per])
             parts.append((g.base, om[:, :2 * no]))                                     # meanUp/Down by order
-            parts.append((g.base + 2 * no, ob[:, :2 * ncol * no]))                     # up/down by order (gather_orders)
+            parts.append((g.base + 2 * no, ob[:, :2 * ncol * no]))                     # up/down by order (bin_fold)
             if nd:
                 parts.append((g.base + 2 * no + 2 * ncol * no, om[:, 2 * no:]))        # meanIntensity by order
                 parts.append((g.base + 2 * no + 2 * ncol * no + nd * no, ob[:, 2 * ncol * no:]))

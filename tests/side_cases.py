@@ -20,7 +20,7 @@ DELTA = 64.0 * 2.0 ** -23       # times the km travelled: the margin by which a 
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the epilogue (mcbrat_kernels.hip: gather_side, gather_side_means, fold_side_means) written out
+# the epilogue (mcbrat_kernels.hip: the side parts -- cell_fold<4> with side_value, their batch_mean and mean_fold) written out
 # ---------------------------------------------------------------------------------------------------------------------
 def side_extents(g):
     """[4, ncol] double: the cell's extent along the crossed axis -- dx of the column for the x parts, dy for the y parts."""

@@ -1,21 +1,41 @@
 // Prints the tally layout (mcbrat3d_amd/csrc/mcbrat_layout.h) of the shapes given on the command line, one line per shape:
 //   tally_layout_dump BUDGET_BYTES nx,ny,nz,nc,nDir,limitContrib,nOrd,levels,direct,actinic ...
+// or, with the word `parts`, the workgroups of every part of the finish kernels (finish_parts) in a launch round of NB batches:
+//   tally_layout_dump parts NB nx,ny,nz,nc,nDir,limitContrib,nOrd,levels,direct,actinic,side ...
 // Built and read by tests/test_tally_layout_host.py, once plainly and once with the sanitizers for the shapes that would overflow.
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../mcbrat3d_amd/csrc/mcbrat_layout.h"
 
 int main(int argc, char **argv) {
   using namespace mcbrat;
   if (argc < 3) return 2;
-  const uint64_t budget = strtoull(argv[1], nullptr, 10);
-  for (int a = 2; a < argc; ++a) {
-    int32_t v[10];
-    if (sscanf(argv[a], "%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32,
-               &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9]) != 10) return 2;
-    const TallyShape s{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
+  const bool parts = strcmp(argv[1], "parts") == 0;
+  if (parts && argc < 4) return 2;
+  const uint64_t budget = parts ? 0 : strtoull(argv[1], nullptr, 10);
+  const int nb = parts ? atoi(argv[2]) : 0;
+  for (int a = parts ? 3 : 2; a < argc; ++a) {
+    int32_t v[11] = {};
+    if (sscanf(argv[a], "%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32 ",%" SCNd32,
+               &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) != (parts ? 11 : 10)) return 2;
+    TallyShape s{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
+    s.side = v[10];
+    if (parts) {
+      const FinishParts p = finish_parts(s, nb);
+#define GATHER(name) printf("gather" #name "=%" PRIu32 " ", p.gather(kGather##name))
+#define FOLD(name) printf("fold" #name "=%" PRIu32 " ", p.fold(kFold##name))
+      GATHER(Columns); GATHER(Volume); GATHER(Reduce); GATHER(Intensity); GATHER(Orders); GATHER(OrderMeans); GATHER(Levels);
+      GATHER(LevelMeans); GATHER(Actinic); GATHER(ActinicMeans); GATHER(Side); GATHER(SideMeans);
+      FOLD(Columns); FOLD(Scalars); FOLD(OrderMeans); FOLD(LevelMeans); FOLD(ActinicMeans); FOLD(SideMeans);
+#undef GATHER
+#undef FOLD
+      // (in order, as the kernels walk them: the position of every part in the list)
+      printf("gatherParts=%d foldParts=%d gatherGrid=%" PRIu32 " foldGrid=%" PRIu32 "\n", (int)kGatherParts, (int)kFoldParts, p.gatherGrid(), p.foldGrid());
+      continue;
+    }
     const TallyLayout l = tally_layout(s);
     const TallyFit fit = tally_fit(s, budget);
 #define FIELD(name) printf(#name "=%" PRId64 " ", l.name)

@@ -54,7 +54,7 @@ def literal_epilogue(g, slabs, ppb, round_size, mom=None, last=None):
         total = ppb * nb
         ns = [min(total - b * ppb, ppb) for b in range(nb)]
         sl = [slabs[b0 + b] for b in range(nb)]
-        # gather_columns, then fold_columns
+        # the columns part, then its mean_fold
         for q in range(3):
             for col in range(ncol):
                 xs = []
@@ -62,11 +62,11 @@ def literal_epilogue(g, slabs, ppb, round_size, mom=None, last=None):
                     raw = sl[b][q * ncol + col] if q < 2 else sum(int(sl[b][2 * ncol + col + ncol * k]) for k in range(nz))
                     xs.append(cv(raw, nppc_of(col, ns[b])))
                 fold(xs, ns, 3 + q * ncol + col)
-        # gather_volume
+        # the volume part (cell_fold, volume_value)
         for v in range(nvox):
             col, k = v % ncol, v // ncol
             fold([volv(sl[b][2 * ncol + v], nppc_of(col, ns[b]), k) for b in range(nb)], ns, 3 + 3 * ncol + nz + v)
-        # gather_reduce, then fold_scalars
+        # the flux means and the profile (batch_mean), then the scalars' mean_fold
         for q in range(3 + nz):
             xs = []
             for b in range(nb):
@@ -79,16 +79,16 @@ def literal_epilogue(g, slabs, ppb, round_size, mom=None, last=None):
                         return volv(sl[b][2 * ncol + ncol * k + c], nppc_of(c, ns[b]), k)
                 xs.append(tree(val))
             fold(xs, ns, q if q < 3 else 3 + 3 * ncol + (q - 3))
-        # gather_intensity
+        # the intensity part (bin_fold)
         for v in range(ncol * nDir):
             col = v % ncol
             fold([cv(sl[b][2 * ncol + nvox + v], nppc_of(col, ns[b])) for b in range(nb)], ns, 3 + 3 * ncol + nz + nvox + v)
-        # gather_orders
+        # the order bins (bin_fold)
         for e in range((2 + nDir) * ncol * nOrd):
             col = e % ncol
             off = base + 2 * nOrd + (e if e < 2 * ncol * nOrd else e + nDir * nOrd)
             fold([cv(sl[b][S + e], nppc_of(col, ns[b])) for b in range(nb)], ns, off)
-        # gather_order_means, then fold_order_means
+        # the order means (batch_mean), then their mean_fold
         for m in range((2 + nDir) * nOrd):
             xs = [tree(lambda c, b=b: cv(sl[b][S + ncol * m + c], nppc_of(c, ns[b]))) for b in range(nb)]
             fold(xs, ns, base + (m if m < 2 * nOrd else 2 * nOrd + 2 * ncol * nOrd + (m - 2 * nOrd)))

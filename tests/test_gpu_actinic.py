@@ -305,7 +305,7 @@ def test_the_epilogue_bit_for_bit(M, grid):
     """The library does not hand out a batch's slab with the setting on (photon fates are refused with it), so the raw bins
     come by construction: in a vacuum under an overhead sun every photon adds ONE known integer to each cell of its column
     (tests/actinic_cases.py: overhead_deposits writes the leg's float arithmetic out), and the photons per column are
-    fluxDown's whole numbers.  From these bins the expressions of gather_actinic, gather_actinic_means and fold_actinic_means,
+    fluxDown's whole numbers.  From these bins the expressions of the actinic parts of the finish kernels (cell_fold, batch_mean, mean_fold),
     written out in tests/actinic_cases.py, give actinicFlux, meanActinicFlux, both moment sums and the last-batch values --
     compared bit for bit."""
     case = AC.vacuum_on(grid)

@@ -11,7 +11,8 @@ tests/epilogue_mirror.py, with no tolerance anywhere.
 2. Fold consistency for what fates cannot rebuild (radiance, fractional albedos, reflecting and per-patch surfaces,
    limitIntensityContributions, thermal emission): one call of nb batches must equal the fold of nb one-batch calls at the
    matching firstPhotonId, launch rounds mirrored; every one-batch call's domain means are the mirror's float tree over
-   that batch's column values.
+   that batch's column values.  The level, direct / diffuse, actinic and side tails (DESIGN.md sections 4.12 to 4.15) are held
+   the same way on the face-by-face plans: each tail is [means | bins], and a batch's means are the float tree over its bins.
 3. The tally capacity: 2^31 - 1 photons into one bin give exactly 1.0; 2^31 is refused."""
 import numpy as np
 import pytest
@@ -92,6 +93,8 @@ def _parts(g):
         no = g.nOrd
         out += [("meanByOrd", g.base, 2 * no), ("upDownByOrd", g.base + 2 * no, 2 * ncol * no),
                 ("intensityByOrd", g.base + 2 * no + 2 * ncol * no, g.nDir * no * (1 + ncol))]
+    for name, s, rows in getattr(g, "tails", ()):
+        out += [(name + " means", s, rows), (name + " bins", s + rows, rows * ncol)]
     return out
 
 
@@ -204,6 +207,26 @@ def test_moments_from_fates_bitwise(M, cid, dims, ppb, nb, k, calls, first, tuni
 
 
 # ---- 2. fold consistency: what fates cannot rebuild ----------------------------------------------------------------------
+# The tallies of the face-by-face plans, in the only combinations the refusal rules (mcbrat_variants.h) allow that between them reach
+# every level, actinic and side part of the epilogue.
+FACE_KINDS = {"levels-direct": dict(recLevelFluxes=True, recDirectLevelFluxes=True),
+              "levels-side": dict(recLevelFluxes=True, recSideFluxes=True),
+              "levels-actinic": dict(recLevelFluxes=True, recActinicFlux=True)}
+
+
+def _tails(g, kw):
+    """-> ([(name, start, rows)], end) of the moment tails behind the mirror's parts, each [means rows | bins rows ncol] in the
+    order of mcbrat_layout.h: levels (up, down by level), direct (direct, diffuse by level), actinic (by layer), side (four parts
+    by layer)."""
+    rows = [(name, n) for name, key, n in (("levels", "recLevelFluxes", 2 * (g.nz + 1)), ("direct", "recDirectLevelFluxes", 2 * (g.nz + 1)),
+                                           ("actinic", "recActinicFlux", g.nz), ("side", "recSideFluxes", 4 * g.nz)) if kw.get(key)]
+    out, at = [], g.base
+    for name, n in rows:
+        out.append((name, at, n))
+        at += n * (1 + g.ncol)
+    return out, at
+
+
 def _fold_case(kind):
     """(case, specifyParameters keywords, source) of a domain the fates cannot rebuild."""
     if kind == "thermal":
@@ -216,6 +239,8 @@ def _fold_case(kind):
     comp["legendre"] = [cases.hg_legendre(0.85, 32)]
     case["albedo"] = 0.3                                        # a reflecting surface
     mus, phis = [1.0, 0.5, -0.3], [0.0, 45.0, 200.0]
+    if kind in FACE_KINDS:
+        return case, dict(FACE_KINDS[kind]), "solar"
     if kind == "radiance":
         return case, dict(intensityMus=mus[:2], intensityPhis=phis[:2], computeIntensity=True, minForwardTableSize=2001), "solar"
     if kind == "limit":
@@ -251,12 +276,21 @@ def _fold_integrator(M, kind, k):
     integ.setTuning(maxBatchesInFlight=k)
     nDir = integ.numIntensityDirections()
     g = _grid(case, nDir, integ.numRecScatOrd + 1 if integ.numRecScatOrd >= 0 else 0)
+    if kind in FACE_KINDS:  # the moments' length from the library: the mirror knows nothing of these tails
+        integ.prepare(dom, photons)  # (the plan is that of the loaded domain)
+        walk = integ.walkMode()
+        assert not walk["blockWalk"] and not walk["layerSkip"] and not walk["widePlan"], walk
+        g.tails, end = _tails(g, kw)
+        g.M = (len(integ.moments()) - 8) // 2
+        assert g.M == end and (g.ncol, g.nvox) == (260, 1560) and {t[0] for t in g.tails} == set(kind.split("-"))
     return integ, dom, photons, g
 
 
 # kind, nb, maxBatchesInFlight
 FOLD_CASES = [("radiance", 65, 3), ("radiance", 1, 64), ("limit", 129, 64), ("limit", 64, 1), ("orders-patches", 65, 64),
-              ("orders-patches", 63, 3), ("orders-ncol300", 64, 3), ("thermal", 65, 64), ("thermal", 129, 1)]
+              ("orders-patches", 63, 3), ("orders-ncol300", 64, 3), ("thermal", 65, 64), ("thermal", 129, 1),
+              ("levels-direct", 65, 3), ("levels-direct", 129, 64), ("levels-side", 65, 64), ("levels-side", 63, 3),
+              ("levels-actinic", 129, 1), ("levels-actinic", 64, 64)]
 
 
 @pytest.mark.timeout(300, method="thread")
@@ -292,9 +326,13 @@ def test_call_equals_fold_of_one_batch_calls(M, kind, nb, k):
                     o = base + 2 * no + 2 * ncol * no
                     ibins = x[o + g.nDir * no:o + g.nDir * no + g.nDir * no * ncol].reshape(g.nDir * no, ncol)
                     assert np.array_equal(x[o:o + g.nDir * no], E.tree_mean(ibins)), (kind, b)
+            for name, s, rows in getattr(g, "tails", ()):  # ... and every tail's means, over that batch's bins of the tail
+                assert np.array_equal(x[s:s + rows], E.tree_mean(x[s + rows:s + rows * (1 + ncol)].reshape(rows, ncol))), (kind, b, name)
             if b == nb - 1:
                 res = integ.reportResults()
                 _check_report(g, res, x)
+        for name, s, rows in getattr(g, "tails", ()):  # (the tails are not degenerate: most means are fed -- the diffuse light from above the top is not)
+            assert np.count_nonzero(vals[:, s:s + rows].max(axis=0) > 0) >= rows - 1, (kind, name)
         integ.resetMoments()
         rng = new_RandomNumberSequence(SEED, first)
         assert integ.computeRadiativeTransfer(dom, rng, photons, ppb, nb) == ppb * nb

@@ -4,7 +4,8 @@ tests/tally_layout_dump.cpp, which includes nothing but that header, is compiled
 of every shape asked for.  Every field is compared with the formulas the library and the finish kernels had before the header --
 written out below in Python, function by function under the names they had -- never with anything the header computes.  Then the
 consumers of the documented layout (driver.unpack_moments, tests/epilogue_mirror.py), the slab starts trace_kernel computes for
-itself, and the shapes whose products would overflow (with the sanitizers: a stand-alone program, nothing is loaded into Python)."""
+itself, the parts of the finish kernels (finish_parts: their order, their workgroups, the two grid sizes) against the lines the host
+had, and the shapes whose products would overflow (with the sanitizers: a stand-alone program, nothing is loaded into Python)."""
 import itertools
 import os
 import shutil
@@ -62,9 +63,10 @@ def exe(tmp_path_factory):
 # the formulas of the commit before the header, under their old names
 # ---------------------------------------------------------------------------------------------------------------------------------
 class Parent:
-    def __init__(self, nx, ny, nz, nc, nDir, limitContrib, numRecScatOrd, levelFluxes, directLevelFluxes, actinicFlux):
+    def __init__(self, nx, ny, nz, nc, nDir, limitContrib, numRecScatOrd, levelFluxes, directLevelFluxes, actinicFlux, sideFluxes=0):
         self.nx, self.ny, self.nz, self.nc, self.nDir, self.limitContrib = nx, ny, nz, nc, nDir, limitContrib
         self.numRecScatOrd, self.levelFluxes, self.directLevelFluxes, self.actinicFlux = numRecScatOrd, levelFluxes, directLevelFluxes, actinicFlux
+        self.sideFluxes = sideFluxes
         self.ncol = nx * ny
 
     # mcbrat_api.hip
@@ -114,6 +116,34 @@ class Parent:
     def actSlab(self): return self.slab_stride() - self.actinic_bins()
     def slabLds(self): return self.slab_stride() - self.global_bins()  # plan_launch
 
+    # mcbrat_compute_radiative_transfer: the workgroups of every part of finish_gather and finish_fold in a launch round of nb
+    # batches, as the lines f.gatherColumns = ... f.foldSideMeans = filled them before finish_parts() (kFinishBlock = 256 lanes,
+    # kVolVox = 32 cells per workgroup), in the order of the two dispatch chains the kernels had
+    def side_on(self): return self.levelFluxes != 0 and self.sideFluxes != 0
+
+    def finish_counts(self, nb):
+        ncol, nvox, nz, nDir = self.ncol, self.ncol * self.nz, self.nz, self.nDir
+        nOrd, nLvl, nLvlQ, act, side = self.nOrd(), self.nLvl(), self.level_quantities(), self.actinic_on(), self.side_on()
+        gather = [("gatherColumns", (ncol * nb + 256 - 1) // 256),
+                  ("gatherVolume", (nvox + 32 - 1) // 32),
+                  ("gatherReduce", (3 + nz) * nb),
+                  ("gatherIntensity", (ncol * nDir + 256 - 1) // 256),
+                  ("gatherOrders", ((2 + nDir) * ncol * nOrd + 256 - 1) // 256),
+                  ("gatherOrderMeans", (2 + nDir) * nOrd * nb),
+                  ("gatherLevels", (nLvlQ * ncol * nLvl + 256 - 1) // 256),
+                  ("gatherLevelMeans", nLvlQ * nLvl * nb),
+                  ("gatherActinic", (nvox + 32 - 1) // 32 if act else 0),
+                  ("gatherActinicMeans", nz * nb if act else 0),
+                  ("gatherSide", (4 * nvox + 32 - 1) // 32 if side else 0),
+                  ("gatherSideMeans", 4 * nz * nb if side else 0)]
+        fold = [("foldColumns", (3 * ncol + 256 - 1) // 256),
+                ("foldScalars", (3 + nz + 256 - 1) // 256),
+                ("foldOrderMeans", ((2 + nDir) * nOrd + 256 - 1) // 256),
+                ("foldLevelMeans", (nLvlQ * nLvl + 256 - 1) // 256),
+                ("foldActinicMeans", (nz + 256 - 1) // 256 if act else 0),
+                ("foldSideMeans", (4 * nz + 256 - 1) // 256 if side else 0)]
+        return gather, fold
+
     # mcbrat_kernels.hip, the finish kernels (from FinishParams: nOrd, nLvl as above, lvlDirect = direct_on, act = actinic_on)
     def k_moments_base(self): return 3 + 3 * self.ncol + self.nz + self.ncol * self.nz + self.nDir * self.ncol
 
@@ -125,7 +155,7 @@ class Parent:
     def k_moments_levels(self): return self.k_moments_base() + self.nOrd() * (2 + self.nDir) * (1 + self.nx * self.ny)
     def k_moments_direct(self): return self.k_moments_levels() + 2 * self.nLvl() * (1 + self.nx * self.ny)
     def k_slab_orders(self): return 2 * self.ncol + self.ncol * self.nz + self.nDir * self.ncol
-    def k_slab_intensity(self): return 2 * self.ncol + self.ncol * self.nz  # gather_intensity, finish_excess
+    def k_slab_intensity(self): return 2 * self.ncol + self.ncol * self.nz  # the intensity part, finish_excess
     def k_slab_by_component(self): return self.k_slab_intensity() + (1 + 0) * self.nDir * self.ncol  # finish_excess: byc of j = 0, d = 0
     def k_slab_excess(self): return self.k_slab_intensity() + (self.nc + 2) * self.nDir * self.ncol
 
@@ -149,7 +179,7 @@ def test_every_field_is_what_the_old_formulas_give(exe):
         p = Parent(*s)
         ncol, nvox = p.ncol, p.ncol * p.nz
         # the slab
-        assert (d["slabFluxUp"], d["slabFluxDown"], d["slabVolume"]) == (0, ncol, 2 * ncol), s  # (column_value, gather_volume)
+        assert (d["slabFluxUp"], d["slabFluxDown"], d["slabVolume"]) == (0, ncol, 2 * ncol), s  # (column_value, the volume part)
         assert d["slabIntensity"] == p.k_slab_intensity() == 2 * ncol + nvox, s
         assert d["slabStride"] == p.slab_stride() and d["fluxRunStride"] == p.slab_stride(True), s
         assert d["slabLds"] == p.slabLds() and d["slabLevels"] == p.lvlSlab() and d["slabActinic"] == p.actSlab(), s
@@ -165,7 +195,7 @@ def test_every_field_is_what_the_old_formulas_give(exe):
         assert d["slabOrders"] + p.nOrd() * (2 + p.nDir) * ncol == p.lvlSlab(), s
         # the moments
         assert (d["momMeans"], d["momColumns"], d["momProfile"], d["momVolume"]) == (0, 3, 3 + 3 * ncol, 3 + 3 * ncol + p.nz), s
-        assert d["momIntensity"] == 3 + 3 * ncol + p.nz + nvox, s  # (mcbrat_report_intensity, gather_intensity)
+        assert d["momIntensity"] == 3 + 3 * ncol + p.nz + nvox, s  # (mcbrat_report_intensity, the intensity part)
         assert d["momOrders"] == p.k_moments_base(), s
         assert d["momentsLen"] == p.moments_len() == p.k_moments_total(), s
         assert d["momLevels"] == p.moments_levels_at() == p.k_moments_levels(), s
@@ -216,6 +246,57 @@ def test_the_fit_answers_are_the_old_ones(exe):
     assert [d["fitOrders"] for d in near[6:]] == [1, 0, 1, 0]         # (2^24 columns x 4 x 8 orders, x 2 x 16: exactly 4 GiB)
 
 
+def _parts(exe, shapes, nb):
+    """-> per shape (11 values, the last one side) the words of finish_parts() in a launch round of nb batches: [(name, count)] in
+    the order printed -- the order of the enums -- and the dict of them"""
+    args = [",".join(str(v) for v in (s[:6] + (max(s[6] + 1, 0),) + s[7:])) for s in shapes]
+    text = subprocess.run([exe, "parts", str(nb)] + args, check=True, capture_output=True, text=True, timeout=60).stdout
+    lines = text.strip().split("\n")
+    assert len(lines) == len(shapes)
+    return [[(k, int(v)) for k, v in (w.split("=") for w in line.split())] for line in lines]
+
+
+ROUNDS = (1, 3, 64, 65)
+# a wider domain beside the small one: more than one workgroup in every thread-per-element and cell part
+PART_DIMS = ((NX, NY, NZ), (37, 29, 11))
+
+
+def _part_shapes():
+    for nx, ny, nz in PART_DIMS:
+        for s in SHAPES:
+            for side in (0, 1):
+                yield (nx, ny, nz) + s[3:] + (side,)
+
+
+def _check_parts(exe):
+    shapes = list(_part_shapes())
+    assert len(shapes) == 2 * 2 * len(SHAPES)
+    on = set()
+    for nb in ROUNDS:
+        for s, words in zip(shapes, _parts(exe, [s[:10] + (int(bool(s[7] and s[10])),) for s in shapes], nb)):  # (side as tally_shape hands it over)
+            p = Parent(*s)
+            gather, fold = p.finish_counts(nb)
+            d = dict(words)
+            # every count is the old formula's, and the printed order -- the enums', which both kernels walk -- is the old chains'
+            assert words[:len(gather) + len(fold)] == gather + fold, (s, nb)
+            assert (d["gatherParts"], d["foldParts"]) == (len(gather), len(fold)) == (12, 6)
+            # each grid is the sum of its parts (the two launch lines)
+            assert d["gatherGrid"] == sum(n for _, n in gather) and d["foldGrid"] == sum(n for _, n in fold), (s, nb)
+            # a part that is off has no workgroup, one that is on has some
+            for names, live in ((("gatherIntensity",), p.nDir > 0), (("gatherOrders", "gatherOrderMeans", "foldOrderMeans"), p.orders_on()),
+                                (("gatherLevels", "gatherLevelMeans", "foldLevelMeans"), p.levels_on()),
+                                (("gatherActinic", "gatherActinicMeans", "foldActinicMeans"), p.actinic_on()),
+                                (("gatherSide", "gatherSideMeans", "foldSideMeans"), p.side_on())):
+                assert all((d[n] > 0) == live for n in names), (s, nb, names)
+                on.update(n for n in names if live)
+            assert all(d[n] > 0 for n in ("gatherColumns", "gatherVolume", "gatherReduce", "foldColumns", "foldScalars"))
+    assert len(on) == 13  # (every optional part was on somewhere)
+
+
+def test_the_finish_parts_are_what_the_old_host_lines_give(exe):
+    _check_parts(exe)
+
+
 def test_the_consumers_place_every_part_where_the_header_does(exe):
     from mcbrat3d_amd import driver
     from tests import epilogue_mirror as EM
@@ -258,3 +339,5 @@ def test_shapes_that_would_overflow_do_not_fit_and_do_not_overflow(tmp_path):
     # (and the sanitized program agrees with the plain one where nothing is near overflowing)
     small = _dump(exe, SHAPES[:10])
     assert all(d["verdict"] == "fits" for d in small)
+    # the part list under the same sanitizers: every count as the plain program gives it
+    _check_parts(exe)
