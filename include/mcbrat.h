@@ -288,6 +288,9 @@ int mcbrat_frequency_distribution(mcbrat_ctx *ctx, uint64_t seed, uint64_t first
 /* The device's Philox4x32-10 (the generator every kernel draws from), for its known-answer test: block i of n from
  * in[6 i .. 6 i + 5] = counter[4], key[2] into out[4 i .. 4 i + 3].  Host arrays; returns when out is written. */
 int mcbrat_philox4x32_10(mcbrat_ctx *ctx, int32_t n, const uint32_t *in, uint32_t *out);
+/* Device allocations the library holds at this moment, over every context of the process (a test aid, an addition under ABI
+ * version 3): the difference around a context's whole life, or around a failed call, is 0. */
+int64_t mcbrat_live_device_allocations(void);
 int mcbrat_reset_moments(mcbrat_ctx *ctx); /* stream-ordered: enqueued before whatever the context does next; a caller
                                               that reads a bound buffer itself calls mcbrat_synchronize first */
 int mcbrat_get_moments(mcbrat_ctx *ctx, double *hostBuffer);

@@ -90,6 +90,7 @@ SYMBOLS = {
     "mcbrat_moments_device_pointer": (_vp, [_vp]),
     "mcbrat_frequency_distribution": (C.c_int, [_vp, _u64, _u64, _i32, _vp, _i64, _vp]),
     "mcbrat_philox4x32_10": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "mcbrat_live_device_allocations": (_i64, []),
     "mcbrat_set_surface_description": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "mcbrat_set_surface_brdf": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mcbrat_brdf_reflectance": (_f, [_i32, _vp, _vp, _vp]),

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include "mcbrat_kernels.hip"
 #include "mcbrat_blockwalk.hip"
 #include "mcbrat_variants.h"
+#include "mcbrat_devmem.h"
 
 using namespace mcbrat;
 
@@ -24,15 +26,23 @@ struct mcbrat_ctx {
   // Per-launch resources.  Synchronous mode uses lane 0 only; asynchronous mode (mcbrat_set_async) rotates
   // over kLanes so that the drain of one call's tracing kernel overlaps the next call's (a launch ends
   // with its longest photon history: DESIGN.md section 5, "launch tail").
-  struct Lane {
+  struct LaneHandles {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the tracing kernel (synchronous mode)
     hipEvent_t evDone = nullptr;              // after the finish kernels of the lane's latest call
-    unsigned long long *dCounter = nullptr;
-    long long *dSlabs = nullptr;
-    size_t slabCapacity = 0;  // ELEMENTS allocated (not batches: the stride changes with nc, nDir and the grid)
-    float *dColVals = nullptr, *dScalVals = nullptr;
-    size_t colCapacity = 0, scalCapacity = 0;  // elements allocated
+    ~LaneHandles() {
+      if (ev0) (void)hipEventDestroy(ev0);
+      if (ev1) (void)hipEventDestroy(ev1);
+      if (evDone) (void)hipEventDestroy(evDone);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  };
+  // Buffers are freed before streams are destroyed: a lane's handles are its base (destroyed after its members), and the lanes
+  // stand in front of every buffer of the context (members go in reverse order).
+  struct Lane : LaneHandles {
+    DeviceBuffer<unsigned long long> dCounter;
+    DeviceBuffer<long long> dSlabs;  // (sized in ELEMENTS, not batches: the stride changes with nc, nDir and the grid)
+    DeviceBuffer<float> dColVals, dScalVals;
   };
   static constexpr int kLanes = 4;
   Lane lane[kLanes];
@@ -58,28 +68,28 @@ struct mcbrat_ctx {
   int xyRegular = 0, zRegular = 0;
   double dX = 0, dY = 0, dZ = 0;
   // device buffers
-  double *dEdges = nullptr;
-  float *dExt = nullptr, *dCum = nullptr, *dSsa = nullptr, *dRelArea = nullptr;
-  uint16_t *dPfi = nullptr;
+  DeviceBuffer<double> dEdges;
+  DeviceBuffer<float> dExt, dCum, dSsa, dRelArea;
+  DeviceBuffer<uint16_t> dPfi;
   // brick layout (see mcbrat_kernels.hip locate_cell)
-  uint32_t *dBrickTable = nullptr;
-  uint32_t *dRec = nullptr;    // packed collision record per cell (nc <= 2), see DevParams::rec
-  float *dLayerExt = nullptr;  // [nz] extinction of a horizontally uniform layer, -1 otherwise
-  int *dLayerRun = nullptr;    // [nz] runs of such layers (DevParams::layerRun)
-  double *dLayerRunT = nullptr;  // [nz+1]
+  DeviceBuffer<uint32_t> dBrickTable;
+  DeviceBuffer<uint32_t> dRec;  // packed collision record per cell (nc <= 2), see DevParams::rec
+  DeviceBuffer<float> dLayerExt;  // [nz] extinction of a horizontally uniform layer, -1 otherwise
+  DeviceBuffer<int> dLayerRun;  // [nz] runs of such layers (DevParams::layerRun)
+  DeviceBuffer<double> dLayerRunT;  // [nz+1]
   // clear-air flight (DevParams::fly...)
-  float *dExtWalk = nullptr, *dBgVal = nullptr;
-  uint16_t *dFlyRange = nullptr;
+  DeviceBuffer<float> dExtWalk, dBgVal;
+  DeviceBuffer<uint16_t> dFlyRange;
   int flyNbx = 0, flyNby = 0;
   bool flyBuilt = false;
   double flyDepth = 0.0;         // vertical optical depth of the background through the layers a flight can cross
   double flightMaxDepth = 0.5;   // MCBRAT_FLIGHT_MAX_DEPTH: largest vertical optical depth of the background with which flights are used
   // block walk (mcbrat_blockwalk.hip)
-  uint32_t *dBlockRec = nullptr;
-  uint16_t *dBlockOf = nullptr;
-  float *dBlockExt = nullptr;  // [nBlocks] extinction of each block
-  float *dBlockSsa = nullptr, *dBlockCum = nullptr;  // [nc][nBlocks] optics per block, where uniform (blockOpticsUniform)
-  uint16_t *dBlockPfi = nullptr;
+  DeviceBuffer<uint32_t> dBlockRec;
+  DeviceBuffer<uint16_t> dBlockOf;
+  DeviceBuffer<float> dBlockExt;  // [nBlocks] extinction of each block
+  DeviceBuffer<float> dBlockSsa, dBlockCum;  // [nc][nBlocks] optics per block, where uniform (blockOpticsUniform)
+  DeviceBuffer<uint16_t> dBlockPfi;
   bool blockOpticsUniform = false;
   int nBlocks = 0;
   int crossThreshold = 8;      // MCBRAT_CROSS_THRESHOLD
@@ -89,24 +99,25 @@ struct mcbrat_ctx {
   bool blockSpansX = true, blockSpansY = true;
   int blockSpanKernel = 0;     // option "blockSpanKernel": 1 keeps the general block-walk instantiation where NOSPAN would do (tests)
   bool noSimple3 = false;      // MCBRAT_NO_SIMPLE3 (tests): the block walk's near-uniform grids run the general kernel, not SIMPLE = 3
-  float *dExtB = nullptr, *dCumB = nullptr, *dSsaB = nullptr, *dBgExt = nullptr, *dBgCum = nullptr, *dBgSsa = nullptr;
-  uint16_t *dPfiB = nullptr, *dBgPfi = nullptr;
+  DeviceBuffer<float> dExtB, dCumB, dSsaB, dBgExt, dBgCum, dBgSsa;
+  DeviceBuffer<uint16_t> dPfiB, dBgPfi;
   int nbx = 0, nby = 0, nbz = 0;
   long long nStored = 0;
   double backgroundFraction = 0.0;  // share of bricks that are pure background
   bool bricksBuilt = false;
   int brickMode = 2;               // 0 dense, 1 bricks, 2 automatic
-  float *dTables = nullptr;
+  DeviceBuffer<float> dTables;
   // surface description (specifyParameters(surfaceBDRF=)); surfNumX == 0: the domain's albedo
   int surfNumX = 0, surfNumY = 0;
-  double *dSurfX = nullptr, *dSurfY = nullptr;
-  float *dSurfRefl = nullptr;
+  DeviceBuffer<double> dSurfX, dSurfY;
+  DeviceBuffer<float> dSurfRefl;
   int surfKind = 0;                // mcbrat_set_surface_brdf: 0 Lambertian (dSurfRefl), 1 RPV, 2 Ross-Li (dSurfBrdf)
-  float4 *dSurfBrdf = nullptr;     // [numY-1][numX-1] the patches' parameters, padded to four
-  double *dVoxelCDF = nullptr;
-  unsigned long long *dEventCounters = nullptr;
-  float *dLast = nullptr;
-  double *dMomentsOwned = nullptr, *dMoments = nullptr;
+  DeviceBuffer<float4> dSurfBrdf;  // [numY-1][numX-1] the patches' parameters, padded to four
+  DeviceBuffer<double> dVoxelCDF;
+  DeviceBuffer<unsigned long long> dEventCounters;
+  DeviceBuffer<float> dLast;
+  DeviceBuffer<double> dMomentsOwned;
+  double *dMoments = nullptr;  // not owned: dMomentsOwned, or the caller's buffer (mcbrat_bind_moments)
   // tables (host, per component)
   std::vector<std::vector<float>> tables;
   std::vector<int> tblNSteps, tblNEntries;
@@ -117,7 +128,7 @@ struct mcbrat_ctx {
   // radiance by local estimation
   int nDir = 0;
   std::vector<float> dirData;  // [nDir][8], see DevParams
-  float *dDirData = nullptr, *dFwd = nullptr, *dFwdOrig = nullptr;
+  DeviceBuffer<float> dDirData, dFwd, dFwdOrig;
   std::vector<std::vector<float>> fwd, fwdOrig;  // per component [nEntries][nAngles]
   std::vector<int> fwdNAngles, fwdNEntries;
   int fwdOffset[MCBRAT_MAX_COMPONENTS] = {0};
@@ -168,21 +179,56 @@ struct mcbrat_ctx {
   int layerSkip = 1;           // layers of one extinction value: cross z faces only; clear-air flight outside the brick columns' cloud
                                // ranges (MCBRAT_LAYER_SKIP / mcbrat_set_walk_options: 0 off, 1 both, 2 the layers only)
   // loop bounds of the kernels (DevParams::bad ...) and the count of what they dropped
-  unsigned long long *dBad = nullptr;   // device: photons / rays dropped since the context was created
-  unsigned long long *hBad = nullptr;   // pinned host copy, written by the last finish kernel of every call (hBadDev: the same word as the device sees it)
+  DeviceBuffer<unsigned long long> dBad;  // device: photons / rays dropped since the context was created
+  PinnedBuffer<unsigned long long> hBad;  // pinned host copy, written by the last finish kernel of every call (hBadDev: the same word as the device sees it)
   unsigned long long *hBadDev = nullptr;
   unsigned maxEvents = 1u << 24, maxEventsNaN = 1u << 20, watchdog = 1u << 20;  // MCBRAT_MAX_EVENTS, MCBRAT_MAX_EVENTS_NAN, MCBRAT_WATCHDOG
   int legacyTies = 0;
   float testRayMaxLen = 0.0f;  // TEST ONLY (MCBRAT_TEST_RAY_MAX_LEN, km): replaces the geometric bound on a view ray's length                   // MCBRAT_TEST_LEGACY_TIES (tests only)
   // mcbrat_frequency_distribution's device buffers, kept and grown with numLambda
-  double *dFreqCdf = nullptr;
-  unsigned long long *dFreqCounts = nullptr;
-  int freqCapacity = 0;
+  DeviceBuffer<double> dFreqCdf;
+  DeviceBuffer<unsigned long long> dFreqCounts;
   bool countersOn = false;
   float lastTraceMs = 0.f;
   mcbrat_counters lastCounters{};
   bool haveLast = false;
+  ~mcbrat_ctx() {
+    for (auto &pr : eventPool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+    if (evExternal) (void)hipEventDestroy(evExternal);
+    if (evChain) (void)hipEventDestroy(evChain);
+  }
 };
+
+// The seam of mcbrat_devmem.h: every allocation of the library, and every free, goes through these four.
+namespace mcbrat {
+
+static std::atomic<long long> liveDeviceAllocations{0};  // mcbrat_live_device_allocations
+
+// -DMCBRAT_POISON (audit build): fresh memory is filled with 0xff, so that a kernel that reads what nothing wrote reads
+// NaNs / huge indices instead of whatever an earlier context left there.
+int device_alloc(void **ptr, size_t bytes) {
+  hipError_t e = hipMalloc(ptr, bytes);
+#ifdef MCBRAT_POISON
+  if (e == hipSuccess) e = hipMemset(*ptr, 0xff, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess && *ptr) (void)hipFree(*ptr);
+#endif
+  if (e == hipSuccess) ++liveDeviceAllocations;
+  else *ptr = nullptr;
+  return (int)e;
+}
+void device_free(void *ptr) {
+  (void)hipFree(ptr);
+  --liveDeviceAllocations;
+}
+int pinned_alloc(void **ptr, size_t bytes) {
+  const hipError_t e = hipHostMalloc(ptr, bytes, hipHostMallocMapped);
+  if (e != hipSuccess) *ptr = nullptr;
+  return (int)e;
+}
+void pinned_free(void *ptr) { (void)hipHostFree(ptr); }
+
+}  // namespace mcbrat
 
 namespace {
 
@@ -190,22 +236,12 @@ int fail(mcbrat_ctx *c, const std::string &msg) {
   if (c) c->err = msg;
   return 1;
 }
+// (call: a hipError_t, or the int an owner of mcbrat_devmem.h hands back for one)
 #define HIP_OK(c, call)                                                                                   \
   do {                                                                                                    \
-    hipError_t e_ = (call);                                                                               \
+    const hipError_t e_ = static_cast<hipError_t>(call);                                                  \
     if (e_ != hipSuccess) return fail(c, std::string(#call) + ": " + hipGetErrorString(e_));              \
   } while (0)
-
-// Every device allocation of the library.  -DMCBRAT_POISON (audit build): fresh memory is filled with 0xff, so that a
-// kernel that reads what nothing wrote reads NaNs / huge indices instead of whatever an earlier context left there.
-hipError_t dev_malloc(void **ptr, size_t bytes) {
-  hipError_t e = hipMalloc(ptr, bytes);
-#ifdef MCBRAT_POISON
-  if (e == hipSuccess) e = hipMemset(*ptr, 0xff, bytes);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-#endif
-  return e;
-}
 
 int init_lane(mcbrat_ctx *c, int i) {
   mcbrat_ctx::Lane &L = c->lane[i];
@@ -214,7 +250,7 @@ int init_lane(mcbrat_ctx *c, int i) {
   HIP_OK(c, hipEventCreate(&L.ev0));
   HIP_OK(c, hipEventCreate(&L.ev1));
   HIP_OK(c, hipEventCreateWithFlags(&L.evDone, hipEventDisableTiming));
-  HIP_OK(c, dev_malloc((void **)&L.dCounter, sizeof(unsigned long long)));
+  HIP_OK(c, L.dCounter.allocate(1));
   return 0;
 }
 
@@ -233,7 +269,7 @@ int sync_all(mcbrat_ctx *c) {
     c->timing.clear();
     c->lastTraceMs = total;
   }
-  if (c->hBad) c->lastCounters.badPhotons = (int64_t)*c->hBad;
+  if (c->hBad) c->lastCounters.badPhotons = (int64_t)*c->hBad.get();
   return 0;
 }
 
@@ -253,10 +289,9 @@ double spacing_d(double x) {
 }
 
 template <typename T>
-int upload(mcbrat_ctx *c, T **dst, const T *src, size_t n) {
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  HIP_OK(c, dev_malloc((void **)dst, sizeof(T) * std::max<size_t>(n, 1)));
-  if (n) HIP_OK(c, hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
+int upload(mcbrat_ctx *c, DeviceBuffer<T> *dst, const T *src, size_t n) {
+  HIP_OK(c, dst->allocate(std::max<size_t>(n, 1)));
+  if (n) HIP_OK(c, hipMemcpy(dst->get(), src, sizeof(T) * n, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -321,7 +356,7 @@ int read_last(mcbrat_ctx *c, size_t base, std::vector<float> &h) {
   if (!c->haveLast) return fail(c, "reportResults: no batch has been traced yet.");
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  HIP_OK(c, hipMemcpy(h.data(), c->dLast + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(h.data(), c->dLast.get() + base, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
   return 0;
 }
 // ... dealt out to the caller's arrays in the order the parts lie in, already in Fortran order (a null array is skipped)
@@ -340,9 +375,9 @@ int deal_last(mcbrat_ctx *c, size_t base, std::initializer_list<LastPart> parts)
 // go, to be made afresh by the next call.  retune: the setting also changes the walk or the kernels, so the event threshold is
 // chosen again.
 void drop_results(mcbrat_ctx *c, bool retune) {
-  if (c->dMomentsOwned) { (void)hipFree(c->dMomentsOwned); c->dMomentsOwned = nullptr; }
+  c->dMomentsOwned.reset();
   c->dMoments = nullptr;
-  if (c->dLast) { (void)hipFree(c->dLast); c->dLast = nullptr; }
+  c->dLast.reset();
   c->haveLast = false;
   if (retune) c->tuned = false;
 }
@@ -350,13 +385,13 @@ void drop_results(mcbrat_ctx *c, bool retune) {
 int ensure_moments(mcbrat_ctx *c) {
   if (c->dMoments) return 0;
   const size_t n = 8 + 2 * (size_t)tally_layout(c).momentsLen;
-  HIP_OK(c, dev_malloc((void **)&c->dMomentsOwned, sizeof(double) * n));
+  HIP_OK(c, c->dMomentsOwned.allocate(n));
   // (on the stream the finish kernels run on: hipMemset on the null stream is asynchronous for device memory and the
   // context's streams are non-blocking, so nothing would order a null-stream memset before the first finish kernels)
   if (init_lane(c, c->cur)) return 1;
-  HIP_OK(c, hipMemsetAsync(c->dMomentsOwned, 0, sizeof(double) * n, c->L().stream));
+  HIP_OK(c, hipMemsetAsync(c->dMomentsOwned.get(), 0, sizeof(double) * n, c->L().stream));
   HIP_OK(c, hipStreamSynchronize(c->L().stream));
-  c->dMoments = c->dMomentsOwned;
+  c->dMoments = c->dMomentsOwned.get();
   return 0;
 }
 
@@ -523,12 +558,8 @@ int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
   const int nx = c->nx, ny = c->ny, nz = c->nz;
   const size_t nvox = (size_t)nx * ny * nz;
   c->nBlocks = 0;
-  if (c->dBlockRec) { (void)hipFree(c->dBlockRec); c->dBlockRec = nullptr; }
-  if (c->dBlockOf) { (void)hipFree(c->dBlockOf); c->dBlockOf = nullptr; }
-  if (c->dBlockExt) { (void)hipFree(c->dBlockExt); c->dBlockExt = nullptr; }
-  if (c->dBlockSsa) { (void)hipFree(c->dBlockSsa); c->dBlockSsa = nullptr; }
-  if (c->dBlockCum) { (void)hipFree(c->dBlockCum); c->dBlockCum = nullptr; }
-  if (c->dBlockPfi) { (void)hipFree(c->dBlockPfi); c->dBlockPfi = nullptr; }
+  c->dBlockRec.reset(); c->dBlockOf.reset(); c->dBlockExt.reset();
+  c->dBlockSsa.reset(); c->dBlockCum.reset(); c->dBlockPfi.reset();
   c->blockOpticsUniform = false;
   c->blockSpansX = c->blockSpansY = true;
   // only grids that can live in LDS are walked this way (plan_launch decides); bounds are packed in 16 bits
@@ -600,9 +631,9 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.dXf = (float)((p.xMax - p.x0) / c->nx); p.dYf = (float)((p.yMax - p.y0) / c->ny); p.dZf = (float)((p.zMax - p.z0) / c->nz);
   p.layerSkip = (c->layerSkip && !facewalk_on(c)) ? 1 : 0;  // (level fluxes: every z face is a stop; actinic flux: every face)
   p.actScale = actinic_on(c) ? (float)(1.0 / actinic_unit(c)) : 0.0f;
-  p.layerRun = c->dLayerRun; p.layerRunT = c->dLayerRunT;
+  p.layerRun = c->dLayerRun.get(); p.layerRunT = c->dLayerRunT.get();
   p.fly = 0; p.flyNbx = p.flyNby = 0;  // (switched on by launch_trace where the plan allows it)
-  p.flyRange = c->dFlyRange; p.bgVal = c->dBgVal;
+  p.flyRange = c->dFlyRange.get(); p.bgVal = c->dBgVal.get();
   p.invLx = 1.0 / p.Lx; p.invLy = 1.0 / p.Ly;
   p.invCellX = (double)c->nx / p.Lx; p.invCellY = (double)c->ny / p.Ly;
   {
@@ -615,23 +646,23 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
     for (int i = 0; i <= c->nz && uz; ++i) uz = std::fabs((c->ze[i] - p.z0) * invCellZ - i) <= 1e-6;
     p.zNearUniform = uz ? 1 : 0;
   }
-  p.edges = c->dEdges;
+  p.edges = c->dEdges.get();
   if (use_bricks(c)) {
-    p.ext = c->dExtB; p.cum = c->dCumB; p.ssa = c->dSsaB; p.pfi = c->dPfiB;
+    p.ext = c->dExtB.get(); p.cum = c->dCumB.get(); p.ssa = c->dSsaB.get(); p.pfi = c->dPfiB.get();
     p.extWalk = p.ext;
-    p.brickTable = c->dBrickTable; p.nbx = c->nbx; p.nby = c->nby; p.nbz = c->nbz; p.nStored = c->nStored;
-    p.bgExt = c->dBgExt; p.bgCum = c->dBgCum; p.bgSsa = c->dBgSsa; p.bgPfi = c->dBgPfi;
+    p.brickTable = c->dBrickTable.get(); p.nbx = c->nbx; p.nby = c->nby; p.nbz = c->nbz; p.nStored = c->nStored;
+    p.bgExt = c->dBgExt.get(); p.bgCum = c->dBgCum.get(); p.bgSsa = c->dBgSsa.get(); p.bgPfi = c->dBgPfi.get();
   } else {
-    p.ext = c->dExt; p.cum = c->dCum; p.ssa = c->dSsa; p.pfi = c->dPfi;
+    p.ext = c->dExt.get(); p.cum = c->dCum.get(); p.ssa = c->dSsa.get(); p.pfi = c->dPfi.get();
     p.extWalk = p.ext;
-    p.bgExt = c->dLayerExt;  // dense layout: the per-layer slot holds the uniform-layer shortcut
-    p.rec = reinterpret_cast<const uint4 *>(c->dRec);
+    p.bgExt = c->dLayerExt.get();  // dense layout: the per-layer slot holds the uniform-layer shortcut
+    p.rec = reinterpret_cast<const uint4 *>(c->dRec.get());
   }
   p.albedo = c->albedo;
-  p.surfNumX = c->surfNumX; p.surfNumY = c->surfNumY; p.surfX = c->dSurfX; p.surfY = c->dSurfY; p.surfRefl = c->dSurfRefl;
+  p.surfNumX = c->surfNumX; p.surfNumY = c->surfNumY; p.surfX = c->dSurfX.get(); p.surfY = c->dSurfY.get(); p.surfRefl = c->dSurfRefl.get();
   p.surfKind = c->surfNumX > 0 ? c->surfKind : 0;
-  if (p.surfKind != 0) p.surfRefl = reinterpret_cast<const float *>(c->dSurfBrdf);  // (float4 per patch)
-  p.tables = c->dTables;
+  if (p.surfKind != 0) p.surfRefl = reinterpret_cast<const float *>(c->dSurfBrdf.get());  // (float4 per patch)
+  p.tables = c->dTables.get();
   for (int k = 0; k < c->nc; ++k) { p.tblOffset[k] = c->tblOffset[k]; p.tblNSteps[k] = c->tblNSteps[k]; p.tblInvN[k] = 1.0f / (float)c->tblNSteps[k]; }
   p.tblTotalFloats = c->tblTotalFloats;
   p.useRR = c->useRR;
@@ -640,17 +671,17 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.dir0[0] = c->dir0[0]; p.dir0[1] = c->dir0[1]; p.dir0[2] = c->dir0[2];
   p.zLaunch = c->zLaunch; p.izLaunch = c->izLaunch;
   p.solarKind = c->solarKind; p.spotX = c->spotX; p.spotY = c->spotY;
-  p.voxelCDF = c->dVoxelCDF; p.fracAtms = c->fracAtms;
+  p.voxelCDF = c->dVoxelCDF.get(); p.fracAtms = c->fracAtms;
   p.nDir = c->nDir;
-  p.dirData = c->dDirData; p.fwdTables = c->dFwd; p.fwdOrig = c->dFwdOrig;
+  p.dirData = c->dDirData.get(); p.fwdTables = c->dFwd.get(); p.fwdOrig = c->dFwdOrig.get();
   for (int k = 0; k < c->nc && c->nDir > 0; ++k) { p.fwdOffset[k] = c->fwdOffset[k]; p.fwdNAngles[k] = c->fwdNAngles[k]; }
   p.useHybrid = c->useHybrid; p.numOrdersOrig = c->numOrdersOrig; p.useRRIntensity = c->useRRIntensity; p.zetaMin = c->zetaMin;
   p.limitContrib = c->limitContrib; p.maxContrib = c->maxContrib;
-  p.nBlocks = c->nBlocks; p.blockRec = reinterpret_cast<const uint4 *>(c->dBlockRec); p.blockOf = c->dBlockOf; p.blockExt = c->dBlockExt;
-  p.blockSsa = c->dBlockSsa; p.blockCum = c->dBlockCum; p.blockPfi = c->dBlockPfi;
+  p.nBlocks = c->nBlocks; p.blockRec = reinterpret_cast<const uint4 *>(c->dBlockRec.get()); p.blockOf = c->dBlockOf.get(); p.blockExt = c->dBlockExt.get();
+  p.blockSsa = c->dBlockSsa.get(); p.blockCum = c->dBlockCum.get(); p.blockPfi = c->dBlockPfi.get();
   p.crossThreshold = std::max(1, std::min(64, c->crossThreshold));
   p.jumpThreshold = std::max(1, std::min(64, c->jumpThreshold));
-  p.bad = c->dBad;
+  p.bad = c->dBad.get();
   p.maxEvents = c->maxEvents; p.maxEventsNaN = std::min(c->maxEventsNaN, c->maxEvents); p.watchdog = c->watchdog;  // (the kernels test the smaller one first)
   p.legacyTies = c->legacyTies;
   {
@@ -660,7 +691,7 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
     p.rayMaxLen = (float)((p.zMax - p.z0) / (double)std::max(muMin, FLT_MIN)) * 1.0001f + 1e-6f;
     if (c->testRayMaxLen > 0.0f) p.rayMaxLen = c->testRayMaxLen;  // TEST ONLY (MCBRAT_TEST_RAY_MAX_LEN): drive the bound on purpose
   }
-  p.counter = c->L().dCounter;
+  p.counter = c->L().dCounter.get();
   p.numRecScatOrd = -1;  // (mcbrat_compute_radiative_transfer switches the order tallies on)
   p.eventThreshold = std::max(1, std::min(64, c->eventThreshold));
   // The thermal source's launch is several hundred instructions (three searches of the emission CDF, double divisions,
@@ -934,7 +965,7 @@ KernelChoice choose_trace(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool
 int launch_trace(mcbrat_ctx *c, DevParams &p, bool debug, int nBatches) {
   const LaunchPlan L = plan_launch(c, (size_t)p.slabStride);
   if (L.fly) {
-    p.fly = 1; p.flyNbx = c->flyNbx; p.flyNby = c->flyNby; p.extWalk = c->dExtWalk;
+    p.fly = 1; p.flyNbx = c->flyNbx; p.flyNby = c->flyNby; p.extWalk = c->dExtWalk.get();
     p.flyInvBrickX = (float)(c->flyNbx / p.Lx); p.flyInvBrickY = (float)(c->flyNby / p.Ly);
   }
   if (block_walk_applies(c, L)) return launch_block(c, p, L, debug, nBatches);
@@ -984,8 +1015,8 @@ int autotune(mcbrat_ctx *c, DevParams p, unsigned long long ppb, int nBatches) {
     p.eventThreshold = thr;
     float ms = 1e30f;
     for (int rep = 0; rep < 2; ++rep) {  // first repetition warms caches / code
-      HIP_OK(c, hipMemsetAsync(c->L().dSlabs, 0, sizeof(long long) * p.slabStride * nb, c->L().stream));
-      HIP_OK(c, hipMemsetAsync(c->L().dCounter, 0, sizeof(unsigned long long), c->L().stream));
+      HIP_OK(c, hipMemsetAsync(c->L().dSlabs.get(), 0, sizeof(long long) * p.slabStride * nb, c->L().stream));
+      HIP_OK(c, hipMemsetAsync(c->L().dCounter.get(), 0, sizeof(unsigned long long), c->L().stream));
       HIP_OK(c, hipEventRecord(c->L().ev0, c->L().stream));
       if (launch_trace(c, p, false, nb)) return 1;
       HIP_OK(c, hipEventRecord(c->L().ev1, c->L().stream));
@@ -1036,16 +1067,16 @@ mcbrat_ctx *mcbrat_create(int device) {
     if (prop.maxSharedMemoryPerMultiProcessor > 0) c->ldsPerCU = prop.maxSharedMemoryPerMultiProcessor;
   }
   if (init_lane(c, 0) || hipEventCreateWithFlags(&c->evExternal, hipEventDisableTiming) != hipSuccess ||
-      dev_malloc((void **)&c->dEventCounters, 32 * sizeof(unsigned long long)) != hipSuccess ||
-      dev_malloc((void **)&c->dBad, kBadWords * sizeof(unsigned long long)) != hipSuccess ||  // count, claim word, record of the first drop
-      hipMemsetAsync(c->dBad, 0, kBadWords * sizeof(unsigned long long), c->lane[0].stream) != hipSuccess ||
+      c->dEventCounters.allocate(32) != 0 ||
+      c->dBad.allocate(kBadWords) != 0 ||  // count, claim word, record of the first drop
+      hipMemsetAsync(c->dBad.get(), 0, kBadWords * sizeof(unsigned long long), c->lane[0].stream) != hipSuccess ||
       hipStreamSynchronize(c->lane[0].stream) != hipSuccess ||
-      hipHostMalloc((void **)&c->hBad, sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&c->hBadDev, c->hBad, 0) != hipSuccess) {
+      c->hBad.allocate(1) != 0 ||
+      hipHostGetDevicePointer((void **)&c->hBadDev, c->hBad.get(), 0) != hipSuccess) {
     mcbrat_destroy(c);
     return nullptr;
   }
-  *c->hBad = 0ull;
+  *c->hBad.get() = 0ull;
   return c;
 }
 
@@ -1053,24 +1084,7 @@ void mcbrat_destroy(mcbrat_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)sync_all(c);
-  void *bufs[] = {c->dEdges, c->dExt, c->dCum, c->dSsa, c->dRelArea, c->dPfi, c->dTables, c->dVoxelCDF,
-                  c->dEventCounters, c->dLast, c->dMomentsOwned, c->dBrickTable, c->dExtB,
-                  c->dBlockRec, c->dBlockOf, c->dBlockExt, c->dBlockSsa, c->dBlockCum, c->dBlockPfi, c->dCumB, c->dSsaB, c->dPfiB, c->dBgExt, c->dBgCum, c->dBgSsa, c->dBgPfi, c->dLayerExt, c->dRec, c->dLayerRun, c->dLayerRunT, c->dExtWalk, c->dBgVal, c->dFlyRange, c->dSurfX, c->dSurfY, c->dSurfRefl, c->dSurfBrdf,
-                  c->dBad, c->dFreqCdf, c->dFreqCounts, c->dDirData, c->dFwd, c->dFwdOrig};
-  if (c->hBad) (void)hipHostFree(c->hBad);
-  for (void *b : bufs) if (b) (void)hipFree(b);
-  for (mcbrat_ctx::Lane &L : c->lane) {
-    void *lb[] = {L.dCounter, L.dSlabs, L.dColVals, L.dScalVals};
-    for (void *b : lb) if (b) (void)hipFree(b);
-    if (L.ev0) (void)hipEventDestroy(L.ev0);
-    if (L.ev1) (void)hipEventDestroy(L.ev1);
-    if (L.evDone) (void)hipEventDestroy(L.evDone);
-    if (L.stream) (void)hipStreamDestroy(L.stream);
-  }
-  for (auto &pr : c->eventPool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (c->evExternal) (void)hipEventDestroy(c->evExternal);
-  if (c->evChain) (void)hipEventDestroy(c->evChain);
-  delete c;
+  delete c;  // (the owners free and destroy: ~mcbrat_ctx, ~LaneHandles, mcbrat_devmem.h; a half-built context of mcbrat_create holds nulls)
 }
 
 const char *mcbrat_last_error(const mcbrat_ctx *c) { return c ? c->err.c_str() : "mcbrat: no context (no usable HIP device)"; }
@@ -1148,7 +1162,7 @@ int mcbrat_set_optics(mcbrat_ctx *c, int32_t nc, const double *totalExt, const d
   if (upload(c, &c->dExt, e.data(), e.size()) || upload(c, &c->dCum, cu.data(), cu.size()) ||
       upload(c, &c->dSsa, s.data(), s.size()) || upload(c, &c->dPfi, pf.data(), pf.size()))
     return 1;
-  if (c->dRec) { (void)hipFree(c->dRec); c->dRec = nullptr; }
+  c->dRec.reset();
   if (nc <= 2) {
     std::vector<uint32_t> rec(4 * nvox);
     for (size_t v = 0; v < nvox; ++v) {
@@ -1291,7 +1305,7 @@ int mcbrat_bind_moments(mcbrat_ctx *c, double *deviceBuffer) {
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
   if (deviceBuffer) c->dMoments = deviceBuffer;
-  else { c->dMoments = c->dMomentsOwned; return ensure_moments(c); }
+  else { c->dMoments = c->dMomentsOwned.get(); return ensure_moments(c); }
   return 0;
 }
 
@@ -1614,7 +1628,7 @@ const char *mcbrat_first_drop(mcbrat_ctx *c) {
   (void)hipSetDevice(c->device);
   c->dropText.clear();
   unsigned long long h[kBadWords] = {0};
-  if (sync_all(c) || hipMemcpy(h, c->dBad, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return c->dropText.c_str();
+  if (sync_all(c) || hipMemcpy(h, c->dBad.get(), sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return c->dropText.c_str();
   if (h[0] == 0ull) return c->dropText.c_str();
   static const char *kinds[] = {"?", "leg budget (maxEvents)", "leg budget of a photon with a NaN direction at full weight (maxEventsNaN)", "wave watchdog (no lane made progress)",
                                 "block crossings of one leg", "horizontal leg through vacuum in a block that spans both periodic axes", "view ray longer than the geometry allows"};
@@ -1726,17 +1740,14 @@ int mcbrat_frequency_distribution(mcbrat_ctx *c, uint64_t seed, uint64_t firstDr
   (void)hipSetDevice(c->device);
   if (init_lane(c, 0)) return 1;
   hipStream_t st = c->lane[0].stream;
-  if (c->freqCapacity < numLambda) {  // the context's own buffers, grown when a longer CDF arrives (freed with the context)
+  const size_t nl = (size_t)numLambda;
+  if (c->dFreqCdf.capacity() < nl || c->dFreqCounts.capacity() < nl) {  // the context's own buffers, grown when a longer CDF arrives
     HIP_OK(c, hipStreamSynchronize(st));
-    if (c->dFreqCdf) { (void)hipFree(c->dFreqCdf); c->dFreqCdf = nullptr; }
-    if (c->dFreqCounts) { (void)hipFree(c->dFreqCounts); c->dFreqCounts = nullptr; }
-    c->freqCapacity = 0;
-    HIP_OK(c, dev_malloc((void **)&c->dFreqCdf, sizeof(double) * numLambda));
-    HIP_OK(c, dev_malloc((void **)&c->dFreqCounts, sizeof(unsigned long long) * numLambda));
-    c->freqCapacity = numLambda;
+    HIP_OK(c, c->dFreqCdf.reserve(nl));
+    HIP_OK(c, c->dFreqCounts.reserve(nl));
   }
-  double *dCdf = c->dFreqCdf;
-  unsigned long long *dCounts = c->dFreqCounts;
+  double *dCdf = c->dFreqCdf.get();
+  unsigned long long *dCounts = c->dFreqCounts.get();
   HIP_OK(c, hipMemcpyAsync(dCdf, cdf, sizeof(double) * numLambda, hipMemcpyHostToDevice, st));
   HIP_OK(c, hipMemsetAsync(dCounts, 0, sizeof(unsigned long long) * numLambda, st));
   if (totalPhotons > 0) {
@@ -1761,20 +1772,18 @@ int mcbrat_philox4x32_10(mcbrat_ctx *c, int32_t n, const uint32_t *in, uint32_t 
   (void)hipSetDevice(c->device);
   if (init_lane(c, 0)) return 1;
   hipStream_t st = c->lane[0].stream;
-  uint32_t *dIn = nullptr, *dOut = nullptr;
-  HIP_OK(c, dev_malloc((void **)&dIn, sizeof(uint32_t) * 6 * (size_t)n));
-  if (dev_malloc((void **)&dOut, sizeof(uint32_t) * 4 * (size_t)n) != hipSuccess) { (void)hipFree(dIn); return fail(c, "philox4x32_10: out of device memory."); }
-  hipError_t e = hipMemcpyAsync(dIn, in, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(philox_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dIn, (int)n, dOut);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(dIn); (void)hipFree(dOut);
-  HIP_OK(c, e);
+  DeviceBuffer<uint32_t> dIn, dOut;
+  HIP_OK(c, dIn.allocate(6 * (size_t)n));
+  HIP_OK(c, dOut.allocate(4 * (size_t)n));
+  HIP_OK(c, hipMemcpyAsync(dIn.get(), in, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(philox_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dIn.get(), (int)n, dOut.get());
+  HIP_OK(c, hipGetLastError());
+  HIP_OK(c, hipMemcpyAsync(out, dOut.get(), sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_OK(c, hipStreamSynchronize(st));
   return 0;
 }
+
+int64_t mcbrat_live_device_allocations(void) { return (int64_t)liveDeviceAllocations.load(); }
 
 int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
   if (!c) return 0;
@@ -1824,39 +1833,25 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
   for (int li = 0; li < mcbrat_ctx::kLanes; ++li) {
     mcbrat_ctx::Lane &L = c->lane[li];
     if (li != c->cur && !(c->asyncOn && L.stream)) continue;
-    const size_t needSlab = slabStride * inFlight, needCol = 3 * ncol * inFlight, needScal = (size_t)lay.scalPerBatch * inFlight;
-    if (L.slabCapacity >= needSlab && L.colCapacity >= needCol && L.scalCapacity >= needScal) continue;
-    HIP_OK(c, hipStreamSynchronize(L.stream));
-    if (L.slabCapacity < needSlab) {
-      if (L.dSlabs) (void)hipFree(L.dSlabs);
-      L.dSlabs = nullptr; L.slabCapacity = 0;
-      HIP_OK(c, dev_malloc((void **)&L.dSlabs, sizeof(long long) * (needSlab + 1)));  // (+1: the launch's photon cursor sits behind the slabs in use, zeroed with them)
-      L.slabCapacity = needSlab;
-    }
-    if (L.colCapacity < needCol) {
-      if (L.dColVals) (void)hipFree(L.dColVals);
-      L.dColVals = nullptr; L.colCapacity = 0;
-      HIP_OK(c, dev_malloc((void **)&L.dColVals, sizeof(float) * needCol));
-      L.colCapacity = needCol;
-    }
-    if (L.scalCapacity < needScal) {
-      if (L.dScalVals) (void)hipFree(L.dScalVals);
-      L.dScalVals = nullptr; L.scalCapacity = 0;
-      HIP_OK(c, dev_malloc((void **)&L.dScalVals, sizeof(float) * needScal));
-      L.scalCapacity = needScal;
-    }
+    // (+ 1: the launch's photon cursor sits behind the slabs in use, zeroed with them)
+    const size_t needSlab = slabStride * inFlight + 1, needCol = 3 * ncol * inFlight, needScal = (size_t)lay.scalPerBatch * inFlight;
+    if (L.dSlabs.capacity() >= needSlab && L.dColVals.capacity() >= needCol && L.dScalVals.capacity() >= needScal) continue;
+    HIP_OK(c, hipStreamSynchronize(L.stream));  // (before any of the three may free)
+    HIP_OK(c, L.dSlabs.reserve(needSlab));
+    HIP_OK(c, L.dColVals.reserve(needCol));
+    HIP_OK(c, L.dScalVals.reserve(needScal));
   }
-  if (!c->dLast) HIP_OK(c, dev_malloc((void **)&c->dLast, sizeof(float) * (size_t)tally_layout(c).momentsLen));
+  if (!c->dLast) HIP_OK(c, c->dLast.allocate((size_t)tally_layout(c).momentsLen));
 
   DevParams p;
   fill_params(c, p);
   p.seedLo = (uint32_t)seed; p.seedHi = (uint32_t)(seed >> 32);
-  p.slabs = c->L().dSlabs; p.slabStride = slabStride;
+  p.slabs = c->L().dSlabs.get(); p.slabStride = slabStride;
   p.numRecScatOrd = c->numRecScatOrd;
   p.ppb = (unsigned long long)ppb;
   p.fates = nullptr;
-  p.counters = c->countersOn ? c->dEventCounters : nullptr;
-  if (c->countersOn) HIP_OK(c, hipMemsetAsync(c->dEventCounters, 0, 32 * sizeof(unsigned long long), c->L().stream));
+  p.counters = c->countersOn ? c->dEventCounters.get() : nullptr;
+  if (c->countersOn) HIP_OK(c, hipMemsetAsync(c->dEventCounters.get(), 0, 32 * sizeof(unsigned long long), c->L().stream));
 
   if (c->autoTune && !c->tuned) {
     if (autotune(c, p, (unsigned long long)ppb, (int)inFlight)) return 1;
@@ -1868,8 +1863,8 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     const int nb = std::min<int>((int)inFlight, nBatches - b0);
     p.total = (unsigned long long)ppb * (unsigned long long)nb;
     p.firstPhoton = firstPhotonId + (unsigned long long)b0 * (unsigned long long)ppb;
-    HIP_OK(c, hipMemsetAsync(c->L().dSlabs, 0, sizeof(long long) * (slabStride * nb + 1), c->L().stream));  // zero tallies :248-252, and the cursor
-    p.counter = reinterpret_cast<unsigned long long *>(c->L().dSlabs + slabStride * nb);
+    HIP_OK(c, hipMemsetAsync(c->L().dSlabs.get(), 0, sizeof(long long) * (slabStride * nb + 1), c->L().stream));  // zero tallies :248-252, and the cursor
+    p.counter = reinterpret_cast<unsigned long long *>(c->L().dSlabs.get() + slabStride * nb);
     std::pair<hipEvent_t, hipEvent_t> bracket(c->L().ev0, c->L().ev1);
     if (async && event_pair(c, bracket)) return 1;
     HIP_OK(c, hipEventRecord(bracket.first, c->L().stream));
@@ -1889,10 +1884,10 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     f.shape = tally_shape(c); f.nBatches = nb; f.xyRegular = c->xyRegular;
     f.ppb = p.ppb; f.total = p.total; f.lay = lay;
     f.parts = finish_parts(f.shape, nb);
-    f.slabs = c->L().dSlabs; f.relArea = c->dRelArea;
-    f.xe = c->dEdges; f.ye = c->dEdges + (c->nx + 1); f.ze = c->dEdges + (c->nx + 1) + (c->ny + 1);
-    f.colVals = c->L().dColVals; f.scalVals = c->L().dScalVals; f.moments = c->dMoments; f.last = c->dLast;
-    f.bad = c->dBad; f.badHost = c->hBadDev;
+    f.slabs = c->L().dSlabs.get(); f.relArea = c->dRelArea.get();
+    f.xe = c->dEdges.get(); f.ye = f.xe + (c->nx + 1); f.ze = f.ye + (c->ny + 1);
+    f.colVals = c->L().dColVals.get(); f.scalVals = c->L().dScalVals.get(); f.moments = c->dMoments; f.last = c->dLast.get();
+    f.bad = c->dBad.get(); f.badHost = c->hBadDev;
     f.actUnit = actinic_unit(c);
     if (c->nDir > 0 && c->limitContrib)
       hipLaunchKernelGGL(finish_excess, dim3(c->nDir, nb), dim3(256), 0, c->L().stream, f);
@@ -1907,14 +1902,14 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     HIP_OK(c, hipEventElapsedTime(&ms, c->L().ev0, c->L().ev1));
     traceMs += ms;
   }
-  if (!async) { c->lastTraceMs = traceMs; c->lastCounters.badPhotons = (int64_t)*c->hBad; }
+  if (!async) { c->lastTraceMs = traceMs; c->lastCounters.badPhotons = (int64_t)*c->hBad.get(); }
   if (c->countersOn) {
     unsigned long long h[16];
-    HIP_OK(c, hipMemcpy(h, c->dEventCounters, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_OK(c, hipMemcpy(h, c->dEventCounters.get(), sizeof(h), hipMemcpyDeviceToHost));
 #ifdef MCBRAT_STAMPS  // development aid: wave cycles per section of the tracing loop
     {
       unsigned long long st[16];
-      HIP_OK(c, hipMemcpy(st, c->dEventCounters + 16, sizeof(st), hipMemcpyDeviceToHost));
+      HIP_OK(c, hipMemcpy(st, c->dEventCounters.get() + 16, sizeof(st), hipMemcpyDeviceToHost));
       const char *names[9] = {"launch", "block crossings (block walk)", "collideA(pos,optics,absorb,roulette)", "collideB(angle,cos)", "collideC(next_direct)",
                               "exits(top,surface)", "leg", "walk", "phase-head(jump,column look-up)"};
       double tot = 0;
@@ -1925,7 +1920,7 @@ int mcbrat_compute_radiative_transfer(mcbrat_ctx *c, uint64_t seed, uint64_t fir
     c->lastCounters = mcbrat_counters{(int64_t)h[0], (int64_t)h[1], (int64_t)h[2], (int64_t)h[3],
                                       (int64_t)h[4], (int64_t)h[5], (int64_t)h[6], (int64_t)h[7],
                                       (int64_t)h[8], (int64_t)h[9], (int64_t)h[10], (int64_t)h[11], (int64_t)h[12], (int64_t)h[13],
-                                      (int64_t)*c->hBad};
+                                      (int64_t)*c->hBad.get()};
   }
   c->haveLast = true;
   if (numPhotonsProcessed) *numPhotonsProcessed = ppb * (int64_t)nBatches;
@@ -1963,32 +1958,32 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
   TallyShape fluxes = flux_run(tally_shape(c));  // the slab of the instrumented kernels: the fluxes and the volume only
   fluxes.nOrd = 0;
   const size_t slabStride = (size_t)tally_layout(fluxes).slabStride;
-  long long *scratch = nullptr;
-  mcbrat_fate *dF = nullptr;
-  HIP_OK(c, dev_malloc((void **)&scratch, sizeof(long long) * slabStride));
-  HIP_OK(c, dev_malloc((void **)&dF, sizeof(mcbrat_fate) * (size_t)n));
-  HIP_OK(c, hipMemsetAsync(scratch, 0, sizeof(long long) * slabStride, c->L().stream));
-  HIP_OK(c, hipMemsetAsync(dF, 0xff, sizeof(mcbrat_fate) * (size_t)n, c->L().stream));
-  HIP_OK(c, hipMemsetAsync(c->L().dCounter, 0, sizeof(unsigned long long), c->L().stream));
-  HIP_OK(c, hipMemsetAsync(c->dEventCounters, 0, 32 * sizeof(unsigned long long), c->L().stream));
+  DeviceBuffer<long long> scratch;  // (the three temporaries of this call go with it, however it returns)
+  DeviceBuffer<mcbrat_fate> dF;
+  DeviceBuffer<double> dTrace;
+  HIP_OK(c, scratch.allocate(slabStride));
+  HIP_OK(c, dF.allocate((size_t)n));
+  HIP_OK(c, hipMemsetAsync(scratch.get(), 0, sizeof(long long) * slabStride, c->L().stream));
+  HIP_OK(c, hipMemsetAsync(dF.get(), 0xff, sizeof(mcbrat_fate) * (size_t)n, c->L().stream));
+  HIP_OK(c, hipMemsetAsync(c->L().dCounter.get(), 0, sizeof(unsigned long long), c->L().stream));
+  HIP_OK(c, hipMemsetAsync(c->dEventCounters.get(), 0, 32 * sizeof(unsigned long long), c->L().stream));
   DevParams p;
   fill_params(c, p);
   p.seedLo = (uint32_t)seed; p.seedHi = (uint32_t)(seed >> 32);
-  p.slabs = scratch; p.slabStride = slabStride;
+  p.slabs = scratch.get(); p.slabStride = slabStride;
   p.ppb = (unsigned long long)n; p.total = (unsigned long long)n; p.firstPhoton = firstPhotonId;
-  p.fates = dF; p.counters = c->dEventCounters;
-  double *dTrace = nullptr;
+  p.fates = dF.get(); p.counters = c->dEventCounters.get();
   const int traceCap = 4096;
   if (const char *tp = getenv("MCBRAT_TRACE_PHOTON")) {  // development aid: per-collision records of one photon
-    HIP_OK(c, dev_malloc((void **)&dTrace, sizeof(double) * 12 * traceCap));
-    HIP_OK(c, hipMemsetAsync(dTrace, 0, sizeof(double) * 12 * traceCap, c->L().stream));
-    p.traceBuf = dTrace; p.traceIndex = strtoull(tp, nullptr, 10); p.traceCap = traceCap;
+    HIP_OK(c, dTrace.allocate((size_t)12 * traceCap));
+    HIP_OK(c, hipMemsetAsync(dTrace.get(), 0, sizeof(double) * 12 * traceCap, c->L().stream));
+    p.traceBuf = dTrace.get(); p.traceIndex = strtoull(tp, nullptr, 10); p.traceCap = traceCap;
   }
   int rc = launch_trace(c, p, true, 1);
   if (!rc && dTrace) {
     std::vector<double> h(12 * traceCap);
     (void)hipStreamSynchronize(c->L().stream);
-    (void)hipMemcpy(h.data(), dTrace, sizeof(double) * h.size(), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(h.data(), dTrace.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost);
     if (h[0] == 777) {
       for (int r = 0; r < 64 && h[20 * r] == 777; ++r) {  // (-DMCBRAT_STUCK_PROBE: state tcur tnx tny tnz rx ry rz px py pz dx dy dz acc tau ext spans id)
         fprintf(stderr, "STUCK %d:", r);
@@ -2000,22 +1995,19 @@ int mcbrat_trace_fates(mcbrat_ctx *c, uint64_t seed, uint64_t firstPhotonId, int
       if (h[12 * i] > 0) fprintf(stderr, "GPUTRACE %d ev %.0f cell %.0f %.0f %.0f pos %.17g %.17g %.17g dir %.9g %.9g %.9g tau %.9g w %.9g\n", i, h[12 * i],
               h[12 * i + 1], h[12 * i + 2], h[12 * i + 3], h[12 * i + 4], h[12 * i + 5], h[12 * i + 6], h[12 * i + 7], h[12 * i + 8],
               h[12 * i + 9], h[12 * i + 10], h[12 * i + 11]);
-    (void)hipFree(dTrace);
   }
   if (!rc) {
     hipError_t e = hipStreamSynchronize(c->L().stream);
-    if (e == hipSuccess) e = hipMemcpy(fates, dF, sizeof(mcbrat_fate) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fates, dF.get(), sizeof(mcbrat_fate) * (size_t)n, hipMemcpyDeviceToHost);
     unsigned long long h[16];
-    if (e == hipSuccess) e = hipMemcpy(h, c->dEventCounters, sizeof(h), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(c->hBad, c->dBad, sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h, c->dEventCounters.get(), sizeof(h), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(c->hBad.get(), c->dBad.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(c, std::string("trace_fates: ") + hipGetErrorString(e));
     else c->lastCounters = mcbrat_counters{(int64_t)h[0], (int64_t)h[1], (int64_t)h[2], (int64_t)h[3],
                                            (int64_t)h[4], (int64_t)h[5], (int64_t)h[6], (int64_t)h[7],
                                            (int64_t)h[8], (int64_t)h[9], (int64_t)h[10], (int64_t)h[11], (int64_t)h[12], (int64_t)h[13],
-                                           (int64_t)*c->hBad};
+                                           (int64_t)*c->hBad.get()};
   }
-  (void)hipFree(scratch);
-  (void)hipFree(dF);
   return rc;
 }
 
