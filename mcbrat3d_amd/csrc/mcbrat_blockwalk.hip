@@ -18,11 +18,16 @@
 // -> distance to the block faces -> collide again or not), and the rare kinds of work -- launches, surface
 // reflections, block crossings -- wait until enough lanes have queued up, as launches and reflections already did.
 //
-// Shared with mcbrat_kernels.hip: Philox slots (same table: the oracle's Philox mode replays these photons), fixed
-// point tallies, private LDS tally slab per workgroup unit, launch / surface / scattering arithmetic (bit for bit).
+// Shared with mcbrat_kernels.hip, through mcbrat_photon.h: the generator and its slots (same table: the oracle's Philox mode
+// replays these photons), the fixed point conversions, the look-ups, the launch rules, the direction of a surface reflection
+// and the flush of a unit's private LDS tally slab, each ONE function that both kernels call.  Written out here AND in
+// trace_kernel, bit for bit, each copy naming the other: the cosine of a Lambertian reflection and the HOT ROWS (component
+// pick, roulette, scattering angle, new direction, a leg's draws).  This file adds the Philox flavour (p1 per photon, the leg
+// block's hoisted half), the accessors to where it keeps the optics, and the walk itself.
 #include <float.h>
 
 #include "mcbrat_device.h"
+#include "mcbrat_photon.h"
 
 namespace mcbrat {
 
@@ -210,7 +215,10 @@ trace_block_kernel(const DevParams p) {
   unsigned long long legQ0 = 0;
   uint32_t legD1 = 0;
   unsigned long long idP1 = 0;         // !HOIST: philox_p1(idLo), the first round's product shared by every block of the photon's stream
-  auto photonP1 = [&]() { if constexpr (HOIST) return philox_p1(idLo); else return idP1; };
+  // block (c0, c1) of the photon's Philox stream, for the rules of mcbrat_photon.h
+  auto rng = [&](uint32_t c0, uint32_t c1, uint32_t (&out)[4]) __attribute__((always_inline)) {
+    philox4x32_10_p1(c0, c1, HOIST ? philox_p1(idLo) : idP1, idHi, p.seedLo, p.seedHi, out);
+  };
   double px = 0, py = 0, pz = 0;      // leg origin (in the periodic image the leg is currently in)
   float dx = 0, dy = 0, dz = 1;       // direction cosines
   float ivx = 0, ivy = 0, ivz = 0;    // 1/direction
@@ -315,7 +323,7 @@ trace_block_kernel(const DevParams p) {
                  watchdog = (DEBUG || kTestBounds) ? p.watchdog : kWatchdog;
 #define MCBRAT_BW_DROP(kind_) do { \
     if constexpr (DEBUG || kTestBounds) record_first_drop(p.bad, (kind_), 2u, idLo, idHi, state, event);  /* (which bound, which photon) */ \
-    if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{3, 0, 0, 0, nScat, nLegs, w}; \
+    if (DEBUG) record_fate(p, idLo, idHi, 3, 0, 0, 0, nScat, nLegs, w); \
     state = BW_DEAD; \
     nBadLane = count_drop(nBadLane, (kind_));  /* (added to *p.bad when the kernel ends: no atomic, no pointer in the loop) */ \
   } while (0)
@@ -390,7 +398,7 @@ trace_block_kernel(const DevParams p) {
         if (top) {
           if (DEBUG) {
             cTop++;
-            if (p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{0, ix + 1, iy + 1, p.nz + 1, nScat, nLegs, w};
+            record_fate(p, idLo, idHi, 0, ix + 1, iy + 1, p.nz + 1, nScat, nLegs, w);
           }
           state = BW_DEAD;
         } else {
@@ -398,12 +406,13 @@ trace_block_kernel(const DevParams p) {
           iz = 0;
           nScat++;
           if (DEBUG) cSurf++;
+          // (the cosine of the Lambertian reflection: the same lines stand in trace_kernel, mcbrat_kernels.hip -- see there why)
           float mu = sqrtf(uX);
           if (!(fabsf(mu) > 2.0f * FLT_MIN)) {
             mu = sqrtf(uZ);
             uint32_t r[4];
             for (uint32_t j = 0; !(fabsf(mu) > 2.0f * FLT_MIN); j++) {
-              if ((j & 3u) == 0) philox4x32_10_p1(event, 2u + (j >> 2), photonP1(), idHi, p.seedLo, p.seedHi, r);
+              if ((j & 3u) == 0) rng(event, 2u + (j >> 2), r);
               mu = sqrtf(u01(pick4(r, j & 3u)));
             }
           }
@@ -411,13 +420,10 @@ trace_block_kernel(const DevParams p) {
           if (SIMPLE == 0 && p.surfNumX > 0) w = w * surface_reflectance(p, px, py);  // useSurfaceBDRF :667-670
           else w = (float)((double)w * (double)p.albedo);              // :673
           if (w <= FLT_MIN) {
-            if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{1, ix + 1, iy + 1, 1, nScat, nLegs, wIn};
+            if (DEBUG) record_fate(p, idLo, idHi, 1, ix + 1, iy + 1, 1, nScat, nLegs, wIn);
             state = BW_DEAD;
           } else {
-            const float sinTheta = sqrtf(1.0f - mu * mu);  // makeDirectionCosines(mu, 2 pi Y) :1876-1894
-            float cphi, sphi;
-            sincos_2pi(uY, cphi, sphi);
-            dx = sinTheta * cphi; dy = sinTheta * sphi; dz = mu;
+            lambert_direction(mu, uY, dx, dy, dz);
             needLeg = true;
           }
         }
@@ -445,72 +451,24 @@ trace_block_kernel(const DevParams p) {
         const unsigned long long mValid = __ballot(valid);
         if (__builtin_amdgcn_inverse_ballot_w64(want)) {  // (this lane is in `want`: dead, and may take a photon)
           if (valid) {
-            // ---- launch: getNextPhoton + computeRT :466-508 (as in trace_kernel, bit for bit) ----
+            // ---- launch: getNextPhoton + computeRT :466-508 (the rules trace_kernel calls, mcbrat_photon.h) ----
             const unsigned long long id = p.firstPhoton + myIdx;
             idLo = (uint32_t)id; idHi = (uint32_t)(id >> 32);
             idP1 = philox_p1(idLo);
             if constexpr (HOIST) { legQ0 = philox_leg_q0(idP1, p.seedLo); legD1 = (uint32_t)idP1; }
             event = 0; nScat = 0; nLegs = 0;
             slabOff = k < unitSplit ? 0 : slabLen;
-            uint32_t r[4];
-            philox4x32_10_p1(0u, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
             double lx, ly, lz;  // fractional launch position in [0,1]
             if (!EMIT) {
               lz = 0.0;
-              if (p.solarKind == 0) {  // newPhotonStream_Directional, monteCarloIllumination.f95:88-96
-                lx = (double)u01(r[0]);
-                ly = (double)u01(r[1]);
-                dx = p.dir0[0]; dy = p.dir0[1]; dz = p.dir0[2];
-              } else {  // RandomAzimuth, Flux, Spotlight (wave-uniform; mcbrat_kernels.hip)
-                solar_launch(p, r[0], r[1], r[2], r[3], [&](uint32_t b) {
-                  uint32_t o[4];
-                  philox4x32_10_p1(0u, b, idP1, idHi, p.seedLo, p.seedHi, o);
-                  return o[0] ? o[0] : (o[1] ? o[1] : (o[2] ? o[2] : o[3]));
-                }, lx, ly, dx, dy, dz);
-              }
-            } else {  // newPhotonStream_BBEmission :481-516
-              float mu = 0.f, phi = 0.f;
-              const float sel = u01(r[0]);
-              if ((double)sel > p.fracAtms) {  // surface emission :484-493
-                lx = (double)u01(r[1]);
-                ly = (double)u01(r[2]);
-                lz = 0.0;
-                uint32_t r1[4];
-                for (uint32_t j = 0;; j++) {
-                  if ((j & 3u) == 0) philox4x32_10_p1(0u, 1u + (j >> 2), idP1, idHi, p.seedLo, p.seedHi, r1);
-                  mu = sqrtf(u01(pick4(r1, j & 3u)));
-                  if (fabsf(mu) > 2.0f * FLT_MIN) break;
-                }
-                phi = (u01(r[3]) * 2.0f) * 3.14159274f;
-              } else {  // atmosphere :495-510
-                const float rn = u01(r[1]);
-                const long long nxy = (long long)p.nx * p.ny;
+              launch_solar(p, p.solarKind == 0, rng, lx, ly, dx, dy, dz);
+            } else {
+              launch_emission(p, rng, [&](float rn, int &ik, int &ij) {
+                if (!cdfTop) { emission_level_row(p, rn, ik, ij); return; }
                 // (level and row from the sums staged in LDS where they are: the same doubles, the same comparisons)
-                const int ik = cdfTop ? find_cdf(s_cdfLevel, p.nz, 1, rn) : find_cdf(p.voxelCDF + ((long long)p.nx - 1) + (long long)p.nx * (p.ny - 1), p.nz, nxy, rn);
-                const int ij = cdfTop ? find_cdf(s_cdfRow + p.ny * (ik - 1), p.ny, 1, rn) : find_cdf(p.voxelCDF + ((long long)p.nx - 1) + nxy * (ik - 1), p.ny, p.nx, rn);
-                const int ii = find_cdf(p.voxelCDF + (long long)p.nx * ((ij - 1) + (long long)p.ny * (ik - 1)), p.nx, 1, rn);
-                uint32_t r1[4];
-                philox4x32_10_p1(0u, 1u, idP1, idHi, p.seedLo, p.seedHi, r1);
-                lz = ((double)(ik - 1) * 1.0 / (double)p.nz) + (double)(u01(r[2]) / (float)p.nz);
-                if (ik == 1 && lz == 0.0) lz = 2.220446049250313e-16;
-                if (ik == p.nz && lz > 1.0 - 2.0 * 2.220446049250313e-16) lz = lz - 2.0 * 2.220446049250313e-16;
-                lx = ((double)(ii - 1) * 1.0 / (double)p.nx) + (double)(u01(r[3]) * (1.0f / (float)p.nx));
-                ly = ((double)(ij - 1) * 1.0 / (double)p.ny) + (double)(u01(r1[0]) * (1.0f / (float)p.ny));
-                uint32_t r2[4];
-                for (uint32_t j = 0;; j++) {
-                  uint32_t uu;
-                  if (j < 2) uu = j ? r1[3] : r1[2];
-                  else {
-                    if (((j - 2) & 3u) == 0) philox4x32_10_p1(0u, 2u + ((j - 2) >> 2), idP1, idHi, p.seedLo, p.seedHi, r2);
-                    uu = pick4(r2, (j - 2) & 3u);
-                  }
-                  mu = 1.0f - (2.0f * u01(uu));
-                  if (fabsf(mu) > 2.0f * FLT_MIN) break;
-                }
-                phi = (u01(r1[1]) * 2.0f) * 3.14159274f;
-              }
-              const float sinTheta = sqrtf(1.0f - mu * mu);  // makeDirectionCosines :1876-1894
-              dx = sinTheta * cosf(phi); dy = sinTheta * sinf(phi); dz = mu;
+                ik = find_cdf(s_cdfLevel, p.nz, 1, rn);
+                ij = find_cdf(s_cdfRow + p.ny * (ik - 1), p.ny, 1, rn);
+              }, lx, ly, lz, dx, dy, dz);
             }
             w = 1.0f;
             px = p.x0 + lx * (p.xMax - p.x0);  // :480-482
@@ -524,14 +482,8 @@ trace_block_kernel(const DevParams p) {
             }
             if (!EMIT) {
               pz = p.zLaunch; iz = p.izLaunch;
-            } else if (zRegular) {  // :485-486
-              pz = p.z0 + lz * (p.zMax - p.z0);
-              iz = min((int)((pz - p.z0) / ((p.zMax - p.z0) / (double)p.nz)), p.nz - 1);
-            } else {  // :491-493 layer-index fraction
-              const double t = (lz - p.z0) * (double)p.nz;
-              const double fl = floor(t);
-              iz = min((int)fl, p.nz - 1);
-              pz = s_edge[offZ + iz] + (t - fl) * (s_edge[offZ + iz + 1] - s_edge[offZ + iz]);
+            } else {
+              launch_height(p, zRegular, s_edge + offZ, lz, pz, iz);
             }
             if (EMIT && p.lwFlag && pz > 0.0)  // :504-508 emission counts as negative absorption
               atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + slabOff + 2 * ncol + (ix + p.nx * (iy + p.ny * iz))), to_fixed(-1.0));
@@ -574,6 +526,8 @@ trace_block_kernel(const DevParams p) {
         int cell = cellOf(ix, iy, iz);
         nScat++;
         if (DEBUG) cColl++;
+        // HOT ROWS: component pick, roulette, scattering angle, new direction and the leg's draws below stand in trace_kernel too
+        // (mcbrat_kernels.hip, HOT ROWS): a change to one of them is made in both.
         int c = 0;  // component pick :759-760 (findIndex over [0, cumExt(:)]), uniform = slot Z of the leg's block
         if (nc > 1) {
           for (int k = 0; k < nc - 1; k++)
@@ -605,10 +559,10 @@ trace_block_kernel(const DevParams p) {
           if (DEBUG) cAbs++;
         }
         if (p.useRR && w < 0.5f) {  // Russian roulette :805-811, RussianRouletteW = 1
-          float uR = uZ;  // one component: Z decides nothing at the component pick and serves here (no second block; mcbrat_kernels.hip)
+          float uR = uZ;  // one component: Z decides nothing at the component pick and serves here (no second block)
           if (nc != 1) {  // (wave-uniform; compile time in the SIMPLE instantiations)
             uint32_t r1[4];
-            philox4x32_10_p1(event, 1u, photonP1(), idHi, p.seedLo, p.seedHi, r1);
+            rng(event, 1u, r1);
             uR = u01(r1[1]);
           }
           if (uR >= w) { w = 0.0f; if (DEBUG) cKill++; }
@@ -616,13 +570,13 @@ trace_block_kernel(const DevParams p) {
         }
         STAMP(2);
         if (w <= FLT_MIN) {  // :812
-          if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{2, ix + 1, iy + 1, iz + 1, nScat, nLegs, 0.0f};
+          if (DEBUG) record_fate(p, idLo, idHi, 2, ix + 1, iy + 1, iz + 1, nScat, nLegs, 0.0f);
           state = BW_DEAD;
         } else {
-          // computeScatteringAngle :1594-1621 (table point count N, floor-type lookup as written)
           const int n = s_tblNSteps[c];
           // (in LDS the table is below 2^16 floats: a 24-bit multiply)
           const float *t = tbl + s_tblOffset[c] + (TBL_LDS ? (long long)__umul24((unsigned)pfEntry, (unsigned)n) : (long long)pfEntry * n);
+          // computeScatteringAngle :1594-1621 (table point count N, floor-type lookup as written)
           const int ai = (int)(uX * (float)n) + 1;
           float ang;
           if (ai < n) {
@@ -676,9 +630,9 @@ trace_block_kernel(const DevParams p) {
           dbgY = unwrapped_index(s_edge + offY, p.ny, p.y0, p.Ly, p.invLy, py);
           dbgZ = iz;
         }
-        uint32_t r[4];
+        uint32_t r[4];  // (HOIST: the leg's block from what the lane keeps of it -- the same words as rng(event, 0, r))
         if constexpr (HOIST) philox4x32_10_leg(event, legQ0, legD1, idHi, p.seedLo, p.seedHi, r);
-        else philox4x32_10_p1(event, 0u, idP1, idHi, p.seedLo, p.seedHi, r);
+        else rng(event, 0u, r);
 #ifdef MCBRAT_PRECISE_MATH
         tau = -logf(fmaxf(FLT_MIN, u01(r[0])));
 #else
@@ -775,38 +729,17 @@ trace_block_kernel(const DevParams p) {
 
     // flush this unit's private tallies into the batch slab, once (launch-wide units: the second LDS slab into the next
     // batch's, which follows in memory; it holds nothing unless the unit reached that batch)
-    __syncthreads();
-    for (int i = threadIdx.x; i < slabsLen; i += BLOCK) {
-      const long long v = s_slab[i];
-      if (v != 0) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(unitSlab + i), (unsigned long long)v);
-        s_slab[i] = 0;
-      }
-    }
-    if (threadIdx.x == 0) s_cursor[0] = 0;
-    __syncthreads();
+    flush_unit_slab<BLOCK>(s_slab, slabsLen, unitSlab, s_cursor);
   }
 
   publish_drops(p.bad, nBadLane);
 #ifdef MCBRAT_STAMPS
   if (DEBUG && p.counters && lane == 0) for (int i = 0; i < 9; i++) atomicAdd(p.counters + 16 + i, s_stamp[threadIdx.x >> 6][i]);
 #endif
-  if (DEBUG && p.counters) {
-    atomicAdd(p.counters + 0, (unsigned long long)cLegs);
-    atomicAdd(p.counters + 1, (unsigned long long)cCross);
-    atomicAdd(p.counters + 2, (unsigned long long)cColl);
-    atomicAdd(p.counters + 3, (unsigned long long)cAbs);
-    atomicAdd(p.counters + 4, (unsigned long long)cTop);
-    atomicAdd(p.counters + 5, (unsigned long long)cSurf);
-    atomicAdd(p.counters + 6, (unsigned long long)cKill);
-    atomicAdd(p.counters + 7, (unsigned long long)cSurv);
-    if (lane == 0) {
-      // slots shared with trace_kernel's report: "walk" = block-crossing phases, "event" = loop iterations
-      atomicAdd(p.counters + 8, wCrossPhases); atomicAdd(p.counters + 9, wCrossLanes);
-      atomicAdd(p.counters + 10, wIters); atomicAdd(p.counters + 11, wEventLanes);
-      atomicAdd(p.counters + 12, wLaunchPhases); atomicAdd(p.counters + 13, wSurfPhases);
-    }
-  }
+  // (slots shared with trace_kernel's report: "walk" = block-crossing phases, "event" = loop iterations)
+  if (DEBUG && p.counters)
+    publish_counters(p.counters, lane == 0, cLegs, cCross, cColl, cAbs, cTop, cSurf, cKill, cSurv, wCrossPhases, wCrossLanes, wIters, wEventLanes,
+                     wLaunchPhases, wSurfPhases);
 }
 
 }  // namespace mcbrat

@@ -5,6 +5,23 @@
 
 #include "../../include/mcbrat.h"
 
+// Development aid: -DMCBRAT_STAMPS makes the DEBUG instantiation report wave cycles per section of the
+// loop (launch, top, collide A/B/C, surface, leg set-up, walk, phase head) on stderr with the event counters.
+#ifdef MCBRAT_STAMPS
+#define STAMP(i) do { if (DEBUG && p.counters) { const unsigned long long t_ = clock64(); \
+    if (lane == __ffsll((long long)__ballot(1)) - 1) { s_stamp[threadIdx.x >> 6][i] += t_ - s_tprev[threadIdx.x >> 6]; s_tprev[threadIdx.x >> 6] = t_; } } } while (0)
+#elif defined(MCBRAT_MARKS)  // development aid: section boundaries as comments in the assembly (static instruction counts)
+#define STAMP(i) asm volatile("; @@mark " #i)
+#else
+#define STAMP(i) do { } while (0)
+#endif
+
+// Register budget: minimum waves per SIMD the compiler must leave room for (the second
+// argument of __launch_bounds__ on AMD).  Measured choice, see DESIGN.md section 5.
+#ifndef MCBRAT_MIN_WAVES_PER_SIMD
+#define MCBRAT_MIN_WAVES_PER_SIMD 4
+#endif
+
 namespace mcbrat {
 
 constexpr int kWave = 64;                     // CDNA wavefront

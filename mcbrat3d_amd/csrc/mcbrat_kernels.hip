@@ -24,21 +24,8 @@
 //    extinction read and no x/y faces; a run of such layers is taken in one step, and the column is found again
 //    from the position when the lane collides, leaves, or reaches a layer with cell-to-cell extinction
 //    (ST_JUMP / ST_ENTER, tryJump / resolveXY below).  The radiance rays do the same.
-//  * counter-based Philox4x32-10: key = seed, counter = (event, block, photon id).  Roles have
-//    fixed slots so that ONE block serves a whole leg in the common case:
-//       event 0 (launch)   block 0 = [x, y, -, -]                        (solar source: Directional)
-//                          block 0 = [x, y, phi, -]                      (solar source: RandomAzimuth)
-//                          block 0 = [x, y, mu, phi], block 1.. = mu again (solar source: Flux; only where mu = 0)
-//                          no draws                                      (solar source: Spotlight)
-//                          block 0 = [select, r1, r2, r3], block 1..   (emission source)
-//       event e >= 1       block 0 = [tau, X, Y, Z], block 1 = [-, roulette, -, -] (a domain of ONE component: roulette = Z)
-//            collision: scattering angle = X, azimuth = 2 pi Y, component = Z
-//            surface:   mu = sqrt(X) (retry Z, then block 2..), phi = 2 pi Y
-//    so ONE block serves a whole leg; block 1 is only generated by the few lanes that play roulette
-//    (weight < 1/2).  The reference draws the azimuth by rejection from the unit square (next_direct
-//    :1929-1936, 1.27 pairs on average); here cos / sin of 2 pi Y give the same uniform azimuth from one
-//    number, because a rejection loop would run at 21 % lane occupancy in nearly every event phase.
-//    The oracle's Philox mode uses the same table (oracle/mcbrat_oracle.c).
+//  * counter-based Philox4x32-10: key = seed, counter = (event, block, photon id); every role has a fixed slot, so that ONE
+//    block serves a whole leg in the common case.  The slot table is in mcbrat_photon.h.
 //  * cell edges and, when they fit, the inverse phase-function tables are staged in LDS by
 //    coalesced loads; extinction / ssa / phase index are float / float / u16 grids in HBM that
 //    stay resident in L1/L2/Infinity Cache.
@@ -55,18 +42,8 @@
 #include "mcbrat_device.h"
 #include "mcbrat_brdf.h"
 #include "mcbrat_layout.h"
+#include "mcbrat_photon.h"
 #include "mcbrat_variants.h"
-
-// Development aid: -DMCBRAT_STAMPS makes the DEBUG instantiation report wave cycles per section of the
-// loop (launch, top, collide A/B/C, surface, leg set-up, walk, phase head) on stderr with the event counters.
-#ifdef MCBRAT_STAMPS
-#define STAMP(i) do { if (DEBUG && p.counters) { const unsigned long long t_ = clock64(); \
-    if (lane == __ffsll((long long)__ballot(1)) - 1) { s_stamp[threadIdx.x >> 6][i] += t_ - s_tprev[threadIdx.x >> 6]; s_tprev[threadIdx.x >> 6] = t_; } } } while (0)
-#elif defined(MCBRAT_MARKS)  // development aid: section boundaries as comments in the assembly (static instruction counts)
-#define STAMP(i) asm volatile("; @@mark " #i)
-#else
-#define STAMP(i) do { } while (0)
-#endif
 
 namespace mcbrat {
 
@@ -77,12 +54,6 @@ constexpr unsigned kChunk = 256;  // photon ids a wave takes per global atomic (
 constexpr float kFlyMinBricks = MCBRAT_FLY_MIN_BRICKS;  // brick columns a flight that ends in a clear-air collision must cross to be worth taking
 constexpr int kWalkCap = 256;     // walk-loop iterations between two event phases at most (a leg crosses ~4-15 faces)
 
-// Register budget: minimum waves per SIMD the compiler must leave room for (the second
-// argument of __launch_bounds__ on AMD).  Measured choice, see DESIGN.md section 5.
-#ifndef MCBRAT_MIN_WAVES_PER_SIMD
-#define MCBRAT_MIN_WAVES_PER_SIMD 4
-#endif
-// Flux runs on grids in global memory wait on L2 gathers: there more resident waves are worth a few spilled registers
 #ifndef MCBRAT_WAVES_GLOBAL_GRID
 #define MCBRAT_WAVES_GLOBAL_GRID 6  // (round 2: without the emission launch code the solar kernel needs 73 VGPRs, no scratch; 7 waves: the same rate with 2-4 spilled; 8: -6 %)
 #endif
@@ -90,258 +61,6 @@ constexpr int kWalkCap = 256;     // walk-loop iterations between two event phas
 #define MCBRAT_WAVES_GLOBAL_GRID_INTEN 4
 #endif
 
-// a ^ b ^ c: one v_bitop3_b32 on gfx950 (truth table 0x96), which the compiler does not form from two xors by itself
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-#if defined(__gfx950__)
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-#else
-  return a ^ b ^ c;
-#endif
-}
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;  // v_mad_u64_u32
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    c0 = xor3((uint32_t)(p1 >> 32), c1, k0);
-    c1 = (uint32_t)p1;
-    c2 = xor3((uint32_t)(p0 >> 32), c3, k1);
-    c3 = (uint32_t)p0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// The product 0xCD9E8D57 * c2 of philox4x32_10's first round: every block of a photon's stream has c2 = the low word of its id.
-__device__ __forceinline__ unsigned long long philox_p1(uint32_t c2) { return (unsigned long long)0xCD9E8D57u * c2; }
-// philox4x32_10(c0, c1, c2, c3, k0, k1) with p1 = philox_p1(c2) computed once per photon: the same words, one 64-bit
-// multiply fewer per block (the block walk)
-__device__ __forceinline__ void philox4x32_10_p1(uint32_t c0, uint32_t c1, unsigned long long p1, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1, uint32_t (&out)[4]) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-  uint32_t d0 = xor3((uint32_t)(p1 >> 32), c1, k0), d1 = (uint32_t)p1, d2 = xor3((uint32_t)(p0 >> 32), c3, k1), d3 = (uint32_t)p0;
-#pragma unroll
-  for (int i = 1; i < 10; i++) {
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-    const unsigned long long q0 = (unsigned long long)0xD2511F53u * d0;
-    const unsigned long long q1 = (unsigned long long)0xCD9E8D57u * d2;
-    d0 = xor3((uint32_t)(q1 >> 32), d1, k0);
-    d1 = (uint32_t)q1;
-    d2 = xor3((uint32_t)(q0 >> 32), d3, k1);
-    d3 = (uint32_t)q0;
-  }
-  out[0] = d0; out[1] = d1; out[2] = d2; out[3] = d3;
-}
-
-// The leg block of the block walk, philox4x32_10(event, 0, idLo, idHi, k0, k1): with the second counter word 0 the first round's
-// d0 = hi(p1) ^ 0 ^ k0 and d1 = lo(p1) depend on the photon only, and so does the second round's product 0xD2511F53 * d0.
-// philox_leg_q0 forms it once per photon; the block then starts from (event, q0, lo(p1), idHi): the same words, one 64-bit
-// multiply and one three-input xor fewer than philox4x32_10_p1.
-__device__ __forceinline__ unsigned long long philox_leg_q0(unsigned long long p1, uint32_t k0) {
-  return (unsigned long long)0xD2511F53u * ((uint32_t)(p1 >> 32) ^ k0);
-}
-__device__ __forceinline__ void philox4x32_10_leg(uint32_t c0, unsigned long long q0, uint32_t p1Lo, uint32_t c3, uint32_t k0,
-                                                  uint32_t k1, uint32_t (&out)[4]) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;  // round 1, the half that depends on the event
-  uint32_t e2 = xor3((uint32_t)(p0 >> 32), c3, k1), e3 = (uint32_t)p0;
-  k0 += 0x9E3779B9u;
-  k1 += 0xBB67AE85u;
-  const unsigned long long r1 = (unsigned long long)0xCD9E8D57u * e2;  // round 2, with q0 from the photon
-  uint32_t d0 = xor3((uint32_t)(r1 >> 32), p1Lo, k0), d1 = (uint32_t)r1, d2 = xor3((uint32_t)(q0 >> 32), e3, k1), d3 = (uint32_t)q0;
-#pragma unroll
-  for (int i = 2; i < 10; i++) {
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-    const unsigned long long q0i = (unsigned long long)0xD2511F53u * d0;
-    const unsigned long long q1i = (unsigned long long)0xCD9E8D57u * d2;
-    d0 = xor3((uint32_t)(q1i >> 32), d1, k0);
-    d1 = (uint32_t)q1i;
-    d2 = xor3((uint32_t)(q0i >> 32), d3, k1);
-    d3 = (uint32_t)q0i;
-  }
-  out[0] = d0; out[1] = d1; out[2] = d2; out[3] = d3;
-}
-
-// getRandomReal semantics (src/RandomNumbersForMC.f95:277-301): a float on the closed interval
-// [0,1] with 32-bit resolution.  The reference forms u/(2^32-1) in double and rounds to float;
-// here u is rounded to float and scaled by 2^-32 (both exact operations, so the CPU oracle
-// reproduces it bit for bit); the two maps differ by at most one float ulp, in 0.4 % of draws.
-__device__ __forceinline__ float u01(uint32_t u) { return (float)u * 2.3283064365386963e-10f; }
-
-// 1/x and a/b with the hardware reciprocal (1 ulp): geometry set-up and direction algebra
-#ifdef MCBRAT_PRECISE_MATH  // A/B switch: correctly rounded division / library log, cos, sqrt everywhere
-__device__ __forceinline__ float rcp_fast(float x) { return 1.0f / x; }
-__device__ __forceinline__ float div_fast(float a, float b) { return a / b; }
-#else
-__device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float div_fast(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-#endif
-
-// cos(x) for a scattering angle x in [0, pi]: one quadrant reduction (q = 0, 1, 2; Cody-Waite pi/2)
-// and the classic single-precision kernels on |r| <= pi/4 (coefficients of the FreeBSD/msun
-// k_cosf / k_sinf minimax polynomials).  About 1 ulp, like the library cosf it replaces, at a
-// third of the instructions: the generic routine must handle any argument, this one need not.
-__device__ __forceinline__ float cos_0_pi(float x) {
-  const float q = rintf(x * 0.636619772f);
-  float r = __fmaf_rn(q, -1.57079637050628662109375f, x);  // exact (Sterbenz)
-  r = __fmaf_rn(q, 4.371138828673793e-8f, r);
-  const float z = r * r;
-  const float c = __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, 2.43904487962774090654e-5f, -1.38867637746099294692e-3f),
-                                                      4.16666233237390631894e-2f), -0.499999997251031003120f), 1.0f);
-  const float s = __fmaf_rn(r * z, __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, 2.7183114939898219064e-6f, -1.98393348360966317347e-4f),
-                                                          8.3333293858894631756e-3f), -0.166666666416265235595f), r);
-  return q == 0.0f ? c : (q == 1.0f ? -s : -c);
-}
-
-// (cos, sin) of 2 pi u for u in [0, 1]: quadrant from rint(4u) (the remainder u - q/4 is exact), then the
-// same single-precision kernels on |r| <= pi/4.  The oracle evaluates the identical expression (fmaf), so
-// both sides turn a uniform into the same azimuth bit for bit.
-__device__ __forceinline__ void sincos_2pi(float u, float &c, float &s) {
-  const float q = rintf(4.0f * u);
-  const float r = (u - 0.25f * q) * 6.28318548202514648f;
-  const float z = r * r;
-  const float cc = __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, 2.43904487962774090654e-5f, -1.38867637746099294692e-3f),
-                                                       4.16666233237390631894e-2f), -0.499999997251031003120f), 1.0f);
-  const float ss = __fmaf_rn(r * z, __fmaf_rn(z, __fmaf_rn(z, __fmaf_rn(z, 2.7183114939898219064e-6f, -1.98393348360966317347e-4f),
-                                                           8.3333293858894631756e-3f), -0.166666666416265235595f), r);
-  const int qi = (int)q & 3;
-  c = qi == 0 ? cc : (qi == 1 ? -ss : (qi == 2 ? -cc : ss));
-  s = qi == 0 ? ss : (qi == 1 ? cc : (qi == 2 ? -ss : -cc));
-}
-
-// element i (0..3) of a Philox block without dynamic register indexing
-__device__ __forceinline__ uint32_t pick4(const uint32_t (&r)[4], uint32_t i) {
-  const uint32_t a = (i & 1u) ? r[1] : r[0], b = (i & 1u) ? r[3] : r[2];
-  return (i & 2u) ? b : a;
-}
-
-// Launch of the solar sources other than Directional (DevParams::solarKind 1..3) from the photon's
-// event-0 block 0 (r0, r1, r2, r3); nonzero(b) returns the first non-zero number of its event-0 block b (0 if all four are).
-// Called only where solarKind != 0 (a scalar branch).
-//   1 RandomAzimuth (newPhotonStream_RandomAzimuth, monteCarloIllumination.f95:103-140): x, y, phi = 2 pi slot 2, mu = dir0[2]
-//   2 Flux (:142-176): x, y, mu = -sqrt(slot 2), phi = 2 pi slot 3.  A slot 2 of exactly 0 (mu = 0: the reference would launch
-//     that photon horizontally) is drawn again from blocks 1, 2, .., as the thermal surface launch does
-//   3 Spotlight (:178-216): every photon at the fractions (spotX, spotY), direction dir0
-// Direction cosines as makeDirectionCosines :1876-1894, with (cos, sin) of 2 pi u from sincos_2pi as the surface reflection
-// forms them: the library cosf / sinf of the thermal launch cost every solar kernel 4-5 more VGPRs (their large-argument
-// reduction), for arguments that never leave [0, 2 pi].
-template <class NonZero>
-__device__ __forceinline__ void solar_launch(const DevParams &p, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, NonZero nonzero,
-                                             double &fx, double &fy, float &dx, float &dy, float &dz) {
-  if (p.solarKind == 3) {
-    fx = p.spotX; fy = p.spotY;
-    dx = p.dir0[0]; dy = p.dir0[1]; dz = p.dir0[2];
-    return;
-  }
-  fx = (double)u01(r0);
-  fy = (double)u01(r1);
-  float mu, uPhi;  // the azimuth is 2 pi uPhi (getRandomReal * 2. * acos(-1.))
-  if (p.solarKind == 1) {
-    mu = p.dir0[2];
-    uPhi = u01(r2);
-  } else {
-    uint32_t uMu = r2;
-    for (uint32_t b = 1; uMu == 0u; b++) uMu = nonzero(b);  // (|mu| <= 2 FLT_MIN exactly where the number is 0)
-    mu = -sqrtf(u01(uMu));
-    uPhi = u01(r3);
-  }
-  const float sinTheta = sqrtf(1.0f - mu * mu);
-  float cphi, sphi;
-  sincos_2pi(uPhi, cphi, sphi);
-  dx = sinTheta * cphi; dy = sinTheta * sphi; dz = mu;
-}
-
-__device__ __forceinline__ unsigned long long to_fixed(double v) {
-  return (unsigned long long)__double2ll_rn(v * kTallyScale);
-}
-// photon weights and deposits lie in [0, 1]: a float times 2^32 is exact, so the conversion needs
-// no double arithmetic (1.0 itself does not fit 32 bits and is handled apart)
-__device__ __forceinline__ unsigned long long weight_to_fixed(float v) {
-  return v >= 1.0f ? (1ull << 32) : (unsigned long long)__float2uint_rn(v * 4294967296.0f);
-}
-// BRDF instantiations: a reflected weight may exceed 1.  The integer part goes to the high word, the
-// fraction to the low one -- exact: above 1 a float's fraction is a multiple of 2^-23.  Equal to weight_to_fixed on [0, 1] (and
-// for NaN); saturates below 2^31, where a single weight would overflow a tally bin on its own.
-__device__ __forceinline__ unsigned long long weight_to_fixed_wide(float v) {
-  if (!(v >= 1.0f)) return (unsigned long long)__float2uint_rn(v * 4294967296.0f);
-  if (!(v < 2147483520.0f)) return 2147483520ull << 32;  // (the largest float below 2^31)
-  const float hi = floorf(v);
-  return ((unsigned long long)hi << 32) + (unsigned long long)__float2uint_rn((v - hi) * 4294967296.0f);
-}
-template <bool WIDE>
-__device__ __forceinline__ unsigned long long weight_fixed(float v) { return WIDE ? weight_to_fixed_wide(v) : weight_to_fixed(v); }
-
-// findIndex(value, table) for cell edges: largest i with e[i] <= v, clamped to [0, n-1]
-// (src/numericUtilities.f95:207-260, no first guess).
-__device__ __forceinline__ int find_cell(const double *e, int n, double v) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (v >= e[mid]) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// findCDFIndex (src/numericUtilities.f95:317-348) on a strided slice of the running CDF:
-// smallest 1-based i with value <= t(i).
-__device__ __forceinline__ int find_cdf(const double *t, int n, long long stride, float vf) {
-  const double v = (double)vf;
-  int lo = 0, hi = n;
-  while (!(lo == n || hi <= lo + 1)) {
-    const int mid = (lo + hi) >> 1;
-    if (v > t[(long long)(mid - 1) * stride]) lo = mid; else hi = mid;
-  }
-  return hi;
-}
-
-// Layer-skipping walk: where a lane stands on a periodic axis after a stretch in which it crossed z faces only.
-// `origin` is the leg origin of the periodic image the stale x (or y) state belonged to, `xw` the position reached.
-// Folds xw into the domain (shifting the origin by whole domain lengths, as the wraps of the face-by-face walk
-// would have) and returns the 0-based cell; the edge table decides, the division is only the first guess.
-__device__ __forceinline__ int locate_periodic(const double *e, int n, double x0, double L, double invL, double invCell,
-                                               bool nearUniform, double &origin, double xw) {
-  const double shift = floor((xw - x0) * invL) * L;
-  origin -= shift;
-  xw -= shift;
-  if (!nearUniform) return find_cell(e, n, xw);
-  int i = min(max((int)((xw - x0) * invCell), 0), n - 1);  // right to within one cell (edges equally spaced to 1e-6 of a cell)
-  const double lo = e[i], hi = e[i + 1];
-  i += (xw >= hi && i < n - 1) ? 1 : 0;
-  i -= (xw < lo && i > 0) ? 1 : 0;
-  return i;
-}
-
-// computeSurfaceReflectance (src/surfaceProperties.f95:119-147) for the reference's Lambertian R (:153-161): the patch
-// under (x, y) on the surface description's own positions.  makePeriodic (:211-230) rounds the position to float;
-// findIndex is the mixed-kind bisection (src/numericUtilities.f95:262-315, no first guess).
-__device__ __forceinline__ float make_periodic_f(double a, double aMin, double aMax) {
-  float r = (float)a;
-  for (int guard = 0; guard < 65536; ++guard) {  // (the reference loops for ever where the period is below the float spacing of r)
-    if ((double)r <= aMax && (double)r > aMin) break;
-    if ((double)r > aMax) r = (float)((double)r - (aMax - aMin));
-    else if ((double)r == aMin) r = (float)aMax;
-    else r = (float)((double)r + (aMax - aMin));
-  }
-  return r;
-}
-__device__ __forceinline__ int find_index_mixed(const double *t, int n, float vf) {  // 1-based answer, 0 below the table
-  const double v = (double)vf;
-  int lo = 0, up = n;
-  while (!(lo == n || up <= lo + 1)) {
-    const int mid = (lo + up) >> 1;
-    if (v >= t[mid - 1]) lo = mid; else up = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ float surface_reflectance(const DevParams &p, double x, double y) {
-  const int xi = min(max(find_index_mixed(p.surfX, p.surfNumX, make_periodic_f(x, p.surfX[0], p.surfX[p.surfNumX - 1])), 1), p.surfNumX - 1);
-  const int yi = min(max(find_index_mixed(p.surfY, p.surfNumY, make_periodic_f(y, p.surfY[0], p.surfY[p.surfNumY - 1])), 1), p.surfNumY - 1);
-  return p.surfRefl[(xi - 1) + (p.surfNumX - 1) * (yi - 1)];
-}
 // the same patch look-up, returning the patch (BRDF surfaces).  (Not shared with surface_reflectance: written in terms of it, the
 // instrumented kernels' register allocation changed.)
 __device__ __forceinline__ int surface_patch(const DevParams &p, double x, double y) {
@@ -389,6 +108,14 @@ __device__ __forceinline__ float load_ext(const DevParams &p, const float *s_bgE
   if (!BRICK) return p.extWalk[r.dense];  // (the walk's copy: sign bit = outside the brick column's range, see FLY)
   return r.stored >= 0 ? p.ext[r.stored] : s_bgExt[iz];
 }
+
+// The slab a lane of trace_kernel deposits into: its workgroup's private one in LDS (PRIV), else its batch's in global memory
+// (tally_slab<0>: the batch's slab whatever the kernel -- the level, actinic and side bins, the combined volume deposits)
+template <int PRIV>
+__device__ __forceinline__ long long *tally_slab(long long *s_slab, const DevParams &p, uint32_t batch) {
+  return PRIV ? s_slab : p.slabs + (unsigned long long)batch * p.slabStride;
+}
+__device__ __forceinline__ void deposit(long long *bin, unsigned long long dep) { atomicAdd(reinterpret_cast<unsigned long long *>(bin), dep); }
 
 // PRIV: 0 tallies by global atomics, 1 LDS-private tally slab, 2 private slab and the optical grid in LDS too
 // INTEN: radiance by local estimation (computeIntensityContribution :1623-1832): every launch of an emitted
@@ -461,18 +188,20 @@ trace_kernel(const DevParams p) {
   const int nEdges = p.nx + p.ny + p.nz + 3;
   const int offZ0 = p.nx + p.ny + 2;
   const int ncol = p.nx * p.ny;
-  const int slabLen = PRIV ? ((LVL || ACT) ? 2 * ncol + ncol * p.nz : (int)p.slabStride) : 0;  // (LVL, ACT: the level and actinic bins stay in global memory)
+  // The starts of the slab parts (mcbrat_layout.h), from this kernel's own counts and flags: they fold per instantiation
+  const int slabLen = PRIV ? ((LVL || ACT) ? (int)slab_intensity_start<long long>(ncol, p.nz) : (int)p.slabStride) : 0;  // (LVL, ACT: the level and actinic bins stay in global memory)
   // ORD: the order bins behind [fluxUp | fluxDown | volume | intensity] of the batch slab (DevParams::numRecScatOrd)
-  const long long ordUp = ORD ? 2LL * ncol + (long long)ncol * p.nz + (long long)p.nDir * ncol : 0;
-  const long long ordDown = ORD ? ordUp + (long long)ncol * (p.numRecScatOrd + 1) : 0;
+  const long long ordUp = ORD ? slab_orders_start<long long>(ncol, p.nz, p.nDir, p.numRecScatOrd + 1, 0) : 0;
+  const long long ordDown = ORD ? slab_orders_start<long long>(ncol, p.nz, p.nDir, p.numRecScatOrd + 1, 1) : 0;
   // LVL: the level bins behind [fluxUp | fluxDown | volume] of the batch slab (a flux run: nothing else lies between)
-  const long long lvlUp = LVL ? 2LL * ncol + (long long)ncol * p.nz : 0;
-  const long long lvlDown = LVL ? lvlUp + (long long)ncol * (p.nz + 1) : 0;
-  const long long lvlDirect = DIRECT ? lvlDown + (long long)ncol * (p.nz + 1) : 0;  // DIRECT: the third part, behind levelDown
+  constexpr long long kFluxRun = 0;  // the LVL, ACT and SIDE kernels trace flux runs without orders: no directions, no order parts in front
+  const long long lvlUp = LVL ? slab_levels_start<long long>(ncol, p.nz, 0, kFluxRun, kFluxRun) : 0;
+  const long long lvlDown = LVL ? slab_levels_start<long long>(ncol, p.nz, 1, kFluxRun, kFluxRun) : 0;
+  const long long lvlDirect = DIRECT ? slab_levels_start<long long>(ncol, p.nz, 2, kFluxRun, kFluxRun) : 0;  // DIRECT: the third part, behind levelDown
   // ACT: the actinic bins behind the level parts (LVL: two of them; DIRECT and ACT are never together), or behind the volume
-  const long long actBins = ACT ? 2LL * ncol + (long long)ncol * p.nz + (LVL ? 2LL * ncol * (p.nz + 1) : 0) : 0;
+  const long long actBins = ACT ? slab_actinic_start<long long>(ncol, p.nz, LVL ? 2 : 0, kFluxRun, kFluxRun) : 0;
   // SIDE: the four side parts behind the two level parts (DIRECT and ACT are never together with it), ncol nz bins each
-  const long long sideBins = SIDE ? lvlDown + (long long)ncol * (p.nz + 1) : 0;
+  const long long sideBins = SIDE ? slab_side_start<long long>(ncol, p.nz, 2, 0, kFluxRun, kFluxRun) : 0;
   const long long sidePart = SIDE ? (long long)ncol * p.nz : 0;
   long long *s_slab = reinterpret_cast<long long *>(s_edge + nEdges);
   unsigned *s_cursor = reinterpret_cast<unsigned *>(s_slab + slabLen);
@@ -557,6 +286,8 @@ trace_kernel(const DevParams p) {
   int state = ST_DEAD;
   bool more = true;
   uint32_t idLo = 0, idHi = 0, event = 0, batch = 0;
+  // block (c0, c1) of the photon's Philox stream, for the rules of mcbrat_photon.h
+  auto rng = [&](uint32_t c0, uint32_t c1, uint32_t (&out)[4]) __attribute__((always_inline)) { philox4x32_10(c0, c1, idLo, idHi, p.seedLo, p.seedHi, out); };
   double px = 0, py = 0, pz = 0;      // leg origin (in the periodic image the walk is currently in)
   float dx = 0, dy = 0, dz = 1;       // direction cosines
   float ivx = 0, ivy = 0, ivz = 0;    // 1/direction
@@ -572,22 +303,22 @@ trace_kernel(const DevParams p) {
   unsigned long long pendDep = 0ull;
   unsigned nBadLane = 0;  // photons this lane dropped at a loop bound; added to *p.bad when the kernel ends
 #define MCBRAT_FLUSH_PENDING() do { if (!PRIV && pendCell >= 0) { \
-    atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + 2 * ncol + pendCell), pendDep); pendCell = -1; } } while (0)
+    deposit(tally_slab<0>(s_slab, p, batch) + 2 * ncol + pendCell, pendDep); pendCell = -1; } } while (0)
   // A photon that exceeds one of the loop bounds (DevParams::bad) is dropped and counted, as computeRT :562-563 does with
   // a photon whose step is not positive.
 #define MCBRAT_DROP_PHOTON(kind_) do { \
     if constexpr (DEBUG || kTestBounds) record_first_drop(p.bad, (kind_), 1u, idLo, idHi, state, event);  /* (which bound, which photon) */ \
-    if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{3, 0, 0, 0, nScat, nLegs, w}; \
+    if (DEBUG) record_fate(p, idLo, idHi, 3, 0, 0, 0, nScat, nLegs, w); \
     MCBRAT_FLUSH_PENDING(); \
     state = ST_DEAD; \
     nBadLane = count_drop(nBadLane, (kind_));  /* (added to *p.bad when the kernel ends: no atomic, no pointer in the loop) */ \
   } while (0)
   // LVL: one crossing of level `lev_` in column `col_` with the fixed-point weight `dep_`, into the batch's slab in global memory
 #define MCBRAT_LEVEL_DEPOSIT(base_, lev_, col_, dep_) \
-    atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + (base_) + (long long)ncol * (lev_) + (col_)), (dep_))
+    deposit(tally_slab<0>(s_slab, p, batch) + (base_) + (long long)ncol * (lev_) + (col_), (dep_))
   // ACT: one piece of path of length `len_` (km) in cell `cell_` carried at weight `w_`, into the batch's slab in global memory
 #define MCBRAT_ACTINIC_DEPOSIT(cell_, w_, len_) \
-    atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + actBins + (cell_)), weight_to_fixed((w_) * (len_) * p.actScale))
+    deposit(tally_slab<0>(s_slab, p, batch) + actBins + (cell_), weight_to_fixed((w_) * (len_) * p.actScale))
   // Layer-skipping walk (dense grids in global memory): while `lazy`, the lane is in a layer with one extinction
   // value, crosses z faces only (tnx = tny = FLT_MAX) and its x/y state (ex, ey, the x/y part of cell, the periodic
   // image of px/py) is stale; the event phase brings it up to date from the position before anything uses it.
@@ -933,21 +664,21 @@ trace_kernel(const DevParams p) {
     }
     if (contrib != 0.0f && (outTop || outBottom)) {  // (a truncated Legendre series can go negative: tallied as is)
       const int col = outTop ? rcell - ncol * (p.nz - 1) : rcell;
-      const long long ibase = 2LL * ncol + (long long)ncol * p.nz;  // [intensity nDir*ncol | byComponent (nc+1)*nDir*ncol | excess (nc+1)*nDir]
-      long long *slab = PRIV ? s_slab : p.slabs + (unsigned long long)rbatch * p.slabStride;
+      const long long ibase = slab_intensity_start<long long>(ncol, p.nz);  // [intensity nDir*ncol | byComponent (nc+1)*nDir*ncol | excess (nc+1)*nDir]
+      long long *slab = tally_slab<PRIV>(s_slab, p, rbatch);
       if (p.limitContrib && contrib > p.maxContrib) {  // :1815-1826 keep track of the excess per direction and component
         const unsigned long long ex = (unsigned long long)__double2ll_rn((double)(contrib - p.maxContrib) * kTallyScale);
-        atomicAdd(reinterpret_cast<unsigned long long *>(slab + ibase + (long long)(nc + 2) * p.nDir * ncol + (long long)rcomp * p.nDir + rd), ex);
+        deposit(slab + ibase + (long long)(nc + 2) * p.nDir * ncol + (long long)rcomp * p.nDir + rd, ex);
         contrib = p.maxContrib;
       }
       const unsigned long long dep = (unsigned long long)__double2ll_rn((double)contrib * kTallyScale);
-      atomicAdd(reinterpret_cast<unsigned long long *>(slab + ibase + (long long)rd * ncol + col), dep);
+      deposit(slab + ibase + (long long)rd * ncol + col, dep);
       if (p.limitContrib)
-        atomicAdd(reinterpret_cast<unsigned long long *>(slab + ibase + ((long long)(1 + rcomp) * p.nDir + rd) * ncol + col), dep);
+        deposit(slab + ibase + ((long long)(1 + rcomp) * p.nDir + rd) * ncol + col, dep);
       if constexpr (ORD) {  // intensityByScatOrd (limitIntensityContributions is refused together with orders)
         if (ord <= p.numRecScatOrd) {
-          const long long ordI = (2LL + p.nDir) * ncol + (long long)ncol * p.nz + 2LL * ncol * (p.numRecScatOrd + 1);  // (ordInten)
-          atomicAdd(reinterpret_cast<unsigned long long *>(slab + ordI + ((long long)ord * p.nDir + rd) * ncol + col), dep);
+          const long long ordI = slab_orders_start<long long>(ncol, p.nz, p.nDir, p.numRecScatOrd + 1, 2);  // (ordInten)
+          deposit(slab + ordI + ((long long)ord * p.nDir + rd) * ncol + col, dep);
         }
       }
     }
@@ -1058,18 +789,14 @@ trace_kernel(const DevParams p) {
       if (state == ST_TOP && doSurface) {
         // out the top: tally and free the lane
         const unsigned long long dep = weight_fixed<BRDF>(w);
-        if (PRIV) atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + (ix + p.nx * iy)), dep);
-        else atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + (ix + p.nx * iy)), dep);
+        deposit(tally_slab<PRIV>(s_slab, p, batch) + (ix + p.nx * iy), dep);
         if constexpr (ORD) {  // fluxUpByScatOrd: the order the photon leaves with
-          if (nScat <= p.numRecScatOrd) {
-            long long *slab = PRIV ? s_slab : p.slabs + (unsigned long long)batch * p.slabStride;
-            atomicAdd(reinterpret_cast<unsigned long long *>(slab + ordUp + (long long)ncol * nScat + (ix + p.nx * iy)), dep);
-          }
+          if (nScat <= p.numRecScatOrd) deposit(tally_slab<PRIV>(s_slab, p, batch) + ordUp + (long long)ncol * nScat + (ix + p.nx * iy), dep);
         }
         if constexpr (LVL) MCBRAT_LEVEL_DEPOSIT(lvlUp, p.nz, ix + p.nx * iy, dep);  // the top exit is an upward crossing of level nz
         if (DEBUG) {
           cTop++;
-          if (p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{0, ix + 1, iy + 1, p.nz + 1, nScat, nLegs, w};
+          record_fate(p, idLo, idHi, 0, ix + 1, iy + 1, p.nz + 1, nScat, nLegs, w);
         }
         MCBRAT_FLUSH_PENDING();
         state = ST_DEAD;
@@ -1082,59 +809,52 @@ trace_kernel(const DevParams p) {
         iz = 0;
         cell = ix + p.nx * iy;
         const unsigned long long dep = weight_fixed<BRDF>(w);
-        if (PRIV) atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + ncol + (ix + p.nx * iy)), dep);
-        else atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + ncol + (ix + p.nx * iy)), dep);
+        deposit(tally_slab<PRIV>(s_slab, p, batch) + ncol + (ix + p.nx * iy), dep);
         if constexpr (ORD) {  // fluxDownByScatOrd: the order before the reflection (computeRT :635-643)
-          if (nScat <= p.numRecScatOrd) {
-            long long *slab = PRIV ? s_slab : p.slabs + (unsigned long long)batch * p.slabStride;
-            atomicAdd(reinterpret_cast<unsigned long long *>(slab + ordDown + (long long)ncol * nScat + (ix + p.nx * iy)), dep);
-          }
+          if (nScat <= p.numRecScatOrd) deposit(tally_slab<PRIV>(s_slab, p, batch) + ordDown + (long long)ncol * nScat + (ix + p.nx * iy), dep);
         }
         if constexpr (DIRECT) MCBRAT_LEVEL_DEPOSIT(event == 1u ? lvlDirect : lvlDown, 0, ix + p.nx * iy, dep);  // (still direct: the reflection below ends it)
         else if constexpr (LVL) MCBRAT_LEVEL_DEPOSIT(lvlDown, 0, ix + p.nx * iy, dep);  // the arrival is a downward crossing of level 0
-        if (DEBUG && p.traceBuf && ((((unsigned long long)idHi << 32) | idLo) - p.firstPhoton) == p.traceIndex && nScat < p.traceCap) {
+        if (DEBUG && p.traceBuf && photon_index(p, idLo, idHi) == p.traceIndex && nScat < p.traceCap) {
           double *t = p.traceBuf + 12 * nScat;  // (development aid: the landing point of the traced photon, marked by a negative layer)
           t[0] = event; t[1] = ix + 1; t[2] = iy + 1; t[3] = -1; t[4] = px; t[5] = py; t[6] = pz;
           t[7] = dx; t[8] = dy; t[9] = dz; t[10] = extCur; t[11] = w;
         }
         nScat++;
         if (DEBUG) cSurf++;
+        // Cosine of the Lambertian reflection: sqrt(X) of the leg's block; below 2 FLT_MIN, Z, then blocks 2.. of the leg's event.
+        // (The same lines stand in trace_block_kernel, mcbrat_blockwalk.hip: as one function of mcbrat_photon.h they cost this
+        // kernel's general instantiation 16 bytes of scratch and the 768-lane block walk two registers, however the function was shaped.)
         float mu = sqrtf(uX);
         if (!(fabsf(mu) > 2.0f * FLT_MIN)) {
           mu = sqrtf(uZ);
           uint32_t r[4];
           for (uint32_t j = 0; !(fabsf(mu) > 2.0f * FLT_MIN); j++) {
-            if ((j & 3u) == 0) philox4x32_10(event, 2u + (j >> 2), idLo, idHi, p.seedLo, p.seedHi, r);
+            if ((j & 3u) == 0) rng(event, 2u + (j >> 2), r);
             mu = sqrtf(u01(pick4(r, j & 3u)));
           }
         }
         const float wIn = w;
         int patch = 0;
-        float ox = 0.0f, oy = 0.0f;
-        if constexpr (BRDF) {  // the Lambertian draw of the direction (below), the weight times R(d_in, d_out) of the patch
-          const float sinTheta = sqrtf(1.0f - mu * mu);
-          float cphi, sphi;
-          sincos_2pi(uY, cphi, sphi);
-          ox = sinTheta * cphi; oy = sinTheta * sphi;
+        float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+        if constexpr (BRDF) {  // the Lambertian draw of the direction, the weight times R(d_in, d_out) of the patch
+          lambert_direction(mu, uY, ox, oy, oz);
           patch = surface_patch(p, px, py);
-          w = w * surface_brdf(p, patch, dx, dy, dz, ox, oy, mu);
+          w = w * surface_brdf(p, patch, dx, dy, dz, ox, oy, oz);
           // local estimates from a BRDF reflection: the weight before it and R(d_in, d_view) / pi (iFlag -1; iEntry: the patch).
           // Also when R(d_in, d_out) = 0 ends the photon: the estimate does not depend on the direction drawn.
           if (INTEN) { iFlag = -1; iW = wIn; iDx = dx; iDy = dy; iDz = dz; iEntry = patch; }
         } else if (surfaceDescription) w = w * surface_reflectance(p, px, py);  // useSurfaceBDRF :667-670
         else w = (float)((double)w * (double)p.albedo);              // :673
         if (w <= FLT_MIN) {
-          if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{1, ix + 1, iy + 1, 1, nScat, nLegs, wIn};
+          if (DEBUG) record_fate(p, idLo, idHi, 1, ix + 1, iy + 1, 1, nScat, nLegs, wIn);
           MCBRAT_FLUSH_PENDING();
           state = ST_DEAD;
         } else if constexpr (BRDF) {
-          dx = ox; dy = oy; dz = mu;
+          dx = ox; dy = oy; dz = oz;
           needLeg = true;
         } else {
-          const float sinTheta = sqrtf(1.0f - mu * mu);  // makeDirectionCosines(mu, 2 pi Y) :1876-1894
-          float cphi, sphi;
-          sincos_2pi(uY, cphi, sphi);
-          dx = sinTheta * cphi; dy = sinTheta * sphi; dz = mu;
+          lambert_direction(mu, uY, dx, dy, dz);
           needLeg = true;
           if constexpr (LVL) MCBRAT_LEVEL_DEPOSIT(lvlUp, 0, ix + p.nx * iy, weight_to_fixed(w));  // the reflected photon crosses level 0 upward
           if (INTEN) { iFlag = 1; iW = w; }  // :680-702 reflected weight, Lambertian
@@ -1182,64 +902,12 @@ trace_kernel(const DevParams p) {
             const unsigned long long id = p.firstPhoton + myIdx;
             idLo = (uint32_t)id; idHi = (uint32_t)(id >> 32);
             event = 0; nScat = 0; nLegs = 0;
-            uint32_t r[4];
-            philox4x32_10(0u, 0u, idLo, idHi, p.seedLo, p.seedHi, r);
             double fx, fy, fz;  // fractional launch position in [0,1]
-            if (!EMIT) {
+            if (!EMIT) {  // (the SPEC kernels' only kind of solar source: Directional)
               fz = 0.0;
-              if (SPEC != 0 || p.solarKind == 0) {  // newPhotonStream_Directional, monteCarloIllumination.f95:88-96 (the SPEC kernels' only kind)
-                fx = (double)u01(r[0]);
-                fy = (double)u01(r[1]);
-                dx = p.dir0[0]; dy = p.dir0[1]; dz = p.dir0[2];
-              } else {  // RandomAzimuth, Flux, Spotlight (wave-uniform)
-                solar_launch(p, r[0], r[1], r[2], r[3], [&](uint32_t b) {
-                  uint32_t o[4];
-                  philox4x32_10(0u, b, idLo, idHi, p.seedLo, p.seedHi, o);
-                  return o[0] ? o[0] : (o[1] ? o[1] : (o[2] ? o[2] : o[3]));
-                }, fx, fy, dx, dy, dz);
-              }
-            } else {  // newPhotonStream_BBEmission :481-516
-              float mu = 0.f, phi = 0.f;
-              const float sel = u01(r[0]);
-              if ((double)sel > p.fracAtms) {  // surface emission :484-493
-                fx = (double)u01(r[1]);
-                fy = (double)u01(r[2]);
-                fz = 0.0;
-                uint32_t r1[4];
-                for (uint32_t j = 0;; j++) {
-                  if ((j & 3u) == 0) philox4x32_10(0u, 1u + (j >> 2), idLo, idHi, p.seedLo, p.seedHi, r1);
-                  mu = sqrtf(u01(pick4(r1, j & 3u)));
-                  if (fabsf(mu) > 2.0f * FLT_MIN) break;
-                }
-                phi = (u01(r[3]) * 2.0f) * 3.14159274f;  // * 2. * acos(-1.)
-              } else {  // atmosphere :495-510: one uniform picks level, row and voxel from one running CDF
-                const float rn = u01(r[1]);
-                const long long nxy = (long long)p.nx * p.ny;
-                const int ik = find_cdf(p.voxelCDF + ((long long)p.nx - 1) + (long long)p.nx * (p.ny - 1), p.nz, nxy, rn);
-                const int ij = find_cdf(p.voxelCDF + ((long long)p.nx - 1) + nxy * (ik - 1), p.ny, p.nx, rn);
-                const int ii = find_cdf(p.voxelCDF + (long long)p.nx * ((ij - 1) + (long long)p.ny * (ik - 1)), p.nx, 1, rn);
-                uint32_t r1[4];
-                philox4x32_10(0u, 1u, idLo, idHi, p.seedLo, p.seedHi, r1);
-                fz = ((double)(ik - 1) * 1.0 / (double)p.nz) + (double)(u01(r[2]) / (float)p.nz);
-                if (ik == 1 && fz == 0.0) fz = 2.220446049250313e-16;  // spacing(1.0_8)
-                if (ik == p.nz && fz > 1.0 - 2.0 * 2.220446049250313e-16) fz = fz - 2.0 * 2.220446049250313e-16;
-                fx = ((double)(ii - 1) * 1.0 / (double)p.nx) + (double)(u01(r[3]) * (1.0f / (float)p.nx));
-                fy = ((double)(ij - 1) * 1.0 / (double)p.ny) + (double)(u01(r1[0]) * (1.0f / (float)p.ny));
-                uint32_t r2[4];
-                for (uint32_t j = 0;; j++) {
-                  uint32_t uu;
-                  if (j < 2) uu = j ? r1[3] : r1[2];
-                  else {
-                    if (((j - 2) & 3u) == 0) philox4x32_10(0u, 2u + ((j - 2) >> 2), idLo, idHi, p.seedLo, p.seedHi, r2);
-                    uu = pick4(r2, (j - 2) & 3u);
-                  }
-                  mu = 1.0f - (2.0f * u01(uu));
-                  if (fabsf(mu) > 2.0f * FLT_MIN) break;
-                }
-                phi = (u01(r1[1]) * 2.0f) * 3.14159274f;
-              }
-              const float sinTheta = sqrtf(1.0f - mu * mu);  // makeDirectionCosines :1876-1894
-              dx = sinTheta * cosf(phi); dy = sinTheta * sinf(phi); dz = mu;
+              launch_solar(p, SPEC != 0 || p.solarKind == 0, rng, fx, fy, dx, dy, dz);
+            } else {
+              launch_emission(p, rng, [&](float rn, int &ik, int &ij) { emission_level_row(p, rn, ik, ij); }, fx, fy, fz, dx, dy, dz);
             }
             w = 1.0f;
             px = p.x0 + fx * (p.xMax - p.x0);  // :480-482
@@ -1253,22 +921,13 @@ trace_kernel(const DevParams p) {
             }
             if (!EMIT) {
               pz = p.zLaunch; iz = p.izLaunch;
-            } else if (p.zRegular) {  // :485-486
-              pz = p.z0 + fz * (p.zMax - p.z0);
-              iz = min((int)((pz - p.z0) / ((p.zMax - p.z0) / (double)p.nz)), p.nz - 1);
-            } else {  // :491-493 layer-index fraction
-              const double t = (fz - p.z0) * (double)p.nz;
-              const double fl = floor(t);
-              iz = min((int)fl, p.nz - 1);
-              pz = s_edge[offZ + iz] + (t - fl) * (s_edge[offZ + iz + 1] - s_edge[offZ + iz]);
+            } else {
+              launch_height(p, p.zRegular != 0, s_edge + offZ, fz, pz, iz);
             }
             cell = ix + p.nx * (iy + p.ny * iz);
             extCur = gridLds ? s_ext[cell] : load_ext<BRICK>(p, s_bgExt, locate_cell<BRICK>(p, ix, iy, iz), iz);
             brickId = -1;
-            if (EMIT && p.lwFlag && pz > 0.0) {  // :504-508 emission counts as negative absorption
-              if (PRIV) atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + 2 * ncol + cell), to_fixed(-1.0));
-              else atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + 2 * ncol + cell), to_fixed(-1.0));
-            }
+            if (EMIT && p.lwFlag && pz > 0.0) deposit(tally_slab<PRIV>(s_slab, p, batch) + 2 * ncol + cell, to_fixed(-1.0));  // :504-508 emission counts as negative absorption
             if constexpr (LVL) {
               // a solar launch lies just inside the top cell: it counts as the downward crossing of level nz the walk never makes;
               // a surface-emitted thermal photon (fz = 0 exactly: an atmospheric launch has fz > 0) crosses level 0 upward
@@ -1293,7 +952,7 @@ trace_kernel(const DevParams p) {
           py = py + s * (double)dy;
           pz = pz + s * (double)dz;
         }
-        if (DEBUG && p.traceBuf && ((((unsigned long long)idHi << 32) | idLo) - p.firstPhoton) == p.traceIndex && nScat < p.traceCap) {
+        if (DEBUG && p.traceBuf && photon_index(p, idLo, idHi) == p.traceIndex && nScat < p.traceCap) {
           double *t = p.traceBuf + 12 * nScat;  // one record per collision of the traced photon
           t[0] = event; t[1] = ix + 1; t[2] = iy + 1; t[3] = iz + 1; t[4] = px; t[5] = py; t[6] = pz;
           t[7] = dx; t[8] = dy; t[9] = dz; t[10] = tau; t[11] = w;
@@ -1321,7 +980,7 @@ trace_kernel(const DevParams p) {
           ssa = __uint_as_float(c ? rc.z : rc.y);
           pfEntry = (int)(c ? (rc.w >> 16) : (rc.w & 0xffffu));
         } else {
-          if (nc > 1) {
+          if (nc > 1) {  // (the component pick: one of the HOT ROWS below)
             for (int k = 0; k < nc - 1; k++)
               if (uZ >= cumA[(long long)k * nvox + oc]) c = k + 1;
           }
@@ -1330,13 +989,14 @@ trace_kernel(const DevParams p) {
         }
         if (ssa < 1.0f) {  // absorption :765-771
           const unsigned long long dep = weight_fixed<BRDF>(w * (1.0f - ssa));
-          if (PRIV) atomicAdd(reinterpret_cast<unsigned long long *>(s_slab + 2 * ncol + cell), dep);
 #ifdef MCBRAT_NO_COMBINE  // A/B: every deposit goes out as its own atomic add
-          else atomicAdd(reinterpret_cast<unsigned long long *>(p.slabs + (unsigned long long)batch * p.slabStride + 2 * ncol + cell), dep);
+          constexpr bool combine = false;
 #else
+          constexpr bool combine = !PRIV;  // (the pending deposit above: tallies in global memory)
+#endif
+          if (!combine) deposit(tally_slab<PRIV>(s_slab, p, batch) + 2 * ncol + cell, dep);
           else if (cell == pendCell) pendDep += dep;
           else { MCBRAT_FLUSH_PENDING(); pendCell = cell; pendDep = dep; }
-#endif
           w = w * ssa;
           if (DEBUG) cAbs++;
         }
@@ -1344,11 +1004,15 @@ trace_kernel(const DevParams p) {
           iFlag = 3 + c; iW = w; iDx = dx; iDy = dy; iDz = dz;
           iEntry = s_fwdOffset[c] + pfEntry * s_fwdNAngles[c];
         }
+        // HOT ROWS.  The component pick above and, from here to the leg set-up, roulette, scattering angle, new direction and the
+        // leg's draws with the zero-cosine rule stand in trace_block_kernel too (mcbrat_blockwalk.hip, HOT ROWS): a change to one
+        // of them is made in both.  (As functions of mcbrat_photon.h called from here, they changed this kernel's register
+        // allocation into one whose radiance-by-order instantiations misreport dropped photons: DESIGN.md section 4.18.)
         if (useRR && w < 0.5f) {  // Russian roulette :805-811, RussianRouletteW = 1
           float uR = uZ;  // one component: Z decides nothing at the component pick and serves here (no second block)
           if (nc != 1) {  // (wave-uniform)
             uint32_t r1[4];
-            philox4x32_10(event, 1u, idLo, idHi, p.seedLo, p.seedHi, r1);
+            rng(event, 1u, r1);
             uR = u01(r1[1]);
           }
           if (uR >= w) { w = 0.0f; if (DEBUG) cKill++; }
@@ -1356,18 +1020,17 @@ trace_kernel(const DevParams p) {
         }
         STAMP(2);
         if (w <= FLT_MIN) {  // :812
-          if (DEBUG && p.fates) p.fates[(((unsigned long long)idHi << 32) | idLo) - p.firstPhoton] = mcbrat_fate{2, ix + 1, iy + 1, iz + 1, nScat, nLegs, 0.0f};
+          if (DEBUG) record_fate(p, idLo, idHi, 2, ix + 1, iy + 1, iz + 1, nScat, nLegs, 0.0f);
           MCBRAT_FLUSH_PENDING();
           state = ST_DEAD;
         } else {
-          // computeScatteringAngle :1594-1621 (table point count N, floor-type lookup as written)
-          const int pf = pfEntry;
           const int n = s_tblNSteps[c];
-          const float *t = tbl + s_tblOffset[c] + (long long)pf * n;
+          // computeScatteringAngle :1594-1621 (table point count N, floor-type lookup as written)
+          const float *t = tbl + s_tblOffset[c] + (long long)pfEntry * n;
           const int ai = (int)(uX * (float)n) + 1;
           float ang;
           if (ai < n) {
-            #ifdef MCBRAT_PRECISE_MATH
+#ifdef MCBRAT_PRECISE_MATH
             const float left = uX - (float)(ai - 1) / (float)n;
 #else
             const float left = uX - (float)(ai - 1) * s_tblInvN[c];
@@ -1513,13 +1176,12 @@ trace_kernel(const DevParams p) {
 #endif
         if (DEBUG) cLegs++;
         uint32_t r[4];
-        philox4x32_10(event, 0u, idLo, idHi, p.seedLo, p.seedHi, r);
+        rng(event, 0u, r);
 #ifdef MCBRAT_PRECISE_MATH
         tau = -logf(fmaxf(FLT_MIN, u01(r[0])));
 #else
-        tau = -0.693147182f * __builtin_amdgcn_logf(fmaxf(FLT_MIN, u01(r[0])));
+        tau = -0.693147182f * __builtin_amdgcn_logf(fmaxf(FLT_MIN, u01(r[0])));  // :554 (hardware log2 * ln 2; u >= 2^-32, no denormals)
 #endif
-         // :554 (hardware log2 * ln 2; u >= 2^-32, no denormals)
         uX = u01(r[1]); uY = u01(r[2]); uZ = u01(r[3]);
         acc = 0.0f; tcur = 0.0f;
         // opticalProperties.f95:1690-1712: side 1 where direction >= 0; huge step for a zero cosine
@@ -1773,38 +1435,16 @@ trace_kernel(const DevParams p) {
     }
 
     if (!PRIV) break;
-    // PRIV: flush this unit's private tallies into the batch slab, once
-    __syncthreads();
-    for (int i = threadIdx.x; i < slabLen; i += BLOCK) {
-      const long long v = s_slab[i];
-      if (v != 0) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(unitSlab + i), (unsigned long long)v);
-        s_slab[i] = 0;
-      }
-    }
-    if (threadIdx.x == 0) s_cursor[0] = 0;
-    __syncthreads();
+    flush_unit_slab<BLOCK>(s_slab, slabLen, unitSlab, s_cursor);  // PRIV: this unit's private tallies into the batch slab, once
   }
 
   publish_drops(p.bad, nBadLane);
 #ifdef MCBRAT_STAMPS
   if (DEBUG && p.counters && lane == 0) for (int i = 0; i < 9; i++) atomicAdd(p.counters + 16 + i, s_stamp[threadIdx.x >> 6][i]);
 #endif
-  if (DEBUG && p.counters) {
-    atomicAdd(p.counters + 0, (unsigned long long)cLegs);
-    atomicAdd(p.counters + 1, (unsigned long long)cCross);
-    atomicAdd(p.counters + 2, (unsigned long long)cColl);
-    atomicAdd(p.counters + 3, (unsigned long long)cAbs);
-    atomicAdd(p.counters + 4, (unsigned long long)cTop);
-    atomicAdd(p.counters + 5, (unsigned long long)cSurf);
-    atomicAdd(p.counters + 6, (unsigned long long)cKill);
-    atomicAdd(p.counters + 7, (unsigned long long)cSurv);
-    if (lane == 0) {
-      atomicAdd(p.counters + 8, wWalkIters); atomicAdd(p.counters + 9, wWalkLanes);
-      atomicAdd(p.counters + 10, wEventPhases); atomicAdd(p.counters + 11, wEventLanes);
-      atomicAdd(p.counters + 12, wLaunchPhases); atomicAdd(p.counters + 13, wSurfPhases);
-    }
-  }
+  if (DEBUG && p.counters)
+    publish_counters(p.counters, lane == 0, cLegs, cCross, cColl, cAbs, cTop, cSurf, cKill, cSurv, wWalkIters, wWalkLanes, wEventPhases, wEventLanes,
+                     wLaunchPhases, wSurfPhases);
 }
 
 // the generator itself, for its known-answer test (mcbrat_philox4x32_10): in[6 i ..] = counter[4], key[2]; out[4 i ..] = block

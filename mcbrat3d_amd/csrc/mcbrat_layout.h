@@ -1,8 +1,8 @@
 // The tally layout: where every part lies in one batch's tally slab, in the moment arrays (and the last batch's results, which
 // have the moments' layout) and in the per-batch scalar scratch of the finish kernels.  This header is the definition: the host
 // library sizes and reads its buffers by it, the finish kernels index by it (FinishParams carries a TallyLayout by value), and
-// tests/tally_layout_dump.cpp prints it.  Plain C++17, no HIP.  (trace_kernel keeps lines of its own for its slab starts -- they
-// are folded per template instantiation; tests/test_tally_layout_host.py holds them to this header.)
+// tests/tally_layout_dump.cpp prints it.  Plain C++17, no HIP.  trace_kernel takes its slab starts from the slab_*_start functions
+// below, from its own counts and template flags, so that they fold per instantiation.
 //
 // One batch's slab, in elements (long long bins), nLvl = nz + 1:
 //   [fluxUp ncol | fluxDown ncol | volume ncol nz | intensity ncol nDir |
@@ -49,7 +49,40 @@ constexpr int64_t tally_times(int64_t a, int64_t b) {
   return a <= 0 || b <= 0 ? 0 : (a > kTallySaturated / b ? kTallySaturated : a * b);
 }
 
-// One forward pass: every part starts where the one before it ended.
+// A count that saturates instead of overflowing: the number type of the host's layout.
+struct TallyCount {
+  int64_t v;
+  constexpr TallyCount(int64_t n) : v(n < 0 ? 0 : n) {}
+  friend constexpr TallyCount operator*(TallyCount a, TallyCount b) { return tally_times(a.v, b.v); }
+  friend constexpr TallyCount operator+(TallyCount a, TallyCount b) { return b.v > kTallySaturated - a.v ? kTallySaturated : a.v + b.v; }
+};
+
+// Where the parts of one batch's slab start: every part starts where the one before it ends.  Functions of counts in a number
+// type N -- TallyCount for tally_layout(), a plain 64-bit integer for trace_kernel, which calls them with its own counts and
+// template flags (the host has seen to it that nothing overflows there) and must not pay for the saturation.
+//   nComp: nc + 1 with limitIntensityContributions, else 0; nOrd: numRecScatOrd + 1, 0 when off; levelParts: 0, 2, or 3 with the
+//   direct tally; nAct: nz with the actinic flux, else 0.  Orders are refused with limitIntensityContributions (nComp defaults
+//   to 0); the level, actinic and side bins belong to flux runs without orders, and trace_kernel says so at its calls (nDir = nOrd = 0).
+template <class N> constexpr N slab_volume_start(N ncol) { return N(2) * ncol; }
+template <class N> constexpr N slab_intensity_start(N ncol, N nz) { return slab_volume_start(ncol) + ncol * nz; }
+template <class N> constexpr N slab_by_component_start(N ncol, N nz, N nDir) { return slab_intensity_start(ncol, nz) + ncol * nDir; }
+template <class N> constexpr N slab_excess_start(N ncol, N nz, N nDir, N nComp) { return slab_by_component_start(ncol, nz, nDir) + ncol * nDir * nComp; }
+// the order parts: 0 fluxUp by order, 1 fluxDown by order, 2 intensity by order (ncol nOrd bins each, the last nDir times that)
+template <class N> constexpr N slab_orders_start(N ncol, N nz, N nDir, N nOrd, int part, N nComp = N(0)) {
+  return slab_excess_start(ncol, nz, nDir, nComp) + nDir * nComp + N(part) * ncol * nOrd;
+}
+// the level parts: 0 up, 1 down (with the direct tally: diffuse), 2 direct (ncol (nz + 1) bins each)
+template <class N> constexpr N slab_levels_start(N ncol, N nz, int part, N nDir, N nOrd, N nComp = N(0)) {
+  return slab_orders_start(ncol, nz, nDir, nOrd, 0, nComp) + ncol * (N(2) + nDir) * nOrd + N(part) * ncol * (nz + N(1));
+}
+template <class N> constexpr N slab_actinic_start(N ncol, N nz, int levelParts, N nDir, N nOrd, N nComp = N(0)) {
+  return slab_levels_start(ncol, nz, levelParts, nDir, nOrd, nComp);
+}
+template <class N> constexpr N slab_side_start(N ncol, N nz, int levelParts, N nAct, N nDir, N nOrd, N nComp = N(0)) {
+  return slab_actinic_start(ncol, nz, levelParts, nDir, nOrd, nComp) + ncol * nAct;
+}
+
+// The slab through the functions above; the moments and the scalar scratch in one forward pass each.
 inline TallyLayout tally_layout(const TallyShape &s) {
   int64_t at = 0;
   const auto take = [&at](int64_t n) {  // -> where the part of n elements starts
@@ -64,19 +97,22 @@ inline TallyLayout tally_layout(const TallyShape &s) {
   const int64_t nAct = s.actinic ? nz : 0;
   const int64_t nSide = s.side ? times(4, nz) : 0;  // (layers of the four side parts)
   TallyLayout l{};
-  l.slabFluxUp = take(ncol);
-  l.slabFluxDown = take(ncol);
-  l.slabVolume = take(times(ncol, nz));
-  l.slabIntensity = take(times(ncol, nDir));
-  l.slabByComponent = take(times(ncol, nDir, nComp));
-  l.slabExcess = take(times(nDir, nComp));
-  l.slabOrders = take(times(ncol, 2 + nDir, nOrd));
-  l.slabLds = at;
-  l.slabLevels = take(times(ncol, nLvl, direct ? 3 : 2));
-  l.slabActinic = take(times(ncol, nAct));
-  l.slabSide = take(times(ncol, nSide));
-  l.slabStride = at;
-  at = 0;
+  {
+    using C = TallyCount;
+    const C cCol = ncol, cNz = nz, cDir = nDir, cOrd = nOrd, cComp = nComp;
+    const int levelParts = s.levels ? (direct ? 3 : 2) : 0;
+    l.slabFluxUp = 0;
+    l.slabFluxDown = ncol;
+    l.slabVolume = slab_volume_start(cCol).v;
+    l.slabIntensity = slab_intensity_start(cCol, cNz).v;
+    l.slabByComponent = slab_by_component_start(cCol, cNz, cDir).v;
+    l.slabExcess = slab_excess_start(cCol, cNz, cDir, cComp).v;
+    l.slabOrders = slab_orders_start(cCol, cNz, cDir, cOrd, 0, cComp).v;
+    l.slabLds = l.slabLevels = slab_levels_start(cCol, cNz, 0, cDir, cOrd, cComp).v;
+    l.slabActinic = slab_actinic_start(cCol, cNz, levelParts, cDir, cOrd, cComp).v;
+    l.slabSide = slab_side_start(cCol, cNz, levelParts, C(nAct), cDir, cOrd, cComp).v;
+    l.slabStride = (C(l.slabSide) + cCol * C(nSide)).v;
+  }
   l.momMeans = take(3);
   l.momColumns = take(times(3, ncol));
   l.momProfile = take(nz);

@@ -65,7 +65,7 @@ typedef struct {
  * BASELINE north_star substitutes.  key = seed, counter = (event, block,
  * photon id lo, photon id hi).  event 0 is the launch, event e >= 1 the e-th
  * leg; each role has a fixed slot (see draw() call sites in mcbrat_oracle.c and
- * the same table in mcbrat3d_amd/csrc/mcbrat_kernels.hip), so the HIP kernel and
+ * the same table in mcbrat3d_amd/csrc/mcbrat_photon.h), so the HIP kernel and
  * this oracle consume identical uniforms for identical roles. */
 typedef struct {
   int32_t mode;

@@ -3,8 +3,8 @@
 no GPU needed).  usage: python scripts/kernel_resources.py [filter-substring] [-- extra hipcc flags]
        python scripts/kernel_resources.py --diff OTHER.s [--asm THIS.s]
 --diff: compares this tree's device assembly (--asm: one compiled before, instead of compiling) with another, kernel symbol by
-kernel symbol: the instruction text between the symbol's label and its end, and VGPRs, SGPRs, scratch and LDS.  Exit status 1
-when a common symbol differs."""
+kernel symbol: the instruction text between the symbol's label and its end, and VGPRs, SGPRs, scratch, LDS and the spill counts
+(both values of every symbol whose resources differ are printed).  Exit status 1 when a common symbol differs."""
 import os
 import re
 import subprocess
@@ -16,13 +16,14 @@ CSRC = os.path.join(ROOT, "mcbrat3d_amd", "csrc")
 
 
 def kernels_of(path):
-    """-> {symbol: (text from the label to the function's end, (vgpr, sgpr, scratch, lds))} of an assembly file"""
+    """-> {symbol: (text from the label to the function's end, (vgpr, sgpr, scratch, lds, spilled sgpr, spilled vgpr))} of an assembly file"""
     text = open(path).read()
     res = {}
     for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, re.S):
         blk = m.group(0)
         g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-        res[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size"))
+        res[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size"),
+                                                            g("sgpr_spill_count"), g("vgpr_spill_count"))
     out = {}
     for m in re.finditer(r"^(\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
         if m.group(1) in res:
@@ -42,7 +43,11 @@ def diff(this, other):
         for n in dem(names) if names else []:
             if n:
                 print("%s: %s" % (title, n))
-    print("kernels: %d here, %d in the other, %d common, %d of them differ" % (len(a), len(b), len(common), len(differ)))
+    fmt = "vgpr %d sgpr %d scratch %d lds %d spill_sgpr %d spill_vgpr %d"
+    changed = [k for k in differ if a[k][1] != b[k][1]]
+    for k, n in zip(changed, dem(changed) if changed else []):
+        print("resources: %s\n  here:  %s\n  other: %s" % (n, fmt % a[k][1], fmt % b[k][1]))
+    print("kernels: %d here, %d in the other, %d common, %d of them differ, %d of those in resources" % (len(a), len(b), len(common), len(differ), len(changed)))
     return 1 if differ else 0
 
 

@@ -3,7 +3,7 @@ the GPU.  The oracle has no such sources, so
 
 1. the launch is pinned photon by photon: over a wide, nearly transparent slab every unscattered photon lands in the
    column a numpy mirror of its launch predicts (Philox4x32-10 on the photon's event-0 counter, the float32 uniforms and
-   direction algebra of solar_launch, mcbrat_kernels.hip), on a regular and on an irregular x/y grid, on both walks;
+   direction algebra of solar_launch, mcbrat_photon.h), on a regular and on an irregular x/y grid, on both walks;
 2. the two walks agree photon by photon on the step cloud, as they do for the Directional source;
 3. the physics is held to transport theory with the solvers of tests/test_analytic.py: isotropic incidence over an
    absorbing slab (2 E3), over Henyey-Greenstein slabs (matrix doubling) and its reflected radiance; a random azimuth

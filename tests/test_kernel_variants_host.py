@@ -6,6 +6,7 @@ stub the library returns; the enumeration and its pruning rules are at the top o
 tests/kernel_variants_dump.cpp, which includes nothing but the header, is compiled with the host C++ compiler and picks for the
 same inputs.  No GPU, and nothing is loaded into Python: the sanitizers run a stand-alone program."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -388,3 +389,62 @@ def test_the_enumerated_launches_pass_the_rules(picked):
     that pass the rules always find their kernel in the table"""
     refused = {l.split("!", 1)[1] for l in picked if "!" in l}
     assert all(r.startswith("computeRadiativeTransfer: event counters / photon fates are not available together with") for r in refused) and len(refused) == 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the two kernel files the variants are instantiated from, and the header of what they share (mcbrat_photon.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+CSRC = os.path.join(ROOT, "mcbrat3d_amd", "csrc")
+
+
+def test_the_block_walk_is_a_translation_unit_of_its_own(tmp_path):
+    """mcbrat_blockwalk.hip declares what it uses: alone in a translation unit (nothing instantiated) the device compiler accepts it"""
+    from mcbrat3d_amd import build
+    tu = tmp_path / "blockwalk_alone.hip"
+    tu.write_text('#include "mcbrat_blockwalk.hip"\n')
+    subprocess.run([build.hipcc(), "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only", "-I", CSRC, str(tu)],
+                   check=True, timeout=300)
+
+
+# one distinctive expression of every rule both kernels take from mcbrat_photon.h: written there, and in neither kernel file
+SHARED_RULES = {
+    "source sampling, solar": "uMu = o[0] ? o[0]",
+    "source sampling, thermal": "(j - 2) & 3u",
+    "launch height": "(t - fl) * (",
+    "Lambertian direction": "sinTheta * cphi",
+    "slab flush": "unitSlab + i",
+    "counters": "counters + 7",
+    "fate record": "mcbrat_fate{",
+}
+# ... and of the rules that stay written out in both kernels, each copy naming the other (DESIGN.md section 4.18): once in each
+# kernel file (the component pick twice in the block walk, which picks again after its clamp), and not in the header
+KEPT_IN_BOTH = {
+    "Lambertian cosine": "float mu = sqrtf(uX);",
+    "component pick": "c = k + 1",
+    "roulette": "uR >= w",
+    "scattering angle": "left * t[ai]",
+    "new direction": "copysignf(fabsf(B), dz * B)",
+    "leg draws": "0.693147182f * __builtin_amdgcn_logf",
+}
+
+
+def test_the_shared_photon_rules_are_written_once():
+    header = open(os.path.join(CSRC, "mcbrat_photon.h")).read()
+    kernels = {f: open(os.path.join(CSRC, f)).read() for f in ("mcbrat_kernels.hip", "mcbrat_blockwalk.hip")}
+    for f, source in kernels.items():
+        assert '#include "mcbrat_photon.h"' in source, f
+    for rule, text in SHARED_RULES.items():
+        assert text in header, rule
+        for f, source in kernels.items():
+            assert text not in source, (rule, f)
+    for rule, text in KEPT_IN_BOTH.items():
+        assert text not in header, rule
+        assert kernels["mcbrat_kernels.hip"].count(text) == 1, rule
+        assert kernels["mcbrat_blockwalk.hip"].count(text) == (2 if rule == "component pick" else 1), rule
+    # both copies of the kept rules say where the other one is
+    assert "HOT ROWS" in kernels["mcbrat_kernels.hip"] and "HOT ROWS" in kernels["mcbrat_blockwalk.hip"]
+    # every function the header defines is called by both kernels (helpers only one kernel uses stay in its file)
+    for name in ("launch_solar", "launch_emission", "launch_height", "lambert_direction", "flush_unit_slab", "publish_counters", "record_fate"):
+        assert ("%s(" % name) in header
+        for f, source in kernels.items():
+            assert re.search(r"\b%s(<\w+>)?\(" % name, source), (name, f)

@@ -166,6 +166,9 @@ class Parent:
     def t_lvlDown(self): return self.t_lvlUp() + self.ncol * (self.nz + 1)
     def t_lvlDirect(self): return self.t_lvlDown() + self.ncol * (self.nz + 1)
     def t_actBins(self): return 2 * self.ncol + self.ncol * self.nz + (2 * self.ncol * (self.nz + 1) if self.levels_on() else 0)
+    def t_sideBins(self): return self.t_lvlDown() + self.ncol * (self.nz + 1)
+    def t_ibase(self): return 2 * self.ncol + self.ncol * self.nz  # rayFinish; also the LDS slab of the LVL and ACT kernels
+    def t_ordI(self): return (2 + self.nDir) * self.ncol + self.ncol * self.nz + 2 * self.ncol * (self.numRecScatOrd + 1)
 
 
 def test_the_shapes_cover_what_was_asked_for():
@@ -209,10 +212,24 @@ def test_every_field_is_what_the_old_formulas_give(exe):
         assert (d["scalOrders"], d["scalLevels"], d["scalActinic"], d["scalPerBatch"]) == (p.ordVals(), p.lvlVals(), p.actVals(), p.needScal()), s
 
 
+def _starts(exe, shapes):
+    """-> per shape what the slab_*_start functions return as trace_kernel calls them (the dump program's `starts` mode)"""
+    args = [",".join(str(v) for v in (s[:6] + (max(s[6] + 1, 0),) + s[7:])) for s in shapes]
+    lines = subprocess.run([exe, "starts"] + args, check=True, capture_output=True, text=True, timeout=60).stdout.strip().split("\n")
+    assert len(lines) == len(shapes)
+    return [{k: int(v) for k, v in (w.split("=") for w in line.split())} for line in lines]
+
+
 def test_the_slab_starts_trace_kernel_computes_for_itself(exe):
     seen = set()
-    for s, d in zip(SHAPES, _dump(exe, SHAPES)):
+    for s, d, k in zip(SHAPES, _dump(exe, SHAPES), _starts(exe, SHAPES)):
         p = Parent(*s)
+        # what the kernel calls, against the lines it had: the level, actinic and side starts and the intensity part whatever the
+        # shape (the lines did not look at directions or orders: the flux runs they serve have none), the order parts where orders are on
+        assert (k["lvlUp"], k["lvlDown"], k["lvlDirect"], k["sideBins"]) == (p.t_lvlUp(), p.t_lvlDown(), p.t_lvlDirect(), p.t_sideBins()), s
+        assert k["actBins"] == p.t_actBins() and k["ibase"] == p.t_ibase(), s
+        if p.orders_on():
+            assert (k["ordUp"], k["ordDown"], k["ordI"]) == (p.t_ordUp(), p.t_ordDown(), p.t_ordI()), s
         face = p.levels_on() or p.actinic_on()
         if p.orders_on() and not p.limitContrib and not face:  # ORD
             assert (d["slabOrders"], d["slabOrders"] + p.ncol * p.nOrd()) == (p.t_ordUp(), p.t_ordDown()), s
