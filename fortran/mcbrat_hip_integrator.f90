@@ -410,7 +410,8 @@ contains
   end subroutine setSurfaceDescription
   !------------------------------------------------------------------------------------------
   ! A surface BRDF per patch (DESIGN.md section 4.11): model "Lambertian" (1 parameter), "RPV" (rho0, k, Theta, rhoC) or
-  ! "RossLi" (fIso, fVol, fGeo); parameters(numberOfParameters, numX-1, numY-1) as the reference's BRDFParameters
+  ! "RossLi" (fIso, fVol, fGeo), or "CoxMunk" (U, n, rhoWc, aW: section 4.11.1);
+  ! parameters(numberOfParameters, numX-1, numY-1) as the reference's BRDFParameters
   subroutine setSurfaceBRDF(this, model, parameters, xPosition, yPosition, ierr)
     type(integrator),        intent(inout) :: this
     character(len=*),        intent(in)    :: model
@@ -427,6 +428,8 @@ contains
       kind = 1
     case ("RossLi")
       kind = 2
+    case ("CoxMunk")
+      kind = 3
     case default
       ierr = 2   ! "new_SurfaceDescription: unknown surface BRDF model"
       return

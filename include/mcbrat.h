@@ -355,6 +355,9 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
  *                 across the launch, two batches' tallies per workgroup where they fit; environment MCBRAT_BATCH_UNITS)
  *   "blockSpanKernel"  1: the block walk keeps its general instantiation where the one without periodic folds inside blocks
  *                 would do (default 0: automatic; both trace every photon bit for bit alike -- tests/test_gpu_blockwalk_nospan.py)
+ * One option does change results, within their noise -- it chooses between two unbiased estimators:
+ *   "glintSampling"  1 (default): a reflection off a Cox-Munk patch draws its direction from the mixture of the glint lobe and
+ *                 the Lambertian draw (mcbrat_set_surface_brdf); 0: the Lambertian draw times R, as the land models
  * The reference has no counterpart (its loop is one photon at a time, monteCarloRadiativeTransfer.f95:463-466). */
 int mcbrat_set_option(mcbrat_ctx *ctx, const char *name, int32_t value);
 
@@ -370,14 +373,21 @@ int mcbrat_set_surface_description(mcbrat_ctx *ctx, int32_t numX, int32_t numY, 
 
 /* A surface BRDF per patch (the reference's template, src/surfaceProperties.f95:8-14, with
  * numberOfParameters > 1).  kind 0 Lambertian {a} (what mcbrat_set_surface_description sets), 1 RPV {rho0, k, Theta, rhoC},
- * 2 Ross-Li (RossThick + LiSparse-Reciprocal) {fIso, fVol, fGeo}; `params` is BRDFParameters(nParams, numX-1, numY-1),
- * x fastest, nParams 1 / 4 / 3.  A reflected photon keeps the Lambertian (cosine-weighted) draw of its direction and its
- * weight is multiplied by the reflectance factor R = pi f of the patch for its arriving and leaving directions; the local
- * estimates of radiance from a reflection use R / pi.  Refused: parameters outside RPV's 0 <= rho0 <= 1, 0.2 <= k <= 2,
- * |Theta| <= 0.95, 0 <= rhoC <= 1, negative Ross-Li weights, and a patch whose directional-hemispherical albedo exceeds
- * 1 + 1e-3 at mu_i = 0.1, 0.2, .., 1.  A non-Lambertian surface is refused together with the thermal source, event counters
- * and photon fates (at computeRadiativeTransfer).  Over it fluxUp, like fluxDown, is not bounded by the capacity rule of
- * mcbrat_compute_radiative_transfer (a reflected weight may exceed 1).  numX <= 0 returns to the domain's albedo. */
+ * 2 Ross-Li (RossThick + LiSparse-Reciprocal) {fIso, fVol, fGeo}, 3 Cox-Munk (the ocean: isotropic wave slopes, Fresnel
+ * reflection, shadowing, whitecaps) {U wind speed at 10 m in m/s, n refractive index, rhoWc whitecap reflectance, aW
+ * water-leaving albedo}; `params` is BRDFParameters(nParams, numX-1, numY-1), x fastest, nParams 1 / 4 / 3 / 4.
+ * A reflected photon keeps the Lambertian (cosine-weighted) draw of its direction and its weight is multiplied by the
+ * reflectance factor R = pi f of the patch for its arriving and leaving directions; the local estimates of radiance from a
+ * reflection use R / pi.  A Cox-Munk patch draws the direction from a one-sample mixture of its glint lobe and the
+ * Lambertian draw instead (balance heuristic; option "glintSampling"), which keeps the reflected weight below about 1.1
+ * where the Lambertian draw times R reaches thousands at low sun; a sampled direction whose cosine is below 2^-16, the
+ * smallest the Lambertian draw gives, ends the photon.
+ * Refused: parameters outside RPV's 0 <= rho0 <= 1, 0.2 <= k <= 2, |Theta| <= 0.95, 0 <= rhoC <= 1, negative Ross-Li
+ * weights, Cox-Munk parameters outside 0 <= U <= 50, 1 <= n <= 2, 0 <= rhoWc <= 1, 0 <= aW <= 1, and a patch whose
+ * directional-hemispherical albedo exceeds 1 + 1e-3 at mu_i = 0.1, 0.2, .., 1.  A non-Lambertian surface is refused
+ * together with the thermal source, event counters and photon fates (at computeRadiativeTransfer).  Over it fluxUp, like
+ * fluxDown, is not bounded by the capacity rule of mcbrat_compute_radiative_transfer (a reflected weight may exceed 1).
+ * numX <= 0 returns to the domain's albedo. */
 int mcbrat_set_surface_brdf(mcbrat_ctx *ctx, int32_t kind, int32_t numX, int32_t numY, const double *xPosition,
                             const double *yPosition, int32_t nParams, const float *params);
 
@@ -388,6 +398,17 @@ float mcbrat_brdf_reflectance(int32_t kind, const float *params, const double *d
 /* Directional-hemispherical albedo rho_dh(muIn) = (1/pi) int R mu_r dOmega (black-sky albedo at incidence cosine muIn),
  * by Gauss quadrature; NaN for an unknown kind or muIn outside (0, 1]. */
 double mcbrat_brdf_albedo(int32_t kind, const float *params, double muIn);
+
+/* The reflection's sampler on the host (no context, no GPU): the function the tracing kernel calls at a BRDF reflection.
+ * For the arriving direction dIn and n triples of uniforms u[n][3] = {component, u1, u2}: the leaving directions dOut[n][3]
+ * and the factors weight[n] the photon's weight is multiplied by (0: the photon ends).  The Lambertian draw -- all there is
+ * for kinds 0 to 2, one of the two components for Cox-Munk -- is mu = sqrt(u1), azimuth 2 pi u2, formed in double.  Unlike
+ * the kernel, where the Lambertian draw comes from the leg's Philox block and (u1, u2) of the glint component from a block
+ * of their own, both components read the one pair here; a draw uses one component only, so the estimate is the same.
+ * The mean of `weight` estimates mcbrat_brdf_albedo(-dIn[2]).  Returns 0, or 1 for a null argument, a negative n or an
+ * unknown kind. */
+int mcbrat_brdf_sample(int32_t kind, const float *params, const double *dIn, int64_t n, const double *u, double *dOut,
+                       float *weight);
 
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air

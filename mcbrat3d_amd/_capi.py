@@ -95,6 +95,7 @@ SYMBOLS = {
     "mcbrat_set_surface_brdf": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mcbrat_brdf_reflectance": (_f, [_i32, _vp, _vp, _vp]),
     "mcbrat_brdf_albedo": (_d, [_i32, _vp, _d]),
+    "mcbrat_brdf_sample": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),
     "mcbrat_inverse_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_inverse_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),

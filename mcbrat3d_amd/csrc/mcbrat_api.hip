@@ -111,7 +111,8 @@ struct mcbrat_ctx {
   int surfNumX = 0, surfNumY = 0;
   DeviceBuffer<double> dSurfX, dSurfY;
   DeviceBuffer<float> dSurfRefl;
-  int surfKind = 0;                // mcbrat_set_surface_brdf: 0 Lambertian (dSurfRefl), 1 RPV, 2 Ross-Li (dSurfBrdf)
+  int surfKind = 0;                // mcbrat_set_surface_brdf: 0 Lambertian (dSurfRefl), 1 RPV, 2 Ross-Li, 3 Cox-Munk (dSurfBrdf)
+  bool glintSampling = true;       // option "glintSampling": a Cox-Munk reflection draws from the glint mixture (brdf_sample)
   DeviceBuffer<float4> dSurfBrdf;  // [numY-1][numX-1] the patches' parameters, padded to four
   DeviceBuffer<double> dVoxelCDF;
   DeviceBuffer<unsigned long long> dEventCounters;
@@ -662,6 +663,7 @@ void fill_params(mcbrat_ctx *c, DevParams &p) {
   p.surfNumX = c->surfNumX; p.surfNumY = c->surfNumY; p.surfX = c->dSurfX.get(); p.surfY = c->dSurfY.get(); p.surfRefl = c->dSurfRefl.get();
   p.surfKind = c->surfNumX > 0 ? c->surfKind : 0;
   if (p.surfKind != 0) p.surfRefl = reinterpret_cast<const float *>(c->dSurfBrdf.get());  // (float4 per patch)
+  if (p.surfKind == BRDF_COXMUNK && c->glintSampling) p.surfKind |= kSurfKindSampled;
   p.tables = c->dTables.get();
   for (int k = 0; k < c->nc; ++k) { p.tblOffset[k] = c->tblOffset[k]; p.tblNSteps[k] = c->tblNSteps[k]; p.tblInvN[k] = 1.0f / (float)c->tblNSteps[k]; }
   p.tblTotalFloats = c->tblTotalFloats;
@@ -1655,6 +1657,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   else if (n == "crossThreshold") c->crossThreshold = std::max(1, std::min(64, (int)value));
   else if (n == "batchUnits") c->batchUnits = value != 0;
   else if (n == "blockSpanKernel") c->blockSpanKernel = value != 0;
+  else if (n == "glintSampling") c->glintSampling = value != 0;
   else return fail(c, "set_option: unknown option '" + n + "'");
   return 0;
 }

@@ -27,6 +27,9 @@ namespace mcbrat {
 constexpr int kWave = 64;                     // CDNA wavefront
 constexpr double kTallyScale = 4294967296.0;  // tallies are signed 64-bit fixed point, 2^-32 resolution
 constexpr double kTallyInv = 1.0 / 4294967296.0;
+// DevParams::surfKind: the BRDF model (mcbrat_brdf.h) in the low byte; this bit on top of it where reflections off the model
+// draw their direction from its own sampler (Cox-Munk with the option glintSampling)
+constexpr int kSurfKindSampled = 0x100, kSurfKindMask = 0xff;
 
 // Loop bounds of the production kernels -- compile-time constants there: as kernel parameters they
 // lived in scalar registers across the whole loop and cost the step cloud 3 % through spilled SGPRs.  The instrumented
@@ -209,7 +212,8 @@ struct DevParams {
   // the solar source's kind (srcKind 0; solar_launch): 0 Directional, 1 RandomAzimuth, 2 Flux, 3 Spotlight, and the
   // spotlight's launch point as fractions of the domain (solarX, solarY)
   int solarKind;
-  // the surface description's model (BRDF instantiations of trace_kernel): 0 Lambertian, 1 RPV, 2 Ross-Li.
+  // the surface description's model (BRDF instantiations of trace_kernel): 0 Lambertian, 1 RPV, 2 Ross-Li,
+  // 3 Cox-Munk; | kSurfKindSampled: a Cox-Munk reflection draws its direction from the glint mixture (section 4.11.1).
   // (In the padding before spotX: the parameter block keeps its size and every other member its offset.)
   int surfKind;
   double spotX, spotY;

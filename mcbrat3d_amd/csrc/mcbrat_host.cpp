@@ -526,6 +526,9 @@ const char *brdf_param_error(int kind, const float *q) {
       return "new_SurfaceDescription: RPV parameters must satisfy 0 <= rho0 <= 1, 0.2 <= k <= 2, |Theta| <= 0.95, 0 <= rhoC <= 1";
   } else if (kind == BRDF_ROSSLI) {
     if (!(q[0] >= 0.f && q[1] >= 0.f && q[2] >= 0.f)) return "new_SurfaceDescription: Ross-Li kernel weights must not be negative";
+  } else if (kind == BRDF_COXMUNK) {
+    if (!(q[0] >= 0.f && q[0] <= 50.f && q[1] >= 1.f && q[1] <= 2.f && q[2] >= 0.f && q[2] <= 1.f && q[3] >= 0.f && q[3] <= 1.f))
+      return "new_SurfaceDescription: Cox-Munk parameters must satisfy 0 <= U <= 50, 1 <= n <= 2, 0 <= rhoWc <= 1, 0 <= aW <= 1";
   } else {
     return "new_SurfaceDescription: unknown surface BRDF model";
   }
@@ -548,4 +551,20 @@ extern "C" double mcbrat_brdf_albedo(int32_t kind, const float *params, double m
   float q[mcbrat::kBrdfMaxParams] = {0.f, 0.f, 0.f, 0.f};
   for (int i = 0; i < mcbrat::brdf_num_params(kind); ++i) q[i] = params[i];
   return brdf_albedo_of(kind, q, muIn);
+}
+
+// The reflection's sampler on the host (brdf_sample, mcbrat_brdf.h): n draws for one arriving direction.  u[i] = {component, u1,
+// u2}.  The Lambertian draw the sampler starts from is mu = sqrt(u1), azimuth 2 pi u2, formed here in double -- the kernel forms
+// its own in float from the leg's block (lambert_direction, mcbrat_photon.h) and hands it to the same brdf_sample.  Here both
+// components read the one pair (u1, u2); a draw uses one component only, so the estimate is the same.
+extern "C" int mcbrat_brdf_sample(int32_t kind, const float *params, const double *dIn, int64_t n, const double *u, double *dOut, float *weight) {
+  if (!params || !dIn || !u || !dOut || !weight || n < 0 || mcbrat::brdf_num_params(kind) == 0) return 1;
+  float q[mcbrat::kBrdfMaxParams] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < mcbrat::brdf_num_params(kind); ++i) q[i] = params[i];
+  for (int64_t i = 0; i < n; ++i) {
+    const double mu = std::sqrt(u[3 * i + 1]), st = std::sqrt(std::max(0.0, 1.0 - mu * mu)), phi = 2.0 * 3.14159265358979323846 * u[3 * i + 2];
+    dOut[3 * i] = st * std::cos(phi); dOut[3 * i + 1] = st * std::sin(phi); dOut[3 * i + 2] = mu;
+    mcbrat::brdf_sample(kind, q, dIn, u + 3 * i, dOut + 3 * i, weight[i]);
+  }
+  return 0;
 }

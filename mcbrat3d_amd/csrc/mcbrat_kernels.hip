@@ -68,16 +68,34 @@ __device__ __forceinline__ int surface_patch(const DevParams &p, double x, doubl
   const int yi = min(max(find_index_mixed(p.surfY, p.surfNumY, make_periodic_f(y, p.surfY[0], p.surfY[p.surfNumY - 1])), 1), p.surfNumY - 1);
   return (xi - 1) + (p.surfNumX - 1) * (yi - 1);
 }
-// the reflectance factor R = pi f of a BRDF patch (mcbrat_brdf.h) for the propagation directions d_in (arriving) and d_out (leaving).
-// Called, not inlined: inlined, the evaluator's double-precision pow / acos added their registers to the whole tracing loop (the
-// BRDF flux kernels spilled 35-129 VGPRs to scratch and ran at 72-84 % of a Lambertian description's rate).
-__device__ __noinline__ float surface_brdf_call(int kind, float4 q4, float ix, float iy, float iz, float ox, float oy, float oz) {
+// A reflection off a BRDF patch: the direction taken and, in w, the factor of the weight.  (lx, ly, lz) is the Lambertian draw,
+// which every model keeps (factor R) but Cox-Munk with the glint mixture (kind 3 | kSurfKindSampled: brdf_sample, mcbrat_brdf.h,
+// DESIGN.md section 4.11.1), whose three uniforms are block kGlintBlock of the photon's event.  ONE called function for all of
+// them, the Philox block included, and for the local estimate's R too (surface_brdf below).  Called, not inlined: inlined, the
+// evaluator's double-precision pow / acos added their registers to the whole tracing loop (the BRDF flux kernels spilled 35-129
+// VGPRs to scratch and ran at 72-84 % of a Lambertian description's rate).  And one function, not two: with
+// the sampler as a second called function beside the evaluator's, the land models' flux kernels ran at 42-55 % of their rate, and
+// with two in the radiance kernels alone those lost 6-7 % on landsatLike128 (profiles/coxmunk_cost.json).
+// (The sampler never returns a cosine below kBrdfSampleMuMin with a factor above 0: the walk's float distances along a leg are
+// built for the Lambertian draw's cosines, and a leg a million times longer than the domain is high stops advancing.)
+__device__ __noinline__ float4 surface_reflect_call(int kind, float4 q4, float ix, float iy, float iz, float lx, float ly, float lz, uint32_t event,
+                                                    uint32_t idLo, uint32_t idHi, uint32_t seedLo, uint32_t seedHi) {
   const float q[4] = {q4.x, q4.y, q4.z, q4.w};
-  return brdf_reflectance(kind, q, (double)ix, (double)iy, (double)iz, (double)ox, (double)oy, (double)oz);
+  if (kind != (BRDF_COXMUNK | kSurfKindSampled))
+    return make_float4(lx, ly, lz, brdf_reflectance(kind & kSurfKindMask, q, (double)ix, (double)iy, (double)iz, (double)lx, (double)ly, (double)lz));
+  uint32_t g[4];
+  philox4x32_10(event, kGlintBlock, idLo, idHi, seedLo, seedHi, g);
+  const double dIn[3] = {(double)ix, (double)iy, (double)iz}, u[3] = {(double)u01(g[0]), (double)u01(g[1]), (double)u01(g[2])};
+  double dOut[3] = {(double)lx, (double)ly, (double)lz};
+  float factor;
+  brdf_sample(BRDF_COXMUNK, q, dIn, u, dOut, factor);
+  return make_float4((float)dOut[0], (float)dOut[1], (float)dOut[2], factor);
 }
+// the reflectance factor R = pi f of a BRDF patch for the propagation directions d_in (arriving) and d_out (leaving): the same
+// called function with the model alone as its kind, which evaluates and draws nothing
 __device__ __forceinline__ float surface_brdf(const DevParams &p, int patch, float ix, float iy, float iz, float ox, float oy, float oz) {
   // (a BRDF surface's parameters, DevParams::surfRefl)
-  return surface_brdf_call(p.surfKind, reinterpret_cast<const float4 *>(p.surfRefl)[patch], ix, iy, iz, ox, oy, oz);
+  return surface_reflect_call(p.surfKind & kSurfKindMask, reinterpret_cast<const float4 *>(p.surfRefl)[patch], ix, iy, iz, ox, oy, oz, 0u, 0u, 0u, 0u, 0u).w;
 }
 
 // Optical-property lookup.  Dense: one gather from the [nz][ny][nx] grid.  BRICK: the grid is cut
@@ -136,6 +154,8 @@ __device__ __forceinline__ void deposit(long long *bin, unsigned long long dep) 
 // SPEC 0, BRICK and DEBUG off only; everything it adds sits behind `if constexpr (ORD)`.
 // BRDF: a surface description whose model is not Lambertian (DevParams::surfKind): a reflection keeps the
 // Lambertian draw of its direction and multiplies the weight by R(d_in, d_out) of the patch; its local estimates use R / pi.
+// A Cox-Munk patch (surfKind 3 | kSurfKindSampled) draws from the mixture of its glint lobe and the Lambertian draw instead
+// (surface_reflect_call; three uniforms of block kGlintBlock of the event, mcbrat_photon.h), local estimates as before.
 // Solar sources, SPEC 0 and DEBUG off only; everything it adds sits behind `if constexpr (BRDF)`.
 // LVL: upward and downward flux through every level (z face) of every column as well (recLevelFluxes):
 // a photon that crosses face k adds its weight to the up or down bin (k, column).  The bins follow [fluxUp | fluxDown | volume] in
@@ -840,7 +860,9 @@ trace_kernel(const DevParams p) {
         if constexpr (BRDF) {  // the Lambertian draw of the direction, the weight times R(d_in, d_out) of the patch
           lambert_direction(mu, uY, ox, oy, oz);
           patch = surface_patch(p, px, py);
-          w = w * surface_brdf(p, patch, dx, dy, dz, ox, oy, oz);
+          const float4 s = surface_reflect_call(p.surfKind, reinterpret_cast<const float4 *>(p.surfRefl)[patch], dx, dy, dz, ox, oy, oz, event, idLo, idHi, p.seedLo, p.seedHi);
+          ox = s.x; oy = s.y; oz = s.z;  // (the Lambertian draw as it went in, but for a glint-sampled direction)
+          w = w * s.w;
           // local estimates from a BRDF reflection: the weight before it and R(d_in, d_view) / pi (iFlag -1; iEntry: the patch).
           // Also when R(d_in, d_out) = 0 ends the photon: the estimate does not depend on the direction drawn.
           if (INTEN) { iFlag = -1; iW = wIn; iDx = dx; iDy = dy; iDz = dz; iEntry = patch; }

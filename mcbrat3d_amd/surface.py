@@ -1,6 +1,6 @@
 """Host-side mirror of src/surfaceProperties.f95: a surface whose reflectance varies with horizontal position.  The
 reference's template for "a few parameters per patch" surface models has one parameter (Lambertian); the RPV and Ross-Li
-BRDFs fill it with four and three."""
+BRDFs fill it with four and three, the Cox-Munk ocean surface with four (section 4.11.1)."""
 import ctypes as C
 
 import numpy as np
@@ -8,7 +8,7 @@ import numpy as np
 from ._capi import McbratError
 
 numberOfParameters = 1  # :28 (Lambertian)
-MODELS = {"Lambertian": (0, 1), "RPV": (1, 4), "RossLi": (2, 3)}  # model: (kind of mcbrat_set_surface_brdf, numberOfParameters)
+MODELS = {"Lambertian": (0, 1), "RPV": (1, 4), "RossLi": (2, 3), "CoxMunk": (3, 4)}  # model: (kind of mcbrat_set_surface_brdf, numberOfParameters)
 ENERGY_GRID = np.arange(1, 11) / 10.0  # incidence cosines of the energy rule (kBrdfAlbedoGrid in mcbrat_brdf.h)
 
 
@@ -29,10 +29,11 @@ class SurfaceDescription:
 
 def new_SurfaceDescription(surfaceParameters, xPosition=None, yPosition=None, model="Lambertian"):
     """newSurfaceDescriptionXY (:58-94) when positions are given, newSurfaceUniform (:96-115) otherwise.  model: "Lambertian"
-    (one parameter, the reflectance), "RPV" (rho0, k, Theta, rhoC) or "RossLi" (fIso, fVol, fGeo); surfaceParameters is
+    (one parameter, the reflectance), "RPV" (rho0, k, Theta, rhoC), "RossLi" (fIso, fVol, fGeo) or "CoxMunk" (U wind speed in
+    m/s, n refractive index, rhoWc whitecap reflectance, aW water-leaving albedo); surfaceParameters is
     [numberOfParameters, numX - 1, numY - 1], or numberOfParameters values for a uniform surface."""
     if model not in MODELS:
-        raise McbratError("new_SurfaceDescription: unknown surface BRDF model '%s' (Lambertian, RPV or RossLi)." % (model,))
+        raise McbratError("new_SurfaceDescription: unknown surface BRDF model '%s' (Lambertian, RPV, RossLi or CoxMunk)." % (model,))
     nParams = MODELS[model][1]
     params = np.asarray(surfaceParameters, np.float32)
     if xPosition is None and yPosition is None:
@@ -66,6 +67,11 @@ def _check_brdf(model, params):
             if not (0.0 <= rho0 <= 1.0 and 0.2 <= k <= 2.0 and abs(th) <= 0.95 and 0.0 <= rhoC <= 1.0):
                 raise McbratError("new_SurfaceDescription: RPV parameters must satisfy 0 <= rho0 <= 1, 0.2 <= k <= 2, "
                                   "|Theta| <= 0.95, 0 <= rhoC <= 1")
+        elif model == "CoxMunk":
+            U, n_, rhoWc, aW = q
+            if not (0.0 <= U <= 50.0 and 1.0 <= n_ <= 2.0 and 0.0 <= rhoWc <= 1.0 and 0.0 <= aW <= 1.0):
+                raise McbratError("new_SurfaceDescription: Cox-Munk parameters must satisfy 0 <= U <= 50, 1 <= n <= 2, "
+                                  "0 <= rhoWc <= 1, 0 <= aW <= 1")
         elif not np.all(q >= 0.0):
             raise McbratError("new_SurfaceDescription: Ross-Li kernel weights must not be negative")
         if any(not (brdf_albedo(kind, q, mu) <= 1.0 + 1e-3) for mu in ENERGY_GRID):
@@ -92,6 +98,24 @@ def brdf_albedo(kind, params, mu_i):
     """Directional-hemispherical albedo rho_dh(mu_i) of one parameter vector (mcbrat_brdf_albedo)."""
     q = np.ascontiguousarray(params, np.float32)
     return float(_lib().mcbrat_brdf_albedo(int(kind), q.ctypes.data_as(C.c_void_p), float(mu_i)))
+
+
+def brdf_sample(kind, params, d_in, u):
+    """The reflection's sampler as the tracing kernel applies it (mcbrat_brdf_sample; no GPU): for one parameter vector, the
+    arriving direction d_in and uniforms u[n, 3] = (component, u1, u2) -> (d_out[n, 3], weight[n]), the leaving directions and
+    the factors of the photon's weight (0: the photon ends).  The Lambertian draw is mu = sqrt(u1), azimuth 2 pi u2; Cox-Munk
+    mixes it with a draw from the glint lobe.  The mean weight estimates brdf_albedo(kind, params, -d_in[2])."""
+    q = np.ascontiguousarray(params, np.float32)
+    a = np.ascontiguousarray(d_in, np.float64)
+    uu = np.ascontiguousarray(u, np.float64)
+    if uu.ndim != 2 or uu.shape[1] != 3 or a.shape != (3,):
+        raise McbratError("brdf_sample: d_in must be a 3-vector and u an [n, 3] array")
+    d_out = np.empty(uu.shape, np.float64)
+    w = np.empty(uu.shape[0], np.float32)
+    if _lib().mcbrat_brdf_sample(int(kind), q.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), uu.shape[0],
+                                 uu.ctypes.data_as(C.c_void_p), d_out.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p)) != 0:
+        raise McbratError("brdf_sample: unknown surface BRDF model")
+    return d_out, w
 
 
 def _patch(edges, v):
