@@ -250,6 +250,17 @@ int mcbrat_specify_side_fluxes(mcbrat_ctx *ctx, int32_t enable);
  * meanSideFluxes(nz, 4), sideFluxes(nx, ny, nz, 4).  Either pointer may be NULL. */
 int mcbrat_report_side_fluxes(mcbrat_ctx *ctx, float *meanSideFluxes, float *sideFluxes);
 
+/* Whether the context could be brought to these settings (an addition under ABI version 3; no Fortran binding): NULL, or the
+ * message with which one of mcbrat_specify_intensity, the five recording setters above and mcbrat_set_surface_brdf would refuse
+ * them together -- a static string that lives as long as the library.  nDirections, limitIntensityContributions: as passed to
+ * mcbrat_specify_intensity; numRecScatOrd: < 0 off; brdfSurface: nonzero for a surface of kind 1 to 3.  The grid, the component
+ * count, the counters and the source are the context's.  Host arithmetic only: it changes nothing -- not mcbrat_last_error
+ * either -- and does not synchronise.  A caller that changes several settings at once asks before it calls the first setter,
+ * which refuse one at a time. */
+const char *mcbrat_settings_refusal(const mcbrat_ctx *ctx, int32_t nDirections, int32_t limitIntensityContributions,
+                                    int32_t numRecScatOrd, int32_t levelFluxes, int32_t directLevelFluxes,
+                                    int32_t actinicFlux, int32_t sideFluxes, int32_t brdfSurface);
+
 /* Batch moments: what the driver keeps in *Stats(...,1:2)
  * (monteCarloDriver.f95:603-616) and reduces with sumAcrossProcesses
  * (:1151-1166).  One double array:

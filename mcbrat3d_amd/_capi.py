@@ -73,6 +73,7 @@ SYMBOLS = {
     "mcbrat_report_actinic_flux": (C.c_int, [_vp, _vp, _vp]),
     "mcbrat_specify_side_fluxes": (C.c_int, [_vp, _i32]),
     "mcbrat_report_side_fluxes": (C.c_int, [_vp, _vp, _vp]),
+    "mcbrat_settings_refusal": (C.c_char_p, [_vp] + [_i32] * 8),
     "mcbrat_forward_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_forward_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
     "mcbrat_hybrid_phase_functions": (C.c_int, [_i32, _i32, _vp, _f, _vp]),
@@ -105,7 +106,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux and side fluxes are additions under 3)
+ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes and mcbrat_settings_refusal are additions under 3)
 
 
 def hip_runtimes():

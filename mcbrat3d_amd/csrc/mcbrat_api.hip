@@ -1421,19 +1421,38 @@ int mcbrat_specify_intensity(mcbrat_ctx *c, int32_t nDirections, const float *mu
   return 0;
 }
 
-int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
+// What the setters below, mcbrat_specify_intensity and mcbrat_set_surface_brdf would refuse these settings with, asked in one
+// question and without a change: host arithmetic on the context's grid, components, counters and source.  (LevelsOff is not
+// asked: its two rules stand under SetDirect and SetSide too.)
+const char *mcbrat_settings_refusal(const mcbrat_ctx *c, int32_t nDirections, int32_t limitIntensityContributions, int32_t numRecScatOrd,
+                                    int32_t levelFluxes, int32_t directLevelFluxes, int32_t actinicFlux, int32_t sideFluxes, int32_t brdfSurface) {
+  if (!c) return mcbrat_last_error(c);
+  if (!c->haveGrid) return "specifyParameters: set the grid first.";
+  Asked a = asked(c);
+  a.nDir = nDirections; a.limitContrib = limitIntensityContributions != 0; a.numRecScatOrd = numRecScatOrd < 0 ? -1 : numRecScatOrd;
+  a.levels = levelFluxes != 0; a.direct = directLevelFluxes != 0; a.actinic = actinicFlux != 0; a.side = sideFluxes != 0; a.brdf = brdfSurface != 0;
+  return refusal(settings_of(c, a), (Stage)(SetIntensity | SetOrders | SetLevels | SetDirect | SetActinic | SetSide | SetBrdf));
+}
+
+// The five recording setters: the setting as the context holds it and as refusal() is asked about it, its new value, the stage
+// asked when it switches on and when it switches off (0: nothing to ask), and whether another walk or other kernels go with it.
+static int specify_recording(mcbrat_ctx *c, int mcbrat_ctx::*held, int Asked::*about, int value, bool on, unsigned onStage, unsigned offStage, bool retune) {
   if (!c) return 1;
   if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
-  const int n = numRecScatOrd < 0 ? -1 : numRecScatOrd;
   Asked a = asked(c);
-  a.numRecScatOrd = n;
-  // (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
-  if (n >= 0) REFUSE(c, a, SetOrders);
+  a.*about = value;
+  REFUSE(c, a, (Stage)(on ? onStage : offStage));
   (void)hipSetDevice(c->device);
   if (sync_all(c)) return 1;
-  if (n != c->numRecScatOrd) drop_results(c, false);  // the moment arrays change length: start them afresh
-  c->numRecScatOrd = n;
+  const TallyShape before = tally_shape(c);
+  c->*held = value;
+  if (!(tally_shape(c) == before)) drop_results(c, retune);  // the moment arrays change length: start them afresh
   return 0;
+}
+
+// (the slab of one batch must fit the tally budget; mcbrat_compute_radiative_transfer checks again, directions may change)
+int mcbrat_specify_scattering_orders(mcbrat_ctx *c, int32_t numRecScatOrd) {
+  return specify_recording(c, &mcbrat_ctx::numRecScatOrd, &Asked::numRecScatOrd, numRecScatOrd < 0 ? -1 : numRecScatOrd, numRecScatOrd >= 0, SetOrders, 0, false);
 }
 
 int mcbrat_report_scattering_orders(mcbrat_ctx *c, float *meanFluxUpByScatOrd, float *meanFluxDownByScatOrd, float *fluxUpByScatOrd,
@@ -1447,18 +1466,9 @@ int mcbrat_report_scattering_orders(mcbrat_ctx *c, float *meanFluxUpByScatOrd, f
                    {fluxDownByScatOrd, ncol * nOrd}, {meanIntensityByScatOrd, nDir * nOrd}, {intensityByScatOrd, ncol * nDir * nOrd}});
 }
 
+// (off: switch the direct and the side tally off first)
 int mcbrat_specify_level_fluxes(mcbrat_ctx *c, int32_t enable) {
-  if (!c) return 1;
-  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
-  const int on = enable ? 1 : 0;
-  Asked a = asked(c);
-  a.levels = on;
-  REFUSE(c, a, on ? SetLevels : LevelsOff);  // (off: switch the direct and the side tally off first)
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  if (on != c->levelFluxes) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
-  c->levelFluxes = on;
-  return 0;
+  return specify_recording(c, &mcbrat_ctx::levelFluxes, &Asked::levels, enable ? 1 : 0, enable != 0, SetLevels, LevelsOff, true);
 }
 
 int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *meanLevelFluxDown, float *levelFluxUp, float *levelFluxDown) {
@@ -1468,18 +1478,9 @@ int mcbrat_report_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxUp, float *mea
   return deal_last(c, (size_t)tally_layout(c).momLevels, {{meanLevelFluxUp, nLvl}, {meanLevelFluxDown, nLvl}, {levelFluxUp, ncol * nLvl}, {levelFluxDown, ncol * nLvl}});
 }
 
+// (what level fluxes are refused with is refused with them: the setting needs them)
 int mcbrat_specify_direct_level_fluxes(mcbrat_ctx *c, int32_t enable) {
-  if (!c) return 1;
-  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
-  const int on = enable ? 1 : 0;
-  Asked a = asked(c);
-  a.direct = on;
-  if (on) REFUSE(c, a, SetDirect);  // (what level fluxes are refused with is refused with them: the setting needs them)
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  if (direct_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
-  c->directLevelFluxes = on;
-  return 0;
+  return specify_recording(c, &mcbrat_ctx::directLevelFluxes, &Asked::direct, enable ? 1 : 0, enable != 0, SetDirect, 0, true);
 }
 
 int mcbrat_report_direct_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxDownDirect, float *meanLevelFluxDownDiffuse, float *levelFluxDownDirect,
@@ -1491,18 +1492,9 @@ int mcbrat_report_direct_level_fluxes(mcbrat_ctx *c, float *meanLevelFluxDownDir
                    {levelFluxDownDiffuse, ncol * nLvl}});
 }
 
+// (level fluxes may be on together with it; their direct tally may not: no kernel has both flags)
 int mcbrat_specify_actinic_flux(mcbrat_ctx *c, int32_t enable) {
-  if (!c) return 1;
-  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
-  const int on = enable ? 1 : 0;
-  Asked a = asked(c);
-  a.actinic = on;
-  if (on) REFUSE(c, a, SetActinic);  // (level fluxes may be on together with it; their direct tally may not: no kernel has both flags)
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  if (on != c->actinicFlux) drop_results(c, true);  // the moment arrays change length; another walk, other kernels
-  c->actinicFlux = on;
-  return 0;
+  return specify_recording(c, &mcbrat_ctx::actinicFlux, &Asked::actinic, enable ? 1 : 0, enable != 0, SetActinic, 0, true);
 }
 
 int mcbrat_report_actinic_flux(mcbrat_ctx *c, float *meanActinicFlux, float *actinicFlux) {
@@ -1511,18 +1503,9 @@ int mcbrat_report_actinic_flux(mcbrat_ctx *c, float *meanActinicFlux, float *act
   return deal_last(c, (size_t)tally_layout(c).momActinic, {{meanActinicFlux, (size_t)c->nz}, {actinicFlux, (size_t)c->nx * c->ny * (size_t)c->nz}});
 }
 
+// (what level fluxes are refused with is refused with them: the setting needs them)
 int mcbrat_specify_side_fluxes(mcbrat_ctx *c, int32_t enable) {
-  if (!c) return 1;
-  if (!c->haveGrid) return fail(c, "specifyParameters: set the grid first.");
-  const int on = enable ? 1 : 0;
-  Asked a = asked(c);
-  a.side = on;
-  if (on) REFUSE(c, a, SetSide);  // (what level fluxes are refused with is refused with them: the setting needs them)
-  (void)hipSetDevice(c->device);
-  if (sync_all(c)) return 1;
-  if (side_on(c) != (levels_on(c) && on)) drop_results(c, true);  // the moment arrays change length; other kernels
-  c->sideFluxes = on;
-  return 0;
+  return specify_recording(c, &mcbrat_ctx::sideFluxes, &Asked::side, enable ? 1 : 0, enable != 0, SetSide, 0, true);
 }
 
 int mcbrat_report_side_fluxes(mcbrat_ctx *c, float *meanSideFluxes, float *sideFluxes) {

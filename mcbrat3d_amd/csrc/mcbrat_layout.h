@@ -27,6 +27,11 @@ struct TallyShape {
   int32_t levels, direct, actinic;
   int32_t side = 0;  // the flux through the vertical faces of every cell (needs levels)
 };
+// (equal shapes have equal layouts: what a setter asks to learn whether the moments change length)
+constexpr bool operator==(const TallyShape &a, const TallyShape &b) {
+  return a.nx == b.nx && a.ny == b.ny && a.nz == b.nz && a.nc == b.nc && a.nDir == b.nDir && a.limitContrib == b.limitContrib && a.nOrd == b.nOrd &&
+         a.levels == b.levels && a.direct == b.direct && a.actinic == b.actinic && a.side == b.side;
+}
 
 // Starts in elements: slab* within one batch's slab, mom* within one sum of the moments (and within the last batch's results), scal*
 // within the scalar scratch per batch.  Kept tally by tally: a finish kernel's part reads neighbours (the kernel argument loads of

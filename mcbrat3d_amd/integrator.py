@@ -27,6 +27,26 @@ _SOLAR_SETTERS = {"Directional": "mcbrat_set_source_solar", "RandomAzimuth": "mc
                   "Flux": "mcbrat_set_source_flux", "Spotlight": "mcbrat_set_source_spotlight"}
 
 
+# The recording settings in dependency order -- a row needs, if anything, rows above it: the integrator's field, its off value
+# and the C setter that takes it
+_RECORDING = {"numRecScatOrd": (-1, "mcbrat_specify_scattering_orders"),
+              "recLevelFluxes": (False, "mcbrat_specify_level_fluxes"),
+              "recDirectLevelFluxes": (False, "mcbrat_specify_direct_level_fluxes"),
+              "recActinicFlux": (False, "mcbrat_specify_actinic_flux"),
+              "recSideFluxes": (False, "mcbrat_specify_side_fluxes")}
+# the fields mcbrat_settings_refusal is asked about, beside the surface
+_ASKED_ABOUT = frozenset(_RECORDING) | {"intensityMus", "computeIntensity", "limitIntensityContributions"}
+
+
+def _push_order(held, wanted, intensityChanged, surfaceGiven):
+    """The calls that bring the library from the recording settings it holds to the wanted ones, in an order in which its
+    setters, which refuse one at a time, refuse none of them where the wanted settings as a whole are acceptable (DESIGN.md
+    section 4.16): the settings that go off, dependents first; "surface"; "intensity"; every other changed setting."""
+    changed = [name for name in _RECORDING if wanted[name] != held[name]]
+    off = [name for name in changed if wanted[name] == _RECORDING[name][0]]
+    return off[::-1] + ["surface"] * bool(surfaceGiven) + ["intensity"] * bool(intensityChanged) + [name for name in changed if name not in off]
+
+
 class RandomNumberSequence:
     """Stands where the reference passes type(randomNumberSequence): the Philox key and the
     id of the next photon.  Photon ids, not generator state, carry the stream, so any split
@@ -87,6 +107,7 @@ class Integrator:
         self.recActinicFlux = False
         # the flux through the vertical faces of every cell; solar sources, needs recLevelFluxes
         self.recSideFluxes = False
+        self._held = {name: off for name, (off, _) in _RECORDING.items()}  # the recording settings the library holds
         self._param_token = None
         self._intensity_token = None
         self._domain_token = None
@@ -151,86 +172,21 @@ class Integrator:
                           limitIntensityContributions=None, maxIntensityContribution=None, surfaceBDRF=None,
                           recScatOrd=None, numRecScatOrd=None, recLevelFluxes=None, recDirectLevelFluxes=None, recActinicFlux=None,
                           recSideFluxes=None, **unsupported):
-        # level fluxes: what they cannot be combined with is refused as the library refuses it -- here,
-        # before anything of this call is kept, so that a refused call leaves the integrator as it was
-        levels = self.recLevelFluxes if recLevelFluxes is None else bool(recLevelFluxes)
-        direct = self.recDirectLevelFluxes if recDirectLevelFluxes is None else bool(recDirectLevelFluxes)
-        if direct:  # (with level fluxes only, and refused with everything they are refused with, below)
-            if not levels:
-                raise McbratError("specifyParameters: direct level fluxes (recDirectLevelFluxes) need level fluxes (recLevelFluxes): "
-                                  "they separate the downward level flux.")
-            nx, ny, nz = self._dims
-            if 3 * nx * ny * (nz + 1) * 8 > 4 << 30:
-                raise McbratError("specifyParameters: direct level fluxes (recDirectLevelFluxes): the level bins of one batch would "
-                                  "not fit the 4 GiB tally budget.")
-        if levels:
-            directions = self.numIntensityDirections()
-            if intensityMus is not None:
-                directions = int(np.size(intensityMus))
-            elif computeIntensity is not None and not computeIntensity:
-                directions = 0
-            if directions > 0:
-                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with intensity directions: "
-                                  "the radiance kernels have no level tallies.")
-            wantOrders = self.numRecScatOrd >= 0
-            if numRecScatOrd is not None:
-                wantOrders = int(numRecScatOrd) >= 0
-            elif recScatOrd is not None and not recScatOrd:
-                wantOrders = False
-            if wantOrders:
-                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with scattering orders "
-                                  "(recScatOrd): no kernel tallies both.")
-            bdrf = surfaceBDRF if surfaceBDRF is not None else self.surfaceBDRF
-            if getattr(bdrf, "kind", 0) != 0:
-                raise McbratError("specifyParameters: level fluxes (recLevelFluxes) cannot be combined with a BRDF surface: "
-                                  "a reflected weight may exceed 1, which the level tallies do not hold.")
-        # the actinic flux: refused as the library refuses it, before anything of this call is kept
-        actinic = self.recActinicFlux if recActinicFlux is None else bool(recActinicFlux)
-        if actinic:
-            directions = self.numIntensityDirections()
-            if intensityMus is not None:
-                directions = int(np.size(intensityMus))
-            elif computeIntensity is not None and not computeIntensity:
-                directions = 0
-            if directions > 0:
-                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with intensity "
-                                  "directions: the radiance kernels have no track-length tally.")
-            wantOrders = self.numRecScatOrd >= 0
-            if numRecScatOrd is not None:
-                wantOrders = int(numRecScatOrd) >= 0
-            elif recScatOrd is not None and not recScatOrd:
-                wantOrders = False
-            if wantOrders:
-                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with scattering orders "
-                                  "(recScatOrd): no kernel tallies both.")
-            bdrf = surfaceBDRF if surfaceBDRF is not None else self.surfaceBDRF
-            if getattr(bdrf, "kind", 0) != 0:
-                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with a BRDF surface: "
-                                  "a reflected weight may exceed 1, which the track-length tally does not hold.")
-            if direct:
-                raise McbratError("specifyParameters: the actinic flux (recActinicFlux) cannot be combined with direct level fluxes "
-                                  "(recDirectLevelFluxes): no kernel tallies both.")
-            nx, ny, nz = self._dims
-            if ((2 * nx * ny * (nz + 1) if levels else 0) + nx * ny * nz) * 8 > 4 << 30:
-                raise McbratError("specifyParameters: the actinic flux (recActinicFlux): the level and actinic bins of one batch "
-                                  "would not fit the 4 GiB tally budget.")
-        # side fluxes: with level fluxes only -- and so refused with everything they are refused with,
-        # above -- and refused as the library refuses them, before anything of this call is kept
-        side = self.recSideFluxes if recSideFluxes is None else bool(recSideFluxes)
-        if side:
-            if not levels:
-                raise McbratError("specifyParameters: side fluxes (recSideFluxes) need level fluxes (recLevelFluxes): the kernels "
-                                  "that stop at every face tally both.")
-            if direct:
-                raise McbratError("specifyParameters: side fluxes (recSideFluxes) cannot be combined with direct level fluxes "
-                                  "(recDirectLevelFluxes): no kernel tallies both.")
-            if actinic:
-                raise McbratError("specifyParameters: side fluxes (recSideFluxes) cannot be combined with the actinic flux "
-                                  "(recActinicFlux): no kernel tallies both.")
-            nx, ny, nz = self._dims
-            if (2 * nx * ny * (nz + 1) + 4 * nx * ny * nz) * 8 > 4 << 30:
-                raise McbratError("specifyParameters: side fluxes (recSideFluxes): the level and side bins of one batch would not "
-                                  "fit the 4 GiB tally budget.")
+        # What the fields would become is worked out first and kept only when nothing has refused it, so that a refused call
+        # leaves the integrator as it was.  What may not be combined is the library's to say (mcbrat_settings_refusal).
+        new = {}
+        want = lambda name: new.get(name, getattr(self, name))  # noqa: E731
+        for k, v in unsupported.items():
+            if v not in (None, False):
+                raise McbratError("specifyParameters: keyword %s is not supported by the MI355X integrator" % k)
+        if minInverseTableSize is not None:  # :1103-1106, :1183-1184 (smaller values are ignored)
+            new["minInverseTableSize"] = max(int(minInverseTableSize), defaultMinInverseTableSize)
+        if useRayTracing is not None:
+            new["useRayTracing"] = bool(useRayTracing)
+        if useRussianRoulette is not None:
+            new["useRussianRoulette"] = bool(useRussianRoulette)
+        if LW_flag is not None:
+            new["LW_flag"] = float(LW_flag)
         # intensity keywords, :1130-1160 and :1186-1283
         if (intensityMus is None) != (intensityPhis is None):
             raise McbratError("specifyParameters: Both or neither of intensityMus, intensityPhis must be supplied")
@@ -239,84 +195,68 @@ class Integrator:
             phis = np.ascontiguousarray(intensityPhis, np.float32).reshape(-1)
             if mus.size != phis.size:
                 raise McbratError("specifyParameters: intensityMus, intensityPhis must be the same length")
-            self.intensityMus, self.intensityPhis = mus, phis
-            self.computeIntensity = mus.size > 0
+            new.update(intensityMus=mus, intensityPhis=phis, computeIntensity=mus.size > 0)
         if computeIntensity is not None:
-            if computeIntensity and self.intensityMus.size == 0:
+            if computeIntensity and want("intensityMus").size == 0:
                 raise McbratError("specifyParameters: Can't compute intensity without specifying directions.")
             if not computeIntensity and intensityMus is None:
-                self.computeIntensity = False
+                new["computeIntensity"] = False
         if minForwardTableSize is not None:
-            self.minForwardTableSize = max(int(minForwardTableSize), defaultMinForwardTableSize)
-            self._domain_token = None
+            new["minForwardTableSize"] = max(int(minForwardTableSize), defaultMinForwardTableSize)
         if useRussianRouletteForIntensity is not None:
-            self.useRussianRouletteForIntensity = bool(useRussianRouletteForIntensity)
+            new["useRussianRouletteForIntensity"] = bool(useRussianRouletteForIntensity)
         if zetaMin is not None and zetaMin >= 0.0:  # :1194-1201 (a negative value is ignored with a warning)
-            self.zetaMin = float(zetaMin)
+            new["zetaMin"] = float(zetaMin)
         if useHybridPhaseFunsForIntenCalcs is not None:
-            self.useHybridPhaseFunsForIntenCalcs = bool(useHybridPhaseFunsForIntenCalcs)
-            self._domain_token = None
+            new["useHybridPhaseFunsForIntenCalcs"] = bool(useHybridPhaseFunsForIntenCalcs)
         if hybridPhaseFunWidth is not None:  # :1108-1114, :1209-1215
             if hybridPhaseFunWidth > maxHybridPhaseFunWidth or hybridPhaseFunWidth < 0.0:
                 raise McbratError("specifyParameters: hybridPhaseFunWidth out of range (0 to 30degrees).")
-            self.hybridPhaseFunWidth = float(hybridPhaseFunWidth) if 0 < hybridPhaseFunWidth < maxHybridPhaseFunWidth \
+            new["hybridPhaseFunWidth"] = float(hybridPhaseFunWidth) if 0 < hybridPhaseFunWidth < maxHybridPhaseFunWidth \
                 else defaultHybridPhaseFunWidth
-            self._domain_token = None
         if numOrdersOrigPhaseFunIntenCalcs is not None:
             if numOrdersOrigPhaseFunIntenCalcs < 0:
                 raise McbratError("specifyParameters: numOrdersOrigPhaseFunIntenCalcs must be >= 0")
-            self.numOrdersOrigPhaseFunIntenCalcs = int(numOrdersOrigPhaseFunIntenCalcs)
+            new["numOrdersOrigPhaseFunIntenCalcs"] = int(numOrdersOrigPhaseFunIntenCalcs)
+        if limitIntensityContributions is not None:
+            new["limitIntensityContributions"] = bool(limitIntensityContributions)
+        if maxIntensityContribution is not None and maxIntensityContribution > 0.0:
+            new["maxIntensityContribution"] = float(maxIntensityContribution)
         # scattering orders (:1159-1171): recScatOrd=True needs numRecScatOrd; numRecScatOrd decides when given (< 0: off)
         if recScatOrd and numRecScatOrd is None:
             raise McbratError("specifyParameters: set recScatOrd to true, but did not provide number of orders to track.")
-        orders = self.numRecScatOrd
-        if numRecScatOrd is not None:
-            orders = int(numRecScatOrd) if int(numRecScatOrd) >= 0 else -1
-        elif recScatOrd is not None and not recScatOrd:
-            orders = -1
-        limit = self.limitIntensityContributions if limitIntensityContributions is None else bool(limitIntensityContributions)
-        if orders >= 0 and limit:
-            raise McbratError("specifyParameters: limitIntensityContributions cannot be combined with scattering orders (recScatOrd): "
-                              "the reference's redistribution adds each direction's clipped excess to every order, which would "
-                              "count it numRecScatOrd + 1 times.")
-        if limitIntensityContributions is not None:
-            self.limitIntensityContributions = bool(limitIntensityContributions)
-        if maxIntensityContribution is not None and maxIntensityContribution > 0.0:
-            self.maxIntensityContribution = float(maxIntensityContribution)
+        if numRecScatOrd is not None or (recScatOrd is not None and not recScatOrd):
+            orders = -1 if numRecScatOrd is None or int(numRecScatOrd) < 0 else int(numRecScatOrd)
+            new.update(numRecScatOrd=orders, recScatOrd=orders >= 0)
+        # the tallies (DESIGN.md sections 4.12 to 4.15)
+        if recLevelFluxes is not None:
+            new["recLevelFluxes"] = bool(recLevelFluxes)
+        if recDirectLevelFluxes is not None:
+            new["recDirectLevelFluxes"] = bool(recDirectLevelFluxes)
+        if recActinicFlux is not None:
+            new["recActinicFlux"] = bool(recActinicFlux)
+        if recSideFluxes is not None:
+            new["recSideFluxes"] = bool(recSideFluxes)
         if surfaceBDRF is not None:  # :1091-1094, :1173-1176
             if not (hasattr(surfaceBDRF, "isReady_surfaceDescription") and surfaceBDRF.isReady_surfaceDescription()):
                 raise McbratError("specifyParameters: surface description isn't valid.")
-            x, y = surfaceBDRF.xPosition, surfaceBDRF.yPosition
-            kind = getattr(surfaceBDRF, "kind", 0)
-            if kind == 0:
-                refl = np.ascontiguousarray(surfaceBDRF.BRDFParameters[0].T, np.float32)  # x fastest
-                self._check(self._lib.mcbrat_set_surface_description(self._ctx, int(x.size), int(y.size), ptr(x), ptr(y), ptr(refl)))
-            else:  # RPV, Ross-Li: [nParams][numY-1][numX-1], x fastest
-                q = np.ascontiguousarray(np.transpose(surfaceBDRF.BRDFParameters, (0, 2, 1)), np.float32)
-                self._check(self._lib.mcbrat_set_surface_brdf(self._ctx, int(kind), int(x.size), int(y.size), ptr(x), ptr(y),
-                                                              int(q.shape[0]), ptr(q)))
-            self.useSurfaceBDRF = True
-            self.surfaceBDRF = surfaceBDRF
-        for k, v in unsupported.items():
-            if v not in (None, False):
-                raise McbratError("specifyParameters: keyword %s is not supported by the MI355X integrator" % k)
-        if minInverseTableSize is not None:  # :1103-1106, :1183-1184 (smaller values are ignored)
-            self.minInverseTableSize = max(int(minInverseTableSize), defaultMinInverseTableSize)
-            self._domain_token = None
-        if useRayTracing is not None:
-            self.useRayTracing = bool(useRayTracing)
-        if useRussianRoulette is not None:
-            self.useRussianRoulette = bool(useRussianRoulette)
-        if LW_flag is not None:
-            self.LW_flag = float(LW_flag)
-        self.numRecScatOrd, self.recScatOrd = orders, orders >= 0
-        self.recLevelFluxes = levels
-        self.recDirectLevelFluxes = direct
-        self.recActinicFlux = actinic
-        self.recSideFluxes = side
-        self._push_parameters()
+        # one question to the library, when this call sets something the question is about (a library of an A/B run may lack it:
+        # the push refuses then)
+        question = (surfaceBDRF is not None or not new.keys().isdisjoint(_ASKED_ABOUT)) and getattr(self._lib, "mcbrat_settings_refusal", None)
+        if question:
+            surface = surfaceBDRF if surfaceBDRF is not None else self.surfaceBDRF
+            refused = question(self._ctx, int(want("intensityMus").size) if want("computeIntensity") else 0,
+                               int(want("limitIntensityContributions")), *(int(want(name)) for name in _RECORDING),
+                               int(getattr(surface, "kind", 0) != 0))
+            if refused:
+                raise McbratError(refused.decode())
+        for name, value in new.items():
+            setattr(self, name, value)
+        if not new.keys().isdisjoint(("minInverseTableSize", "minForwardTableSize", "useHybridPhaseFunsForIntenCalcs", "hybridPhaseFunWidth")):
+            self._domain_token = None  # (the tables depend on them)
+        self._push_parameters(surfaceBDRF)
 
-    def _push_parameters(self):
+    def _push_parameters(self, surface=None):
         # (what the library holds is remembered by content: a step of a small domain is two milliseconds, and the host side
         # of a call is part of it)
         token = (self.useRayTracing, self.useRussianRoulette, self.LW_flag)
@@ -324,68 +264,40 @@ class Integrator:
             self._check(self._lib.mcbrat_specify_parameters(self._ctx, int(self.useRayTracing),
                                                             int(self.useRussianRoulette), C.c_float(self.LW_flag)))
             self._param_token = token
-        self._push_intensity()
-
-    def _push_levels(self):
-        # (the direct tally needs level fluxes: off before them, on after them)
-        if not self.recDirectLevelFluxes:
-            self._push_direct_levels()
-        if self.recLevelFluxes != getattr(self, "_levels_token", False):
-            self._check(self._lib.mcbrat_specify_level_fluxes(self._ctx, int(self.recLevelFluxes)))
-            self._levels_token = self.recLevelFluxes
-        self._push_direct_levels()
-
-    def _push_direct_levels(self):
-        if self.recDirectLevelFluxes != getattr(self, "_direct_levels_token", False):
-            self._check(self._lib.mcbrat_specify_direct_level_fluxes(self._ctx, int(self.recDirectLevelFluxes)))
-            self._direct_levels_token = self.recDirectLevelFluxes
-
-    def _push_actinic(self):
-        if self.recActinicFlux != getattr(self, "_actinic_token", False):
-            self._check(self._lib.mcbrat_specify_actinic_flux(self._ctx, int(self.recActinicFlux)))
-            self._actinic_token = self.recActinicFlux
-
-    def _push_side(self):
-        if self.recSideFluxes != getattr(self, "_side_token", False):
-            self._check(self._lib.mcbrat_specify_side_fluxes(self._ctx, int(self.recSideFluxes)))
-            self._side_token = self.recSideFluxes
-
-    def _push_intensity(self):
-        if not self.recSideFluxes:
-            self._push_side()  # (off first: level fluxes cannot be switched off under it, the direct and actinic tallies not on)
-        if not self.recActinicFlux:
-            self._push_actinic()  # (off first, as level fluxes: what follows may be refused together with it -- the direct tally too)
-        if not self.recLevelFluxes:
-            self._push_levels()  # (off first: the settings below may be ones the library refuses together with level fluxes)
-        self._push_intensity_and_orders()
-        self._push_levels()
-        self._push_actinic()
-        self._push_side()
-
-    def _push_intensity_and_orders(self):
         n = int(self.intensityMus.size) if self.computeIntensity else 0
-        token = (n, self.intensityMus.tobytes(), self.intensityPhis.tobytes(), self.useRussianRouletteForIntensity, self.zetaMin,
-                 self.useHybridPhaseFunsForIntenCalcs, self.numOrdersOrigPhaseFunIntenCalcs, self.limitIntensityContributions,
-                 self.maxIntensityContribution)
-        if token == self._intensity_token:
-            self._push_orders()
+        intensity = (n, self.intensityMus.tobytes(), self.intensityPhis.tobytes(), self.useRussianRouletteForIntensity, self.zetaMin,
+                     self.useHybridPhaseFunsForIntenCalcs, self.numOrdersOrigPhaseFunIntenCalcs, self.limitIntensityContributions,
+                     self.maxIntensityContribution)
+        wanted = {name: getattr(self, name) for name in _RECORDING}
+        if wanted == self._held and intensity == self._intensity_token and surface is None:
             return
-        if self.numRecScatOrd != getattr(self, "_orders_token", -1) and self.numRecScatOrd < 0:
-            self._push_orders()  # (orders off first: the new intensity settings may be ones the library refuses together with orders)
-        self._check(self._lib.mcbrat_specify_intensity(
-            self._ctx, n, ptr(self.intensityMus) if n else None, ptr(self.intensityPhis) if n else None,
-            int(self.useRussianRouletteForIntensity), C.c_float(self.zetaMin), int(self.useHybridPhaseFunsForIntenCalcs),
-            int(self.numOrdersOrigPhaseFunIntenCalcs), int(self.limitIntensityContributions),
-            C.c_float(self.maxIntensityContribution)))
-        self._intensity_token = token
-        self._domain_token = None  # forward tables go with the optics
-        self._push_orders()
+        for step in _push_order(self._held, wanted, intensity != self._intensity_token, surface is not None):
+            if step == "surface":
+                self._push_surface(surface)
+            elif step == "intensity":
+                self._check(self._lib.mcbrat_specify_intensity(
+                    self._ctx, n, ptr(self.intensityMus) if n else None, ptr(self.intensityPhis) if n else None,
+                    int(self.useRussianRouletteForIntensity), C.c_float(self.zetaMin), int(self.useHybridPhaseFunsForIntenCalcs),
+                    int(self.numOrdersOrigPhaseFunIntenCalcs), int(self.limitIntensityContributions),
+                    C.c_float(self.maxIntensityContribution)))
+                self._intensity_token = intensity
+                self._domain_token = None  # forward tables go with the optics
+            else:
+                self._check(getattr(self._lib, _RECORDING[step][1])(self._ctx, int(wanted[step])))
+                self._held[step] = wanted[step]
 
-    def _push_orders(self):
-        # (after the intensity: the library refuses orders together with limitIntensityContributions in either order of calls)
-        if self.numRecScatOrd != getattr(self, "_orders_token", -1):
-            self._check(self._lib.mcbrat_specify_scattering_orders(self._ctx, int(self.numRecScatOrd)))
-            self._orders_token = self.numRecScatOrd
+    def _push_surface(self, surface):
+        x, y = surface.xPosition, surface.yPosition
+        kind = getattr(surface, "kind", 0)
+        if kind == 0:
+            refl = np.ascontiguousarray(surface.BRDFParameters[0].T, np.float32)  # x fastest
+            self._check(self._lib.mcbrat_set_surface_description(self._ctx, int(x.size), int(y.size), ptr(x), ptr(y), ptr(refl)))
+        else:  # RPV, Ross-Li, Cox-Munk: [nParams][numY-1][numX-1], x fastest
+            q = np.ascontiguousarray(np.transpose(surface.BRDFParameters, (0, 2, 1)), np.float32)
+            self._check(self._lib.mcbrat_set_surface_brdf(self._ctx, int(kind), int(x.size), int(y.size), ptr(x), ptr(y),
+                                                          int(q.shape[0]), ptr(q)))
+        self.useSurfaceBDRF = True
+        self.surfaceBDRF = surface
 
     def numIntensityDirections(self):
         return int(self.intensityMus.size) if self.computeIntensity else 0

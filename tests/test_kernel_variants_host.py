@@ -291,16 +291,25 @@ def messages():
 
 
 def _refuse(exe, messages, asks):
-    """asks: [(stage name, Asked, debug)] -> the rule list's answer to each, by the constant's name (None: not refused)"""
+    """asks: [(stage name or mask of stages, Asked, debug)] -> the rule list's answer to each, by the constant's name (None: not refused)"""
     lines = []
     for stage, c, debug in asks:
         bits = [c.inten, c.orders, c.limit, c.levels, c.direct, c.actinic, c.side, c.brdf, debug, c.emit,
                 c.O * c.orders <= c.B, c.bins(c.levels, c.direct, 0), c.all_bins(), c.stride()]
-        lines.append("%x %x\n" % (STAGES[stage], sum(1 << i for i, b in enumerate(bits) if b)))
+        lines.append("%x %x\n" % (STAGES.get(stage, stage), sum(1 << i for i, b in enumerate(bits) if b)))
     text = subprocess.run([exe, "refuse"], input="".join(lines), check=True, capture_output=True, text=True, timeout=300).stdout
     got = text.rstrip("\n").split("\n")
     assert len(got) == len(asks)
     return [None if g == "-" else messages[g] for g in got]
+
+
+def combinable(f):
+    """whether the setters let a context hold these flags together (the sizes apart)"""
+    if (f["direct"] or f["side"]) and not f["levels"]: return False
+    if (f["levels"] or f["actinic"]) and (f["inten"] or f["orders"] or f["brdf"] or f["counters"]): return False
+    if f["actinic"] and f["direct"]: return False
+    if f["side"] and (f["direct"] or f["actinic"]): return False
+    return not (f["limit"] and f["orders"])
 
 
 def _contexts():
@@ -310,11 +319,7 @@ def _contexts():
     out = []
     for flags in itertools.product((0, 1), repeat=len(FLAGS)):
         f = dict(zip(FLAGS, flags))
-        if (f["direct"] or f["side"]) and not f["levels"]: continue
-        if (f["levels"] or f["actinic"]) and (f["inten"] or f["orders"] or f["brdf"] or f["counters"]): continue
-        if f["actinic"] and f["direct"]: continue
-        if f["side"] and (f["direct"] or f["actinic"]): continue
-        if f["limit"] and f["orders"]: continue
+        if not combinable(f): continue
         for L, D, A, S, O, rest in itertools.product((1, 5), (1, 5), (1, 5), (1, 5), (1, 5), (0, 5)):
             c = Asked(f, L=L, D=D, A=A, S=S, O=O, rest=rest, B=4)
             if c.levels and not c.bins(c.levels, c.direct, 0): continue
@@ -368,6 +373,98 @@ def test_the_second_line_of_defence_refuses_the_same_settings(exe, messages):
         assert len(holds) != 1 or g == says
         if parent_check_ready(c) is None and (parent_trace_fates(c) if debug else parent_compute(c.with_(counters=0))) is None and not (debug and (c.brdf or c.inten or c.orders)):
             assert g is None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the one question (mcbrat_settings_refusal): refusal() at the union of the setters' stages, and the order in which the Python
+# integrator then calls the setters (mcbrat3d_amd/integrator.py: _push_order)
+# ---------------------------------------------------------------------------------------------------------------------------------
+QUESTION = ("SetIntensity", "SetOrders", "SetLevels", "SetDirect", "SetActinic", "SetSide", "SetBrdf")  # (LevelsOff stays out: its rules stand under SetDirect and SetSide)
+UNION = sum(STAGES[s] for s in QUESTION)
+
+
+def test_the_question_passes_every_state_a_context_can_be_in(exe, messages):
+    """... but those whose order bins do not fit: a context gets there through set_grid only (mcbrat_specify_scattering_orders
+    refuses the orders on such a grid, and a trace of that context refuses them again), an integrator never -- it sets its grid
+    once, before any setting -- and the question says of them what the setter would"""
+    states = _contexts()
+    got = _refuse(exe, messages, [(UNION, c, c.counters) for c in states])
+    for c, g in zip(states, got):
+        assert g == ("kOrdersBudgetMsg" if c.orders and not c.O <= c.B else None), (dict(c), g)
+
+
+def test_the_question_refuses_what_a_setter_refuses(exe, messages):
+    """over EVERY combination of the settings, at sizes that fit: refused exactly when one of the setters' stages refuses the same
+    settings, with the message of one of them -- and so with the rule's own where one rule holds (the allowance of the second
+    line of defence above)"""
+    import itertools
+    asks = []
+    for flags in itertools.product((0, 1), repeat=len(FLAGS)):
+        c = Asked(dict(zip(FLAGS, flags)), L=1, D=1, A=1, S=1, O=1, rest=0, B=9)
+        asks += [(UNION, c, c.counters)] + [(s, c, c.counters) for s in QUESTION]
+    got = _refuse(exe, messages, asks)
+    n = 1 + len(QUESTION)
+    refused = 0
+    for i in range(0, len(asks), n):
+        union, single = got[i], {g for g in got[i + 1:i + n] if g is not None}
+        assert (union is None) == (not single), (dict(asks[i][1]), union, single)
+        assert union is None or union in single, (dict(asks[i][1]), union, single)
+        refused += union is not None
+    assert 0 < refused < len(asks) // n
+
+
+def _push_steps(old, new):
+    """_push_order's steps from the state old to the state new -> [(the step's own stage or None, the state after it)]; the
+    intensity is always pushed and a BRDF surface given whenever new has one (a call may carry them unchanged: the steps of a
+    call that does not are these without some that change nothing)"""
+    from mcbrat3d_amd.integrator import _push_order
+    fields = {"numRecScatOrd": "orders", "recLevelFluxes": "levels", "recDirectLevelFluxes": "direct", "recActinicFlux": "actinic", "recSideFluxes": "side"}
+    on = {"orders": "SetOrders", "levels": "SetLevels", "direct": "SetDirect", "actinic": "SetActinic", "side": "SetSide"}
+    value = lambda c, name: (2 if c.orders else -1) if name == "numRecScatOrd" else bool(c[fields[name]])  # noqa: E731
+    held, wanted = ({name: value(c, name) for name in fields} for c in (old, new))
+    out, state = [], old
+    for step in _push_order(held, wanted, True, bool(new.brdf)):
+        if step == "surface":
+            stage, state = "SetBrdf", state.with_(brdf=1)
+        elif step == "intensity":
+            stage, state = "SetIntensity", state.with_(inten=new.inten, limit=new.limit)
+        else:
+            flag = fields[step]
+            stage = on[flag] if new[flag] else ("LevelsOff" if flag == "levels" else None)  # (the other setters ask nothing when they switch off)
+            state = state.with_(**{flag: new[flag]})
+        out.append((stage, state))
+    return out
+
+
+def test_the_push_order_is_never_refused_on_the_way(exe, messages):
+    """every ordered pair of states a context can be in, on one grid with the counters and the source as they are -- but a BRDF
+    surface taken away, which the integrator cannot do, and a new state the question refuses (above): none of the setter calls
+    from the old state to the new one is refused, and they end in the new state"""
+    import collections
+    groups = collections.defaultdict(list)
+    for c in _contexts():
+        groups[(c.L, c.D, c.A, c.S, c.O, c.rest, c.B, c.counters, c.emit)].append(c)
+    pairs = 0
+    lines = []
+    for states in groups.values():
+        for old in states:
+            for new in states:
+                if (old.brdf and not new.brdf) or (new.orders and not new.O <= new.B):
+                    continue
+                steps = _push_steps(old, new)
+                assert steps[-1][1] == new, (dict(old), dict(new))
+                lines += [(stage, state, state.counters, old, new) for stage, state in steps if stage]
+                pairs += 1
+    got = _refuse(exe, messages, [l[:3] for l in lines])
+    wrong = [(stage, dict(old), dict(new), g) for (stage, _, _, old, new), g in zip(lines, got) if g is not None]
+    assert not wrong, wrong[:5]
+    assert pairs > 10000 and len(lines) > pairs
+
+
+def test_the_push_order_needs_no_native_library():
+    import sys
+    code = "from mcbrat3d_amd.integrator import _push_order; from mcbrat3d_amd import _capi; assert _capi._lib is None"
+    subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT, timeout=120)
 
 
 def test_rule_precedence(exe, messages):
