@@ -32,7 +32,19 @@ module mcbrat_hip_integrator
             setSurfaceDescription, setSurfaceBRDF, setWalkOptions, setOption, getFrequencyDistr, shareMoments, chainAfter, numBadPhotons, &
             specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes, &
             specifyDirectLevelFluxes, reportDirectLevelFluxes, specifyActinicFlux, reportActinicFlux, &
-            specifySideFluxes, reportSideFluxes
+            specifySideFluxes, reportSideFluxes, &
+            camera, renderCamera, sunTransmittance
+
+  ! mcbrat_camera of include/mcbrat.h, member for member (the backward camera, DESIGN.md section 4.19): kind 0 orthographic --
+  ! mu, phiDeg, the footprint xLo .. yHi and the height z -- or 1 pinhole -- position, look, up, fovXDeg
+  type, bind(C) :: camera
+    integer(c_int32_t) :: kind = 0, npx = 1, npy = 1, jitter = 1, gridInLds = -1
+    real(c_float)      :: mu = 1., phiDeg = 0.
+    real(c_double)     :: xLo = 0., xHi = 1., yLo = 0., yHi = 1., z = 0.
+    real(c_double)     :: position(3) = 0., look(3) = (/ 0._c_double, 0._c_double, -1._c_double /), &
+                          up(3) = (/ 0._c_double, 1._c_double, 0._c_double /)
+    real(c_float)      :: fovXDeg = 60.
+  end type camera
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -244,6 +256,25 @@ module mcbrat_hip_integrator
     function mcbrat_report_side_fluxes(ctx, mSide, fSide) bind(C, name="mcbrat_report_side_fluxes") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, mSide, fSide   ! (c_null_ptr: not wanted)
+      integer(c_int) :: rc
+    end function
+    function mcbrat_render_camera(ctx, cam, seed, firstSample, samplesPerPixel, numBatches, radiance, radianceStdErr, &
+                                  batchMeans, dropped) bind(C, name="mcbrat_render_camera") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, camera
+      type(c_ptr), value :: ctx
+      type(camera), intent(in) :: cam
+      integer(c_int64_t), value :: seed, firstSample, samplesPerPixel
+      integer(c_int32_t), value :: numBatches
+      type(c_ptr), value :: radiance, radianceStdErr, batchMeans   ! (c_null_ptr: not wanted; radiance is needed)
+      integer(c_int64_t), intent(out) :: dropped
+      integer(c_int) :: rc
+    end function
+    function mcbrat_sun_transmittance(ctx, n, xyz, transmittance) bind(C, name="mcbrat_sun_transmittance") result(rc)
+      import :: c_ptr, c_int, c_int64_t, c_double, c_float
+      type(c_ptr), value :: ctx
+      integer(c_int64_t), value :: n
+      real(c_double), intent(in) :: xyz(*)
+      real(c_float), intent(out) :: transmittance(*)
       integer(c_int) :: rc
     end function
     function mcbrat_forward_table_legendre(nCoef, coef, nAngles, table) bind(C, name="mcbrat_forward_table_legendre") result(rc)
@@ -849,4 +880,43 @@ contains
     ierr = mcbrat_inverse_table_legendre(int(size(coefficients), c_int32_t), coefficients, &
                                          int(size(table), c_int32_t), table)
   end subroutine inverseTableLegendre
+  !------------------------------------------------------------------------------------------
+  ! The backward camera (include/mcbrat.h: mcbrat_render_camera): numBatches batches of samplesPerPixel paths per pixel for the
+  ! domain and the Directional solar source the integrator holds (the forward tables must have been set: setForwardTable).
+  ! radiance(npx, npy) is the mean of the batch means, radianceStdErr its standard error; numDropped the paths a loop bound ended.
+  subroutine renderCamera(this, cam, seed, firstSample, samplesPerPixel, numBatches, radiance, radianceStdErr, numDropped, ierr)
+    type(integrator), intent(inout) :: this
+    type(camera), intent(in) :: cam
+    integer(c_int64_t), intent(in) :: seed, firstSample, samplesPerPixel
+    integer, intent(in) :: numBatches
+    real, dimension(:, :), contiguous, target, intent(out) :: radiance
+    real, dimension(:, :), contiguous, optional, target, intent(out) :: radianceStdErr
+    integer(c_int64_t), optional, intent(out) :: numDropped
+    integer, intent(out) :: ierr
+    type(c_ptr) :: pErr
+    integer(c_int64_t) :: dropped
+    ierr = 1
+    if (any(shape(radiance) /= (/ cam%npx, cam%npy /))) return
+    pErr = c_null_ptr
+    if (present(radianceStdErr)) then
+      if (any(shape(radianceStdErr) /= (/ cam%npx, cam%npy /))) return
+      pErr = c_loc(radianceStdErr)
+    end if
+    dropped = 0
+    ierr = mcbrat_render_camera(this%ctx, cam, seed, firstSample, samplesPerPixel, int(numBatches, c_int32_t), c_loc(radiance), &
+                                pErr, c_null_ptr, dropped)
+    if (present(numDropped)) numDropped = dropped
+  end subroutine renderCamera
+
+  ! exp(-optical depth) from each point xyz(3, n) toward the sun up to the top of the domain (mcbrat_sun_transmittance)
+  subroutine sunTransmittance(this, xyz, transmittance, ierr)
+    type(integrator), intent(inout) :: this
+    real(c_double), dimension(:, :), contiguous, intent(in) :: xyz
+    real, dimension(:), contiguous, intent(out) :: transmittance
+    integer, intent(out) :: ierr
+    ierr = 1
+    if (size(xyz, 1) /= 3 .or. size(xyz, 2) /= size(transmittance)) return
+    ierr = mcbrat_sun_transmittance(this%ctx, int(size(transmittance), c_int64_t), xyz, transmittance)
+  end subroutine sunTransmittance
+
 end module mcbrat_hip_integrator

@@ -366,6 +366,7 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
  *                 across the launch, two batches' tallies per workgroup where they fit; environment MCBRAT_BATCH_UNITS)
  *   "blockSpanKernel"  1: the block walk keeps its general instantiation where the one without periodic folds inside blocks
  *                 would do (default 0: automatic; both trace every photon bit for bit alike -- tests/test_gpu_blockwalk_nospan.py)
+ *   "cameraGridInLds"  where mcbrat_sun_transmittance reads the grid: -1 (default) LDS where it fits, 0 global memory, 1 LDS
  * One option does change results, within their noise -- it chooses between two unbiased estimators:
  *   "glintSampling"  1 (default): a reflection off a Cox-Munk patch draws its direction from the mixture of the glint lobe and
  *                 the Lambertian draw (mcbrat_set_surface_brdf); 0: the Lambertian draw times R, as the land models
@@ -420,6 +421,56 @@ double mcbrat_brdf_albedo(int32_t kind, const float *params, double muIn);
  * unknown kind. */
 int mcbrat_brdf_sample(int32_t kind, const float *params, const double *dIn, int64_t n, const double *u, double *dOut,
                        float *weight);
+
+/* ---- backward Monte Carlo camera (an addition under ABI version 3) -------------------------------------
+ * Radiance at a sensor anywhere in the domain, per pixel: paths start at the sensor and walk BACKWARD; every collision and
+ * every surface reflection takes a local estimate toward the sun.  Units: radiance per unit solar flux through a horizontal
+ * plane at the top, as `intensity` (a vacuum over a Lambertian albedo a gives a / pi).  Needs the grid, the optics, the inverse
+ * and the forward tables (mcbrat_set_forward_table; of a hybrid pair the original ones) and the Directional solar source
+ * (mcbrat_set_source_solar); the surface is Lambertian -- the domain's albedo or mcbrat_set_surface_description. */
+typedef struct mcbrat_camera {
+  int32_t kind;          /* 0 orthographic, 1 pinhole */
+  int32_t npx, npy;
+  int32_t jitter;        /* 1: samples uniform in the pixel; 0: every sample at the pixel centre */
+  int32_t gridInLds;     /* -1 library's choice, 0, 1: the extinction grid and the edges staged in LDS (1 is refused where they do not fit) */
+  /* orthographic: the light arriving travels along (mu, phiDeg) -- the convention of intensityMus / intensityPhis;
+     pixel (i, j) is the footprint cell of [xLo, xHi] x [yLo, yHi] cut npx x npy, at height z (z0 <= z <= zMax) */
+  float mu, phiDeg;
+  double xLo, xHi, yLo, yHi, z;
+  /* pinhole: position (folded periodically in x, y; z0 <= z <= zMax), look and up vectors (need not be normalised,
+     not parallel), full horizontal field of view in degrees (0 < fov < 180) */
+  double position[3], look[3], up[3];
+  float fovXDeg;
+} mcbrat_camera;
+
+/* numBatches batches of samplesPerPixel paths per pixel.  Sample k of batch b of a pixel has the index firstSample +
+ * b * samplesPerPixel + k; its random numbers are Philox4x32-10(key = seed, counter = (event | block << 24, pixel, index)), and
+ * the tallies are 64-bit integers, so the result of a (pixel, sample range) depends on nothing else -- not on scheduling, not
+ * on gridInLds, not on what else the call renders.  radiance[npy][npx] (x fastest; j grows upward for the pinhole) is the mean
+ * of the batch means, radianceStdErr its standard error (0 where numBatches == 1), batchMeans[numBatches][npy][npx] the means
+ * themselves; *dropped counts the paths a loop bound ended (section 4.7; they contribute nothing).  Any of the last three may
+ * be NULL.  The call waits for what the context has in flight, works on device buffers of its own and leaves the context's
+ * settings, tallies, moments and walk mode as they were.
+ * Refused, before any launch: no grid / optics / inverse or forward tables; a source other than the Directional solar one; a
+ * BRDF surface (mcbrat_set_surface_brdf kinds 1 to 3); mu == 0, z or position[2] outside [z0, zMax], a degenerate footprint,
+ * look parallel to up, a field of view outside (0, 180); more bins (npx * npy * numBatches) than the 4 GiB tally budget holds;
+ * samplesPerPixel < 1 or numBatches < 1. */
+int mcbrat_render_camera(mcbrat_ctx *ctx, const mcbrat_camera *cam, uint64_t seed, uint64_t firstSample,
+                         int64_t samplesPerPixel /* per batch */, int32_t numBatches,
+                         float *radiance /* [npy][npx] mean of the batch means */,
+                         float *radianceStdErr /* [npy][npx], may be NULL; 0 where numBatches == 1 */,
+                         float *batchMeans /* [numBatches][npy][npx], may be NULL */,
+                         int64_t *dropped /* may be NULL */);
+/* The mapping the kernel uses, on the host (no context): origin and backward direction (unit vector) of the position (i + u,
+ * j + v) of the image, 0 <= u, v <= 1.  The origin is not folded into the domain.  Non-zero for a camera that
+ * mcbrat_render_camera refuses on its own members. */
+int mcbrat_camera_ray(const mcbrat_camera *cam, int32_t i, int32_t j, double u, double v,
+                      double origin[3], double direction[3]);
+/* exp(-optical depth) from each of n points (x, y, z; x and y folded periodically, z0 <= z <= zMax) against the sun's direction
+ * of travel to the top of the domain: the direct transmittance / cloud shadow at a point, without noise -- the camera kernel's
+ * own device function.  Needs grid, optics and the Directional solar source.  Option "cameraGridInLds" (mcbrat_set_option: -1
+ * library's choice, 0, 1) chooses where it reads the grid; the results are the same bit for bit. */
+int mcbrat_sun_transmittance(mcbrat_ctx *ctx, int64_t n, const double *xyz /* [n][3] */, float *transmittance /* [n] */);
 
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air

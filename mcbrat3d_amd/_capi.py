@@ -35,6 +35,14 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Camera(C.Structure):
+    """mcbrat_camera of include/mcbrat.h (the backward camera)."""
+    _fields_ = [("kind", C.c_int32), ("npx", C.c_int32), ("npy", C.c_int32), ("jitter", C.c_int32), ("gridInLds", C.c_int32),
+                ("mu", C.c_float), ("phiDeg", C.c_float),
+                ("xLo", C.c_double), ("xHi", C.c_double), ("yLo", C.c_double), ("yHi", C.c_double), ("z", C.c_double),
+                ("position", C.c_double * 3), ("look", C.c_double * 3), ("up", C.c_double * 3), ("fovXDeg", C.c_float)]
+
+
 # every symbol include/mcbrat.h declares: (restype, argtypes)
 _vp, _i32, _i64, _u64, _f, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 SYMBOLS = {
@@ -97,6 +105,9 @@ SYMBOLS = {
     "mcbrat_brdf_reflectance": (_f, [_i32, _vp, _vp, _vp]),
     "mcbrat_brdf_albedo": (_d, [_i32, _vp, _d]),
     "mcbrat_brdf_sample": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mcbrat_render_camera": (C.c_int, [_vp, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "mcbrat_camera_ray": (C.c_int, [_vp, _i32, _i32, _d, _d, _vp, _vp]),
+    "mcbrat_sun_transmittance": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),
     "mcbrat_inverse_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_inverse_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
@@ -106,7 +117,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes and mcbrat_settings_refusal are additions under 3)
+ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes, mcbrat_settings_refusal and the backward camera are additions under 3)
 
 
 def hip_runtimes():

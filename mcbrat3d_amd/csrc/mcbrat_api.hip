@@ -18,6 +18,7 @@
 #include "mcbrat_blockwalk.hip"
 #include "mcbrat_variants.h"
 #include "mcbrat_devmem.h"
+#include "mcbrat_camera_ctx.h"
 
 using namespace mcbrat;
 
@@ -189,6 +190,7 @@ struct mcbrat_ctx {
   // mcbrat_frequency_distribution's device buffers, kept and grown with numLambda
   DeviceBuffer<double> dFreqCdf;
   DeviceBuffer<unsigned long long> dFreqCounts;
+  int cameraGridInLds = -1;  // option "cameraGridInLds": where mcbrat_sun_transmittance reads the grid (-1: LDS where it fits)
   bool countersOn = false;
   float lastTraceMs = 0.f;
   mcbrat_counters lastCounters{};
@@ -1034,6 +1036,34 @@ int autotune(mcbrat_ctx *c, DevParams p, unsigned long long ppb, int nBatches) {
 
 }  // namespace
 
+// The backward camera's view of a context (mcbrat_camera_ctx.h; mcbrat_camera.hip is a translation unit of its own)
+int mcbrat_camera_fail(mcbrat_ctx *c, const char *msg) { return fail(c, msg); }
+int mcbrat_camera_context(mcbrat_ctx *c, CameraContext *out, bool needTables) {
+  if (!c || !out) return 1;
+  (void)hipSetDevice(c->device);
+  if (sync_all(c)) return 1;
+  *out = CameraContext{};
+  out->device = c->device; out->numCUs = c->numCUs; out->ldsPerCU = c->ldsPerCU;
+  out->haveGrid = c->haveGrid; out->haveOptics = c->haveGrid && c->haveOptics; out->haveSource = c->haveSource;
+  out->solarDirectional = c->haveSource && c->srcKind == 0 && c->solarKind == 0;
+  out->brdfSurface = c->surfNumX > 0 && c->surfKind != 0;
+  out->nc = c->nc; out->gridInLds = c->cameraGridInLds;
+  out->xe = &c->xe; out->ye = &c->ye; out->ze = &c->ze;
+  out->fwd = &c->fwdOrig; out->fwdNAngles = &c->fwdNAngles; out->fwdNEntries = &c->fwdNEntries; out->maxPfi = &c->maxPfi;
+  if (!out->haveOptics) return 0;
+  if (init_lane(c, c->cur)) return 1;
+  out->stream = c->L().stream;
+  if (needTables) {
+    if (sync_tables(c)) return 1;
+    out->haveInverseTables = true;
+  }
+  fill_params(c, out->p);
+  out->p.ext = c->dExt.get(); out->p.cum = c->dCum.get(); out->p.ssa = c->dSsa.get(); out->p.pfi = c->dPfi.get();
+  out->p.extWalk = out->p.ext;
+  out->p.brickTable = nullptr;
+  return 0;
+}
+
 extern "C" {
 
 int mcbrat_abi_version(void) { return MCBRAT_ABI_VERSION; }
@@ -1641,6 +1671,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   else if (n == "batchUnits") c->batchUnits = value != 0;
   else if (n == "blockSpanKernel") c->blockSpanKernel = value != 0;
   else if (n == "glintSampling") c->glintSampling = value != 0;
+  else if (n == "cameraGridInLds") c->cameraGridInLds = std::max(-1, std::min(1, (int)value));
   else return fail(c, "set_option: unknown option '" + n + "'");
   return 0;
 }

@@ -1,0 +1,557 @@
+// mcbrat_camera.hip -- the backward Monte Carlo camera (include/mcbrat.h: mcbrat_render_camera,
+// mcbrat_camera_ray, mcbrat_sun_transmittance).  A translation unit of its own: camera_kernel and its host code; the tracing
+// kernels, their variant table and their parameter block are not touched.
+//
+// One lane per path.  A path starts at the sensor (mcbrat_camera_ray.h) and walks BACKWARD.  Leg: tau = -ln u, cell face by cell
+// face through the periodic grid until tau is used up, the top (the path ends: nothing diffuse comes in from above) or the
+// surface.  Collision: component pick, w *= omega0, local estimate w P(Theta) T_sun(r) / (4 pi mu0) toward the sun, roulette,
+// new direction from the inverse table (the phase function is symmetric: the sampler is the forward one).  Surface (Lambertian):
+// w *= a(x, y), estimate w T_sun / pi, cosine-weighted upward direction from zSurf.  T_sun walks from the point against the
+// sun's direction of travel to the top: deterministic, no roulette.  march() below is both walks: the hot path.
+//
+// Random numbers: Philox4x32-10, key = seed, counter = (event | block << 24, pixel, sample index lo, hi).
+//    event 0          block 0 = [u, v, -, -]            the position in the pixel (jitter)
+//    event e >= 1     block 0 = [tau, X, Y, Z]          collision: scattering angle X, azimuth 2 pi Y, component Z
+//                                                       surface:   mu = sqrt(X) (X = 0: Z), azimuth 2 pi Y
+//                     block 1 = [-, roulette, -, -]
+// Tally: a lane sums its path's estimates in a float, converts the sum to i64 fixed point (CamParams::scale) at the path's end
+// and adds it to the bin (batch, pixel): integer sums, so an image does not depend on scheduling.
+//
+// Component pick, roulette, scattering angle and new direction are written out here as they are in trace_kernel
+// (mcbrat_kernels.hip, HOT ROWS) and trace_block_kernel (mcbrat_blockwalk.hip, HOT ROWS): a change to one of those rules is made
+// in all three.  What mcbrat_photon.h shares (Philox, u01, lambert_direction, find_cell, surface_reflectance, ...) is called.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mcbrat_photon.h"
+#include "mcbrat_camera_ray.h"
+#include "mcbrat_camera_ctx.h"
+#include "mcbrat_devmem.h"
+
+namespace mcbrat {
+
+constexpr unsigned kCameraMaxEvents = 1u << 20;  // legs per path (the event has 24 bits of the counter)
+
+struct CamParams {
+  CameraGeometry g;
+  int jitter;
+  unsigned long long spp;          // samples per pixel and batch
+  unsigned long long npix;
+  unsigned long long firstSample;
+  unsigned long long total;        // paths of the launch: bins * spp, index = (batch * npix + pixel) * spp + k
+  unsigned long long pathsPerLane; // a wave takes 64 * pathsPerLane consecutive indices, lane l the indices l, l + 64, ...
+  long long *bins;                 // [nBatches][npix] fixed point
+  unsigned long long *dropped;
+  double scale;                    // fixed-point units per unit radiance (a power of two)
+  double pathMax;                  // a path's sum saturates here, in units: spp * pathMax < 2^62
+  unsigned maxSunCross, maxLegCross, maxEvents;  // loop bounds (host, from the geometry)
+  float sun[3];                    // unit vector TOWARD the sun: minus the direction of travel
+  float invFourPiMu0;
+  const float *fwd;                // forward tables, components concatenated, [entry][angle]
+  int fwdOffset[MCBRAT_MAX_COMPONENTS], fwdNAngles[MCBRAT_MAX_COMPONENTS];
+  // mcbrat_sun_transmittance
+  const double *points;
+  float *transmittance;
+  long long nPoints;
+};
+
+struct GridView { const double *xe, *ye, *ze; const float *ext; };
+
+// The extinction grid and the edges: staged in LDS (every lane of the workgroup calls this), or where they lie in global memory
+template <int BLOCK, bool GRID_LDS>
+__device__ __forceinline__ GridView grid_view(const DevParams &p, unsigned char *smem) {
+  GridView g;
+  if (GRID_LDS) {
+    double *s_edge = reinterpret_cast<double *>(smem);
+    const int nEdge = p.nx + p.ny + p.nz + 3, nvox = p.nx * p.ny * p.nz;
+    float *s_ext = reinterpret_cast<float *>(s_edge + nEdge);
+    for (int i = threadIdx.x; i < nEdge; i += BLOCK) s_edge[i] = p.edges[i];
+    for (int i = threadIdx.x; i < nvox; i += BLOCK) s_ext[i] = p.ext[i];
+    __syncthreads();
+    g.xe = s_edge; g.ext = s_ext;
+  } else {
+    g.xe = p.edges; g.ext = p.ext;
+  }
+  g.ye = g.xe + p.nx + 1;
+  g.ze = g.ye + p.ny + 1;
+  return g;
+}
+
+struct Ray {
+  double ox, oy, oz;   // origin, in the periodic image the walk stands in
+  float dx, dy, dz;
+  int ix, iy, iz;      // cell, 0-based
+};
+enum : int { END_COLLISION = 0, END_TOP = 1, END_SURFACE = 2, END_BOUND = 3 };
+
+// Folds (x, y) into the domain and finds the cell of the point (z clamped to the layers: zMax belongs to the top one)
+__device__ __forceinline__ void locate(const DevParams &p, const GridView &g, Ray &r) {
+  r.ox -= floor((r.ox - p.x0) * p.invLx) * p.Lx;
+  if (r.ox < p.x0) r.ox += p.Lx;
+  if (r.ox >= p.xMax) r.ox -= p.Lx;
+  r.oy -= floor((r.oy - p.y0) * p.invLy) * p.Ly;
+  if (r.oy < p.y0) r.oy += p.Ly;
+  if (r.oy >= p.yMax) r.oy -= p.Ly;
+  r.ix = find_cell(g.xe, p.nx, r.ox);
+  r.iy = find_cell(g.ye, p.ny, r.oy);
+  r.iz = find_cell(g.ze, p.nz, r.oz);
+}
+
+// Walks from the ray's origin along its direction, cell face by cell face, periodic in x and y, marching by cell INDEX (a face
+// is crossed exactly once, whatever the rounding of its distance), until `target` optical depth is used up (END_COLLISION), the
+// top, the surface, or maxCross crossings.  tEnd: the distance walked; acc: the optical depth walked through.  Distances to
+// faces are differences in double against the origin, times 1 / direction in float; a tie crosses its faces one after the other
+// over a segment of length 0.  r.ix, iy, iz, ox, oy end as the cell and the periodic image of the end point.
+__device__ __forceinline__ int march(const DevParams &p, const GridView &g, Ray &r, float target, unsigned maxCross, float &tEnd, float &acc) {
+  const float jx = fabsf(r.dx) >= 2.0f * FLT_MIN ? 1.0f / r.dx : 0.0f;
+  const float jy = fabsf(r.dy) >= 2.0f * FLT_MIN ? 1.0f / r.dy : 0.0f;
+  const float jz = fabsf(r.dz) >= 2.0f * FLT_MIN ? 1.0f / r.dz : 0.0f;
+  const int hx = r.dx >= 0.0f ? 1 : 0, hy = r.dy >= 0.0f ? 1 : 0, hz = r.dz >= 0.0f ? 1 : 0;
+  int ix = r.ix, iy = r.iy, iz = r.iz;
+  double ox = r.ox, oy = r.oy;
+  float tx = jx != 0.0f ? (float)(g.xe[ix + hx] - ox) * jx : FLT_MAX;
+  float ty = jy != 0.0f ? (float)(g.ye[iy + hy] - oy) * jy : FLT_MAX;
+  float tz = jz != 0.0f ? (float)(g.ze[iz + hz] - r.oz) * jz : FLT_MAX;
+  float tcur = 0.0f;
+  int end = END_BOUND;
+  acc = 0.0f;
+  for (unsigned n = 0; n < maxCross; ++n) {
+    const float e = g.ext[(iz * p.ny + iy) * p.nx + ix];
+    const float tmin = fminf(tx, fminf(ty, tz));
+    const float seg = fmaxf(tmin - tcur, 0.0f);
+    const float tauSeg = seg * e;
+    if (e > 0.0f && acc + tauSeg >= target) {
+      tcur = fminf(tcur + (target - acc) / e, fmaxf(tmin, tcur));
+      acc = target;
+      end = END_COLLISION;
+      break;
+    }
+    acc += tauSeg;
+    tcur = fmaxf(tmin, tcur);
+    if (tz <= tx && tz <= ty) {
+      iz += hz ? 1 : -1;
+      if (iz < 0) { iz = 0; end = END_SURFACE; break; }
+      if (iz >= p.nz) { iz = p.nz - 1; end = END_TOP; break; }
+      tz = (float)(g.ze[iz + hz] - r.oz) * jz;
+    } else if (tx <= ty) {
+      ix += hx ? 1 : -1;
+      if (ix < 0) { ix = p.nx - 1; ox += p.Lx; }
+      if (ix >= p.nx) { ix = 0; ox -= p.Lx; }
+      tx = (float)(g.xe[ix + hx] - ox) * jx;
+    } else {
+      iy += hy ? 1 : -1;
+      if (iy < 0) { iy = p.ny - 1; oy += p.Ly; }
+      if (iy >= p.ny) { iy = 0; oy -= p.Ly; }
+      ty = (float)(g.ye[iy + hy] - oy) * jy;
+    }
+  }
+  r.ix = ix; r.iy = iy; r.iz = iz; r.ox = ox; r.oy = oy;
+  tEnd = tcur;
+  return end;
+}
+
+// exp(-optical depth) from (x, y, z) in cell (ix, iy, iz) toward the sun up to the top; `bound`: the walk did not get there
+__device__ __forceinline__ float sun_transmittance(const DevParams &p, const CamParams &cp, const GridView &g, double x, double y, double z,
+                                                   int ix, int iy, int iz, bool &bound) {
+  Ray s{x, y, z, cp.sun[0], cp.sun[1], cp.sun[2], ix, iy, iz};
+  float t, tau;
+  const int end = march(p, g, s, FLT_MAX, cp.maxSunCross, t, tau);
+  bound = end != END_TOP;
+  return expf(-tau);
+}
+
+__device__ __forceinline__ float camera_albedo(const DevParams &p, double x, double y) {
+  return p.surfNumX > 0 ? surface_reflectance(p, x, y) : p.albedo;
+}
+
+template <int BLOCK, bool GRID_LDS>
+__global__ void __launch_bounds__(BLOCK, MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
+  constexpr float kPi = 3.14159265358979312f;
+  const int lane = threadIdx.x & (kWave - 1);
+  const unsigned long long wave = ((unsigned long long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  const unsigned long long chunk = wave * (unsigned long long)kWave * cp.pathsPerLane;
+  const int nvox = p.nx * p.ny * p.nz;
+
+  unsigned long long pendBin = ~0ull;  // the bin the lane is summing for, and its sum
+  long long pend = 0;
+  unsigned nDropped = 0;
+
+  for (unsigned long long j = 0; j < cp.pathsPerLane; ++j) {
+    const unsigned long long index = chunk + j * kWave + (unsigned long long)lane;
+    if (index >= cp.total) break;
+    const unsigned long long bin = index / cp.spp, k = index - bin * cp.spp;
+    const unsigned long long batch = bin / cp.npix, pixel = bin - batch * cp.npix;
+    const unsigned long long sample = cp.firstSample + batch * cp.spp + k;
+    const uint32_t sLo = (uint32_t)sample, sHi = (uint32_t)(sample >> 32), pix = (uint32_t)pixel;
+    if (bin != pendBin) {
+      if (pend != 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
+      pendBin = bin; pend = 0;
+    }
+    Ray r;
+    {
+      double u = 0.5, v = 0.5, o[3], d[3];
+      if (cp.jitter) {
+        uint32_t q[4];
+        philox4x32_10(0u, pix, sLo, sHi, p.seedLo, p.seedHi, q);
+        u = (double)u01(q[0]); v = (double)u01(q[1]);
+      }
+      camera_ray(cp.g, (int)(pixel % (unsigned long long)cp.g.npx), (int)(pixel / (unsigned long long)cp.g.npx), u, v, o, d);
+      r.ox = o[0]; r.oy = o[1]; r.oz = o[2];
+      r.dx = (float)d[0]; r.dy = (float)d[1]; r.dz = (float)d[2];
+      locate(p, g, r);
+    }
+    float w = 1.0f, sum = 0.0f;
+    bool dropped = false;
+    for (uint32_t event = 1;; ++event) {
+      if (event > cp.maxEvents) { dropped = true; break; }
+      uint32_t q[4];
+      philox4x32_10(event, pix, sLo, sHi, p.seedLo, p.seedHi, q);
+      const float uX = u01(q[1]), uY = u01(q[2]), uZ = u01(q[3]);
+      const float tau = fmaxf(-logf(fmaxf(u01(q[0]), FLT_MIN)), FLT_MIN);
+      float t, acc;
+      const int end = march(p, g, r, tau, cp.maxLegCross, t, acc);
+      if (end == END_TOP) break;
+      if (end == END_BOUND) { dropped = true; break; }
+      // where the leg ended, in the periodic image the walk stands in
+      r.ox = r.ox + (double)r.dx * (double)t;
+      r.oy = r.oy + (double)r.dy * (double)t;
+      if (end == END_SURFACE) {
+        r.oz = p.zSurf;
+        w *= camera_albedo(p, r.ox, r.oy);
+        if (!(w > 0.0f)) break;
+        bool bound;
+        const float T = sun_transmittance(p, cp, g, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, bound);
+        if (bound) { dropped = true; break; }
+        sum += w * T * (1.0f / kPi);
+        float mu = sqrtf(uX);
+        if (mu == 0.0f) mu = fmaxf(sqrtf(uZ), 1.52587890625e-05f);  // (a draw of exactly 0: the spare number, at least 2^-16)
+        lambert_direction(mu, uY, r.dx, r.dy, r.dz);
+        continue;
+      }
+      r.oz = r.oz + (double)r.dz * (double)t;
+      const int cell = (r.iz * p.ny + r.iy) * p.nx + r.ix;
+      int c = 0;  // component pick: findIndex over [0, cumExt(:)]
+      for (int kc = 0; kc < p.nc - 1; kc++)
+        if (uZ >= p.cum[(long long)kc * nvox + cell]) c = kc + 1;
+      w *= p.ssa[(long long)c * nvox + cell];
+      if (!(w > 0.0f)) break;
+      const int pfEntry = p.pfi[(long long)c * nvox + cell];
+      {
+        // the local estimate toward the sun: Theta between the sun's direction of travel and -d, the direction the light
+        // travels along this leg; P by the reference's linear interpolation in angle (lookUpPhaseFuncValsFromTable)
+        float proj = r.dx * cp.sun[0] + r.dy * cp.sun[1] + r.dz * cp.sun[2];
+        if (fabsf(proj) > 1.0f) proj = copysignf(1.0f, proj);
+        const float ang = acosf(proj);
+        const int nA = cp.fwdNAngles[c];
+        const float *ft = cp.fwd + cp.fwdOffset[c] + (long long)pfEntry * nA;
+        const float deltaTheta = kPi / (float)(nA - 1);
+        const int ai = (int)(ang / deltaTheta) + 1;
+        float val;
+        if (ai < nA) {
+          const float wt = 1.0f - (ang - (float)(ai - 1) * deltaTheta) / deltaTheta;
+          val = wt * ft[ai - 1] + (1.0f - wt) * ft[ai];
+        } else {
+          val = ft[nA - 1];
+        }
+        bool bound;
+        const float T = sun_transmittance(p, cp, g, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, bound);
+        if (bound) { dropped = true; break; }
+        sum += (w * val) * (T * cp.invFourPiMu0);
+      }
+      if (p.useRR && w < 0.5f) {  // Russian roulette, RussianRouletteW = 1
+        uint32_t q1[4];
+        philox4x32_10(event | (1u << 24), pix, sLo, sHi, p.seedLo, p.seedHi, q1);
+        const float uR = u01(q1[1]);
+        if (uR >= w) break;
+        w = 1.0f;
+      }
+      {
+        // computeScatteringAngle (floor-type lookup of the inverse table) and next_direct with (cos, sin) of a uniform azimuth
+        const int n = p.tblNSteps[c];
+        const float *tb = p.tables + p.tblOffset[c] + (long long)pfEntry * n;
+        const int ai = (int)(uX * (float)n) + 1;
+        float ang;
+        if (ai < n) {
+          const float left = uX - (float)(ai - 1) * p.tblInvN[c];
+          ang = (1.0f - left) * tb[ai - 1] + left * tb[ai];
+        } else {
+          ang = tb[n - 1];
+        }
+        const float cs = cos_0_pi(ang);
+        float AX, AY;
+        sincos_2pi(uY, AX, AY);
+        float B = sqrtf(fmaxf(1.0f - cs * cs, 0.0f));
+        AX = AX * B;
+        AY = AY * B;
+        B = r.dx * AX - r.dy * AY;
+        const float D = cs - B / (1.0f + fabsf(r.dz));
+        r.dx = r.dx * D + AX;
+        r.dy = r.dy * D - AY;
+        r.dz = r.dz * cs - copysignf(fabsf(B), r.dz * B);
+      }
+    }
+    if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
+      nDropped++;
+    } else {
+      pend += __double2ll_rn(fmin((double)sum * cp.scale, cp.pathMax));
+    }
+  }
+
+  // The lanes of a wave mostly hold sums for ONE bin (pixel-major indices, samplesPerPixel >= 64): then one add per wave.
+  const bool have = pend != 0;
+  const unsigned long long haveMask = __ballot(have);
+  if (haveMask != 0ull) {
+    const int first = __ffsll((long long)haveMask) - 1;
+    const unsigned long long firstBin = __shfl(pendBin, first);
+    if (__ballot(have && pendBin != firstBin) == 0ull) {
+      long long v = have ? pend : 0;
+      for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + firstBin), (unsigned long long)v);
+    } else if (have) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
+    }
+  }
+  if (nDropped != 0u) atomicAdd(cp.dropped, (unsigned long long)nDropped);
+}
+
+// mcbrat_sun_transmittance: the kernel's own T_sun on given points, one lane per point
+template <int BLOCK, bool GRID_LDS>
+__global__ void __launch_bounds__(BLOCK) sun_transmittance_kernel(const DevParams p, const CamParams cp) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
+  unsigned nDropped = 0;
+  for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < cp.nPoints; i += (long long)gridDim.x * BLOCK) {
+    Ray r{cp.points[3 * i], cp.points[3 * i + 1], cp.points[3 * i + 2], 0.f, 0.f, 0.f, 0, 0, 0};
+    locate(p, g, r);
+    bool bound;
+    const float T = sun_transmittance(p, cp, g, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, bound);
+    cp.transmittance[i] = bound ? __uint_as_float(0x7fc00000u) : T;
+    if (bound) nDropped++;
+  }
+  if (nDropped != 0u) atomicAdd(cp.dropped, (unsigned long long)nDropped);
+}
+
+}  // namespace mcbrat
+
+using namespace mcbrat;
+
+namespace {
+
+constexpr size_t kCameraBinBudget = (size_t)4 << 30;  // bytes of bins at most, as the tracing kernels' batch slabs
+constexpr size_t kCameraGridLds = 80 * 1024 - 1024;   // half of a compute unit's 160 KB, less the static part: two workgroups of 512 lanes
+
+#define CAM_HIP(c, call)                                                                                          \
+  do {                                                                                                            \
+    const hipError_t e_ = static_cast<hipError_t>(call);                                                          \
+    if (e_ != hipSuccess) return mcbrat_camera_fail(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+  } while (0)
+
+size_t grid_lds_bytes(const DevParams &p) {
+  return sizeof(double) * (size_t)(p.nx + p.ny + p.nz + 3) + sizeof(float) * (size_t)p.nx * p.ny * p.nz;
+}
+
+// the sun: unit vector toward it, and the bound on the crossings of a ray toward it, from the geometry: nz layers, and nx (ny)
+// faces per domain length travelled along x (y), one length more for the part periods at both ends
+void sun_setup(const DevParams &p, CamParams &cp) {
+  for (int a = 0; a < 3; ++a) cp.sun[a] = -p.dir0[a];
+  const double H = p.zMax - p.z0, muz = std::max((double)std::fabs(cp.sun[2]), (double)FLT_MIN);
+  const double wrapsX = std::floor(H * std::fabs((double)cp.sun[0]) / muz / p.Lx) + 2.0, wrapsY = std::floor(H * std::fabs((double)cp.sun[1]) / muz / p.Ly) + 2.0;
+  const double n = (double)p.nz + wrapsX * p.nx + wrapsY * p.ny + 8.0;
+  cp.maxSunCross = (unsigned)std::min(n, 4294967295.0);
+  cp.invFourPiMu0 = (float)(1.0 / (4.0 * 3.14159265358979323846 * muz));
+}
+
+// 0: global memory, 1: LDS; -1 refused (asked for, does not fit)
+int choose_grid_lds(const CameraContext &v, int asked) {
+  const bool fits = grid_lds_bytes(v.p) <= std::min(kCameraGridLds, v.ldsPerCU / 2);
+  if (asked == 1 && !fits) return -1;
+  return asked == 0 ? 0 : (fits ? 1 : 0);
+}
+
+template <typename K>
+int allow_lds(mcbrat_ctx *c, K kernel, size_t lds) {
+  if (lds > 48 * 1024) CAM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcbrat_camera_ray(const mcbrat_camera *cam, int32_t i, int32_t j, double u, double v, double origin[3], double direction[3]) {
+  if (!cam || !origin || !direction || camera_refusal(*cam)) return 1;
+  CameraGeometry g;
+  camera_geometry(*cam, g);
+  camera_ray(g, i, j, u, v, origin, direction);
+  return 0;
+}
+
+int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float *transmittance) {
+  if (!c) return 1;
+  if (n < 0 || (n > 0 && (!xyz || !transmittance))) return mcbrat_camera_fail(c, "sunTransmittance: no points.");
+  CameraContext v;
+  if (mcbrat_camera_context(c, &v, false)) return 1;
+  if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "sunTransmittance: problem not completely specified (grid and optical properties).");
+  if (!v.solarDirectional) return mcbrat_camera_fail(c, "sunTransmittance: needs the Directional solar source.");
+  for (int64_t i = 0; i < n; ++i) {
+    const double z = xyz[3 * i + 2];
+    if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !(z >= v.p.z0 && z <= v.p.zMax))
+      return mcbrat_camera_fail(c, "sunTransmittance: a point is not finite or lies outside [z0, zMax].");
+  }
+  if (n == 0) return 0;
+  const int lds = choose_grid_lds(v, v.gridInLds);
+  if (lds < 0) return mcbrat_camera_fail(c, "sunTransmittance: the grid does not fit the LDS share (option cameraGridInLds = 1).");
+  DeviceBuffer<double> dPoints;
+  DeviceBuffer<float> dT;
+  DeviceBuffer<unsigned long long> dDropped;
+  CAM_HIP(c, dPoints.allocate((size_t)3 * n));
+  CAM_HIP(c, dT.allocate((size_t)n));
+  CAM_HIP(c, dDropped.allocate(1));
+  CAM_HIP(c, hipMemcpyAsync(dPoints.get(), xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, v.stream));
+  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  sun_setup(v.p, cp);
+  cp.points = dPoints.get(); cp.transmittance = dT.get(); cp.nPoints = n; cp.dropped = dDropped.get();
+  constexpr int kBlock = 256;
+  const unsigned grid = (unsigned)std::min<long long>((n + kBlock - 1) / kBlock, (long long)v.numCUs * 8);
+  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
+  if (lds) {
+    if (allow_lds(c, sun_transmittance_kernel<kBlock, true>, bytes)) return 1;
+    hipLaunchKernelGGL((sun_transmittance_kernel<kBlock, true>), dim3(grid), dim3(kBlock), bytes, v.stream, v.p, cp);
+  } else {
+    hipLaunchKernelGGL((sun_transmittance_kernel<kBlock, false>), dim3(grid), dim3(kBlock), 0, v.stream, v.p, cp);
+  }
+  CAM_HIP(c, hipGetLastError());
+  unsigned long long dropped = 0;
+  CAM_HIP(c, hipMemcpyAsync(transmittance, dT.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipMemcpyAsync(&dropped, dDropped.get(), sizeof(dropped), hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipStreamSynchronize(v.stream));
+  if (dropped != 0) return mcbrat_camera_fail(c, "sunTransmittance: a ray did not reach the top within the bound on its crossings.");
+  return 0;
+}
+
+int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed, uint64_t firstSample, int64_t samplesPerPixel,
+                         int32_t numBatches, float *radiance, float *radianceStdErr, float *batchMeans, int64_t *dropped) {
+  if (!c) return 1;
+  if (!cam || !radiance) return mcbrat_camera_fail(c, "renderCamera: no camera or no array for the radiance.");
+  if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
+  if (samplesPerPixel < 1) return mcbrat_camera_fail(c, "renderCamera: samplesPerPixel must be at least 1.");
+  if (numBatches < 1) return mcbrat_camera_fail(c, "renderCamera: numBatches must be at least 1.");
+  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy;
+  const unsigned long long nBins = npix * (unsigned long long)numBatches;
+  if (npix > 0x7fffffffull || nBins > kCameraBinBudget / sizeof(long long))
+    return mcbrat_camera_fail(c, "renderCamera: the bins of the image's batches (npx * npy * numBatches) do not fit the tally budget of 4 GiB.");
+  if ((double)nBins * (double)samplesPerPixel >= 9.0e18 || (double)firstSample + (double)numBatches * (double)samplesPerPixel >= 1.8e19)
+    return mcbrat_camera_fail(c, "renderCamera: more paths than a 64-bit index counts.");
+  CameraContext v;
+  if (mcbrat_camera_context(c, &v, false)) return 1;
+  if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "renderCamera: problem not completely specified (grid and optical properties).");
+  if (!v.haveSource || !v.solarDirectional) return mcbrat_camera_fail(c, "renderCamera: the backward camera needs the Directional solar source.");
+  if (v.brdfSurface) return mcbrat_camera_fail(c, "renderCamera: a BRDF surface is not supported by the backward camera (Lambertian surfaces only).");
+  const double zCam = cam->kind == 0 ? cam->z : cam->position[2];
+  if (!(zCam >= v.p.z0 && zCam <= v.p.zMax)) return mcbrat_camera_fail(c, "renderCamera: the camera's height lies outside the domain [z0, zMax].");
+  std::vector<float> fwdAll;
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  float fwdMax = 0.0f;
+  for (int k = 0; k < v.nc; ++k) {
+    if ((int)v.fwd->size() <= k || (*v.fwd)[k].empty())
+      return mcbrat_camera_fail(c, ("renderCamera: no forward phase function table for component " + std::to_string(k + 1)).c_str());
+    if ((*v.maxPfi)[k] >= (*v.fwdNEntries)[k])
+      return mcbrat_camera_fail(c, ("renderCamera: phaseFunctionIndex exceeds forward table entries for component " + std::to_string(k + 1)).c_str());
+    cp.fwdOffset[k] = (int)fwdAll.size(); cp.fwdNAngles[k] = (*v.fwdNAngles)[k];
+    fwdAll.insert(fwdAll.end(), (*v.fwd)[k].begin(), (*v.fwd)[k].end());
+    for (float x : (*v.fwd)[k]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
+  }
+  if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
+  const int lds = choose_grid_lds(v, cam->gridInLds);
+  if (lds < 0) return mcbrat_camera_fail(c, "renderCamera: gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+
+  camera_geometry(*cam, cp.g);
+  cp.jitter = cam->jitter != 0;
+  cp.spp = (unsigned long long)samplesPerPixel; cp.npix = npix; cp.firstSample = firstSample;
+  cp.total = nBins * cp.spp;
+  sun_setup(v.p, cp);
+  {
+    // a leg: as a ray whose |cosine| is 2^-16, the smallest a Lambertian draw gives; a flatter one that has not ended by then
+    // (in a vacuum) is dropped and counted
+    const double H = v.p.zMax - v.p.z0, travel = H * 65536.0;
+    const double n = (double)v.p.nz + (std::floor(travel / v.p.Lx) + 2.0) * v.p.nx + (std::floor(travel / v.p.Ly) + 2.0) * v.p.ny + 8.0;
+    cp.maxLegCross = (unsigned)std::min(n, (double)(1u << 26));
+    cp.maxEvents = kCameraMaxEvents;
+  }
+  {
+    // the fixed-point scale, as actScale is chosen: the power of two that keeps a batch's sum of paths that each hold 64 of
+    // the largest possible estimate below 2^62; a path's own sum saturates where samplesPerPixel of it would pass that
+    const double largest = std::max((double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846);
+    int e = 0;
+    std::frexp(4.611686018427387904e18 / ((double)samplesPerPixel * largest * 64.0), &e);
+    e = std::max(0, std::min(e - 1, 40));
+    cp.scale = std::ldexp(1.0, e);
+    cp.pathMax = std::floor(4.611686018427387904e18 / (double)samplesPerPixel);
+  }
+  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
+
+  DeviceBuffer<long long> dBins;
+  DeviceBuffer<float> dFwd;
+  DeviceBuffer<unsigned long long> dDropped;
+  CAM_HIP(c, dBins.allocate((size_t)nBins));
+  CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
+  CAM_HIP(c, dDropped.allocate(1));
+  CAM_HIP(c, hipMemsetAsync(dBins.get(), 0, sizeof(long long) * (size_t)nBins, v.stream));
+  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
+  CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
+  cp.bins = dBins.get(); cp.fwd = dFwd.get(); cp.dropped = dDropped.get();
+
+  // 16 waves per compute unit (four per SIMD); a wave's lanes take 64 consecutive indices at a time
+  const int block = lds ? 512 : 256;
+  const unsigned long long lanes = (unsigned long long)v.numCUs * 16ull * kWave;
+  cp.pathsPerLane = std::max<unsigned long long>(1, (cp.total + lanes - 1) / lanes);
+  const unsigned long long perBlock = cp.pathsPerLane * (unsigned long long)block;
+  const unsigned long long blocks = (cp.total + perBlock - 1) / perBlock;
+  if (blocks > 0x7fffffffull) return mcbrat_camera_fail(c, "renderCamera: more paths than one launch takes.");
+  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
+  if (lds) {
+    if (allow_lds(c, camera_kernel<512, true>, bytes)) return 1;
+    hipLaunchKernelGGL((camera_kernel<512, true>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
+  } else {
+    hipLaunchKernelGGL((camera_kernel<256, false>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
+  }
+  CAM_HIP(c, hipGetLastError());
+  std::vector<long long> bins((size_t)nBins);
+  unsigned long long nDropped = 0;
+  CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * (size_t)nBins, hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipStreamSynchronize(v.stream));
+  if (dropped) *dropped = (int64_t)nDropped;
+
+  // batch means; their mean and its standard error from the differences to the first batch (identical batches: exactly 0)
+  const double unit = 1.0 / (cp.scale * (double)samplesPerPixel);
+  for (unsigned long long px = 0; px < npix; ++px) {
+    const double m0 = (double)bins[px] * unit;
+    double s1 = 0.0, s2 = 0.0;
+    for (int b = 0; b < numBatches; ++b) {
+      const double m = (double)bins[(size_t)b * npix + px] * unit;
+      if (batchMeans) batchMeans[(size_t)b * npix + px] = (float)m;
+      s1 += m - m0; s2 += (m - m0) * (m - m0);
+    }
+    const double dm = s1 / (double)numBatches;
+    radiance[px] = (float)(m0 + dm);
+    if (radianceStdErr) {
+      const double var = numBatches > 1 ? std::max(0.0, s2 - (double)numBatches * dm * dm) / ((double)numBatches * (double)(numBatches - 1)) : 0.0;
+      radianceStdErr[px] = (float)std::sqrt(var);
+    }
+  }
+  return 0;
+}
+
+}  // extern "C"

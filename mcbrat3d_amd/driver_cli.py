@@ -24,6 +24,11 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
                    reportlevelfluxes=False, reportdirectlevelfluxes=False, reportactinicflux=False, reportsidefluxes=False),
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
+    # the backward camera (no counterpart in the reference driver): absent -- cameraKind empty -- it changes
+    # nothing.  cameraFootprint = xLo, xHi, yLo, yHi (default: the domain), cameraHeight (default: the top of the domain)
+    "camera": dict(camerakind="", camerapixels=[1, 1], cameraposition=[0.0, 0.0, 0.0], cameralook=[0.0, 0.0, -1.0],
+                   cameraup=[0.0, 1.0, 0.0], camerafov=60.0, cameramu=1.0, cameraphi=0.0, camerafootprint=[], cameraheight=None,
+                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile=""),
 }
 
 
@@ -116,6 +121,23 @@ def writeResults_ASCII_radiance(path, cfg, domainName, stats, xe, ye, ze, solarF
                 for i in range(nx):
                     f.write("%7.3f%7.3f %9.4f %9.4f\n" % (0.5 * (xe[i] + xe[i + 1]), 0.5 * (ye[j] + ye[j + 1]),
                                                         stats["intensity"][i, j, k], stats["intensity_StdErr"][i, j, k]))
+
+
+def camera_from_namelist(cfg, xe, ye, ze):
+    """The camera of the /camera/ group (None where cameraKind is empty), with the domain for the defaults of the footprint and
+    the height."""
+    from mcbrat3d_amd.camera import new_Camera
+    kind = str(cfg["camerakind"]).strip().lower()
+    if not kind:
+        return None
+    pixels = np.atleast_1d(cfg["camerapixels"]).astype(int)
+    npx, npy = int(pixels[0]), int(pixels[1] if pixels.size > 1 else pixels[0])
+    if kind == "orthographic":
+        fp = list(np.atleast_1d(cfg["camerafootprint"]).astype(float)) or [xe[0], xe[-1], ye[0], ye[-1]]
+        height = ze[-1] if cfg["cameraheight"] is None else float(cfg["cameraheight"])
+        return new_Camera(kind, npx=npx, npy=npy, mu=float(cfg["cameramu"]), phi=float(cfg["cameraphi"]), footprint=fp, height=height)
+    return new_Camera(kind, npx=npx, npy=npy, position=cfg["cameraposition"], look=cfg["cameralook"], up=cfg["cameraup"],
+                      fov=float(cfg["camerafov"]))
 
 
 def builtin_domain(name):
@@ -244,6 +266,9 @@ def main(argv=None):
         if cfg["reportsidefluxes"]:
             raise SystemExit("reportSideFluxes: side fluxes are not available for spectrally integrated runs (numLambda > 1 or "
                              "thermal emission)")
+        if str(cfg["camerakind"]).strip():
+            raise SystemExit("cameraKind: the backward camera is not available for spectrally integrated runs (numLambda > 1 or "
+                             "thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -292,6 +317,7 @@ def main(argv=None):
         integ.specifyParameters(recActinicFlux=True)
     if cfg["reportsidefluxes"]:  # (refused by specifyParameters without reportLevelFluxes, with the direct tally or the actinic flux)
         integ.specifyParameters(recSideFluxes=True)
+    camera = camera_from_namelist(cfg, dom.xPosition, dom.yPosition, dom.zPosition)  # (a bad camera ends the run before it traces)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -301,6 +327,15 @@ def main(argv=None):
     setup = time.time() - t0
     stats = driver.run(integ, dom, photons, cfg["numphotonsperbatch"], cfg["numbatches"], new_RandomNumberSequence(cfg["iseed"]),
                        solarFlux=1.0, dist=dist, moments_tensor=moments)
+    cameraResult = None
+    if camera is not None and rank == 0:  # the image: rank 0 renders it after the forward run, with sample indices of its own stream
+        cameraResult = integ.renderCamera(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
+                                          int(cfg["camerabatches"]))
+        cameraResult["samplesPerPixel"] = int(cfg["camerasamplesperpixel"])
+        print(" camera %s %d x %d: mean radiance %.6g, largest standard error %.3g, %d paths dropped" % (
+            camera.kind, camera.npx, camera.npy, cameraResult["radiance"].mean(), cameraResult["radiance_StdErr"].max(), cameraResult["dropped"]))
+        if cfg["outputcamerafile"]:
+            ncio.writeCamera_netcdf(cfg["outputcamerafile"], camera, cameraResult)
     if rank == 0:
         print(" mean flux up/down/absorbed: " + "  ".join("%9.6f +-%9.6f" % (stats[k], stats[k + "_StdErr"])
                                                             for k in ("meanFluxUp", "meanFluxDown", "meanFluxAbsorbed")))
@@ -345,7 +380,8 @@ def main(argv=None):
                                      hybridPhaseFunWidth=cfg["hybridphasefunwidth"],
                                      useRussianRouletteForIntensity=cfg["userussianrouletteforintensity"], zetaMin=cfg["zetamin"],
                                      limitIntensityContributions=cfg["limitintensitycontributions"],
-                                     maxIntensityContribution=cfg["maxintensitycontribution"])
+                                     maxIntensityContribution=cfg["maxintensitycontribution"],
+                                     camera=camera, cameraResult=cameraResult)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -444,6 +444,50 @@ class Integrator:
         incomingPhotons.currentPhoton += done.value
         return done.value
 
+    # -- the backward camera -----------------------------------------
+    def _load_camera_tables(self):
+        """The forward tables the camera's local estimates read: pushed for the loaded domain where no intensity
+        directions have brought them (_load_domain pushes them only then)."""
+        dom = self._loaded_domain
+        if dom is None:
+            raise McbratError("renderCamera: no domain loaded: call prepare(domain, photons) or computeRadiativeTransfer first.")
+        if self.numIntensityDirections() > 0:
+            return
+        token = (dom._version, self._domain_token, self.minForwardTableSize)
+        if token == getattr(self, "_camera_token", None):
+            return
+        tab, _ = dom.tabulateForwardPhaseFunctions(self.minForwardTableSize, False, self.hybridPhaseFunWidth)
+        for c, t in enumerate(tab):
+            t = np.ascontiguousarray(t, np.float32)
+            self._check(self._lib.mcbrat_set_forward_table(self._ctx, c + 1, t.shape[1], t.shape[0], ptr(t), None))
+        self._camera_token = token
+
+    def renderCamera(self, camera, randomNumbers, samplesPerPixel, numBatches=1):
+        """The radiance at `camera` (mcbrat3d_amd.camera.new_Camera) by backward Monte Carlo, numBatches batches of
+        samplesPerPixel paths per pixel, for the domain and the Directional solar source this integrator has loaded (prepare,
+        computeRadiativeTransfer).  Returns {"radiance", "radiance_StdErr", "batchMeans", "dropped"}: [npy, npx] arrays (batchMeans
+        [numBatches, npy, npx]) in units of radiance per unit solar flux through a horizontal plane at the top, and the number of
+        paths a loop bound ended.  Sample indices continue from randomNumbers.nextPhotonId; tallies, moments and settings of the
+        integrator are left alone."""
+        self._load_camera_tables()
+        s = camera.struct()
+        npx, npy, nb = camera.npx, camera.npy, int(numBatches)
+        rad, err = np.zeros((npy, npx), np.float32), np.zeros((npy, npx), np.float32)
+        means = np.zeros((max(nb, 1), npy, npx), np.float32)
+        dropped = C.c_int64(0)
+        self._check(self._lib.mcbrat_render_camera(self._ctx, C.addressof(s), randomNumbers.seed, randomNumbers.nextPhotonId,
+                                                   int(samplesPerPixel), nb, ptr(rad), ptr(err), ptr(means), C.addressof(dropped)))
+        randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
+        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value)}
+
+    def sunTransmittance(self, points):
+        """exp(-optical depth) from each point (an [n, 3] array of x, y, z) toward the sun up to the top of the loaded
+        domain: the direct transmittance at a point, without noise (mcbrat_sun_transmittance)."""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        out = np.zeros(pts.shape[0], np.float32)
+        self._check(self._lib.mcbrat_sun_transmittance(self._ctx, pts.shape[0], ptr(pts), ptr(out)))
+        return out
+
     # -- reportResults ----------------------------------------------------------------
     def reportResults(self):
         nx, ny, nz = self._dims

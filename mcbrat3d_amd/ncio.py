@@ -150,8 +150,9 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
                         reportAbsorptionProfile=False, reportVolumeAbsorption=False, cpuTimeTotal=0.0, cpuTimeSetup=0.0,
                         numProcs=1, intensityMus=None, intensityPhis=None, useHybridPhaseFunsForIntenCalcs=False,
                         hybridPhaseFunWidth=0.0, useRussianRouletteForIntensity=False, zetaMin=0.0,
-                        limitIntensityContributions=False, maxIntensityContribution=0.0):
-    """monteCarloDriver.f95:1499-1807.  `stats` is driver.statistics(...) output ([ix, iy(, iz)] arrays)."""
+                        limitIntensityContributions=False, maxIntensityContribution=0.0, camera=None, cameraResult=None):
+    """monteCarloDriver.f95:1499-1807.  `stats` is driver.statistics(...) output ([ix, iy(, iz)] arrays).  camera, cameraResult:
+    a backward camera and what Integrator.renderCamera returned for it (cameraRadiance, cameraRadiance_StdErr)."""
     xe, ye, ze = (np.asarray(a, np.float64) for a in (xPosition, yPosition, zPosition))
     f = netcdf_file(outputFileName, "w", version=2)  # nf90_64bit_offset (:1559)
     try:
@@ -239,6 +240,38 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
                 mean = "mean" + side[0].upper() + side[1:]
                 for name in (mean, mean + "_StdErr"):
                     f.createVariable(name, "f", ("z",))[:] = np.asarray(stats[name])
+        if camera is not None and cameraResult is not None:
+            _add_camera(f, camera, cameraResult)
+    finally:
+        f.close()
+    return outputFileName
+
+
+def _add_camera(f, camera, result):
+    """The backward camera's image: cameraRadiance, cameraRadiance_StdErr (cameraY, cameraX) -- row j of
+    the pinhole grows upward -- and the camera's parameters as attributes of the file."""
+    for name, value in camera.attributes().items():
+        if isinstance(value, str):
+            setattr(f, name, value)
+        elif name in ("cameraPixels", "cameraJitter"):
+            setattr(f, name, np.asarray(value, np.int32))
+        else:
+            setattr(f, name, np.asarray(value, np.float64))
+    f.cameraSamplesPerPixel = np.float64(result.get("samplesPerPixel", 0))
+    f.cameraBatches = np.int32(np.asarray(result["batchMeans"]).shape[0])
+    f.cameraDroppedPaths = np.float64(result["dropped"])
+    f.createDimension("cameraX", camera.npx)
+    f.createDimension("cameraY", camera.npy)
+    f.createVariable("cameraRadiance", "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance"], np.float32)
+    f.createVariable("cameraRadiance_StdErr", "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance_StdErr"], np.float32)
+
+
+def writeCamera_netcdf(outputFileName, camera, result):
+    """A file of the camera's image alone (the driver's outputCameraFile)."""
+    f = netcdf_file(outputFileName, "w", version=2)
+    try:
+        f.description = "Backward Monte Carlo camera image"
+        _add_camera(f, camera, result)
     finally:
         f.close()
     return outputFileName
