@@ -366,6 +366,9 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
  *                 across the launch, two batches' tallies per workgroup where they fit; environment MCBRAT_BATCH_UNITS)
  *   "blockSpanKernel"  1: the block walk keeps its general instantiation where the one without periodic folds inside blocks
  *                 would do (default 0: automatic; both trace every photon bit for bit alike -- tests/test_gpu_blockwalk_nospan.py)
+ *   "blockRareKernel"  1: the block walk keeps its general exit and launch phases where the instantiation with a black surface
+ *                 and the parallel sun compiled in would do (default 0: automatic; both trace every photon bit for bit alike --
+ *                 tests/test_gpu_blockwalk_rare.py)
  *   "cameraGridInLds"  where mcbrat_sun_transmittance reads the grid: -1 (default) LDS where it fits, 0 global memory, 1 LDS
  * One option does change results, within their noise -- it chooses between two unbiased estimators:
  *   "glintSampling"  1 (default): a reflection off a Cox-Munk patch draws its direction from the mixture of the glint lobe and
@@ -504,7 +507,10 @@ int mcbrat_set_walk_options(mcbrat_ctx *ctx, int32_t layerSkip, int32_t blockWal
  * in LDS), bit 7 the block walk with the optics per BLOCK in LDS (every block uniform in them), bit 8 the thermal source's level
  * and row sums of the emission CDF staged in LDS, bit 9 (512) the block walk's instantiation with the periodic folds inside blocks
  * compiled out (no block of the medium spans a whole periodic axis, solar source, equally spaced axes, one component, the
- * domain's albedo, 768-lane workgroups, option "blockSpanKernel" not set).  Before grid and optics are loaded: the options. */
+ * domain's albedo, 768-lane workgroups, option "blockSpanKernel" not set), bit 10 (1024) that instantiation with a black surface
+ * and the parallel sun compiled into its exit and launch phases (bit 9, and: the albedo compares equal to 0, no surface
+ * description, every single-scattering albedo handed over is finite, the Directional solar source, option "blockRareKernel" not
+ * set).  Before grid and optics are loaded: the options. */
 int mcbrat_get_walk_mode(const mcbrat_ctx *ctx);
 
 /* The event threshold in use (after the first call of a domain: the one chosen by the trial launches). */

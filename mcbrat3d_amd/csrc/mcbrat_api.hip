@@ -99,6 +99,10 @@ struct mcbrat_ctx {
   // no record of the block decomposition has bit 0 / bit 1 of w: no block spans the whole periodic x / y axis (build_blocks)
   bool blockSpansX = true, blockSpansY = true;
   int blockSpanKernel = 0;     // option "blockSpanKernel": 1 keeps the general block-walk instantiation where NOSPAN would do (tests)
+  // every single-scattering albedo handed to set_optics is finite (build_blocks walks them); with an albedo of 0, no surface
+  // description and the parallel sun: the block walk's RARE instantiation (pick_block)
+  bool ssaFinite = false;
+  int blockRareKernel = 0;     // option "blockRareKernel": 1 keeps the general exit and launch phases where RARE would do (tests)
   bool noSimple3 = false;      // MCBRAT_NO_SIMPLE3 (tests): the block walk's near-uniform grids run the general kernel, not SIMPLE = 3
   DeviceBuffer<float> dExtB, dCumB, dSsaB, dBgExt, dBgCum, dBgSsa;
   DeviceBuffer<uint16_t> dPfiB, dBgPfi;
@@ -557,10 +561,14 @@ int build_bricks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<f
 // Block walk (mcbrat_blockwalk.hip): the grid cut into axis-aligned blocks of cells that carry one extinction value
 // (mcbrat_block_decomposition, mcbrat_host.cpp), uploaded for the kernel.
 int build_blocks(mcbrat_ctx *c, const std::vector<float> &e, const std::vector<float> &cu, const std::vector<float> &ssa,
-                 const std::vector<uint16_t> &pf, int nc) {
+                 const std::vector<uint16_t> &pf, int nc, const double *ssaGiven) {
   const int nx = c->nx, ny = c->ny, nz = c->nz;
   const size_t nvox = (size_t)nx * ny * nz;
   c->nBlocks = 0;
+  // RARE (mcbrat_variants.h): no weight can become a NaN.  Read from the array as it was handed over, vacuum cells included (the
+  // upload stores 0 there, and set_optics has refused a NaN where there is extinction): one NaN anywhere keeps the general kernel.
+  c->ssaFinite = true;
+  for (size_t i = 0; i < nvox * (size_t)nc && c->ssaFinite; ++i) c->ssaFinite = std::isfinite(ssaGiven[i]) && std::isfinite(ssa[i]);
   c->dBlockRec.reset(); c->dBlockOf.reset(); c->dBlockExt.reset();
   c->dBlockSsa.reset(); c->dBlockCum.reset(); c->dBlockPfi.reset();
   c->blockOpticsUniform = false;
@@ -885,7 +893,15 @@ const void *trace_entry() {
 template <int I>
 const void *block_entry() {
   constexpr BlockVariant v = kBlockList.v[I];
-  return (const void *)trace_block_kernel<v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan>;
+  return (const void *)trace_block_kernel<v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan, v.rare>;
+}
+constexpr auto kBlockRareList = block_rare_variants();
+static_assert(kBlockRareList.n == kBlockRareVariants, "the list is as long as it says");
+template <int I>
+const void *block_rare_entry() {
+  constexpr BlockVariant v = kBlockRareList.v[I];
+  static_assert(valid(v) && v.rare != 0, "the RARE list holds RARE instantiations");
+  return (const void *)trace_block_kernel<v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan, v.rare>;
 }
 template <int... I>
 std::array<const void *, sizeof...(I)> trace_table(std::integer_sequence<int, I...>) { return {{trace_entry<I>()...}}; }
@@ -893,12 +909,16 @@ template <int... I>
 std::array<const void *, sizeof...(I)> block_table(std::integer_sequence<int, I...>) { return {{block_entry<I>()...}}; }
 const std::array<const void *, kTraceVariants> kTraceKernels = trace_table(std::make_integer_sequence<int, kTraceVariants>{});
 const std::array<const void *, kBlockVariants> kBlockKernels = block_table(std::make_integer_sequence<int, kBlockVariants>{});
+template <int... I>
+std::array<const void *, sizeof...(I)> block_rare_table(std::integer_sequence<int, I...>) { return {{block_rare_entry<I>()...}}; }
+const std::array<const void *, kBlockRareVariants> kBlockRareKernels = block_rare_table(std::make_integer_sequence<int, kBlockRareVariants>{});
 const char *const kNoKernelMsg = "computeRadiativeTransfer: no kernel is built for this combination of settings.";
 
 // What the block walk's instantiations decide at compile time, of this context (the near-uniform flags: fill_params)
 BlockWalk block_walk_of(const mcbrat_ctx *c, bool xyNearUniform, bool zNearUniform) {
   return BlockWalk{c->xyRegular != 0, c->zRegular != 0, c->nc == 1, c->surfNumX != 0, c->ny == 1, xyNearUniform, zNearUniform, c->noSimple3,
-                   c->blockSpansX, c->blockSpansY, c->blockSpanKernel != 0, c->blockSize};
+                   c->blockSpansX, c->blockSpansY, c->blockSpanKernel != 0, c->blockSize,
+                   c->albedo == 0.0f && c->surfNumX == 0 && c->ssaFinite, c->solarKind == 0, c->blockRareKernel != 0};
 }
 
 // The block walk applies where the face-by-face plan already keeps grid, tallies (and tables) in LDS -- or, in the wide
@@ -914,9 +934,9 @@ struct KernelChoice { const void *kernel; int block; size_t lds; };
 // (lds: the layout of launch_block, which knows the slabs)
 KernelChoice choose_block(mcbrat_ctx *c, const DevParams &p, const LaunchPlan &L, bool debug) {
   const BlockVariant v = pick_block(L, debug, c->srcKind != 0, block_walk_of(c, p.xyNearUniform != 0, p.zNearUniform != 0));
-  const int i = find_variant(kBlockList, v);
+  const int i = v.rare != 0 ? find_variant(kBlockRareList, v) : find_variant(kBlockList, v);
   if (i < 0) { fail(c, kNoKernelMsg); return {nullptr, 0, 0}; }
-  return {kBlockKernels[(size_t)i], v.block, 0};
+  return {v.rare != 0 ? kBlockRareKernels[(size_t)i] : kBlockKernels[(size_t)i], v.block, 0};
 }
 
 int launch_block(mcbrat_ctx *c, DevParams &p, const LaunchPlan &L, bool debug, int nBatches) {
@@ -1209,7 +1229,7 @@ int mcbrat_set_optics(mcbrat_ctx *c, int32_t nc, const double *totalExt, const d
   }
   c->bricksBuilt = false;
   if (build_bricks(c, e, cu, s, pf, nc)) return 1;
-  if (build_blocks(c, e, cu, s, pf, nc)) return 1;
+  if (build_blocks(c, e, cu, s, pf, nc, ssa)) return 1;
   c->nc = nc;
   c->albedo = (float)albedo;
   c->maxPfi = maxPfi;
@@ -1670,6 +1690,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   else if (n == "crossThreshold") c->crossThreshold = std::max(1, std::min(64, (int)value));
   else if (n == "batchUnits") c->batchUnits = value != 0;
   else if (n == "blockSpanKernel") c->blockSpanKernel = value != 0;
+  else if (n == "blockRareKernel") c->blockRareKernel = value != 0;
   else if (n == "glintSampling") c->glintSampling = value != 0;
   else if (n == "cameraGridInLds") c->cameraGridInLds = std::max(-1, std::min(1, (int)value));
   else return fail(c, "set_option: unknown option '" + n + "'");
@@ -1812,7 +1833,10 @@ int mcbrat_get_walk_mode(const mcbrat_ctx *c) {
         (L.wide ? 16 : 0) | ((L.blockLite && L.optics == 1) ? 32 : 0) | (L.priv ? 64 : 0) | ((L.blockLite && L.optics == 2) ? 128 : 0) |
         (L.cdfTop ? 256 : 0);
     // (a NOSPAN instantiation: the near-uniform flags have no say in that)
-    if (block_walk_applies(c, L) && pick_block(L, false, c->srcKind != 0, block_walk_of(c, false, false)).nospan) m |= 512;
+    if (block_walk_applies(c, L)) {
+      const BlockVariant v = pick_block(L, false, c->srcKind != 0, block_walk_of(c, false, false));
+      m |= (v.nospan ? 512 : 0) | (v.rare != 0 ? 1024 : 0);  // (1024: RARE, a black surface and the parallel sun compiled in)
+    }
   }
   return m;
 }

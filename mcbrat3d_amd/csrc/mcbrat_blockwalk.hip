@@ -112,10 +112,17 @@ __host__ __device__ inline BlockLds block_lds_layout(int nx, int ny, int nz, int
 // principal image inside a block: the `spans` bits do not exist, the periodic folds that depend on them (collision, block
 // crossing) and the tests of rec.w are compiled out.  The forced fold of an exit and the wrap through the domain boundary of a
 // crossing stay.  Any medium with horizontal structure is of this kind; plane-parallel and homogeneous media are not.
-template <int BLOCK, bool TBL_LDS, bool DEBUG, bool EMIT, int SIMPLE, int OPT = 0, bool NOSPAN = false>
+// RARE: two facts about the run that the host has checked (pick_block, mcbrat_variants.h), compiled into the rare phases, which
+// run at 8-12 of 64 lanes.  Bit 0, BLACK: the surface is the domain's albedo and that albedo is 0, and no weight is a NaN --
+// every photon that reaches the surface is tallied and dies; nothing of the reflection is compiled, nor the repair of the leg
+// origin against the clamped column (an exit of either kind ends its lane).  Bit 1, SUN: the source is the parallel sun
+// (solarKind 0); the other solar sources and the reloads of their kind leave the launch.
+template <int BLOCK, bool TBL_LDS, bool DEBUG, bool EMIT, int SIMPLE, int OPT = 0, bool NOSPAN = false, int RARE = 0>
 __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK > 512 ? BLOCK / 128 : MCBRAT_MIN_WAVES_PER_SIMD))
 trace_block_kernel(const DevParams p) {
   constexpr bool NOY = SIMPLE == 2 && !DEBUG;
+  constexpr bool BLACK = (RARE & 1) != 0, SUN = (RARE & 2) != 0;
+  static_assert(RARE == 0 || (!DEBUG && !EMIT && (SIMPLE == 1 || SIMPLE == 2)), "the instrumented, thermal and general instantiations keep the general rare phases");
   // HOIST: what is constant per photon (Philox) and per block (1 / extinction) is kept in the lane instead of being formed in every
   // leg and collision.  Two lane registers: taken where the budget has them -- the kernels of 128 registers and, of the 768-lane
   // ones (80 registers), the solar x-z instantiation; the others and the instrumented ones would pay with scratch.
@@ -371,14 +378,16 @@ trace_block_kernel(const DevParams p) {
         {
           const double xw = __fma_rn((double)tcur, (double)dx, px), yw = __fma_rn((double)tcur, (double)dy, py);  // where the leg met the face (:1801-1812); exact product, see the collision
           if (DEBUG) countCrossings(xw, yw, top ? p.nz : -1);
-          px = xw;
-          if (!NOY) py = yw;
+          if constexpr (!BLACK) {  // (BLACK: the lane dies below, its origin is never read again)
+            px = xw;
+            if (!NOY) py = yw;
+          }
           // (always folded here: the surface description takes the position itself.  A position on the domain boundary
           // folds to either side of it by rounding: where the clamp then keeps a cell at the other end of the axis, the
           // origin takes the image next to that cell -- cell and position must agree when the reflected leg starts.)
           const int jx = locX(xw, true, true);
           ix = inRange(jx, rx);
-          if (ix != jx) {
+          if (!BLACK && ix != jx) {
             const double lo = s_edge[rx & 0xffffu], hi = s_edge[rx >> 16];
             if (px < lo && lo - px > px + p.Lx - hi) px += p.Lx;
             else if (px > hi && px - hi > lo - (px - p.Lx)) px -= p.Lx;
@@ -387,7 +396,7 @@ trace_block_kernel(const DevParams p) {
           if (!NOY) {
             const int jy = locY(yw, true, true);
             iy = inRange(jy, ry);
-            if (iy != jy) {
+            if (!BLACK && iy != jy) {
               const double lo = s_edge[offY + (ry & 0xffffu)], hi = s_edge[offY + (ry >> 16)];
               if (py < lo && lo - py > py + p.Ly - hi) py += p.Ly;
               else if (py > hi && py - hi > lo - (py - p.Ly)) py -= p.Ly;
@@ -401,6 +410,8 @@ trace_block_kernel(const DevParams p) {
             record_fate(p, idLo, idHi, 0, ix + 1, iy + 1, p.nz + 1, nScat, nLegs, w);
           }
           state = BW_DEAD;
+        } else if constexpr (BLACK) {
+          state = BW_DEAD;  // (albedo 0: fluxDown has the incident weight (:634), the product with the albedo is 0 <= FLT_MIN, :673-676)
         } else {
           pz = p.zSurf;
           iz = 0;
@@ -461,7 +472,7 @@ trace_block_kernel(const DevParams p) {
             double lx, ly, lz;  // fractional launch position in [0,1]
             if (!EMIT) {
               lz = 0.0;
-              launch_solar(p, p.solarKind == 0, rng, lx, ly, dx, dy, dz);
+              launch_solar(p, SUN || p.solarKind == 0, rng, lx, ly, dx, dy, dz);
             } else {
               launch_emission(p, rng, [&](float rn, int &ik, int &ij) {
                 if (!cdfTop) { emission_level_row(p, rn, ik, ij); return; }

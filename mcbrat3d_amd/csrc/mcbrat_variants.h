@@ -26,10 +26,11 @@ struct BlockVariant {
   bool tblLds, debug, emit;
   int simple, opt;
   bool nospan;
+  int rare;  // RARE: bit 0 a black surface, bit 1 the parallel sun, compiled into the exit and launch phases (0: neither)
 };
 
 constexpr auto fields(const TraceVariant &v) { return std::tie(v.block, v.tblLds, v.priv, v.brick, v.debug, v.inten, v.emit, v.spec, v.ord, v.brdf, v.lvl, v.direct, v.act, v.side); }
-constexpr auto fields(const BlockVariant &v) { return std::tie(v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan); }
+constexpr auto fields(const BlockVariant &v) { return std::tie(v.block, v.tblLds, v.debug, v.emit, v.simple, v.opt, v.nospan, v.rare); }
 
 // What trace_kernel can be instantiated with.
 constexpr bool valid(const TraceVariant &v) {
@@ -52,7 +53,8 @@ constexpr bool valid(const TraceVariant &v) {
 }
 // trace_block_kernel takes every combination of its flags that is listed below.
 constexpr bool valid(const BlockVariant &v) {
-  return v.simple >= 0 && v.simple <= 3 && v.opt >= 0 && v.opt <= 2 && (!v.nospan || (!v.debug && !v.emit && (v.simple == 1 || v.simple == 2) && v.opt == 0));
+  return v.simple >= 0 && v.simple <= 3 && v.opt >= 0 && v.opt <= 2 && (!v.nospan || (!v.debug && !v.emit && (v.simple == 1 || v.simple == 2) && v.opt == 0)) &&
+         (v.rare == 0 || (v.rare == 3 && v.nospan && v.block == 768));  // (both facts together, in the NOSPAN kernels only)
 }
 
 template <class V, int N>
@@ -128,19 +130,30 @@ constexpr VariantList<BlockVariant, kBlockVariants> block_variants() {
       // the shared plan: 256, 512 or 768 lanes (the option blockSize; 768 is the library's own) x SIMPLE 0, 1, 2 (x-z problems);
       // 768 lanes also SIMPLE 3 (near-uniform axes) -- 40 kernels
       for (int block = 256; block <= 768; block += 256)
-        for (int simple = 0; simple <= (block == 768 ? 3 : 2); ++simple) l.add({block, tbl, false, emit, simple, 0, false});
+        for (int simple = 0; simple <= (block == 768 ? 3 : 2); ++simple) l.add({block, tbl, false, emit, simple, 0, false, 0});
       // the wide plan: 1024 lanes x OPT 0, 1, 2 x SIMPLE 0, 1, 3 -- 36 kernels
       for (int opt = 0; opt <= 2; ++opt)
         for (int simple = 0; simple <= 3; ++simple)
-          if (simple != 2) l.add({1024, tbl, false, emit, simple, opt, false});
+          if (simple != 2) l.add({1024, tbl, false, emit, simple, opt, false, 0});
       // instrumented: 512 lanes x OPT 0, 1, 2 x SIMPLE 0, 1 (it keeps y: no x-z instantiation) -- 24 kernels
       for (int opt = 0; opt <= 2; ++opt)
-        for (int simple = 0; simple <= 1; ++simple) l.add({512, tbl, true, emit, simple, opt, false});
+        for (int simple = 0; simple <= 1; ++simple) l.add({512, tbl, true, emit, simple, opt, false, 0});
     }
     // NOSPAN (mcbrat_blockwalk.hip): the solar SIMPLE 1 and 2 kernels of 768 lanes, for media none of whose blocks spans a
     // periodic axis the kernel looks at -- 4 kernels
-    for (int simple = 1; simple <= 2; ++simple) l.add({768, tbl, false, false, simple, 0, true});
+    for (int simple = 1; simple <= 2; ++simple) l.add({768, tbl, false, false, simple, 0, true, 0});
   }
+  return l;
+}
+// ... and the RARE instantiations, a list of their own: the NOSPAN kernels again, with a black surface and the parallel sun compiled
+// into their exit and launch phases (RARE = 3) -- 4 kernels.  The list above is the recorded one (tests/golden/kernel_choice.txt: its
+// inputs are the plan and the walk's geometry, and every one of them picks RARE = 0); what picks these is the medium's surface, its
+// single-scattering albedos and the source, pick_block below.
+constexpr int kBlockRareVariants = 4;
+constexpr VariantList<BlockVariant, kBlockRareVariants> block_rare_variants() {
+  VariantList<BlockVariant, kBlockRareVariants> l{};
+  for (int t = 0; t < 2; ++t)
+    for (int simple = 1; simple <= 2; ++simple) l.add({768, t != 0, false, false, simple, 0, true, 3});
   return l;
 }
 
@@ -190,6 +203,10 @@ struct BlockWalk {
   bool xyNearUniform, zNearUniform, noSimple3;
   bool spansX, spansY, spanKernel;  // a block spans the whole periodic x / y axis; the option blockSpanKernel
   int blockSize;                    // the option blockSize, 0: the library's choice
+  // RARE.  blackSurface: the Lambertian albedo compares equal to 0, no surface description or BRDF is set, and every
+  // single-scattering albedo handed over is finite (a NaN weight is reflected by the general kernel, albedo * NaN <= FLT_MIN being
+  // false, and would be killed by BLACK).  sun: solarKind == 0.  rareKernel: the option blockRareKernel, which keeps the general phases.
+  bool blackSurface, sun, rareKernel;
 };
 
 // WHAT MAY NOT BE COMBINED, and the words it is refused with.
@@ -342,7 +359,7 @@ constexpr size_t ray_lds(int block, size_t planLds, int cap) { return ray_lds_ba
 
 // The trace_block_kernel of a launch the block walk applies to.
 constexpr BlockVariant pick_block(const LaunchPlan &L, bool debug, bool emit, const BlockWalk &w) {
-  BlockVariant v{512, L.tblLds, debug, emit, 0, 0, false};
+  BlockVariant v{512, L.tblLds, debug, emit, 0, 0, false, 0};
   if (L.wide) {  // one workgroup per compute unit: 1024 lanes (the instrumented instantiation: 512)
     if (!debug) v.block = 1024;
     v.opt = L.blockLite ? L.optics : 0;
@@ -360,6 +377,8 @@ constexpr BlockVariant pick_block(const LaunchPlan &L, bool debug, bool emit, co
   if (simple && w.xz && !debug && v.opt == 0 && v.block != 1024) v.simple = 2;  // an x-z problem
   // NOSPAN: the 768-lane solar SIMPLE 1 and 2 kernels, where no block spans a periodic axis the kernel looks at (an x-z problem has no y)
   v.nospan = simple && v.block == 768 && !emit && !w.spanKernel && !w.spansX && (w.xz || !w.spansY);
+  // RARE: built for both facts together, in the NOSPAN kernels (where the library's own plan lands with the step cloud)
+  v.rare = (v.nospan && w.blackSurface && !w.surface && w.sun && !w.rareKernel) ? 3 : 0;
   return v;
 }
 

@@ -323,7 +323,10 @@ class Integrator:
                 "privateTallies": bool(m & 64), "widePlan": bool(m & 16), "opticsInGlobalMemory": bool(m & 32),
                 "opticsPerBlock": bool(m & 128), "emissionCdfTopInLds": bool(m & 256),
                 # the block walk's instantiation without periodic folds inside blocks (no block of the medium spans a periodic axis)
-                "foldsCompiledOut": bool(m & 512)}
+                "foldsCompiledOut": bool(m & 512),
+                # ... with a black surface and the parallel sun compiled into its exit and launch phases (albedo 0, no surface
+                # description, finite single-scattering albedos, the Directional source; option blockRareKernel=1 keeps the general one)
+                "blackSurfaceSunCompiledIn": bool(m & 1024)}
 
     def badPhotons(self):
         """Photons dropped by a loop bound of the kernels since this integrator was created (the reference's nBad, :562-563)."""

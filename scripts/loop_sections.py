@@ -2,12 +2,13 @@
 """Static instruction counts of the block walk's collision loop, section by section (no GPU needed).
 
 Compiles the device code with -DMCBRAT_MARKS (each STAMP(i) of mcbrat_blockwalk.hip becomes an `@@mark i` comment in the
-assembly), takes the step cloud's instantiation trace_block_kernel<768, true, false, false, 2, 0, true>, keeps the basic blocks of its
+assembly), takes the step cloud's instantiation trace_block_kernel<768, true, false, false, 2, 0, true, 3> (or the one whose mangled name is given), keeps the basic blocks of its
 inner loop and counts, per section between two marks, vector / scalar / LDS instructions, s_nop / s_waitcnt, and the classes
 worth watching (moves, 64-bit address and multiply-add ops, SGPR spills into VGPR lanes, f32 <-> f64 conversions, kernel-argument
 reloads, exec-mask saves).  Sections follow the layout of the code, so a section holds the rare branch that follows its mark.
 
-    python scripts/loop_sections.py [assembly.s]      (without an argument: compiles mcbrat_api.hip first, about a minute)"""
+    python scripts/loop_sections.py [assembly.s [mangled kernel name]]      (without an argument: compiles mcbrat_api.hip first,
+    about a minute; "-" for the assembly compiles too)"""
 import collections
 import os
 import re
@@ -16,7 +17,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_ZN6mcbrat18trace_block_kernelILi768ELb1ELb0ELb0ELi2ELi0ELb1EEEvNS_9DevParamsE"
+KERNEL = sys.argv[2] if len(sys.argv) > 2 else "_ZN6mcbrat18trace_block_kernelILi768ELb1ELb0ELb0ELi2ELi0ELb1ELi3EEEvNS_9DevParamsE"
 SECTIONS = {"7": "loop head + exits", "5": "launch", "0": "collision", "2": "scattering angle",
             "3": "next_direct", "4": "next_direct + drop test + leg set-up", "6": "crossings + exit test", "1": "move (loop end)"}
 ORDER = ["loop head + exits", "launch", "collision", "scattering angle", "next_direct + drop test + leg set-up",
@@ -27,7 +28,7 @@ CLASSES = [("v_mov", "v_mov_b"), ("cndmask", "v_cndmask"), ("addr_u64", "v_lshl_
 
 
 def assembly():
-    if len(sys.argv) > 1:
+    if len(sys.argv) > 1 and sys.argv[1] != "-":
         return open(sys.argv[1]).read()
     out = os.path.join(tempfile.mkdtemp(prefix="loopsec"), "mcbrat_api.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
@@ -39,12 +40,21 @@ def main():
     txt = assembly()
     i = txt.index("\n" + KERNEL + ":")
     body = txt[i:txt.index(".Lfunc_end", i)].split("\n")
-    hdr = next(re.match(r"\.LBB(\d+_\d+):", l).group(1) for k, l in enumerate(body)
-               if re.match(r"\.LBB\d+_\d+:", l) and "This Loop Header: Depth=2" in body[k + 1])
+    # the iteration loop: the loop of depth 2 that holds the marks (an inner loop where no rare branch loops, as under RARE)
+    hdrs = [re.match(r"\.LBB(\d+_\d+):", l).group(1) for k, l in enumerate(body)
+            if re.match(r"\.LBB\d+_\d+:", l) and re.search(r"This (Inner )?Loop Header: Depth=2", body[k + 1])]
+    marks = collections.Counter()
+    cur = None
+    for l in body:
+        if re.match(r"(\.LBB\d+_\d+|; %bb\.\d+):", l):
+            cur = next((h for h in hdrs if "Header=BB%s " % h in l or "Loop BB%s " % h in l or l.startswith(".LBB%s:" % h)), None)
+        elif cur and "@@mark" in l:
+            marks[cur] += 1
+    hdr = marks.most_common(1)[0][0]
     inloop, sec, cnt = False, "move (loop end)", collections.defaultdict(collections.Counter)
     for l in body:
         if re.match(r"(\.LBB\d+_\d+|; %bb\.\d+):", l):  # a basic block: in the loop if it is its header or one of its blocks
-            inloop = ("Header=BB%s" % hdr in l) or ("Loop BB%s" % hdr in l) or l.startswith(".LBB%s:" % hdr)
+            inloop = ("Header=BB%s " % hdr in l) or ("Loop BB%s " % hdr in l) or l.startswith(".LBB%s:" % hdr)
             continue
         t = l.strip()
         m = re.search(r"@@mark (\d+)", t)
