@@ -19,7 +19,8 @@
  * the surface description.  Not the reference's at all: the level tallies of orc_compute_rt_levels, which restate
  * DESIGN.md section 4.12 and are held to identities, the MT mode and transport theory by tests/test_oracle_levels.py, and the
  * track-length tally of orc_compute_rt_actinic, which restates DESIGN.md section 4.14 and is held the same way by
- * tests/test_oracle_actinic.py.
+ * tests/test_oracle_actinic.py; and the surface BRDFs of orc_compute_rt_brdf, which restate DESIGN.md sections 4.11 and 4.11.1
+ * (from those sections and the papers they cite, not from the product's evaluator) and are held by tests/test_oracle_brdf.py.
  */
 #include "mcbrat_oracle.h"
 #include <float.h>
@@ -896,14 +897,17 @@ float orc_lookup_phase_value(const float *table, int nAngleSteps, float scatteri
 static void intensity_contribution(const orc_problem *P, const orc_intensity *I, orc_rng *R, float photonWeight,
                                    double xPos, double yPos, double zPos, int xIndex, int yIndex, int zIndex,
                                    const float dir[3], int component, int scatteringOrder, float *contributions,
-                                   int *xIndexF, int *yIndexF, float *intensityExcess) {
+                                   int *xIndexF, int *yIndexF, float *intensityExcess, int brdfKind, const float *brdfQ) {
   const float Pi = 3.14159265358979312f;
   const int nDir = I->nDirections;
   const int zIndexMax = P->nz + 1; /* size(zPosition) */
   for (int i = 0; i < nDir; i++) {
     const float *D = I->directions + 3 * i;
     float normalizedPhaseFunc;
-    if (component == 0) normalizedPhaseFunc = 1.0f / Pi;                            /* :1691 Lambertian surface */
+    if (component == 0 && brdfQ) { /* a BRDF patch: R(d_in, d_view) / pi, dir the arriving direction */
+      const double di[3] = {dir[0], dir[1], dir[2]}, dv[3] = {D[0], D[1], D[2]};
+      normalizedPhaseFunc = (float)orc_brdf_reflectance(brdfKind, brdfQ, di, dv) / Pi;
+    } else if (component == 0) normalizedPhaseFunc = 1.0f / Pi;                     /* :1691 Lambertian surface */
     else if (component < 0) normalizedPhaseFunc = 1.0f / ((4.0f * Pi) * fabsf(D[2])); /* :1696 isotropic emission */
     else {
       float projection = dir[0] * D[0] + dir[1] * D[1] + dir[2] * D[2]; /* :1704 */
@@ -970,6 +974,185 @@ static void add_intensity(const orc_problem *P, const orc_intensity *I, const fl
 }
 
 /* ------------------------------------------------------------------------ */
+/* Surface BRDFs (ours, not the reference's): DESIGN.md sections 4.11, 4.11.1 */
+/* ------------------------------------------------------------------------ */
+/* Stated from the formulas of those sections and the papers they cite (Rahman, Pinty and Verstraete 1993; Lucht, Schaaf and
+ * Strahler 2000; Cox and Munk 1954 with the shadowing of Smith 1967), in double.  d_in: the arriving propagation direction
+ * (z < 0), d_out: the leaving one (z > 0).  R = pi f. */
+#define BRDF_MU_MIN 0.01
+static const double kPiD = 3.14159265358979323846;
+
+static double clamp1(double v) { return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v); }
+
+static double rpv_R(const float *q, const double *di, const double *dv) {
+  const double rho0 = q[0], k = q[1], th = q[2], rhoC = q[3];
+  const double mi = fmax(-di[2], BRDF_MU_MIN), mr = fmax(dv[2], BRDF_MU_MIN);
+  const double cg = clamp1(-(di[0] * dv[0] + di[1] * dv[1] + di[2] * dv[2]));
+  const double G = hypot(di[0] / mi + dv[0] / mr, di[1] / mi + dv[1] / mr);
+  const double R = rho0 * pow(mi * mr * (mi + mr), k - 1.0) * (1.0 - th * th) / pow(1.0 + 2.0 * th * cg + th * th, 1.5) *
+                   (1.0 + (1.0 - rhoC) / (1.0 + G));
+  return R > 0.0 ? R : 0.0;
+}
+
+static double rossli_R(const float *q, const double *di, const double *dv) {
+  const double fIso = q[0], fVol = q[1], fGeo = q[2];
+  const double mi = fmax(-di[2], BRDF_MU_MIN), mr = fmax(dv[2], BRDF_MU_MIN);
+  const double cg = clamp1(-(di[0] * dv[0] + di[1] * dv[1] + di[2] * dv[2]));
+  const double ax = di[0] / mi, ay = di[1] / mi, bx = dv[0] / mr, by = dv[1] / mr;
+  const double G = hypot(ax + bx, ay + by), S = ax * by - ay * bx;
+  const double g = acos(cg);
+  const double kvol = ((kPiD / 2.0 - g) * cg + sin(g)) / (mi + mr) - kPiD / 4.0; /* RossThick */
+  const double si = 1.0 / mi, sr = 1.0 / mr;                                    /* LiSparse-Reciprocal, h/b = 2, b/r = 1 */
+  const double ct = clamp1(2.0 * sqrt(G * G + S * S) / (si + sr));
+  const double t = acos(ct);
+  const double O = (t - sin(t) * ct) * (si + sr) / kPiD;
+  const double kgeo = O - si - sr + (1.0 + cg) * si * sr / 2.0;
+  const double R = fIso + fVol * kvol + fGeo * kgeo;
+  return R > 0.0 ? R : 0.0;
+}
+
+/* Cox-Munk (section 4.11.1): isotropic slopes, sigma^2 = 0.003 + 0.00512 U */
+static double cm_fresnel(double n, double c) { /* unpolarised, through g = n cos(theta_t) = sqrt((n^2 - 1) + c^2) */
+  const double g = sqrt((n * n - 1.0) + c * c);
+  const double rs = (c - g) / (c + g), rp = (n * n * c - g) / (n * n * c + g);
+  return 0.5 * (rs * rs + rp * rp);
+}
+static double cm_lambda(double s2, double mu) { /* Lambda(1) = 0 */
+  const double s = sqrt(fmax(1.0 - mu * mu, 0.0));
+  if (!(s > 0.0)) return 0.0;
+  const double sig = sqrt(s2);
+  return 0.5 * (sig * s / (mu * sqrt(kPiD)) * exp(-mu * mu / (s2 * s * s)) - erfc(mu / (sig * s)));
+}
+static double cm_whitecaps(const float *q) { return q[2] > 0.0f ? fmin(1.0, 2.95e-6 * pow((double)q[0], 3.52)) : 0.0; }
+/* P, cos beta and cos omega of the facet that mirrors d_in into d_out */
+static void cm_facet(double s2, const double *di, const double *dv, double *P, double *cb, double *cw) {
+  const double hx = dv[0] - di[0], hy = dv[1] - di[1], hz = dv[2] - di[2];
+  const double hn = sqrt(hx * hx + hy * hy + hz * hz);
+  *cb = hz / hn;
+  *cw = 0.5 * hn;
+  *P = exp(-((1.0 - *cb * *cb) / (*cb * *cb)) / s2) / (kPiD * s2);
+}
+static double coxmunk_R(const float *q, const double *di, const double *dv) {
+  const double n = q[1], rhoWc = q[2], aW = q[3], s2 = 0.003 + 0.00512 * (double)q[0];
+  const double mi = fmax(-di[2], BRDF_MU_MIN), mr = fmax(dv[2], BRDF_MU_MIN);
+  double P, cb, cw;
+  cm_facet(s2, di, dv, &P, &cb, &cw);
+  const double S = 1.0 / (1.0 + cm_lambda(s2, mi) + cm_lambda(s2, mr));
+  const double glint = kPiD * P * cm_fresnel(n, cw) * S / (4.0 * mi * mr * (cb * cb * cb * cb));
+  const double W = cm_whitecaps(q);
+  return (1.0 - W) * (glint + aW) + W * rhoWc;
+}
+
+/* p_g of the sampler's mixture: (1 - W) F(-d_in.z) against the Lambertian part (1 - W) a_w + W rho_wc; 0 where both vanish */
+static double cm_glint_probability(const float *q, const double *di) {
+  const double W = cm_whitecaps(q);
+  const double g = (1.0 - W) * cm_fresnel((double)q[1], -di[2]), L = (1.0 - W) * (double)q[3] + W * (double)q[2];
+  return g + L > 0.0 ? g / (g + L) : 0.0;
+}
+
+double orc_brdf_reflectance(int32_t kind, const float *q, const double *dIn, const double *dOut) {
+  switch (kind) {
+    case 1: return rpv_R(q, dIn, dOut);
+    case 2: return rossli_R(q, dIn, dOut);
+    case 3: return coxmunk_R(q, dIn, dOut);
+    default: return (double)q[0];
+  }
+}
+
+int32_t orc_brdf_reflect(int32_t kind, const float *q, int32_t glintSampling, const double *dIn, const double *lambert,
+                         const double *u, double *dOut, double *factor) {
+  double lam[3];
+  if (lambert) { lam[0] = lambert[0]; lam[1] = lambert[1]; lam[2] = lambert[2]; }
+  else { /* mu = sqrt(u1), azimuth 2 pi u2 */
+    const double mu = sqrt(u[1]), s = sqrt(fmax(0.0, 1.0 - mu * mu));
+    lam[0] = s * cos(2.0 * kPiD * u[2]); lam[1] = s * sin(2.0 * kPiD * u[2]); lam[2] = mu;
+  }
+  dOut[0] = lam[0]; dOut[1] = lam[1]; dOut[2] = lam[2];
+  /* the one-sample mixture of the glint lobe and the Lambertian draw (balance heuristic) */
+  const double pg = kind == 3 && glintSampling ? cm_glint_probability(q, dIn) : 0.0;
+  if (!(pg > 0.0)) { /* the plain estimator: the Lambertian draw, the weight times R */
+    *factor = orc_brdf_reflectance(kind, q, dIn, dOut);
+    return 0;
+  }
+  const double s2 = 0.003 + 0.00512 * (double)q[0];
+  int32_t comp = 0;
+  if (u[0] <= pg) { /* a facet slope from P, the mirror direction */
+    comp = 1;
+    const double t2 = -s2 * log(fmax(1.0 - u[1], DBL_MIN)), t = sqrt(t2), nrm = sqrt(1.0 + t2);
+    const double m[3] = {t * cos(2.0 * kPiD * u[2]) / nrm, t * sin(2.0 * kPiD * u[2]) / nrm, 1.0 / nrm};
+    const double c = -(dIn[0] * m[0] + dIn[1] * m[1] + dIn[2] * m[2]);
+    for (int a = 0; a < 3; a++) dOut[a] = dIn[a] + 2.0 * c * m[a];
+    /* a unit vector where d_in is one; d_in arrives as floats, so to 2^-24: scaled to length 1, the facet terms below see a direction */
+    const double len = sqrt(dOut[0] * dOut[0] + dOut[1] * dOut[1] + dOut[2] * dOut[2]);
+    for (int a = 0; a < 3; a++) dOut[a] /= len;
+    if (!(c > 0.0) || dOut[2] < ldexp(1.0, -16)) { *factor = 0.0; return comp | 2; }
+  }
+  double P, cb, cw;
+  cm_facet(s2, dIn, dOut, &P, &cb, &cw);
+  const double lamDen = dOut[2] / kPiD;
+  const double den = pg * P / (4.0 * cb * cb * cb * cw) + (1.0 - pg) * lamDen;
+  *factor = den > 0.0 ? coxmunk_R(q, dIn, dOut) * lamDen / den : 0.0;
+  return comp;
+}
+
+int32_t orc_brdf_reflect_bracket(int32_t kind, const float *q, int32_t glintSampling, const double *dIn, const double *lambert,
+                                 const double *u, double delta, double *dOut, double *factor, double *variation, int32_t *tie) {
+  double lam[3];
+  const int32_t comp = orc_brdf_reflect(kind, q, glintSampling, dIn, lambert, u, dOut, factor);
+  /* (the Lambertian draw as the base evaluation took it) */
+  if (lambert) { lam[0] = lambert[0]; lam[1] = lambert[1]; lam[2] = lambert[2]; }
+  else if (comp == 0) { lam[0] = dOut[0]; lam[1] = dOut[1]; lam[2] = dOut[2]; }
+  else { const double mu = sqrt(u[1]), s = sqrt(fmax(0.0, 1.0 - mu * mu)); lam[0] = s * cos(2.0 * kPiD * u[2]); lam[1] = s * sin(2.0 * kPiD * u[2]); lam[2] = mu; }
+  *variation = 0.0;
+  *tie = 0;
+  if (!(delta > 0.0)) return comp;
+  for (int v = 0; v < 2; v++)
+    for (int a = 0; a < 3; a++)
+      for (int sgn = -1; sgn <= 1; sgn += 2) {
+        double di[3] = {dIn[0], dIn[1], dIn[2]}, dl[3] = {lam[0], lam[1], lam[2]}, o[3], f;
+        (v == 0 ? di : dl)[a] += sgn * delta;
+        const int32_t c2 = orc_brdf_reflect(kind, q, glintSampling, di, dl, u, o, &f);
+        if (c2 != comp) *tie = 1;
+        if (fabs(f - *factor) > *variation) *variation = fabs(f - *factor);
+      }
+  return comp;
+}
+
+/* the patch under (xPos, yPos): the look-up of surface_reflectance above, returning the index */
+static size_t surface_patch_index(const orc_problem *P, double xPos, double yPos) {
+  const int nX = P->surfNumX, nY = P->surfNumY;
+  int xi = orc_find_index_mixed(make_periodic(xPos, P->surfXPosition[0], P->surfXPosition[nX - 1]), P->surfXPosition, nX, 0);
+  int yi = orc_find_index_mixed(make_periodic(yPos, P->surfYPosition[0], P->surfYPosition[nY - 1]), P->surfYPosition, nY, 0);
+  if (xi < 1) xi = 1;
+  if (xi > nX - 1) xi = nX - 1;
+  if (yi < 1) yi = 1;
+  if (yi > nY - 1) yi = nY - 1;
+  return (size_t)(xi - 1) + (size_t)(nX - 1) * (yi - 1);
+}
+
+/* next_direct with the direction in double: the same expressions, the unit vector of the azimuth and the scattering cosine
+ * as the float code forms them; S is rounded to float by the caller, where the float code reads it */
+static void next_direct_double(orc_rng *R, float scatteringCosine, double S[3]) {
+  float fx = 0.f, fy = 0.f, fD = 2.0f;
+  if (R->mode == 1) { sincos_2pi(draw(R, 0, 2), &fx, &fy); fD = 1.0f; }
+  else {
+    while (fD > 1.0f) {
+      fx = 1.0f - 2.0f * draw(R, 0, 0);
+      fy = 1.0f - 2.0f * draw(R, 0, 0);
+      fD = fx * fx + fy * fy;
+    }
+  }
+  const double sc = (double)scatteringCosine;
+  double B = sqrt((1.0 - sc * sc) / (double)fD);
+  const double AX = (double)fx * B, AY = (double)fy * B;
+  B = S[0] * AX - S[1] * AY;
+  const double D = sc - B / (1.0 + fabs(S[2]));
+  S[0] = S[0] * D + AX;
+  S[1] = S[1] * D - AY;
+  S[2] = S[2] * sc - copysign(fabs(B), S[2] * B);
+}
+
+/* ------------------------------------------------------------------------ */
 /* computeRT :393-841                                                        */
 /* ------------------------------------------------------------------------ */
 int64_t orc_compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
@@ -982,7 +1165,7 @@ int64_t orc_compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, in
 static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
                           float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
                           orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
-                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace);
+                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace, orc_brdf *B);
 static double leg_length(const orc_problem *P, const float dir[3], const double before[3], const double after[3]);
 
 int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
@@ -990,7 +1173,7 @@ int64_t orc_compute_rt_intensity(const orc_problem *P, const orc_source *S, orc_
                                  orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
                                  float *intensityByComponent, float *intensityExcess) {
   return compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, I, intensity,
-                    intensityByComponent, intensityExcess, NULL, NULL);
+                    intensityByComponent, intensityExcess, NULL, NULL, NULL);
 }
 
 /* computeRT with the level tallies of DESIGN.md section 4.12 (ours, not the reference's: restated from that section's
@@ -1010,7 +1193,7 @@ int64_t orc_compute_rt_levels(const orc_problem *P, const orc_source *S, orc_rng
   if (levelUpCount) memset(levelUpCount, 0, sizeof(int64_t) * nbins);
   if (levelDownCount) memset(levelDownCount, 0, sizeof(int64_t) * nbins);
   return compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, NULL, NULL, NULL, NULL,
-                    &T, nearFace);
+                    &T, nearFace, NULL);
 }
 
 /* computeRT with the level tallies and the track-length tally of DESIGN.md section 4.14 (ours, restated from that section's
@@ -1035,8 +1218,23 @@ int64_t orc_compute_rt_actinic(const orc_problem *P, const orc_source *S, orc_rn
   if (actinicCount) memset(actinicCount, 0, sizeof(int64_t) * nvox);
   if (actinicSlack) memset(actinicSlack, 0, sizeof(double) * nvox);
   const int64_t n = compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, NULL, NULL, NULL,
-                               NULL, &T, nearFace);
+                               NULL, &T, nearFace, NULL);
   if (legSum) *legSum = T.legSum;
+  return n;
+}
+
+/* computeRT over a surface of kind 0-3, with the BRDF tallies of B beside the floats (ours: DESIGN.md sections 3 and 4.11).  The
+ * level tallies run beside it for the path length that the nearFace margin needs; they are dropped. */
+int64_t orc_compute_rt_brdf(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons, float *fluxUp,
+                            float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C, orc_fate *fates,
+                            const orc_intensity *I, float *intensity, orc_brdf *B) {
+  const size_t nbins = (size_t)P->nx * P->ny * ((size_t)P->nz + 1);
+  double *lup = (double *)calloc(nbins, sizeof(double)), *ldn = (double *)calloc(nbins, sizeof(double));
+  level_tally T = {lup, ldn, NULL, NULL, 1.0f, 0.0};
+  B->nArrivals = B->reflections = B->aboveOne = B->endedByZero = B->glintTaken = B->lambertTaken = B->ties = 0;
+  const int64_t n = compute_rt(P, S, R, numPhotons, fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, C, fates, I, intensity, NULL,
+                               NULL, &T, B->nearFace, B);
+  free(lup); free(ldn);
   return n;
 }
 
@@ -1053,6 +1251,13 @@ static double leg_length(const orc_problem *P, const float dir[3], const double 
   return (after[a] + wraps * period - before[a]) / (double)dir[a];
 }
 
+/* a deposit of the BRDF tallies: the double sum, the count, and w rho into the slack */
+static void brdf_deposit(double *sum, int64_t *count, double *slack, size_t bin, float w, double rho) {
+  if (sum) sum[bin] += (double)w;
+  if (count) count[bin]++;
+  if (slack) slack[bin] += (double)w * rho;
+}
+
 static int near_any(double v, const double *t, int n, double delta) {
   for (int i = 0; i < n; i++) if (fabs(v - t[i]) <= delta) return 1;
   return 0;
@@ -1061,7 +1266,7 @@ static int near_any(double v, const double *t, int n, double delta) {
 static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons,
                           float *fluxUp, float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption,
                           orc_counters *C, orc_fate *fates, const orc_intensity *I, float *intensity,
-                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace) {
+                          float *intensityByComponent, float *intensityExcess, level_tally *T, uint8_t *nearFace, orc_brdf *B) {
   const int nx = P->nx, ny = P->ny, nz = P->nz, nc = P->nc;
   const size_t ncol = (size_t)nx * ny, nvox = ncol * nz;
   const float Pi = 3.14159265358979312f; /* :31 */
@@ -1134,6 +1339,9 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
       zPos = P->ze[zIndex - 1] + remainder * (P->ze[zIndex] - P->ze[zIndex - 1]);
     }
     int flagged = 0;
+    /* BRDF tallies (B): rho, the relative uncertainty of the weight since the first BRDF reflection; the direction in double
+     * where B->doubleDirections; what the photon has given up so far, for the closure of its energy */
+    double rho = 0.0, dird[3] = {dir[0], dir[1], dir[2]}, given = 0.0, givenBound = 0.0;
     if (T) { /* section 4.12: a solar launch is the downward crossing of level nz, a surface-emitted photon the upward crossing
               * of level 0, each with weight 1 in the launch column; an atmospheric launch crosses nothing */
       T->path = 0.0;
@@ -1151,7 +1359,7 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
       }
       if (nDir > 0) { /* :510-541 emission seen directly: surface (component 0) or atmosphere (-1) */
         intensity_contribution(P, I, R, photonWeight, xPos, yPos, zPos, xIndex, yIndex, zIndex, dir,
-                               zPos == 0.0 ? 0 : -1, scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess);
+                               zPos == 0.0 ? 0 : -1, scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess, 0, NULL);
         add_intensity(P, I, contributions, xIndexF, yIndexF, 0, intensity, intensityByComponent);
       }
     }
@@ -1178,6 +1386,11 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
         size_t c2 = (size_t)(xIndex - 1) + (size_t)nx * (yIndex - 1);
         fluxUp[c2] = fluxUp[c2] + photonWeight;
         if (T) level_deposit(P, T, 1, nz, xIndex, yIndex, photonWeight); /* section 4.12: beside the fluxUp deposit */
+        if (B) {
+          brdf_deposit(B->up, B->nUp, B->kUp, c2, photonWeight, rho);
+          if (scatteringOrder < B->nOrders) brdf_deposit(B->upOrd, B->nUpOrd, B->kUpOrd, ncol * (size_t)scatteringOrder + c2, photonWeight, rho);
+          given += (double)photonWeight;
+        }
         cnt.topExits++;
         fate = 0; fateWeight = photonWeight;
         break;
@@ -1191,18 +1404,75 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
           const double delta = 64.0 * ldexp(1.0, -23) * T->path;
           if (near_any(xPos, P->surfXPosition, P->surfNumX, delta) || near_any(yPos, P->surfYPosition, P->surfNumY, delta)) flagged = 1;
         }
+        if (B) { /* the order before the reflection, as fluxDownByScatOrd (computeRT :635-643) */
+          brdf_deposit(B->down, B->nDown, B->kDown, c2, photonWeight, rho);
+          if (scatteringOrder < B->nOrders) brdf_deposit(B->downOrd, B->nDownOrd, B->kDownOrd, ncol * (size_t)scatteringOrder + c2, photonWeight, rho);
+          if (B->arrivalDir && B->nArrivals < B->arrivalCap) {
+            for (int a = 0; a < 3; a++) B->arrivalDir[3 * B->nArrivals + a] = B->doubleDirections ? dird[a] : (double)dir[a];
+            if (B->arrivalPhoton) B->arrivalPhoton[B->nArrivals] = (int32_t)ip;
+          }
+          B->nArrivals++;
+        }
         cnt.surfaceHits++;
         scatteringOrder++;
         for (uint32_t j = 0;; j++) { /* Philox slots: mu attempt 0 = X, 1 = Z, then block 2.. ; phi = Y */
           mu = sqrtf(j == 0 ? draw(R, 0, 1) : j == 1 ? draw(R, 0, 3) : draw(R, 2 + (j - 2) / 4, (j - 2) % 4));
           if (fabsf(mu) > 2.0f * FLT_MIN) break;
         }
-        phi = (2.0f * Pi) * draw(R, 0, 2);
+        const float uY = draw(R, 0, 2);
+        phi = (2.0f * Pi) * uY;
         float wBefore = photonWeight;
+        if (P->surfNumX > 0 && P->surfKind > 0) {
+          /* a BRDF patch (DESIGN.md sections 4.11, 4.11.1): the Lambertian draw of the direction, the weight times R(d_in, d_out);
+           * Cox-Munk with glint sampling draws from the mixture instead, its three uniforms block 0xffffffff of the event (MT
+           * mode: three further draws).  Local estimates: the weight before the reflection, R(d_in, d_view) / pi, also where
+           * the reflection ends the photon. */
+          float lamf[3];
+          if (R->mode == 1) {
+            float sinTheta = sqrtf(1.0f - mu * mu), c, s;
+            sincos_2pi(uY, &c, &s);
+            lamf[0] = sinTheta * c; lamf[1] = sinTheta * s; lamf[2] = mu;
+          } else {
+            make_direction_cosines(mu, phi, lamf);
+          }
+          const float *q = P->surfParams + 4 * surface_patch_index(P, xPos, yPos);
+          const double dIn[3] = {dir[0], dir[1], dir[2]}, lam[3] = {lamf[0], lamf[1], lamf[2]};
+          /* (where p_g = 0 -- n = 1 -- the reflection is the plain one and reads no uniform of the glint block) */
+          const int sampled = P->surfKind == 3 && P->glintSampling && cm_glint_probability(q, dIn) > 0.0;
+          double u[3] = {0.0, 0.0, 0.0};
+          if (sampled) for (uint32_t e = 0; e < 3; e++) u[e] = (double)draw(R, 0xffffffffu, e);
+          double dOut[3], factor, variation = 0.0;
+          int32_t tie = 0;
+          const int32_t comp = orc_brdf_reflect_bracket(P->surfKind, q, P->glintSampling, dIn, lam, u, B ? B->delta : 0.0, dOut, &factor,
+                                                        &variation, &tie);
+          photonWeight = photonWeight * (float)factor;
+          if (B) {
+            B->reflections++;
+            if (sampled) { if (comp & 1) B->glintTaken++; else B->lambertTaken++; }
+            /* a tie: the component or the end of the photon changes under the moves, or R is not above its own variation (the
+             * clamp at 0 may fall either way) */
+            if (tie || (variation > 0.0 && !(factor > variation))) { flagged = 1; B->ties++; }
+            if (factor > 0.0) rho += variation / factor + ldexp(1.0, -23);
+            if (photonWeight > 1.0f) B->aboveOne++;
+            if (photonWeight <= FLT_MIN) B->endedByZero++;
+            given += (double)wBefore - (double)photonWeight;
+          }
+          if (nDir > 0) {
+            intensity_contribution(P, I, R, wBefore, xPos, yPos, zPos, xIndex, yIndex, zIndex, dir, 0, scatteringOrder,
+                                   contributions, xIndexF, yIndexF, intensityExcess, P->surfKind, q);
+            add_intensity(P, I, contributions, xIndexF, yIndexF, 0, intensity, intensityByComponent);
+          }
+          if (photonWeight <= FLT_MIN) { cnt.surfaceAbsorbed++; fate = 1; fateWeight = wBefore; break; }
+          if (T) level_deposit(P, T, 1, 0, xIndex, yIndex, photonWeight);
+          if (R->mode == 1) (void)draw(R, 0, 2); /* (the Lambertian path reads slot Y once more where the photon goes on: the same count of uniforms) */
+          for (int a = 0; a < 3; a++) { dird[a] = dOut[a]; dir[a] = (float)dOut[a]; }
+          continue;
+        }
         if (P->surfNumX > 0) /* useSurfaceBDRF :667-670 (incoming / outgoing angles are not used by the reference's R) */
           photonWeight = photonWeight * surface_reflectance(P, xPos, yPos);
         else
           photonWeight = (float)((double)photonWeight * albedo); /* :673 */
+        if (B) { B->reflections++; given += (double)wBefore - (double)photonWeight; }
         if (photonWeight <= FLT_MIN) { cnt.surfaceAbsorbed++; fate = 1; fateWeight = wBefore; break; }
         if (T) level_deposit(P, T, 1, 0, xIndex, yIndex, photonWeight); /* section 4.12: the reflected photon, the weight after the albedo */
         if (R->mode == 1) { /* Philox mode: cos / sin of 2 pi Y by the kernel's expression (sincos_2pi), as in next_direct */
@@ -1212,9 +1482,10 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
         } else {
           make_direction_cosines(mu, phi, dir);
         }
+        for (int a = 0; a < 3; a++) dird[a] = (double)dir[a];
         if (nDir > 0) { /* :680-702 */
           intensity_contribution(P, I, R, photonWeight, xPos, yPos, zPos, xIndex, yIndex, zIndex, dir, 0,
-                                 scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess);
+                                 scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess, 0, NULL);
           add_intensity(P, I, contributions, xIndexF, yIndexF, 0, intensity, intensityByComponent);
         }
       } else { /* scattering event :703-821 */
@@ -1267,30 +1538,52 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
           size_t v3 = IDX3(P, xIndex, yIndex, zIndex);
           fluxAbsorbed[c2] = (float)((double)fluxAbsorbed[c2] + (double)photonWeight * (1.0 - (double)ssa));
           volumeAbsorption[v3] = (float)((double)volumeAbsorption[v3] + (double)photonWeight * (1.0 - (double)ssa));
+          if (B) { /* the deposit as one float, w (1 - ssa): what a float tally adds */
+            const float dep = photonWeight * (1.0f - ssa);
+            brdf_deposit(B->vol, B->nVol, B->kVol, v3, dep, rho);
+            given += (double)dep;
+            givenBound += 3.0 * ldexp(1.0, -24) * (double)photonWeight; /* fl(w fl(1 - s)) + fl(w s) against w */
+          }
           photonWeight = photonWeight * ssa;
           cnt.absorbEvents++;
         }
         if (nDir > 0) { /* :776-790 */
           intensity_contribution(P, I, R, photonWeight, xPos, yPos, zPos, xIndex, yIndex, zIndex, dir, component,
-                                 scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess);
+                                 scatteringOrder, contributions, xIndexF, yIndexF, intensityExcess, 0, NULL);
           add_intensity(P, I, contributions, xIndexF, yIndexF, component, intensity, intensityByComponent);
         }
+        if (B && P->useRussianRoulette && rho > 0.0) { /* the roulette's two comparisons within w rho of their thresholds */
+          const double wr = (double)photonWeight * rho;
+          if (fabs((double)photonWeight - 0.5) <= wr) { flagged = 1; B->ties++; }
+        }
+        const float wRoulette = photonWeight;
         if (P->useRussianRoulette && photonWeight < RussianRouletteW / 2.0f) { /* :805-811 */
           /* Philox mode: block 1 elem 1 -- or, in a domain of ONE component, elem 3 of the leg's own block (Z: the uniform of the
            * component pick, which with one component decides nothing), so that the kernels need no second block for it */
-          if (draw(R, P->nc == 1 ? 0 : 1, P->nc == 1 ? 3 : 1) >= photonWeight / RussianRouletteW) { photonWeight = 0.0f; cnt.rouletteKills++; }
-          else { photonWeight = RussianRouletteW; cnt.rouletteSurvivals++; }
+          const float uRoulette = draw(R, P->nc == 1 ? 0 : 1, P->nc == 1 ? 3 : 1);
+          if (B && rho > 0.0 && fabs((double)uRoulette - (double)photonWeight) <= (double)photonWeight * rho) { flagged = 1; B->ties++; }
+          if (uRoulette >= photonWeight / RussianRouletteW) { photonWeight = 0.0f; cnt.rouletteKills++; }
+          else { photonWeight = RussianRouletteW; cnt.rouletteSurvivals++; rho = 0.0; } /* (exactly 1 on both sides) */
+          if (B) given += (double)wRoulette - (double)photonWeight;
         }
         if (photonWeight <= FLT_MIN) { fate = 2; break; } /* :812 */
         int pfi = P->pfIndex[IDX4(P, xIndex, yIndex, zIndex, component)]; /* :816 */
         int ns = P->invNSteps[component - 1];
         const float *tblf = P->invTables + P->invOffset[component - 1] + (size_t)(pfi - 1) * ns;
         float scatteringAngle = compute_scattering_angle(draw(R, 0, 1), tblf, ns); /* slot X */
-        next_direct(R, cosf(scatteringAngle), dir); /* :819 */
+        if (B && B->doubleDirections) {
+          next_direct_double(R, cosf(scatteringAngle), dird);
+          for (int a = 0; a < 3; a++) dir[a] = (float)dird[a];
+        } else {
+          next_direct(R, cosf(scatteringAngle), dir); /* :819 */
+          for (int a = 0; a < 3; a++) dird[a] = (double)dir[a];
+        }
       }
     }
     if (T && T->act && T->edge) flagged = 1;
     if (nearFace) nearFace[ip] = (uint8_t)flagged;
+    if (B && B->closure) B->closure[ip] = 1.0 - given;
+    if (B && B->closureBound) B->closureBound[ip] = givenBound + ldexp(1.0, -50) * (double)(scatteringOrder + 1);
     if (fates) {
       fates[ip].fate = fate;
       fates[ip].ix = xIndex; fates[ip].iy = yIndex; fates[ip].iz = zIndex;

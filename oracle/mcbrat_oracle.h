@@ -49,6 +49,10 @@ typedef struct {
   int32_t surfNumX, surfNumY;        /* size(xPosition), size(yPosition)      */
   const double *surfXPosition, *surfYPosition;
   const float *surfReflectance;      /* BRDFParameters(1, :, :): [numY-1][numX-1], x fastest */
+  /* surface BRDF models of DESIGN.md section 4.11 / 4.11.1 (not in the reference): the kinds of include/mcbrat.h */
+  int32_t surfKind;                  /* 0 Lambertian (surfReflectance), 1 RPV, 2 Ross-Li, 3 Cox-Munk           */
+  int32_t glintSampling;             /* kind 3: draw the reflection from the glint mixture (section 4.11.1)    */
+  const float *surfParams;           /* kinds 1-3: four floats per patch, [numY-1][numX-1][4], x fastest       */
 } orc_problem;
 
 /* Photon source (src/monteCarloIllumination.f95). */
@@ -206,6 +210,45 @@ int64_t orc_compute_rt_actinic(const orc_problem *P, const orc_source *S, orc_rn
                                orc_fate *fates, double *levelUp, double *levelDown,
                                int64_t *levelUpCount, int64_t *levelDownCount, uint8_t *nearFace,
                                double *actinic, int64_t *actinicCount, double *actinicSlack, double *legSum);
+/* ---- surface BRDFs (DESIGN.md sections 4.11 and 4.11.1; not in the reference) ---------------------------------------- */
+/* The reflectance factor R = pi f of kind 1-3 (kind 0: q[0]) for the parameters q[4] and the propagation directions d_in
+ * (arriving, z < 0) and d_out (leaving, z > 0), in double: this file's own statement of the models. */
+double orc_brdf_reflectance(int32_t kind, const float *q, const double *dIn, const double *dOut);
+/* One reflection: the direction taken and the factor of the weight (0: the photon ends).  lambert: the Lambertian draw of the
+ * direction (NULL: mu = sqrt(u[1]), azimuth 2 pi u[2]); u[3] = (component, u1, u2) for kind 3 with glintSampling, unread
+ * otherwise.  Returns 0 for the Lambertian draw, 1 for the glint lobe, | 2 where the sampled direction ended the photon. */
+int32_t orc_brdf_reflect(int32_t kind, const float *q, int32_t glintSampling, const double *dIn, const double *lambert,
+                         const double *u, double *dOut, double *factor);
+/* orc_brdf_reflect with the twelve moves of one component of d_in or of the Lambertian draw by +-delta: *variation is
+ * max |factor' - factor|, *tie is set where a move changes the component taken or whether the direction ends the photon. */
+int32_t orc_brdf_reflect_bracket(int32_t kind, const float *q, int32_t glintSampling, const double *dIn, const double *lambert,
+                                 const double *u, double delta, double *dOut, double *factor, double *variation, int32_t *tie);
+
+/* What orc_compute_rt_brdf tallies beside computeRT's floats: per bin the double sum of the deposits, their number, and the
+ * slack sum of w rho (rho: the relative uncertainty the photon's weight carries since its first BRDF reflection).  Every
+ * pointer may be NULL. */
+typedef struct {
+  int32_t nOrders;                   /* > 0: fluxes by scattering order 0 .. nOrders-1 as well                 */
+  int32_t doubleDirections;          /* carry the direction through scatterings in double, rounded to float where read */
+  double delta;                      /* the move of a direction component in the bracket of R                  */
+  double *up, *down, *vol;           /* [ncol], [ncol], [nvox]                                                 */
+  int64_t *nUp, *nDown, *nVol;
+  double *kUp, *kDown, *kVol;
+  double *upOrd, *downOrd;           /* [nOrders][ncol]                                                        */
+  int64_t *nUpOrd, *nDownOrd;
+  double *kUpOrd, *kDownOrd;
+  uint8_t *nearFace;                 /* [numPhotons]: orc_compute_rt_levels' flag, or a tie of this file's     */
+  double *closure, *closureBound;    /* [numPhotons]: 1 - (what left, was absorbed, lost at the surface or to the roulette) */
+  int64_t arrivalCap;                /* surface arrivals recorded at most                                      */
+  double *arrivalDir;                /* [arrivalCap][3]: the arriving direction                                */
+  int32_t *arrivalPhoton;            /* [arrivalCap]: index of the photon in this call                         */
+  /* out */
+  int64_t nArrivals, reflections, aboveOne, endedByZero, glintTaken, lambertTaken, ties;
+} orc_brdf;
+/* computeRT over a surface of kind 0-3 (P->surfKind), with radiance when I and intensity are given (NULL: none). */
+int64_t orc_compute_rt_brdf(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons, float *fluxUp,
+                            float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C, orc_fate *fates,
+                            const orc_intensity *I, float *intensity, orc_brdf *B);
 /* normalisation of computeRadiativeTransfer (:328-364), in place. */
 void orc_normalize(const orc_problem *P, int64_t numPhotonsProcessed, float *fluxUp,
                    float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption);

@@ -32,7 +32,16 @@ class OrcProblem(C.Structure):
         ("lwFlag", C.c_float),
         ("surfNumX", C.c_int32), ("surfNumY", C.c_int32),
         ("surfXPosition", C.c_void_p), ("surfYPosition", C.c_void_p), ("surfReflectance", C.c_void_p),
+        ("surfKind", C.c_int32), ("glintSampling", C.c_int32), ("surfParams", C.c_void_p),
     ]
+
+
+class OrcBrdf(C.Structure):
+    _fields_ = ([("nOrders", C.c_int32), ("doubleDirections", C.c_int32), ("delta", C.c_double)]
+                + [(n, C.c_void_p) for n in ("up", "down", "vol", "nUp", "nDown", "nVol", "kUp", "kDown", "kVol", "upOrd", "downOrd",
+                                             "nUpOrd", "nDownOrd", "kUpOrd", "kDownOrd", "nearFace", "closure", "closureBound")]
+                + [("arrivalCap", C.c_int64), ("arrivalDir", C.c_void_p), ("arrivalPhoton", C.c_void_p)]
+                + [(n, C.c_int64) for n in ("nArrivals", "reflections", "aboveOne", "endedByZero", "glintTaken", "lambertTaken", "ties")])
 
 
 class OrcIntensity(C.Structure):
@@ -106,6 +115,14 @@ def lib():
         L.orc_compute_rt_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 11
         L.orc_compute_rt_actinic.restype = C.c_int64
         L.orc_compute_rt_actinic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 15
+        L.orc_compute_rt_brdf.restype = C.c_int64
+        L.orc_compute_rt_brdf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9
+        L.orc_brdf_reflectance.restype = C.c_double
+        L.orc_brdf_reflectance.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_brdf_reflect.restype = C.c_int32
+        L.orc_brdf_reflect.argtypes = [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+        L.orc_brdf_reflect_bracket.restype = C.c_int32
+        L.orc_brdf_reflect_bracket.argtypes = [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 4
         L.orc_find_index_double.argtypes = [C.c_double, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_real.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
         L.orc_find_index_mixed.argtypes = [C.c_float, C.c_void_p, C.c_int, C.c_int]
@@ -295,8 +312,10 @@ class Problem:
                             _p(self.totalExt), _p(self.cumExt), _p(self.ssa), _p(self.pfIndex),
                             self.albedo, _p(self.invTables), _p(self.invOffset), _p(self.invNSteps),
                             _p(self.invNEntries), 1 if use_russian_roulette else 0, float(lw_flag),
-                            0, 0, None, None, None)
-        if surface is not None:
+                            0, 0, None, None, None, 0, 0, None)
+        if surface is not None and isinstance(surface[0], str):
+            self.set_surface_brdf(*surface)
+        elif surface is not None:
             self.set_surface(*surface)
 
     def set_surface(self, reflectance, x_position, y_position):
@@ -309,6 +328,23 @@ class Problem:
         self.surfR = np.ascontiguousarray(r.T).reshape(-1)  # x fastest
         self.c.surfNumX, self.c.surfNumY = self.surfX.size, self.surfY.size
         self.c.surfXPosition, self.c.surfYPosition, self.c.surfReflectance = _p(self.surfX), _p(self.surfY), _p(self.surfR)
+
+    def set_surface_brdf(self, model, params, x_position, y_position, glint_sampling=True):
+        """A surface description of DESIGN.md section 4.11 / 4.11.1: model "Lambertian", "RPV", "RossLi" or "CoxMunk" (kinds 0-3 of
+        include/mcbrat.h), params[nParams, numX-1, numY-1], positions increasing.  Kind 0 is set_surface()."""
+        kind = BRDF_KINDS[model]
+        q = np.asarray(params, np.float32)
+        if kind == 0:
+            return self.set_surface(q[0], x_position, y_position)
+        self.surfX = np.ascontiguousarray(x_position, np.float64)
+        self.surfY = np.ascontiguousarray(y_position, np.float64)
+        assert q.ndim == 3 and q.shape[1:] == (self.surfX.size - 1, self.surfY.size - 1) and q.shape[0] <= 4
+        full = np.zeros((self.surfY.size - 1, self.surfX.size - 1, 4), np.float32)  # x fastest, four floats per patch
+        full[:, :, :q.shape[0]] = q.transpose(2, 1, 0)
+        self.surfQ = np.ascontiguousarray(full).reshape(-1)
+        self.c.surfNumX, self.c.surfNumY = self.surfX.size, self.surfY.size
+        self.c.surfXPosition, self.c.surfYPosition, self.c.surfReflectance = _p(self.surfX), _p(self.surfY), None
+        self.c.surfKind, self.c.glintSampling, self.c.surfParams = kind, int(bool(glint_sampling)), _p(self.surfQ)
 
     def surface_reflectance(self, x, y):
         """computeSurfaceReflectance(surfaceBDRF, xPos, yPos, ...), src/surfaceProperties.f95:119-147."""
@@ -398,6 +434,100 @@ def compute_rt_levels(problem, source, rng, n_photons, want_fates=False):
            "nearFace": near[:int(n_photons)].astype(bool)}
     if want_fates:
         res["fates"] = fates
+    return res
+
+
+BRDF_KINDS = {"Lambertian": 0, "RPV": 1, "RossLi": 2, "CoxMunk": 3}
+
+
+def brdf_reflectance(kind, params, d_in, d_out):
+    """The oracle's own R = pi f of kinds 0-3 (double) for one parameter vector; d_in, d_out [..., 3] broadcast."""
+    q = np.zeros(4, np.float32)
+    q[:len(params)] = np.asarray(params, np.float32)
+    a, b = np.broadcast_arrays(np.asarray(d_in, np.float64), np.asarray(d_out, np.float64))
+    a, b = np.ascontiguousarray(a).reshape(-1, 3), np.ascontiguousarray(b).reshape(-1, 3)
+    f = lib().orc_brdf_reflectance
+    out = np.array([f(int(kind), _p(q), a[i].ctypes.data, b[i].ctypes.data) for i in range(a.shape[0])], np.float64)
+    return out.reshape(np.broadcast(np.asarray(d_in)[..., 0], np.asarray(d_out)[..., 0]).shape)
+
+
+def brdf_reflect(kind, params, d_in, u, glint_sampling=True, delta=0.0):
+    """The oracle's reflection for uniforms u[n, 3] = (component, u1, u2), the Lambertian draw mu = sqrt(u1), azimuth 2 pi u2:
+    -> dict(d_out [n, 3], factor [n] (double), comp [n] (0 Lambertian draw, 1 glint lobe, | 2: the direction ended the photon),
+    variation [n] (max |factor' - factor| over the twelve moves by delta), tie [n])."""
+    q = np.zeros(4, np.float32)
+    q[:len(params)] = np.asarray(params, np.float32)
+    a = np.ascontiguousarray(d_in, np.float64)
+    uu = np.ascontiguousarray(u, np.float64).reshape(-1, 3)
+    n = uu.shape[0]
+    d_out, factor, var = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+    comp, tie = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    f = lib().orc_brdf_reflect_bracket
+    for i in range(n):
+        comp[i] = f(int(kind), _p(q), int(bool(glint_sampling)), _p(a), None, uu[i].ctypes.data, float(delta), d_out[i].ctypes.data,
+                    factor[i:].ctypes.data, var[i:].ctypes.data, tie[i:].ctypes.data)
+    return dict(d_out=d_out, factor=factor, comp=comp, variation=var, tie=tie.astype(bool))
+
+
+def compute_rt_brdf(problem, source, rng, n_photons, intensity=None, orders=0, delta=0.0, double_directions=False, want_fates=False,
+                    arrivals=False):
+    """computeRT over a surface of kind 0-3 (Problem(surface=(model, params, x, y))) with, per column and per cell, the double sum,
+    the deposit count and the slack sum (the sum of w rho: DESIGN.md section 3) of every tally: fluxUp / fluxUpCount / fluxUpSlack
+    [ny, nx], fluxDown..., volumeAbsorption... [nz, ny, nx] and the column absorption fluxAbsorbed... [ny, nx] (the sum of the
+    former over the layers); with orders > 0 the same by scattering order, fluxUpByOrd... / fluxDownByOrd... [orders, ny, nx].
+    Beside them compute_rt()'s float tallies under the key "float", nearFace [n], the counters, the BRDF counts (reflections,
+    aboveOne, endedByZero, glintTaken, lambertTaken, ties), closure / closureBound [n] (the photon's energy balance and the
+    rounding it may show) and, with `intensity` (an Intensity), the raw radiance sums intensity [nDir, ny nx].
+    delta: the move of a direction component in the bracket of R.  double_directions: the direction is carried through
+    scatterings in double; arrivals: also arrivalDir [m, 3], arrivalPhoton [m], every surface arrival's direction."""
+    nx, ny, nz, n = problem.nx, problem.ny, problem.nz, int(n_photons)
+    ncol, nvox = nx * ny, nx * ny * nz
+    up, dn, ab = (np.zeros(ncol, np.float32) for _ in range(3))
+    vol = np.zeros(nvox, np.float32)
+    col, cell, ords = (ny, nx), (nz, ny, nx), (max(int(orders), 1), ny, nx)
+    arr = {}
+    for name, shape in (("fluxUp", col), ("fluxDown", col), ("volumeAbsorption", cell), ("fluxUpByOrd", ords), ("fluxDownByOrd", ords)):
+        arr[name], arr[name + "Count"], arr[name + "Slack"] = np.zeros(shape), np.zeros(shape, np.int64), np.zeros(shape)
+    near = np.zeros(max(n, 1), np.uint8)
+    closure, bound = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    cap = 64 * max(n, 1) if arrivals else 0
+    adir, aph = np.zeros((max(cap, 1), 3)), np.zeros(max(cap, 1), np.int32)
+    B = OrcBrdf()
+    B.nOrders, B.doubleDirections, B.delta = int(orders), int(bool(double_directions)), float(delta)
+    for f, k in (("up", "fluxUp"), ("down", "fluxDown"), ("vol", "volumeAbsorption")):
+        setattr(B, f, _p(arr[k])), setattr(B, "n" + f[0].upper() + f[1:], _p(arr[k + "Count"])), setattr(B, "k" + f[0].upper() + f[1:], _p(arr[k + "Slack"]))
+    if orders > 0:
+        for f, k in (("upOrd", "fluxUpByOrd"), ("downOrd", "fluxDownByOrd")):
+            setattr(B, f, _p(arr[k])), setattr(B, "n" + f[0].upper() + f[1:], _p(arr[k + "Count"])), setattr(B, "k" + f[0].upper() + f[1:], _p(arr[k + "Slack"]))
+    B.nearFace, B.closure, B.closureBound = _p(near), _p(closure), _p(bound)
+    if arrivals:
+        B.arrivalCap, B.arrivalDir, B.arrivalPhoton = cap, _p(adir), _p(aph)
+    cnt = OrcCounters()
+    fates = np.zeros(n, FATE_DTYPE) if want_fates else None
+    I = np.zeros((intensity.nDir, ncol), np.float32) if intensity is not None else None
+    src = source.c if hasattr(source, "c") else source
+    done = lib().orc_compute_rt_brdf(C.addressof(problem.c), C.addressof(src), C.addressof(rng), n, _p(up), _p(dn), _p(ab), _p(vol),
+                                     C.addressof(cnt), _p(fates) if want_fates else None,
+                                     C.addressof(intensity.c) if intensity is not None else None, _p(I) if I is not None else None,
+                                     C.addressof(B))
+    res = {"n": int(done), "float": {"fluxUp": up, "fluxDown": dn, "fluxAbsorbed": ab, "volumeAbsorption": vol},
+           "counters": cnt.as_dict(), "nearFace": near[:n].astype(bool), "closure": closure[:n], "closureBound": bound[:n]}
+    res.update({k: int(getattr(B, k)) for k in ("reflections", "aboveOne", "endedByZero", "glintTaken", "lambertTaken", "ties")})
+    if orders <= 0:
+        for k in list(arr):
+            if "ByOrd" in k:
+                del arr[k]
+    res.update(arr)
+    for suffix in ("", "Count", "Slack"):
+        res["fluxAbsorbed" + suffix] = arr["volumeAbsorption" + suffix].sum(axis=0)
+    if want_fates:
+        res["fates"] = fates
+    if intensity is not None:
+        res["intensity"] = I
+    if arrivals:
+        m = int(B.nArrivals)
+        assert m <= cap
+        res.update(arrivalDir=adir[:m].copy(), arrivalPhoton=aph[:m].copy())
     return res
 
 

@@ -121,9 +121,13 @@ def oracle_problem(case, nsteps=10001, use_russian_roulette=True, lw_flag=-1.0):
                                     for a, v in comp["tabulated"]]))
         else:
             tables.append(np.stack([O.inverse_table_legendre(c, nsteps) for c in comp["legendre"]]))
-    # case["surface"] = (reflectance[numX-1, numY-1], xPosition, yPosition): specifyParameters(surfaceBDRF=)
+    # case["surface"] = (reflectance[numX-1, numY-1], xPosition, yPosition): specifyParameters(surfaceBDRF=);
+    # case["surface_brdf"] = (model, params[nParams, numX-1, numY-1], xPosition, yPosition), case["glint_sampling"] (default on)
+    surface = case.get("surface")
+    if case.get("surface_brdf") is not None:
+        surface = tuple(case["surface_brdf"]) + (bool(case.get("glint_sampling", True)),)
     return O.Problem(case["xe"], case["ye"], case["ze"], tot, cum, ssa, pfi, case["albedo"], tables,
-                     use_russian_roulette=use_russian_roulette, lw_flag=lw_flag, surface=case.get("surface"))
+                     use_russian_roulette=use_russian_roulette, lw_flag=lw_flag, surface=surface)
 
 
 def oracle_intensity(case, mus, phis_deg, n_angles=9001, hybrid_width=None, **kw):
@@ -163,6 +167,9 @@ def product_domain(case):
 def product_surface(case):
     """The case's surface description for the PRODUCT (None: the domain's albedo)."""
     import mcbrat3d_amd as M
+    if case.get("surface_brdf") is not None:
+        model, params, x, y = case["surface_brdf"]
+        return M.new_SurfaceDescription(np.asarray(params, np.float32), x, y, model=model)
     if case.get("surface") is None:
         return None
     refl, x, y = case["surface"]

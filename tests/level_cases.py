@@ -83,6 +83,14 @@ def clean_runs(near):
 # ---------------------------------------------------------------------------------------------------------------------
 # bracket of the product's results from the oracle's sums (the exact tier's tolerance)
 # ---------------------------------------------------------------------------------------------------------------------
+def tally_ends(s, c, k=0.0):
+    """The two ends of what a bin's integer tally times 2^-32 may be, from the oracle's double sum s, its deposit count c and a
+    slack sum k (0: none): s -+ (k + c 2^-33 + c 2^-53 s), the lower end not below 0.  product_bracket derives the terms."""
+    c = np.asarray(c, np.float64)
+    slack = c * 2.0 ** -53 * s
+    return np.maximum(s - c * 2.0 ** -33 - slack - k, 0.0), s + c * 2.0 ** -33 + slack + k
+
+
 def product_bracket(res, xe, ye, n):
     """[lo, hi] for every number reportLevelFluxes() may return for the photons whose oracle sums are `res`
     (oracle.compute_rt_levels): dict name -> (lo, hi), float32, levels [nz + 1, ny, nx] and means [nz + 1].
@@ -99,11 +107,10 @@ def product_bracket(res, xe, ye, n):
     nppc = g.photons_per_column(n)
     out = {}
     for name, key in (("levelFluxUp", "levelUp"), ("levelFluxDown", "levelDown")):
-        s, c = res[key], res[key + "Count"].astype(np.float64)
+        s = res[key]
         nl = s.shape[0]
-        slack = c * 2.0 ** -53 * s
         ends = []
-        for raw in (np.maximum(s - c * 2.0 ** -33 - slack, 0.0), s + c * 2.0 ** -33 + slack):
+        for raw in tally_ends(s, res[key + "Count"]):
             ends.append(raw.reshape(nl, -1).astype(np.float32) / nppc[None, :])
         out[name] = tuple(e.reshape(s.shape) for e in ends)
         out["mean" + name[0].upper() + name[1:]] = tuple(EM.tree_mean(e) for e in ends)

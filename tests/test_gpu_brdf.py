@@ -1,4 +1,5 @@
-"""Surface BRDFs (RPV, Ross-Li) on the GPU.  The oracle has no BRDF, so the evidence is
+"""Surface BRDFs (RPV, Ross-Li) on the GPU.  The photon-by-photon comparison with the oracle's own statement
+of the models is tests/test_gpu_brdf_oracle.py; the evidence here is
 
 1. the Lambertian limits (RPV with k = 1, Theta = 0, rhoC = 1; Ross-Li with fVol = fGeo = 0) follow the photon histories of a
    Lambertian surface description: identical flux and absorption moments, radiance to 1e-6 (the product w_in R / pi rounds
