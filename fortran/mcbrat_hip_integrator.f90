@@ -33,7 +33,8 @@ module mcbrat_hip_integrator
             specifyScatteringOrders, reportResultsByScatOrd, specifyLevelFluxes, reportLevelFluxes, &
             specifyDirectLevelFluxes, reportDirectLevelFluxes, specifyActinicFlux, reportActinicFlux, &
             specifySideFluxes, reportSideFluxes, &
-            camera, renderCamera, sunTransmittance
+            camera, renderCamera, sunTransmittance, &
+            sensor, renderSensors
 
   ! mcbrat_camera of include/mcbrat.h, member for member (the backward camera, DESIGN.md section 4.19): kind 0 orthographic --
   ! mu, phiDeg, the footprint xLo .. yHi and the height z -- or 1 pinhole -- position, look, up, fovXDeg
@@ -45,6 +46,15 @@ module mcbrat_hip_integrator
                           up(3) = (/ 0._c_double, 1._c_double, 0._c_double /)
     real(c_float)      :: fovXDeg = 60.
   end type camera
+
+  ! mcbrat_sensor of include/mcbrat.h, member for member (the backward sensors, DESIGN.md section 4.20): kind 0 planar -- a cosine
+  ! response on the side `normal` points to -- or 1 spherical; id keys the sensor's random numbers (an unsigned 32-bit word);
+  ! the receiver is position + u e1 + v e2 (both zero: a point)
+  type, bind(C) :: sensor
+    integer(c_int32_t) :: kind = 0, id = 0
+    real(c_double)     :: position(3) = 0., e1(3) = 0., e2(3) = 0., &
+                          normal(3) = (/ 0._c_double, 0._c_double, 1._c_double /)
+  end type sensor
 
   ! MCBRAT_ABI_VERSION of include/mcbrat.h this module was written against: mcbrat_counters has 15 fields (badPhotons) since 2
   integer(c_int), parameter :: expectedAbiVersion = 3
@@ -266,6 +276,19 @@ module mcbrat_hip_integrator
       integer(c_int64_t), value :: seed, firstSample, samplesPerPixel
       integer(c_int32_t), value :: numBatches
       type(c_ptr), value :: radiance, radianceStdErr, batchMeans   ! (c_null_ptr: not wanted; radiance is needed)
+      integer(c_int64_t), intent(out) :: dropped
+      integer(c_int) :: rc
+    end function
+    function mcbrat_render_sensors(ctx, n, sensors, seed, firstSample, samplesPerSensor, numBatches, gridInLds, diffuse, direct, &
+                                   diffuseStdErr, directStdErr, totalStdErr, batchMeans, dropped) &
+                                   bind(C, name="mcbrat_render_sensors") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_float, sensor
+      type(c_ptr), value :: ctx
+      integer(c_int64_t), value :: n, seed, firstSample, samplesPerSensor
+      type(sensor), intent(in) :: sensors(*)
+      integer(c_int32_t), value :: numBatches, gridInLds
+      real(c_float), intent(out) :: diffuse(*), direct(*)
+      type(c_ptr), value :: diffuseStdErr, directStdErr, totalStdErr, batchMeans   ! (c_null_ptr: not wanted)
       integer(c_int64_t), intent(out) :: dropped
       integer(c_int) :: rc
     end function
@@ -907,6 +930,36 @@ contains
                                 pErr, c_null_ptr, dropped)
     if (present(numDropped)) numDropped = dropped
   end subroutine renderCamera
+
+  ! Backward sensors (include/mcbrat.h: mcbrat_render_sensors): numBatches batches of samplesPerSensor paths per sensor for the
+  ! domain and the Directional solar source the integrator holds (the forward tables must have been set: setForwardTable).
+  ! diffuse + direct is the irradiance of a planar sensor, the actinic flux of a spherical one; totalStdErr the standard error
+  ! of that sum; numDropped the paths a loop bound ended.
+  subroutine renderSensors(this, sensors, seed, firstSample, samplesPerSensor, numBatches, diffuse, direct, totalStdErr, &
+                           numDropped, ierr)
+    type(integrator), intent(inout) :: this
+    type(sensor), dimension(:), contiguous, intent(in) :: sensors
+    integer(c_int64_t), intent(in) :: seed, firstSample, samplesPerSensor
+    integer, intent(in) :: numBatches
+    real, dimension(:), contiguous, intent(out) :: diffuse, direct
+    real, dimension(:), contiguous, optional, target, intent(out) :: totalStdErr
+    integer(c_int64_t), optional, intent(out) :: numDropped
+    integer, intent(out) :: ierr
+    type(c_ptr) :: pErr
+    integer(c_int64_t) :: dropped
+    ierr = 1
+    if (size(diffuse) /= size(sensors) .or. size(direct) /= size(sensors)) return
+    pErr = c_null_ptr
+    if (present(totalStdErr)) then
+      if (size(totalStdErr) /= size(sensors)) return
+      pErr = c_loc(totalStdErr)
+    end if
+    dropped = 0
+    ierr = mcbrat_render_sensors(this%ctx, int(size(sensors), c_int64_t), sensors, seed, firstSample, samplesPerSensor, &
+                                 int(numBatches, c_int32_t), -1_c_int32_t, diffuse, direct, c_null_ptr, c_null_ptr, pErr, &
+                                 c_null_ptr, dropped)
+    if (present(numDropped)) numDropped = dropped
+  end subroutine renderSensors
 
   ! exp(-optical depth) from each point xyz(3, n) toward the sun up to the top of the domain (mcbrat_sun_transmittance)
   subroutine sunTransmittance(this, xyz, transmittance, ierr)

@@ -475,6 +475,46 @@ int mcbrat_camera_ray(const mcbrat_camera *cam, int32_t i, int32_t j, double u, 
  * library's choice, 0, 1) chooses where it reads the grid; the results are the same bit for bit. */
 int mcbrat_sun_transmittance(mcbrat_ctx *ctx, int64_t n, const double *xyz /* [n][3] */, float *transmittance /* [n] */);
 
+/* ---- backward sensors (an addition under ABI version 3) --------------------------------------------------
+ * Irradiance on a plane and actinic flux at a point, anywhere in the domain: the camera's backward paths, started on a receiver
+ * with a cosine-weighted (planar) or a uniform (spherical) direction.  Units: per unit solar flux through a horizontal plane at
+ * the top -- a horizontal planar sensor measures what levelFluxDown / levelFluxUp average over a column's face, a spherical one
+ * what actinicFlux averages over a cell (1 / mu0 in a vacuum over a black surface).  Needs what mcbrat_render_camera needs. */
+typedef struct mcbrat_sensor {
+  int32_t kind;        /* 0 planar (cosine response on the side the normal points to), 1 spherical (uniform response) */
+  uint32_t id;         /* stands where the camera's pixel stands in the Philox counter: the sensor's random numbers */
+  double position[3];  /* x and y are folded periodically; z0 <= z <= zMax for every corner of the receiver */
+  double e1[3], e2[3]; /* the receiver is position + u e1 + v e2, 0 <= u, v <= 1; both zero: a point */
+  double normal[3];    /* planar: the side that receives light; need not be normalised; perpendicular to e1 and e2.  Spherical: ignored */
+} mcbrat_sensor;
+
+/* numBatches batches of samplesPerSensor paths per sensor.  Sample k of batch b has the index firstSample + b * samplesPerSensor
+ * + k; its random numbers are Philox4x32-10(key = seed, counter = (event | block << 24, id, index)): event 0, block 0 is
+ * [u, v, a, c] of mcbrat_sensor_ray, events >= 1 are the camera's.  Every path adds its sum of local estimates S to the sensor's
+ * diffuse bin and T_sun(origin) c to its direct bin, c = max(0, n . s) / mu0 (planar; s the unit vector toward the sun) or
+ * 1 / mu0 (spherical); where c = 0 no sun ray is walked.  diffuse[n] = w0 mean(S) with w0 = pi (planar) or 4 pi (spherical),
+ * direct[n] = mean(T_sun c); the irradiance (the actinic flux) is their sum.  Tallies are 64-bit integers, so the result of an
+ * (id, geometry, seed, sample range) depends on nothing else -- not on scheduling, not on gridInLds, not on the other sensors
+ * of the call.  The three standard errors are those of the mean of the batch means (0 where numBatches == 1; the direct part
+ * of a point sensor: exactly 0), totalStdErr that of the per-batch sums diffuse + direct.  batchMeans[b][0][i] is batch b's
+ * diffuse mean of sensor i, batchMeans[b][1][i] its direct mean.  *dropped counts the paths a loop bound ended; they contribute
+ * to neither part.  The optional outputs may be NULL.  The context's settings, tallies, moments and walk mode stay as they were.
+ * Refused, before any launch: n < 1; a kind other than 0 or 1; a member that is not finite; a planar sensor with a zero normal
+ * or an edge that is not perpendicular to its normal (|e . n| > 1e-6 |e|); a corner of a receiver outside [z0, zMax];
+ * samplesPerSensor < 1 or numBatches < 1; 2 n numBatches bins beyond the 4 GiB tally budget; gridInLds outside -1, 0, 1, or 1
+ * where the grid does not fit; and what mcbrat_render_camera refuses about the context. */
+int mcbrat_render_sensors(mcbrat_ctx *ctx, int64_t n, const mcbrat_sensor *sensors, uint64_t seed, uint64_t firstSample,
+                          int64_t samplesPerSensor /* per batch */, int32_t numBatches,
+                          int32_t gridInLds /* -1 library's choice, 0, 1 */,
+                          float *diffuse /* [n] */, float *direct /* [n] */,
+                          float *diffuseStdErr /* [n], may be NULL */, float *directStdErr /* [n], may be NULL */,
+                          float *totalStdErr /* [n], may be NULL */,
+                          float *batchMeans /* [numBatches][2][n], may be NULL */, int64_t *dropped /* may be NULL */);
+/* The mapping the kernel uses, on the host (no context; csrc/mcbrat_sensor_ray.h): origin (not folded into the domain) and
+ * backward direction (unit vector) of the draws u, v, a, c in [0, 1].  Non-zero for a sensor that mcbrat_render_sensors
+ * refuses on its own members. */
+int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a, double c, double origin[3], double direction[3]);
+
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air
  * above and below a cloud field -- a photon crosses z faces only; its column is found again from its position when

@@ -43,6 +43,12 @@ class Camera(C.Structure):
                 ("position", C.c_double * 3), ("look", C.c_double * 3), ("up", C.c_double * 3), ("fovXDeg", C.c_float)]
 
 
+class Sensor(C.Structure):
+    """mcbrat_sensor of include/mcbrat.h (the backward sensors)."""
+    _fields_ = [("kind", C.c_int32), ("id", C.c_uint32), ("position", C.c_double * 3), ("e1", C.c_double * 3),
+                ("e2", C.c_double * 3), ("normal", C.c_double * 3)]
+
+
 # every symbol include/mcbrat.h declares: (restype, argtypes)
 _vp, _i32, _i64, _u64, _f, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 SYMBOLS = {
@@ -108,6 +114,8 @@ SYMBOLS = {
     "mcbrat_render_camera": (C.c_int, [_vp, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_camera_ray": (C.c_int, [_vp, _i32, _i32, _d, _d, _vp, _vp]),
     "mcbrat_sun_transmittance": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "mcbrat_render_sensors": (C.c_int, [_vp, _i64, _vp, _u64, _u64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcbrat_sensor_ray": (C.c_int, [_vp, _d, _d, _d, _d, _vp, _vp]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),
     "mcbrat_inverse_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_inverse_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
@@ -117,7 +125,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes, mcbrat_settings_refusal and the backward camera are additions under 3)
+ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes, mcbrat_settings_refusal, the backward camera and the backward sensors are additions under 3)
 
 
 def hip_runtimes():

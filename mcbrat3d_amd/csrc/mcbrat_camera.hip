@@ -17,6 +17,11 @@
 // Tally: a lane sums its path's estimates in a float, converts the sum to i64 fixed point (CamParams::scale) at the path's end
 // and adds it to the bin (batch, pixel): integer sums, so an image does not depend on scheduling.
 //
+// Backward sensors (mcbrat_render_sensors, mcbrat_sensor_ray): camera_kernel<.., SENSOR = true> is the same
+// path started on a receiver (mcbrat_sensor_ray.h) -- event 0, block 0 = [u, v, a, c]: the point of the receiver, and a
+// cosine-weighted (planar) or uniform (spherical) direction; the sensor's id stands where the pixel stands in the counter --,
+// with a second bin array for the direct beam at the path's origin.
+//
 // Component pick, roulette, scattering angle and new direction are written out here as they are in trace_kernel
 // (mcbrat_kernels.hip, HOT ROWS) and trace_block_kernel (mcbrat_blockwalk.hip, HOT ROWS): a change to one of those rules is made
 // in all three.  What mcbrat_photon.h shares (Philox, u01, lambert_direction, find_cell, surface_reflectance, ...) is called.
@@ -31,12 +36,16 @@
 
 #include "mcbrat_photon.h"
 #include "mcbrat_camera_ray.h"
+#include "mcbrat_sensor_ray.h"
 #include "mcbrat_camera_ctx.h"
 #include "mcbrat_devmem.h"
 
 namespace mcbrat {
 
 constexpr unsigned kCameraMaxEvents = 1u << 20;  // legs per path (the event has 24 bits of the counter)
+// The sensor instantiations carry a second pending sum and the direct estimate through the path: the register budget of six
+// waves per SIMD (80 VGPRs), the occupancy the camera instantiations have by their 79 registers, is asked for by name
+constexpr int kSensorWavesPerSimd = 6;
 
 struct CamParams {
   CameraGeometry g;
@@ -59,6 +68,9 @@ struct CamParams {
   const double *points;
   float *transmittance;
   long long nPoints;
+  // mcbrat_render_sensors (SENSOR instantiations; npix = the number of sensors, spp = samples per sensor and batch)
+  const SensorGeometry *sensors;   // [npix]
+  long long *binsDirect;           // [nBatches][npix] fixed point, in units of w0 like bins
 };
 
 struct GridView { const double *xe, *ye, *ze; const float *ext; };
@@ -170,8 +182,28 @@ __device__ __forceinline__ float camera_albedo(const DevParams &p, double x, dou
   return p.surfNumX > 0 ? surface_reflectance(p, x, y) : p.albedo;
 }
 
-template <int BLOCK, bool GRID_LDS>
-__global__ void __launch_bounds__(BLOCK, MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
+// Every lane of a wave calls this in step: adds the lanes' values to their bins -- one atomic for the wave where the lanes that
+// have something share a bin (sensor-major indices, samplesPerSensor >= 64), one per lane otherwise
+__device__ __forceinline__ void wave_add(long long *bins, uint32_t bin, long long value, int lane) {
+  const bool have = value != 0;
+  const unsigned long long haveMask = __ballot(have);
+  if (haveMask == 0ull) return;
+  const int first = __ffsll((long long)haveMask) - 1;
+  const uint32_t firstBin = __shfl(bin, first);
+  if (__ballot(have && bin != firstBin) == 0ull) {
+    long long v = value;
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(bins + firstBin), (unsigned long long)v);
+  } else if (have) {
+    atomicAdd(reinterpret_cast<unsigned long long *>(bins + bin), (unsigned long long)value);
+  }
+}
+
+// SENSOR: the path starts on a receiver (mcbrat_sensor_ray.h) instead of in a pixel, the sensor's id
+// stands where the pixel stands in the counter, and a second sum takes the direct beam at the origin; from there on the path is
+// the camera's.
+template <int BLOCK, bool GRID_LDS, bool SENSOR>
+__global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
   constexpr float kPi = 3.14159265358979312f;
@@ -180,23 +212,47 @@ __global__ void __launch_bounds__(BLOCK, MCBRAT_MIN_WAVES_PER_SIMD) camera_kerne
   const unsigned long long chunk = wave * (unsigned long long)kWave * cp.pathsPerLane;
   const int nvox = p.nx * p.ny * p.nz;
 
-  unsigned long long pendBin = ~0ull;  // the bin the lane is summing for, and its sum
+  unsigned long long pendBin = ~0ull;  // the bin the lane is summing for, and its sum (the camera; a sensor's wave adds after every path)
   long long pend = 0;
   unsigned nDropped = 0;
 
   for (unsigned long long j = 0; j < cp.pathsPerLane; ++j) {
     const unsigned long long index = chunk + j * kWave + (unsigned long long)lane;
-    if (index >= cp.total) break;
+    if constexpr (!SENSOR) {
+      if (index >= cp.total) break;
+    }
+    // SENSOR: every lane of the wave goes through every round, so that the wave can add its two sums together after each path;
+    // a lane past the last index walks nothing (its sensor, read below, is one of the call's: pixel < npix whatever the index)
+    const bool valid = SENSOR ? index < cp.total : true;
     const unsigned long long bin = index / cp.spp, k = index - bin * cp.spp;
     const unsigned long long batch = bin / cp.npix, pixel = bin - batch * cp.npix;
     const unsigned long long sample = cp.firstSample + batch * cp.spp + k;
-    const uint32_t sLo = (uint32_t)sample, sHi = (uint32_t)(sample >> 32), pix = (uint32_t)pixel;
-    if (bin != pendBin) {
-      if (pend != 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
-      pendBin = bin; pend = 0;
+    const uint32_t sLo = (uint32_t)sample, sHi = (uint32_t)(sample >> 32);
+    uint32_t pix = (uint32_t)pixel;
+    if constexpr (!SENSOR) {
+      if (bin != pendBin) {
+        if (pend != 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
+        pendBin = bin; pend = 0;
+      }
     }
     Ray r;
-    {
+    bool dropped = !valid;
+    const uint32_t bin32 = (uint32_t)bin;  // (SENSOR: 2 * bins fit the 4 GiB budget, so 32 bits hold a bin's index through the path)
+    if constexpr (SENSOR) {
+      const SensorGeometry &sg = cp.sensors[pixel];
+      pix = sg.id;
+      uint32_t q[4];
+      philox4x32_10(0u, pix, sLo, sHi, p.seedLo, p.seedHi, q);
+      double o[3], d[3];
+      // sensor_ray() in its two halves, one after the other: taken together their eighteen doubles of geometry are the
+      // kernel's widest point by registers
+      sensor_direction(sg, (double)u01(q[2]), (double)u01(q[3]), d);
+      r.dx = (float)d[0]; r.dy = (float)d[1]; r.dz = (float)d[2];
+      __builtin_amdgcn_sched_barrier(0);
+      sensor_origin(sg, (double)u01(q[0]), (double)u01(q[1]), o);
+      r.ox = o[0]; r.oy = o[1]; r.oz = o[2];
+      locate(p, g, r);
+    } else {
       double u = 0.5, v = 0.5, o[3], d[3];
       if (cp.jitter) {
         uint32_t q[4];
@@ -209,8 +265,10 @@ __global__ void __launch_bounds__(BLOCK, MCBRAT_MIN_WAVES_PER_SIMD) camera_kerne
       locate(p, g, r);
     }
     float w = 1.0f, sum = 0.0f;
-    bool dropped = false;
     for (uint32_t event = 1;; ++event) {
+      if constexpr (SENSOR) {
+        if (dropped) break;
+      }
       if (event > cp.maxEvents) { dropped = true; break; }
       uint32_t q[4];
       philox4x32_10(event, pix, sLo, sHi, p.seedLo, p.seedHi, q);
@@ -298,28 +356,60 @@ __global__ void __launch_bounds__(BLOCK, MCBRAT_MIN_WAVES_PER_SIMD) camera_kerne
         r.dz = r.dz * cs - copysignf(fabsf(B), r.dz * B);
       }
     }
-    if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
-      nDropped++;
+    if constexpr (SENSOR) {
+      // (a NaN from a table: counted like a path a bound ended, contributes to neither part)
+      // The direct beam on the receiver at the path's origin, found again from the path's first block: nothing of it is carried
+      // through the legs (registers).  A sun ray a bound ends drops the path.
+      float sumDirect = 0.0f;
+      {
+        const SensorGeometry &sg = cp.sensors[bin32 % (uint32_t)cp.npix];
+        const float direct = sg.direct;
+        if (!dropped && direct > 0.0f) {
+          uint32_t q[4];
+          philox4x32_10(0u, pix, sLo, sHi, p.seedLo, p.seedHi, q);
+          double o[3];
+          sensor_origin(sg, (double)u01(q[0]), (double)u01(q[1]), o);
+          Ray s;
+          s.ox = o[0]; s.oy = o[1]; s.oz = o[2];
+          locate(p, g, s);
+          const float T = sun_transmittance(p, cp, g, s.ox, s.oy, s.oz, s.ix, s.iy, s.iz, dropped);
+          sumDirect = T * direct;
+        }
+      }
+      const bool ok = !dropped && sum == sum;
+      if (valid && !ok) atomicAdd(cp.dropped, 1ull);  // (rare: counted at once, not carried in a register from path to path)
+      const long long vDiffuse = ok ? __double2ll_rn(fmin((double)sum * cp.scale, cp.pathMax)) : 0;
+      const long long vDirect = ok ? __double2ll_rn(fmin((double)sumDirect * cp.scale, cp.pathMax)) : 0;
+      wave_add(cp.bins, bin32, vDiffuse, lane);
+      wave_add(cp.binsDirect, bin32, vDirect, lane);
     } else {
-      pend += __double2ll_rn(fmin((double)sum * cp.scale, cp.pathMax));
+      if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
+        nDropped++;
+      } else {
+        pend += __double2ll_rn(fmin((double)sum * cp.scale, cp.pathMax));
+      }
     }
   }
 
-  // The lanes of a wave mostly hold sums for ONE bin (pixel-major indices, samplesPerPixel >= 64): then one add per wave.
-  const bool have = pend != 0;
-  const unsigned long long haveMask = __ballot(have);
-  if (haveMask != 0ull) {
-    const int first = __ffsll((long long)haveMask) - 1;
-    const unsigned long long firstBin = __shfl(pendBin, first);
-    if (__ballot(have && pendBin != firstBin) == 0ull) {
-      long long v = have ? pend : 0;
-      for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-      if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + firstBin), (unsigned long long)v);
-    } else if (have) {
-      atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
+  if constexpr (!SENSOR) {
+    // The lanes of a wave mostly hold sums for ONE bin (pixel-major indices, samplesPerPixel >= 64): then one add per wave.
+    const bool have = pend != 0;
+    const unsigned long long haveMask = __ballot(have);
+    if (haveMask != 0ull) {
+      const int first = __ffsll((long long)haveMask) - 1;
+      const unsigned long long firstBin = __shfl(pendBin, first);
+      if (__ballot(have && pendBin != firstBin) == 0ull) {
+        long long v = have ? pend : 0;
+        for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + firstBin), (unsigned long long)v);
+      } else if (have) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
+      }
     }
   }
-  if (nDropped != 0u) atomicAdd(cp.dropped, (unsigned long long)nDropped);
+  if constexpr (!SENSOR) {
+    if (nDropped != 0u) atomicAdd(cp.dropped, (unsigned long long)nDropped);
+  }
 }
 
 // mcbrat_sun_transmittance: the kernel's own T_sun on given points, one lane per point
@@ -521,10 +611,10 @@ int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed,
   if (blocks > 0x7fffffffull) return mcbrat_camera_fail(c, "renderCamera: more paths than one launch takes.");
   const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
   if (lds) {
-    if (allow_lds(c, camera_kernel<512, true>, bytes)) return 1;
-    hipLaunchKernelGGL((camera_kernel<512, true>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
+    if (allow_lds(c, camera_kernel<512, true, false>, bytes)) return 1;
+    hipLaunchKernelGGL((camera_kernel<512, true, false>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
   } else {
-    hipLaunchKernelGGL((camera_kernel<256, false>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
+    hipLaunchKernelGGL((camera_kernel<256, false, false>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
   }
   CAM_HIP(c, hipGetLastError());
   std::vector<long long> bins((size_t)nBins);
@@ -549,6 +639,166 @@ int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed,
     if (radianceStdErr) {
       const double var = numBatches > 1 ? std::max(0.0, s2 - (double)numBatches * dm * dm) / ((double)numBatches * (double)(numBatches - 1)) : 0.0;
       radianceStdErr[px] = (float)std::sqrt(var);
+    }
+  }
+  return 0;
+}
+
+int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a, double cc, double origin[3], double direction[3]) {
+  if (!sensor || !origin || !direction || sensor_refusal(*sensor)) return 1;
+  SensorGeometry g;
+  sensor_geometry(*sensor, g);
+  sensor_ray(g, u, v, a, cc, origin, direction);
+  return 0;
+}
+
+int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, uint64_t seed, uint64_t firstSample,
+                          int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds, float *diffuse, float *direct,
+                          float *diffuseStdErr, float *directStdErr, float *totalStdErr, float *batchMeans, int64_t *dropped) {
+  if (!c) return 1;
+  if (n < 1) return mcbrat_camera_fail(c, "renderSensors: at least one sensor is needed (n < 1).");
+  if (!sensors || !diffuse || !direct) return mcbrat_camera_fail(c, "renderSensors: no sensors or no arrays for the diffuse and the direct part.");
+  if (gridInLds < -1 || gridInLds > 1) return mcbrat_camera_fail(c, "renderSensors: gridInLds must be -1, 0 or 1.");
+  if (samplesPerSensor < 1) return mcbrat_camera_fail(c, "renderSensors: samplesPerSensor must be at least 1.");
+  if (numBatches < 1) return mcbrat_camera_fail(c, "renderSensors: numBatches must be at least 1.");
+  const unsigned long long ns = (unsigned long long)n;
+  const unsigned long long nBins = ns * (unsigned long long)numBatches;
+  if (ns > 0x7fffffffull || 2ull * nBins > kCameraBinBudget / sizeof(long long))
+    return mcbrat_camera_fail(c, "renderSensors: the bins of the sensors' batches (2 * n * numBatches) do not fit the tally budget of 4 GiB.");
+  if ((double)nBins * (double)samplesPerSensor >= 9.0e18 || (double)firstSample + (double)numBatches * (double)samplesPerSensor >= 1.8e19)
+    return mcbrat_camera_fail(c, "renderSensors: more paths than a 64-bit index counts.");
+  for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
+    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+  CameraContext v;
+  if (mcbrat_camera_context(c, &v, false)) return 1;
+  if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "renderSensors: problem not completely specified (grid and optical properties).");
+  if (!v.haveSource || !v.solarDirectional) return mcbrat_camera_fail(c, "renderSensors: the backward sensors need the Directional solar source.");
+  if (v.brdfSurface) return mcbrat_camera_fail(c, "renderSensors: a BRDF surface is not supported by the backward sensors (Lambertian surfaces only).");
+  for (int64_t i = 0; i < n; ++i) {
+    const mcbrat_sensor &s = sensors[i];
+    for (int k = 0; k < 4; ++k) {
+      const double z = s.position[2] + ((k & 1) ? s.e1[2] : 0.0) + ((k & 2) ? s.e2[2] : 0.0);
+      if (!(z >= v.p.z0 && z <= v.p.zMax)) return mcbrat_camera_fail(c, "renderSensors: a corner of a sensor's receiver lies outside the domain [z0, zMax].");
+    }
+  }
+  std::vector<float> fwdAll;
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  float fwdMax = 0.0f;
+  for (int k = 0; k < v.nc; ++k) {
+    if ((int)v.fwd->size() <= k || (*v.fwd)[k].empty())
+      return mcbrat_camera_fail(c, ("renderSensors: no forward phase function table for component " + std::to_string(k + 1)).c_str());
+    if ((*v.maxPfi)[k] >= (*v.fwdNEntries)[k])
+      return mcbrat_camera_fail(c, ("renderSensors: phaseFunctionIndex exceeds forward table entries for component " + std::to_string(k + 1)).c_str());
+    cp.fwdOffset[k] = (int)fwdAll.size(); cp.fwdNAngles[k] = (*v.fwdNAngles)[k];
+    fwdAll.insert(fwdAll.end(), (*v.fwd)[k].begin(), (*v.fwd)[k].end());
+    for (float x : (*v.fwd)[k]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
+  }
+  if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
+  const int lds = choose_grid_lds(v, gridInLds);
+  if (lds < 0) return mcbrat_camera_fail(c, "renderSensors: gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+
+  cp.spp = (unsigned long long)samplesPerSensor; cp.npix = ns; cp.firstSample = firstSample;
+  cp.total = nBins * cp.spp;
+  sun_setup(v.p, cp);
+  const double kPi = 3.14159265358979323846;
+  // the sun in double, as mcbrat_set_source_solar's float direction gives it; mu0 = its cosine
+  double sun[3], sn = 0.0;
+  for (int a = 0; a < 3; ++a) { sun[a] = -(double)v.p.dir0[a]; sn += sun[a] * sun[a]; }
+  sn = std::sqrt(sn);
+  for (int a = 0; a < 3; ++a) sun[a] /= sn;
+  const double mu0 = std::max(std::fabs(sun[2]), (double)FLT_MIN);
+  std::vector<SensorGeometry> geo((size_t)n);
+  std::vector<double> w0((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    sensor_geometry(sensors[i], geo[(size_t)i]);
+    double cDirect = 1.0 / mu0;
+    if (sensors[i].kind == 0) {
+      const double *nv = geo[(size_t)i].n;
+      cDirect = std::max(0.0, nv[0] * sun[0] + nv[1] * sun[1] + nv[2] * sun[2]) / mu0;
+    }
+    w0[(size_t)i] = sensors[i].kind == 0 ? kPi : 4.0 * kPi;
+    geo[(size_t)i].direct = (float)(cDirect / w0[(size_t)i]);  // (both parts are tallied in units of w0)
+  }
+  {
+    const double H = v.p.zMax - v.p.z0, travel = H * 65536.0;  // a leg's bound: as mcbrat_render_camera's
+    const double nc = (double)v.p.nz + (std::floor(travel / v.p.Lx) + 2.0) * v.p.nx + (std::floor(travel / v.p.Ly) + 2.0) * v.p.ny + 8.0;
+    cp.maxLegCross = (unsigned)std::min(nc, (double)(1u << 26));
+    cp.maxEvents = kCameraMaxEvents;
+  }
+  {
+    // the fixed-point scale, as mcbrat_render_camera chooses it; the direct estimate, c / w0, is at most 1 / (pi mu0)
+    const double largest = std::max(std::max((double)fwdMax * (double)cp.invFourPiMu0, 1.0 / kPi), 1.0 / (kPi * mu0));
+    int e = 0;
+    std::frexp(4.611686018427387904e18 / ((double)samplesPerSensor * largest * 64.0), &e);
+    e = std::max(0, std::min(e - 1, 40));
+    cp.scale = std::ldexp(1.0, e);
+    cp.pathMax = std::floor(4.611686018427387904e18 / (double)samplesPerSensor);
+  }
+  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
+
+  DeviceBuffer<long long> dBins;  // [2][numBatches][n]: diffuse, then direct
+  DeviceBuffer<float> dFwd;
+  DeviceBuffer<unsigned long long> dDropped;
+  DeviceBuffer<SensorGeometry> dGeo;
+  CAM_HIP(c, dBins.allocate((size_t)(2 * nBins)));
+  CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
+  CAM_HIP(c, dDropped.allocate(1));
+  CAM_HIP(c, dGeo.allocate((size_t)n));
+  CAM_HIP(c, hipMemsetAsync(dBins.get(), 0, sizeof(long long) * (size_t)(2 * nBins), v.stream));
+  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
+  CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
+  CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo.data(), sizeof(SensorGeometry) * (size_t)n, hipMemcpyHostToDevice, v.stream));
+  cp.bins = dBins.get(); cp.binsDirect = dBins.get() + nBins; cp.fwd = dFwd.get(); cp.dropped = dDropped.get(); cp.sensors = dGeo.get();
+
+  // the camera's launch shape: indices are sensor-major, so a wave's lanes share a bin wherever samplesPerSensor >= 64
+  const int block = lds ? 512 : 256;
+  const unsigned long long lanes = (unsigned long long)v.numCUs * 16ull * kWave;
+  cp.pathsPerLane = std::max<unsigned long long>(1, (cp.total + lanes - 1) / lanes);
+  const unsigned long long perBlock = cp.pathsPerLane * (unsigned long long)block;
+  const unsigned long long blocks = (cp.total + perBlock - 1) / perBlock;
+  if (blocks > 0x7fffffffull) return mcbrat_camera_fail(c, "renderSensors: more paths than one launch takes.");
+  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
+  if (lds) {
+    if (allow_lds(c, camera_kernel<512, true, true>, bytes)) return 1;
+    hipLaunchKernelGGL((camera_kernel<512, true, true>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
+  } else {
+    hipLaunchKernelGGL((camera_kernel<256, false, true>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
+  }
+  CAM_HIP(c, hipGetLastError());
+  std::vector<long long> bins((size_t)(2 * nBins));
+  unsigned long long nDropped = 0;
+  CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * (size_t)(2 * nBins), hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipStreamSynchronize(v.stream));
+  if (dropped) *dropped = (int64_t)nDropped;
+
+  // batch means; their means and standard errors from the differences to the first batch (identical batches: exactly 0), for
+  // the diffuse part, the direct part and the per-batch sum of the two
+  const double unit = 1.0 / (cp.scale * (double)samplesPerSensor);
+  const double nb = (double)numBatches;
+  for (unsigned long long i = 0; i < ns; ++i) {
+    const double u = unit * w0[(size_t)i];
+    const double f0 = (double)bins[i] * u, d0 = (double)bins[(size_t)nBins + i] * u;
+    double s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
+    for (int b = 0; b < numBatches; ++b) {
+      const double f = (double)bins[(size_t)b * ns + i] * u, d = (double)bins[(size_t)nBins + (size_t)b * ns + i] * u;
+      if (batchMeans) {
+        batchMeans[((size_t)b * 2 + 0) * ns + i] = (float)f;
+        batchMeans[((size_t)b * 2 + 1) * ns + i] = (float)d;
+      }
+      const double diff[3] = {f - f0, d - d0, (f - f0) + (d - d0)};
+      for (int k = 0; k < 3; ++k) { s1[k] += diff[k]; s2[k] += diff[k] * diff[k]; }
+    }
+    float *err[3] = {diffuseStdErr, directStdErr, totalStdErr};
+    for (int k = 0; k < 3; ++k) {
+      const double dm = s1[k] / nb;
+      if (k == 0) diffuse[i] = (float)(f0 + dm);
+      if (k == 1) direct[i] = (float)(d0 + dm);
+      if (err[k]) {
+        const double var = numBatches > 1 ? std::max(0.0, s2[k] - nb * dm * dm) / (nb * (nb - 1.0)) : 0.0;
+        err[k][i] = (float)std::sqrt(var);
+      }
     }
   }
   return 0;

@@ -29,6 +29,10 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     "camera": dict(camerakind="", camerapixels=[1, 1], cameraposition=[0.0, 0.0, 0.0], cameralook=[0.0, 0.0, -1.0],
                    cameraup=[0.0, 1.0, 0.0], camerafov=60.0, cameramu=1.0, cameraphi=0.0, camerafootprint=[], cameraheight=None,
                    camerasamplesperpixel=1000, camerabatches=10, outputcamerafile=""),
+    # backward sensors (no counterpart in the reference driver): absent -- sensorKind empty -- they change
+    # nothing.  sensorPositions = x, y, z of every sensor in turn; sensorTilt, sensorAzimuth in degrees, one for all or one per sensor
+    "sensors": dict(sensorkind="", sensorpositions=[], sensortilt=0.0, sensorazimuth=0.0, sensorsamples=10000, sensorbatches=10,
+                    outputsensorfile=""),
 }
 
 
@@ -138,6 +142,21 @@ def camera_from_namelist(cfg, xe, ye, ze):
         return new_Camera(kind, npx=npx, npy=npy, mu=float(cfg["cameramu"]), phi=float(cfg["cameraphi"]), footprint=fp, height=height)
     return new_Camera(kind, npx=npx, npy=npy, position=cfg["cameraposition"], look=cfg["cameralook"], up=cfg["cameraup"],
                       fov=float(cfg["camerafov"]))
+
+
+def sensors_from_namelist(cfg):
+    """The sensors of the /sensors/ group (None where sensorKind is empty)."""
+    from mcbrat3d_amd.sensors import new_Sensors
+    from mcbrat3d_amd._capi import McbratError
+    kind = str(cfg["sensorkind"]).strip().lower()
+    if not kind:
+        return None
+    pos = np.atleast_1d(np.asarray(cfg["sensorpositions"], np.float64)).reshape(-1)
+    if pos.size < 3 or pos.size % 3:
+        raise McbratError("sensorPositions: x, y, z of at least one sensor are needed (a multiple of three numbers).")
+    if int(cfg["sensorsamples"]) < 1 or int(cfg["sensorbatches"]) < 1:
+        raise McbratError("sensorSamples and sensorBatches must be at least 1.")
+    return new_Sensors(pos.reshape(-1, 3), tilt=cfg["sensortilt"], azimuth=cfg["sensorazimuth"], kind=kind)
 
 
 def builtin_domain(name):
@@ -269,6 +288,9 @@ def main(argv=None):
         if str(cfg["camerakind"]).strip():
             raise SystemExit("cameraKind: the backward camera is not available for spectrally integrated runs (numLambda > 1 or "
                              "thermal emission)")
+        if str(cfg["sensorkind"]).strip():
+            raise SystemExit("sensorKind: the backward sensors are not available for spectrally integrated runs (numLambda > 1 or "
+                             "thermal emission)")
         setup = time.time() - t0
         stats, flux = run_spectral(cfg, doms, rank, world, local, dist)
         if rank == 0:
@@ -318,6 +340,7 @@ def main(argv=None):
     if cfg["reportsidefluxes"]:  # (refused by specifyParameters without reportLevelFluxes, with the direct tally or the actinic flux)
         integ.specifyParameters(recSideFluxes=True)
     camera = camera_from_namelist(cfg, dom.xPosition, dom.yPosition, dom.zPosition)  # (a bad camera ends the run before it traces)
+    sensors = sensors_from_namelist(cfg)  # (bad sensors end the run before it traces)
     photons = M.new_PhotonStream(cfg["solarmu"], cfg["solarazimuth"], numberOfPhotons=cfg["numphotonsperbatch"] * cfg["numbatches"])
     moments = None
     if dist is not None:
@@ -336,6 +359,17 @@ def main(argv=None):
             camera.kind, camera.npx, camera.npy, cameraResult["radiance"].mean(), cameraResult["radiance_StdErr"].max(), cameraResult["dropped"]))
         if cfg["outputcamerafile"]:
             ncio.writeCamera_netcdf(cfg["outputcamerafile"], camera, cameraResult)
+    sensorResult = None
+    if sensors is not None and rank == 0:  # rank 0 renders the sensors after the forward run, with sample indices of their own stream
+        sensorResult = integ.renderSensors(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]), int(cfg["sensorbatches"]))
+        sensorResult["samplesPerSensor"] = int(cfg["sensorsamples"])
+        for i in range(len(sensors)):
+            print(" sensor %3d %-9s at %9.4f %9.4f %9.4f: %9.6f +-%9.6f  direct/diffuse: %9.6f  %9.6f" % (
+                i, sensors.kindNames()[i], *sensors.positions[i], sensorResult["irradiance"][i], sensorResult["irradiance_StdErr"][i],
+                sensorResult["direct"][i], sensorResult["diffuse"][i]))
+        print(" sensors: %d paths dropped" % sensorResult["dropped"])
+        if cfg["outputsensorfile"]:
+            ncio.writeSensors_netcdf(cfg["outputsensorfile"], sensors, sensorResult)
     if rank == 0:
         print(" mean flux up/down/absorbed: " + "  ".join("%9.6f +-%9.6f" % (stats[k], stats[k + "_StdErr"])
                                                             for k in ("meanFluxUp", "meanFluxDown", "meanFluxAbsorbed")))
@@ -381,7 +415,7 @@ def main(argv=None):
                                      useRussianRouletteForIntensity=cfg["userussianrouletteforintensity"], zetaMin=cfg["zetamin"],
                                      limitIntensityContributions=cfg["limitintensitycontributions"],
                                      maxIntensityContribution=cfg["maxintensitycontribution"],
-                                     camera=camera, cameraResult=cameraResult)
+                                     camera=camera, cameraResult=cameraResult, sensors=sensors, sensorResult=sensorResult)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

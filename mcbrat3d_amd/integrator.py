@@ -483,6 +483,27 @@ class Integrator:
         randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
         return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value)}
 
+    def renderSensors(self, sensors, randomNumbers, samplesPerSensor, numBatches=1, gridInLds=-1):
+        """Irradiance (planar sensors) and actinic flux (spherical ones) at `sensors` (mcbrat3d_amd.sensors.new_Sensors) by
+        backward Monte Carlo: numBatches batches of samplesPerSensor paths per sensor, for the domain
+        and the Directional solar source this integrator has loaded.  Returns arrays of one value per sensor, per unit solar
+        flux through a horizontal plane at the top: "irradiance" (= "diffuse" + "direct") with "irradiance_StdErr",
+        "diffuse_StdErr", "direct_StdErr" (standard errors of the mean of the batch means), "batchMeans" [numBatches, 2, n]
+        (diffuse, direct) and "dropped", the number of paths a loop bound ended.  Sample indices continue from
+        randomNumbers.nextPhotonId; tallies, moments and settings of the integrator are left alone."""
+        self._load_camera_tables()
+        n, nb = len(sensors), int(numBatches)
+        arr = sensors.structs()
+        dif, dirc, eDif, eDir, eTot = (np.zeros(n, np.float32) for _ in range(5))
+        means = np.zeros((max(nb, 1), 2, n), np.float32)
+        dropped = C.c_int64(0)
+        self._check(self._lib.mcbrat_render_sensors(self._ctx, n, C.addressof(arr), randomNumbers.seed, randomNumbers.nextPhotonId,
+                                                    int(samplesPerSensor), nb, int(gridInLds), ptr(dif), ptr(dirc), ptr(eDif),
+                                                    ptr(eDir), ptr(eTot), ptr(means), C.addressof(dropped)))
+        randomNumbers.nextPhotonId += int(samplesPerSensor) * nb
+        return {"irradiance": dif + dirc, "irradiance_StdErr": eTot, "diffuse": dif, "direct": dirc, "diffuse_StdErr": eDif,
+                "direct_StdErr": eDir, "batchMeans": means, "dropped": int(dropped.value)}
+
     def sunTransmittance(self, points):
         """exp(-optical depth) from each point (an [n, 3] array of x, y, z) toward the sun up to the top of the loaded
         domain: the direct transmittance at a point, without noise (mcbrat_sun_transmittance)."""

@@ -150,9 +150,11 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
                         reportAbsorptionProfile=False, reportVolumeAbsorption=False, cpuTimeTotal=0.0, cpuTimeSetup=0.0,
                         numProcs=1, intensityMus=None, intensityPhis=None, useHybridPhaseFunsForIntenCalcs=False,
                         hybridPhaseFunWidth=0.0, useRussianRouletteForIntensity=False, zetaMin=0.0,
-                        limitIntensityContributions=False, maxIntensityContribution=0.0, camera=None, cameraResult=None):
+                        limitIntensityContributions=False, maxIntensityContribution=0.0, camera=None, cameraResult=None, sensors=None,
+                        sensorResult=None):
     """monteCarloDriver.f95:1499-1807.  `stats` is driver.statistics(...) output ([ix, iy(, iz)] arrays).  camera, cameraResult:
-    a backward camera and what Integrator.renderCamera returned for it (cameraRadiance, cameraRadiance_StdErr)."""
+    a backward camera and what Integrator.renderCamera returned for it (cameraRadiance, cameraRadiance_StdErr).  sensors,
+    sensorResult: backward sensors and what Integrator.renderSensors returned for them (dimension `sensor`)."""
     xe, ye, ze = (np.asarray(a, np.float64) for a in (xPosition, yPosition, zPosition))
     f = netcdf_file(outputFileName, "w", version=2)  # nf90_64bit_offset (:1559)
     try:
@@ -242,9 +244,56 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
                     f.createVariable(name, "f", ("z",))[:] = np.asarray(stats[name])
         if camera is not None and cameraResult is not None:
             _add_camera(f, camera, cameraResult)
+        if sensors is not None and sensorResult is not None:
+            _add_sensors(f, sensors, sensorResult)
     finally:
         f.close()
     return outputFileName
+
+
+SENSOR_VARIABLES = ("sensorIrradiance", "sensorIrradiance_StdErr", "sensorDiffuse", "sensorDirect")
+
+
+def _add_sensors(f, sensors, result):
+    """The backward sensors, dimension `sensor`: where they are (sensorPosition, sensorNormal (sensor,
+    xyz), sensorKind: 0 planar, 1 spherical) and what they measure (sensorIrradiance = sensorDiffuse + sensorDirect with its
+    standard error; the actinic flux for a spherical sensor)."""
+    n = len(sensors)
+    f.sensorSamples = np.float64(result.get("samplesPerSensor", 0))
+    f.sensorBatches = np.int32(np.asarray(result["batchMeans"]).shape[0])
+    f.sensorDroppedPaths = np.float64(result["dropped"])
+    f.createDimension("sensor", n)
+    f.createDimension("xyz", 3)
+    f.createVariable("sensorPosition", "d", ("sensor", "xyz"))[:] = np.asarray(sensors.positions, np.float64)
+    f.createVariable("sensorNormal", "d", ("sensor", "xyz"))[:] = np.asarray(sensors.normals, np.float64)
+    f.createVariable("sensorKind", "i", ("sensor",))[:] = np.asarray(sensors.kinds, np.int32)
+    for name, key in zip(SENSOR_VARIABLES, ("irradiance", "irradiance_StdErr", "diffuse", "direct")):
+        f.createVariable(name, "f", ("sensor",))[:] = np.asarray(result[key], np.float32)
+
+
+def writeSensors_netcdf(outputFileName, sensors, result):
+    """A file of the sensors alone (the driver's outputSensorFile)."""
+    f = netcdf_file(outputFileName, "w", version=2)
+    try:
+        f.description = "Backward Monte Carlo sensors"
+        _add_sensors(f, sensors, result)
+    finally:
+        f.close()
+    return outputFileName
+
+
+def readSensors_netcdf(fileName):
+    """The sensor variables of a file writeResults_netcdf or writeSensors_netcdf wrote, as a dict of arrays (None where the file
+    holds no sensors)."""
+    f = netcdf_file(fileName, "r", mmap=False)
+    try:
+        if "sensor" not in f.dimensions:
+            return None
+        out = {k: np.array(f.variables[k][:]) for k in ("sensorPosition", "sensorNormal", "sensorKind") + SENSOR_VARIABLES}
+        out.update(sensorSamples=float(f.sensorSamples), sensorBatches=int(f.sensorBatches), sensorDroppedPaths=float(f.sensorDroppedPaths))
+        return out
+    finally:
+        f.close()
 
 
 def _add_camera(f, camera, result):
