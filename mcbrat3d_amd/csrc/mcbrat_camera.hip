@@ -2,6 +2,11 @@
 // mcbrat_camera_ray, mcbrat_sun_transmittance).  A translation unit of its own: camera_kernel and its host code; the tracing
 // kernels, their variant table and their parameter block are not touched.
 //
+// The host half: mcbrat_render_camera and mcbrat_render_sensors are front ends -- arguments, geometry,
+// output arrays -- over one path in three stages, check_counts(), backward_context() and backward_render(), worded by the entry's
+// Entry; its arithmetic (bounds, scale, capacity, launch shape, batch statistics) is mcbrat_backward.h's, plain C++ that runs
+// without a GPU.  launch() is the one LDS-or-global launch, mcbrat_sun_transmittance's too.
+//
 // One lane per path.  A path starts at the sensor (mcbrat_camera_ray.h) and walks BACKWARD.  Leg: tau = -ln u, cell face by cell
 // face through the periodic grid until tau is used up, the top (the path ends: nothing diffuse comes in from above) or the
 // surface.  Collision: component pick, w *= omega0, local estimate w P(Theta) T_sun(r) / (4 pi mu0) toward the sun, roulette,
@@ -38,6 +43,7 @@
 #include "mcbrat_camera_ray.h"
 #include "mcbrat_sensor_ray.h"
 #include "mcbrat_camera_ctx.h"
+#include "mcbrat_backward.h"
 #include "mcbrat_devmem.h"
 
 namespace mcbrat {
@@ -435,7 +441,6 @@ using namespace mcbrat;
 
 namespace {
 
-constexpr size_t kCameraBinBudget = (size_t)4 << 30;  // bytes of bins at most, as the tracing kernels' batch slabs
 constexpr size_t kCameraGridLds = 80 * 1024 - 1024;   // half of a compute unit's 160 KB, less the static part: two workgroups of 512 lanes
 
 #define CAM_HIP(c, call)                                                                                          \
@@ -447,16 +452,13 @@ constexpr size_t kCameraGridLds = 80 * 1024 - 1024;   // half of a compute unit'
 size_t grid_lds_bytes(const DevParams &p) {
   return sizeof(double) * (size_t)(p.nx + p.ny + p.nz + 3) + sizeof(float) * (size_t)p.nx * p.ny * p.nz;
 }
+bool inside(const DevParams &p, double z) { return z >= p.z0 && z <= p.zMax; }
 
-// the sun: unit vector toward it, and the bound on the crossings of a ray toward it, from the geometry: nz layers, and nx (ny)
-// faces per domain length travelled along x (y), one length more for the part periods at both ends
+// the sun: unit vector toward it, the bound on the crossings of a ray toward it, 1 / (4 pi mu0)
 void sun_setup(const DevParams &p, CamParams &cp) {
   for (int a = 0; a < 3; ++a) cp.sun[a] = -p.dir0[a];
-  const double H = p.zMax - p.z0, muz = std::max((double)std::fabs(cp.sun[2]), (double)FLT_MIN);
-  const double wrapsX = std::floor(H * std::fabs((double)cp.sun[0]) / muz / p.Lx) + 2.0, wrapsY = std::floor(H * std::fabs((double)cp.sun[1]) / muz / p.Ly) + 2.0;
-  const double n = (double)p.nz + wrapsX * p.nx + wrapsY * p.ny + 8.0;
-  cp.maxSunCross = (unsigned)std::min(n, 4294967295.0);
-  cp.invFourPiMu0 = (float)(1.0 / (4.0 * 3.14159265358979323846 * muz));
+  const SunBound b = sun_bound(p.nx, p.ny, p.nz, p.zMax - p.z0, p.Lx, p.Ly, cp.sun);
+  cp.maxSunCross = b.maxCross; cp.invFourPiMu0 = b.invFourPiMu0;
 }
 
 // 0: global memory, 1: LDS; -1 refused (asked for, does not fit)
@@ -466,9 +468,105 @@ int choose_grid_lds(const CameraContext &v, int asked) {
   return asked == 0 ? 0 : (fits ? 1 : 0);
 }
 
-template <typename K>
-int allow_lds(mcbrat_ctx *c, K kernel, size_t lds) {
-  if (lds > 48 * 1024) CAM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// One launch of a kernel that has an instantiation for the grid in LDS and one for the grid in global memory
+using BackwardKernel = void (*)(const DevParams, const CamParams);
+int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp) {
+  const BackwardKernel kernel = lds ? inLds : inGlobal;
+  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
+  if (bytes > 48 * 1024) CAM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), bytes, v.stream, v.p, cp);
+  CAM_HIP(c, hipGetLastError());
+  return 0;
+}
+
+// What is an entry's own in the shared path of a backward render: how it words the refusals, its bin arrays, its instantiations
+struct Entry {
+  const char *name;                // the prefix of every message
+  const char *samples;             // its argument for the samples per bin
+  const char *bins;                // its bins, as the budget's refusal names them
+  const char *subject, *needs;     // "the backward camera", "the backward camera needs"
+  unsigned long long arrays;       // bin arrays: 1, or 2 (diffuse, then direct)
+  BackwardKernel inLds, inGlobal;  // workgroups of 512 and of 256 lanes
+};
+struct Counts { unsigned long long n; int64_t samples; int32_t numBatches; uint64_t firstSample; };  // n: pixels or sensors
+
+int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat_camera_fail(c, (std::string(e.name) + ": " + text).c_str()); }
+
+// Stage 1, before anything of the call's arrays or of the context is read: samples, batches, budget, index count
+int check_counts(mcbrat_ctx *c, const Entry &e, const Counts &k) {
+  if (k.samples < 1) return fail(c, e, std::string(e.samples) + " must be at least 1.");
+  if (k.numBatches < 1) return fail(c, e, "numBatches must be at least 1.");
+  if (!bins_fit(k.n, (unsigned long long)k.numBatches, (int)e.arrays)) return fail(c, e, std::string("the bins of ") + e.bins + " do not fit the tally budget of 4 GiB.");
+  if (!paths_fit(k.n * (unsigned long long)k.numBatches, k.samples, k.firstSample, k.numBatches)) return fail(c, e, "more paths than a 64-bit index counts.");
+  return 0;
+}
+
+// Stage 2: the view of the context, and what a backward render needs of it
+int backward_context(mcbrat_ctx *c, const Entry &e, CameraContext &v) {
+  if (mcbrat_camera_context(c, &v, false)) return 1;
+  if (!v.haveGrid || !v.haveOptics) return fail(c, e, "problem not completely specified (grid and optical properties).");
+  if (!v.haveSource || !v.solarDirectional) return fail(c, e, std::string(e.needs) + " the Directional solar source.");
+  if (v.brdfSurface) return fail(c, e, std::string("a BRDF surface is not supported by ") + e.subject + " (Lambertian surfaces only).");
+  return 0;
+}
+
+// Stage 3, after the entry's own checks against the domain: the forward and the inverse tables, the LDS share, then the launch.
+// cp: zeroed but for the entry's own members; geo: the sensors, or NULL; largestOwn: the largest estimate the entry adds to the
+// paths' (0: none).  -> bins [arrays][numBatches][n] in units of 1 / cp.scale, *dropped
+int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInLds, const Counts &k, uint64_t seed, CamParams &cp,
+                    const std::vector<SensorGeometry> *geo, double largestOwn, std::vector<long long> &bins, int64_t *dropped) {
+  std::vector<float> fwdAll;  // the forward tables, components concatenated, and the largest value they hold
+  float fwdMax = 0.0f;
+  for (int i = 0; i < v.nc; ++i) {
+    if ((int)v.fwd->size() <= i || (*v.fwd)[i].empty()) return fail(c, e, "no forward phase function table for component " + std::to_string(i + 1));
+    if ((*v.maxPfi)[i] >= (*v.fwdNEntries)[i]) return fail(c, e, "phaseFunctionIndex exceeds forward table entries for component " + std::to_string(i + 1));
+    cp.fwdOffset[i] = (int)fwdAll.size(); cp.fwdNAngles[i] = (*v.fwdNAngles)[i];
+    fwdAll.insert(fwdAll.end(), (*v.fwd)[i].begin(), (*v.fwd)[i].end());
+    for (float x : (*v.fwd)[i]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
+  }
+  if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
+  const int lds = choose_grid_lds(v, gridInLds);
+  if (lds < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+
+  const unsigned long long nBins = k.n * (unsigned long long)k.numBatches;
+  cp.spp = (unsigned long long)k.samples; cp.npix = k.n; cp.firstSample = k.firstSample;
+  cp.total = nBins * cp.spp;
+  sun_setup(v.p, cp);
+  cp.maxLegCross = leg_bound(v.p.nx, v.p.ny, v.p.nz, v.p.zMax - v.p.z0, v.p.Lx, v.p.Ly); cp.maxEvents = kCameraMaxEvents;
+  const FixedPoint fixed = fixed_point(k.samples, {(double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846, largestOwn});
+  cp.scale = fixed.scale; cp.pathMax = fixed.pathMax;
+  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
+
+  DeviceBuffer<long long> dBins;
+  DeviceBuffer<float> dFwd;
+  DeviceBuffer<unsigned long long> dDropped;
+  DeviceBuffer<SensorGeometry> dGeo;
+  const size_t allBins = (size_t)(e.arrays * nBins);
+  CAM_HIP(c, dBins.allocate(allBins));
+  CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
+  CAM_HIP(c, dDropped.allocate(1));
+  CAM_HIP(c, hipMemsetAsync(dBins.get(), 0, sizeof(long long) * allBins, v.stream));
+  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
+  CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
+  cp.bins = dBins.get(); cp.binsDirect = e.arrays == 2 ? dBins.get() + nBins : nullptr; cp.fwd = dFwd.get(); cp.dropped = dDropped.get();
+  if (geo) {
+    CAM_HIP(c, dGeo.allocate(geo->size()));
+    CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo->data(), sizeof(SensorGeometry) * geo->size(), hipMemcpyHostToDevice, v.stream));
+    cp.sensors = dGeo.get();
+  }
+
+  // indices are bin-major, so a wave's lanes share a bin wherever the samples per bin are 64 or more
+  const int block = lds ? 512 : 256;
+  const LaunchShape shape = launch_shape(cp.total, v.numCUs, block);
+  cp.pathsPerLane = shape.pathsPerLane;
+  if (shape.blocks > 0x7fffffffull) return fail(c, e, "more paths than one launch takes.");
+  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp)) return 1;
+  bins.resize(allBins);
+  unsigned long long nDropped = 0;
+  CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * allBins, hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
+  CAM_HIP(c, hipStreamSynchronize(v.stream));
+  if (dropped) *dropped = (int64_t)nDropped;
   return 0;
 }
 
@@ -491,11 +589,9 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
   if (mcbrat_camera_context(c, &v, false)) return 1;
   if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "sunTransmittance: problem not completely specified (grid and optical properties).");
   if (!v.solarDirectional) return mcbrat_camera_fail(c, "sunTransmittance: needs the Directional solar source.");
-  for (int64_t i = 0; i < n; ++i) {
-    const double z = xyz[3 * i + 2];
-    if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !(z >= v.p.z0 && z <= v.p.zMax))
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !inside(v.p, xyz[3 * i + 2]))
       return mcbrat_camera_fail(c, "sunTransmittance: a point is not finite or lies outside [z0, zMax].");
-  }
   if (n == 0) return 0;
   const int lds = choose_grid_lds(v, v.gridInLds);
   if (lds < 0) return mcbrat_camera_fail(c, "sunTransmittance: the grid does not fit the LDS share (option cameraGridInLds = 1).");
@@ -513,14 +609,7 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
   cp.points = dPoints.get(); cp.transmittance = dT.get(); cp.nPoints = n; cp.dropped = dDropped.get();
   constexpr int kBlock = 256;
   const unsigned grid = (unsigned)std::min<long long>((n + kBlock - 1) / kBlock, (long long)v.numCUs * 8);
-  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
-  if (lds) {
-    if (allow_lds(c, sun_transmittance_kernel<kBlock, true>, bytes)) return 1;
-    hipLaunchKernelGGL((sun_transmittance_kernel<kBlock, true>), dim3(grid), dim3(kBlock), bytes, v.stream, v.p, cp);
-  } else {
-    hipLaunchKernelGGL((sun_transmittance_kernel<kBlock, false>), dim3(grid), dim3(kBlock), 0, v.stream, v.p, cp);
-  }
-  CAM_HIP(c, hipGetLastError());
+  if (launch(c, v, lds, sun_transmittance_kernel<kBlock, true>, sun_transmittance_kernel<kBlock, false>, grid, kBlock, cp)) return 1;
   unsigned long long dropped = 0;
   CAM_HIP(c, hipMemcpyAsync(transmittance, dT.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v.stream));
   CAM_HIP(c, hipMemcpyAsync(&dropped, dDropped.get(), sizeof(dropped), hipMemcpyDeviceToHost, v.stream));
@@ -531,115 +620,33 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
 
 int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed, uint64_t firstSample, int64_t samplesPerPixel,
                          int32_t numBatches, float *radiance, float *radianceStdErr, float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderCamera", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the backward camera", "the backward camera needs", 1,
+                   camera_kernel<512, true, false>, camera_kernel<256, false, false>};
   if (!c) return 1;
-  if (!cam || !radiance) return mcbrat_camera_fail(c, "renderCamera: no camera or no array for the radiance.");
+  if (!cam || !radiance) return fail(c, e, "no camera or no array for the radiance.");
   if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
-  if (samplesPerPixel < 1) return mcbrat_camera_fail(c, "renderCamera: samplesPerPixel must be at least 1.");
-  if (numBatches < 1) return mcbrat_camera_fail(c, "renderCamera: numBatches must be at least 1.");
   const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy;
-  const unsigned long long nBins = npix * (unsigned long long)numBatches;
-  if (npix > 0x7fffffffull || nBins > kCameraBinBudget / sizeof(long long))
-    return mcbrat_camera_fail(c, "renderCamera: the bins of the image's batches (npx * npy * numBatches) do not fit the tally budget of 4 GiB.");
-  if ((double)nBins * (double)samplesPerPixel >= 9.0e18 || (double)firstSample + (double)numBatches * (double)samplesPerPixel >= 1.8e19)
-    return mcbrat_camera_fail(c, "renderCamera: more paths than a 64-bit index counts.");
+  const Counts k = {npix, samplesPerPixel, numBatches, firstSample};
   CameraContext v;
-  if (mcbrat_camera_context(c, &v, false)) return 1;
-  if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "renderCamera: problem not completely specified (grid and optical properties).");
-  if (!v.haveSource || !v.solarDirectional) return mcbrat_camera_fail(c, "renderCamera: the backward camera needs the Directional solar source.");
-  if (v.brdfSurface) return mcbrat_camera_fail(c, "renderCamera: a BRDF surface is not supported by the backward camera (Lambertian surfaces only).");
-  const double zCam = cam->kind == 0 ? cam->z : cam->position[2];
-  if (!(zCam >= v.p.z0 && zCam <= v.p.zMax)) return mcbrat_camera_fail(c, "renderCamera: the camera's height lies outside the domain [z0, zMax].");
-  std::vector<float> fwdAll;
+  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
+  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
   CamParams cp;
   std::memset(&cp, 0, sizeof(cp));
-  float fwdMax = 0.0f;
-  for (int k = 0; k < v.nc; ++k) {
-    if ((int)v.fwd->size() <= k || (*v.fwd)[k].empty())
-      return mcbrat_camera_fail(c, ("renderCamera: no forward phase function table for component " + std::to_string(k + 1)).c_str());
-    if ((*v.maxPfi)[k] >= (*v.fwdNEntries)[k])
-      return mcbrat_camera_fail(c, ("renderCamera: phaseFunctionIndex exceeds forward table entries for component " + std::to_string(k + 1)).c_str());
-    cp.fwdOffset[k] = (int)fwdAll.size(); cp.fwdNAngles[k] = (*v.fwdNAngles)[k];
-    fwdAll.insert(fwdAll.end(), (*v.fwd)[k].begin(), (*v.fwd)[k].end());
-    for (float x : (*v.fwd)[k]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
-  }
-  if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
-  const int lds = choose_grid_lds(v, cam->gridInLds);
-  if (lds < 0) return mcbrat_camera_fail(c, "renderCamera: gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
+  std::vector<long long> bins;
+  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped)) return 1;
 
-  camera_geometry(*cam, cp.g);
-  cp.jitter = cam->jitter != 0;
-  cp.spp = (unsigned long long)samplesPerPixel; cp.npix = npix; cp.firstSample = firstSample;
-  cp.total = nBins * cp.spp;
-  sun_setup(v.p, cp);
-  {
-    // a leg: as a ray whose |cosine| is 2^-16, the smallest a Lambertian draw gives; a flatter one that has not ended by then
-    // (in a vacuum) is dropped and counted
-    const double H = v.p.zMax - v.p.z0, travel = H * 65536.0;
-    const double n = (double)v.p.nz + (std::floor(travel / v.p.Lx) + 2.0) * v.p.nx + (std::floor(travel / v.p.Ly) + 2.0) * v.p.ny + 8.0;
-    cp.maxLegCross = (unsigned)std::min(n, (double)(1u << 26));
-    cp.maxEvents = kCameraMaxEvents;
-  }
-  {
-    // the fixed-point scale, as actScale is chosen: the power of two that keeps a batch's sum of paths that each hold 64 of
-    // the largest possible estimate below 2^62; a path's own sum saturates where samplesPerPixel of it would pass that
-    const double largest = std::max((double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846);
-    int e = 0;
-    std::frexp(4.611686018427387904e18 / ((double)samplesPerPixel * largest * 64.0), &e);
-    e = std::max(0, std::min(e - 1, 40));
-    cp.scale = std::ldexp(1.0, e);
-    cp.pathMax = std::floor(4.611686018427387904e18 / (double)samplesPerPixel);
-  }
-  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
-
-  DeviceBuffer<long long> dBins;
-  DeviceBuffer<float> dFwd;
-  DeviceBuffer<unsigned long long> dDropped;
-  CAM_HIP(c, dBins.allocate((size_t)nBins));
-  CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
-  CAM_HIP(c, dDropped.allocate(1));
-  CAM_HIP(c, hipMemsetAsync(dBins.get(), 0, sizeof(long long) * (size_t)nBins, v.stream));
-  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
-  CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
-  cp.bins = dBins.get(); cp.fwd = dFwd.get(); cp.dropped = dDropped.get();
-
-  // 16 waves per compute unit (four per SIMD); a wave's lanes take 64 consecutive indices at a time
-  const int block = lds ? 512 : 256;
-  const unsigned long long lanes = (unsigned long long)v.numCUs * 16ull * kWave;
-  cp.pathsPerLane = std::max<unsigned long long>(1, (cp.total + lanes - 1) / lanes);
-  const unsigned long long perBlock = cp.pathsPerLane * (unsigned long long)block;
-  const unsigned long long blocks = (cp.total + perBlock - 1) / perBlock;
-  if (blocks > 0x7fffffffull) return mcbrat_camera_fail(c, "renderCamera: more paths than one launch takes.");
-  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
-  if (lds) {
-    if (allow_lds(c, camera_kernel<512, true, false>, bytes)) return 1;
-    hipLaunchKernelGGL((camera_kernel<512, true, false>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
-  } else {
-    hipLaunchKernelGGL((camera_kernel<256, false, false>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
-  }
-  CAM_HIP(c, hipGetLastError());
-  std::vector<long long> bins((size_t)nBins);
-  unsigned long long nDropped = 0;
-  CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * (size_t)nBins, hipMemcpyDeviceToHost, v.stream));
-  CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
-  CAM_HIP(c, hipStreamSynchronize(v.stream));
-  if (dropped) *dropped = (int64_t)nDropped;
-
-  // batch means; their mean and its standard error from the differences to the first batch (identical batches: exactly 0)
   const double unit = 1.0 / (cp.scale * (double)samplesPerPixel);
   for (unsigned long long px = 0; px < npix; ++px) {
     const double m0 = (double)bins[px] * unit;
-    double s1 = 0.0, s2 = 0.0;
+    BatchSeries s;
     for (int b = 0; b < numBatches; ++b) {
       const double m = (double)bins[(size_t)b * npix + px] * unit;
       if (batchMeans) batchMeans[(size_t)b * npix + px] = (float)m;
-      s1 += m - m0; s2 += (m - m0) * (m - m0);
+      s.add(m - m0);
     }
-    const double dm = s1 / (double)numBatches;
-    radiance[px] = (float)(m0 + dm);
-    if (radianceStdErr) {
-      const double var = numBatches > 1 ? std::max(0.0, s2 - (double)numBatches * dm * dm) / ((double)numBatches * (double)(numBatches - 1)) : 0.0;
-      radianceStdErr[px] = (float)std::sqrt(var);
-    }
+    radiance[px] = (float)(m0 + s.shift(numBatches));
+    if (radianceStdErr) radianceStdErr[px] = (float)s.error(numBatches);
   }
   return 0;
 }
@@ -655,52 +662,24 @@ int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a,
 int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, uint64_t seed, uint64_t firstSample,
                           int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds, float *diffuse, float *direct,
                           float *diffuseStdErr, float *directStdErr, float *totalStdErr, float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderSensors", "samplesPerSensor", "the sensors' batches (2 * n * numBatches)", "the backward sensors", "the backward sensors need", 2,
+                   camera_kernel<512, true, true>, camera_kernel<256, false, true>};
   if (!c) return 1;
-  if (n < 1) return mcbrat_camera_fail(c, "renderSensors: at least one sensor is needed (n < 1).");
-  if (!sensors || !diffuse || !direct) return mcbrat_camera_fail(c, "renderSensors: no sensors or no arrays for the diffuse and the direct part.");
-  if (gridInLds < -1 || gridInLds > 1) return mcbrat_camera_fail(c, "renderSensors: gridInLds must be -1, 0 or 1.");
-  if (samplesPerSensor < 1) return mcbrat_camera_fail(c, "renderSensors: samplesPerSensor must be at least 1.");
-  if (numBatches < 1) return mcbrat_camera_fail(c, "renderSensors: numBatches must be at least 1.");
+  if (n < 1) return fail(c, e, "at least one sensor is needed (n < 1).");
+  if (!sensors || !diffuse || !direct) return fail(c, e, "no sensors or no arrays for the diffuse and the direct part.");
+  if (gridInLds < -1 || gridInLds > 1) return fail(c, e, "gridInLds must be -1, 0 or 1.");
   const unsigned long long ns = (unsigned long long)n;
-  const unsigned long long nBins = ns * (unsigned long long)numBatches;
-  if (ns > 0x7fffffffull || 2ull * nBins > kCameraBinBudget / sizeof(long long))
-    return mcbrat_camera_fail(c, "renderSensors: the bins of the sensors' batches (2 * n * numBatches) do not fit the tally budget of 4 GiB.");
-  if ((double)nBins * (double)samplesPerSensor >= 9.0e18 || (double)firstSample + (double)numBatches * (double)samplesPerSensor >= 1.8e19)
-    return mcbrat_camera_fail(c, "renderSensors: more paths than a 64-bit index counts.");
+  const Counts k = {ns, samplesPerSensor, numBatches, firstSample};
+  if (check_counts(c, e, k)) return 1;
   for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
     if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
   CameraContext v;
-  if (mcbrat_camera_context(c, &v, false)) return 1;
-  if (!v.haveGrid || !v.haveOptics) return mcbrat_camera_fail(c, "renderSensors: problem not completely specified (grid and optical properties).");
-  if (!v.haveSource || !v.solarDirectional) return mcbrat_camera_fail(c, "renderSensors: the backward sensors need the Directional solar source.");
-  if (v.brdfSurface) return mcbrat_camera_fail(c, "renderSensors: a BRDF surface is not supported by the backward sensors (Lambertian surfaces only).");
-  for (int64_t i = 0; i < n; ++i) {
-    const mcbrat_sensor &s = sensors[i];
-    for (int k = 0; k < 4; ++k) {
-      const double z = s.position[2] + ((k & 1) ? s.e1[2] : 0.0) + ((k & 2) ? s.e2[2] : 0.0);
-      if (!(z >= v.p.z0 && z <= v.p.zMax)) return mcbrat_camera_fail(c, "renderSensors: a corner of a sensor's receiver lies outside the domain [z0, zMax].");
-    }
+  if (backward_context(c, e, v)) return 1;
+  for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
+    const mcbrat_sensor &s = sensors[i / 4];
+    if (!inside(v.p, s.position[2] + ((i & 1) ? s.e1[2] : 0.0) + ((i & 2) ? s.e2[2] : 0.0)))
+      return fail(c, e, "a corner of a sensor's receiver lies outside the domain [z0, zMax].");
   }
-  std::vector<float> fwdAll;
-  CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  float fwdMax = 0.0f;
-  for (int k = 0; k < v.nc; ++k) {
-    if ((int)v.fwd->size() <= k || (*v.fwd)[k].empty())
-      return mcbrat_camera_fail(c, ("renderSensors: no forward phase function table for component " + std::to_string(k + 1)).c_str());
-    if ((*v.maxPfi)[k] >= (*v.fwdNEntries)[k])
-      return mcbrat_camera_fail(c, ("renderSensors: phaseFunctionIndex exceeds forward table entries for component " + std::to_string(k + 1)).c_str());
-    cp.fwdOffset[k] = (int)fwdAll.size(); cp.fwdNAngles[k] = (*v.fwdNAngles)[k];
-    fwdAll.insert(fwdAll.end(), (*v.fwd)[k].begin(), (*v.fwd)[k].end());
-    for (float x : (*v.fwd)[k]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
-  }
-  if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
-  const int lds = choose_grid_lds(v, gridInLds);
-  if (lds < 0) return mcbrat_camera_fail(c, "renderSensors: gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
-
-  cp.spp = (unsigned long long)samplesPerSensor; cp.npix = ns; cp.firstSample = firstSample;
-  cp.total = nBins * cp.spp;
-  sun_setup(v.p, cp);
   const double kPi = 3.14159265358979323846;
   // the sun in double, as mcbrat_set_source_solar's float direction gives it; mu0 = its cosine
   double sun[3], sn = 0.0;
@@ -720,88 +699,34 @@ int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors
     w0[(size_t)i] = sensors[i].kind == 0 ? kPi : 4.0 * kPi;
     geo[(size_t)i].direct = (float)(cDirect / w0[(size_t)i]);  // (both parts are tallied in units of w0)
   }
-  {
-    const double H = v.p.zMax - v.p.z0, travel = H * 65536.0;  // a leg's bound: as mcbrat_render_camera's
-    const double nc = (double)v.p.nz + (std::floor(travel / v.p.Lx) + 2.0) * v.p.nx + (std::floor(travel / v.p.Ly) + 2.0) * v.p.ny + 8.0;
-    cp.maxLegCross = (unsigned)std::min(nc, (double)(1u << 26));
-    cp.maxEvents = kCameraMaxEvents;
-  }
-  {
-    // the fixed-point scale, as mcbrat_render_camera chooses it; the direct estimate, c / w0, is at most 1 / (pi mu0)
-    const double largest = std::max(std::max((double)fwdMax * (double)cp.invFourPiMu0, 1.0 / kPi), 1.0 / (kPi * mu0));
-    int e = 0;
-    std::frexp(4.611686018427387904e18 / ((double)samplesPerSensor * largest * 64.0), &e);
-    e = std::max(0, std::min(e - 1, 40));
-    cp.scale = std::ldexp(1.0, e);
-    cp.pathMax = std::floor(4.611686018427387904e18 / (double)samplesPerSensor);
-  }
-  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  std::vector<long long> bins;  // [2][numBatches][n]: diffuse, then direct
+  if (backward_render(c, e, v, gridInLds, k, seed, cp, &geo, 1.0 / (kPi * mu0), bins, dropped)) return 1;  // (the direct estimate, c / w0, is at most 1 / (pi mu0))
 
-  DeviceBuffer<long long> dBins;  // [2][numBatches][n]: diffuse, then direct
-  DeviceBuffer<float> dFwd;
-  DeviceBuffer<unsigned long long> dDropped;
-  DeviceBuffer<SensorGeometry> dGeo;
-  CAM_HIP(c, dBins.allocate((size_t)(2 * nBins)));
-  CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
-  CAM_HIP(c, dDropped.allocate(1));
-  CAM_HIP(c, dGeo.allocate((size_t)n));
-  CAM_HIP(c, hipMemsetAsync(dBins.get(), 0, sizeof(long long) * (size_t)(2 * nBins), v.stream));
-  CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
-  CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
-  CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo.data(), sizeof(SensorGeometry) * (size_t)n, hipMemcpyHostToDevice, v.stream));
-  cp.bins = dBins.get(); cp.binsDirect = dBins.get() + nBins; cp.fwd = dFwd.get(); cp.dropped = dDropped.get(); cp.sensors = dGeo.get();
-
-  // the camera's launch shape: indices are sensor-major, so a wave's lanes share a bin wherever samplesPerSensor >= 64
-  const int block = lds ? 512 : 256;
-  const unsigned long long lanes = (unsigned long long)v.numCUs * 16ull * kWave;
-  cp.pathsPerLane = std::max<unsigned long long>(1, (cp.total + lanes - 1) / lanes);
-  const unsigned long long perBlock = cp.pathsPerLane * (unsigned long long)block;
-  const unsigned long long blocks = (cp.total + perBlock - 1) / perBlock;
-  if (blocks > 0x7fffffffull) return mcbrat_camera_fail(c, "renderSensors: more paths than one launch takes.");
-  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
-  if (lds) {
-    if (allow_lds(c, camera_kernel<512, true, true>, bytes)) return 1;
-    hipLaunchKernelGGL((camera_kernel<512, true, true>), dim3((unsigned)blocks), dim3(512), bytes, v.stream, v.p, cp);
-  } else {
-    hipLaunchKernelGGL((camera_kernel<256, false, true>), dim3((unsigned)blocks), dim3(256), 0, v.stream, v.p, cp);
-  }
-  CAM_HIP(c, hipGetLastError());
-  std::vector<long long> bins((size_t)(2 * nBins));
-  unsigned long long nDropped = 0;
-  CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * (size_t)(2 * nBins), hipMemcpyDeviceToHost, v.stream));
-  CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
-  CAM_HIP(c, hipStreamSynchronize(v.stream));
-  if (dropped) *dropped = (int64_t)nDropped;
-
-  // batch means; their means and standard errors from the differences to the first batch (identical batches: exactly 0), for
-  // the diffuse part, the direct part and the per-batch sum of the two
+  // the diffuse part, the direct part and the per-batch sum of the two, each a series of its own
+  const size_t nBins = (size_t)ns * (size_t)numBatches;
   const double unit = 1.0 / (cp.scale * (double)samplesPerSensor);
-  const double nb = (double)numBatches;
   for (unsigned long long i = 0; i < ns; ++i) {
     const double u = unit * w0[(size_t)i];
-    const double f0 = (double)bins[i] * u, d0 = (double)bins[(size_t)nBins + i] * u;
-    double s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
+    const double f0 = (double)bins[i] * u, d0 = (double)bins[nBins + i] * u;
+    BatchSeries s[3];
     for (int b = 0; b < numBatches; ++b) {
-      const double f = (double)bins[(size_t)b * ns + i] * u, d = (double)bins[(size_t)nBins + (size_t)b * ns + i] * u;
+      const double f = (double)bins[(size_t)b * ns + i] * u, d = (double)bins[nBins + (size_t)b * ns + i] * u;
       if (batchMeans) {
         batchMeans[((size_t)b * 2 + 0) * ns + i] = (float)f;
         batchMeans[((size_t)b * 2 + 1) * ns + i] = (float)d;
       }
-      const double diff[3] = {f - f0, d - d0, (f - f0) + (d - d0)};
-      for (int k = 0; k < 3; ++k) { s1[k] += diff[k]; s2[k] += diff[k] * diff[k]; }
+      s[0].add(f - f0); s[1].add(d - d0); s[2].add((f - f0) + (d - d0));
     }
+    diffuse[i] = (float)(f0 + s[0].shift(numBatches));
+    direct[i] = (float)(d0 + s[1].shift(numBatches));
     float *err[3] = {diffuseStdErr, directStdErr, totalStdErr};
-    for (int k = 0; k < 3; ++k) {
-      const double dm = s1[k] / nb;
-      if (k == 0) diffuse[i] = (float)(f0 + dm);
-      if (k == 1) direct[i] = (float)(d0 + dm);
-      if (err[k]) {
-        const double var = numBatches > 1 ? std::max(0.0, s2[k] - nb * dm * dm) / (nb * (nb - 1.0)) : 0.0;
-        err[k][i] = (float)std::sqrt(var);
-      }
-    }
+    for (int q = 0; q < 3; ++q)
+      if (err[q]) err[q][i] = (float)s[q].error(numBatches);
   }
   return 0;
 }
 
 }  // extern "C"
+
