@@ -515,6 +515,35 @@ int mcbrat_render_sensors(mcbrat_ctx *ctx, int64_t n, const mcbrat_sensor *senso
  * refuses on its own members. */
 int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a, double c, double origin[3], double direction[3]);
 
+/* ---- emission renders: the backward thermal camera and sensors (additions under ABI version 3) ---------
+ * The radiance a medium and its surface EMIT, by the camera's and the sensors' backward paths: same (origin, direction), same
+ * Philox counters, same bounds; no ray toward the sun, no forward table.  A collision in cell v, component c adds
+ * w (1 - omega0[c, v]) cellSource[v] and then takes w *= omega0; the surface at (x, y) adds w (1 - a(x, y)) surfaceSource[column]
+ * and then takes w *= a; at the top the path ends.  cellSource[nz][ny][nx] (x fastest) and surfaceSource[ny][nx] are the caller's
+ * Planck radiances in the caller's units (mcbrat_planck_radiance: W m-2 sr-1 um-1); results are in the same units.  1 - omega0
+ * and 1 - a come from the optics and the Lambertian surface the context holds; its SOURCE is not consulted -- a thermal context,
+ * a solar one and one with no source set render the same bytes.  Needs the grid, the optics and the inverse tables (no forward
+ * tables).  Outputs, batches, sample indices, determinism and `dropped` are those of mcbrat_render_camera and
+ * mcbrat_render_sensors; a sensor has no direct part: irradiance[i] = w0 mean(S), batchMeans[numBatches][n].
+ * Refused, before any launch: what the solar entries refuse about the camera, the sensors, the counts, the budget (one bin
+ * array), grid, optics, inverse tables and gridInLds; a BRDF surface (its emissivity is directional); a null source array; a
+ * source value that is negative or not finite; sources that are all zero (nothing emits). */
+int mcbrat_render_camera_emission(mcbrat_ctx *ctx, const mcbrat_camera *cam, const float *cellSource /* [nz][ny][nx] */,
+                                  const float *surfaceSource /* [ny][nx] */, uint64_t seed, uint64_t firstSample,
+                                  int64_t samplesPerPixel /* per batch */, int32_t numBatches,
+                                  float *radiance /* [npy][npx] */, float *radianceStdErr /* may be NULL */,
+                                  float *batchMeans /* [numBatches][npy][npx], may be NULL */, int64_t *dropped /* may be NULL */);
+int mcbrat_render_sensors_emission(mcbrat_ctx *ctx, int64_t n, const mcbrat_sensor *sensors, const float *cellSource,
+                                   const float *surfaceSource, uint64_t seed, uint64_t firstSample,
+                                   int64_t samplesPerSensor /* per batch */, int32_t numBatches,
+                                   int32_t gridInLds /* -1 library's choice, 0, 1 */,
+                                   float *irradiance /* [n] */, float *irradianceStdErr /* [n], may be NULL */,
+                                   float *batchMeans /* [numBatches][n], may be NULL */, int64_t *dropped /* may be NULL */);
+/* The Planck function exactly as mcbrat_emission_weighting evaluates it (one function serves both): out[i] = B(lambda, temps[i])
+ * in W m-2 sr-1 um-1, so that forward `intensity` x totalFlux / dLambda and the emission camera's radiance on these sources are
+ * one quantity.  Host arithmetic only.  Returns 1 for a null array, a negative n or a wavelength that is not positive. */
+int mcbrat_planck_radiance(double lambdaMicrons, int64_t n, const double *temps, double *out);
+
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air
  * above and below a cloud field -- a photon crosses z faces only; its column is found again from its position when

@@ -15,7 +15,7 @@ include/mcbrat.h and hand-written HIP kernels for gfx950:
 from ._capi import McbratError  # noqa: F401
 from .phase import PhaseFunction, PhaseFunctionTable, new_PhaseFunction, new_PhaseFunctionTable  # noqa: F401
 from .domain import Domain, new_Domain  # noqa: F401
-from .illumination import PhotonStream, Weights, new_PhotonStream, new_Weights, emission_weighting  # noqa: F401
+from .illumination import PhotonStream, Weights, new_PhotonStream, new_Weights, emission_weighting, planck_radiance, planck_sources  # noqa: F401
 from .integrator import Integrator, new_Integrator  # noqa: F401
 from .surface import SurfaceDescription, new_SurfaceDescription  # noqa: F401
 from .sensors import Sensors, new_Sensors  # noqa: F401

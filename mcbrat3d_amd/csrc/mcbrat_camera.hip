@@ -27,6 +27,10 @@
 // cosine-weighted (planar) or uniform (spherical) direction; the sensor's id stands where the pixel stands in the counter --,
 // with a second bin array for the direct beam at the path's origin.
 //
+// Emission renders (mcbrat_render_camera_emission, mcbrat_render_sensors_emission): camera_kernel<.., EMIT =
+// true> is the same path with the thermal estimator -- a collision deposits w (1 - omega0) S_cell and the surface w (1 - a) S_sfc
+// before the weight is cut, no ray walks toward the sun, a sensor has no direct part.
+//
 // Component pick, roulette, scattering angle and new direction are written out here as they are in trace_kernel
 // (mcbrat_kernels.hip, HOT ROWS) and trace_block_kernel (mcbrat_blockwalk.hip, HOT ROWS): a change to one of those rules is made
 // in all three.  What mcbrat_photon.h shares (Philox, u01, lambert_direction, find_cell, surface_reflectance, ...) is called.
@@ -77,6 +81,10 @@ struct CamParams {
   // mcbrat_render_sensors (SENSOR instantiations; npix = the number of sensors, spp = samples per sensor and batch)
   const SensorGeometry *sensors;   // [npix]
   long long *binsDirect;           // [nBatches][npix] fixed point, in units of w0 like bins
+  // the emission renders (EMIT instantiations): the caller's Planck radiances, left in global memory
+  const float *srcCell;            // [nz][ny][nx], x fastest
+  const float *srcSurface;         // [ny][nx]
+  double invSrcMax;                // 1 / the largest source value: a path's sum is tallied in units of it
 };
 
 struct GridView { const double *xe, *ye, *ze; const float *ext; };
@@ -208,7 +216,9 @@ __device__ __forceinline__ void wave_add(long long *bins, uint32_t bin, long lon
 // SENSOR: the path starts on a receiver (mcbrat_sensor_ray.h) instead of in a pixel, the sensor's id
 // stands where the pixel stands in the counter, and a second sum takes the direct beam at the origin; from there on the path is
 // the camera's.
-template <int BLOCK, bool GRID_LDS, bool SENSOR>
+// EMIT: the thermal estimator on the same path.  No ray toward the sun and no forward table: a collision
+// deposits w (1 - omega0) S_cell BEFORE w *= omega0, the surface w (1 - a) S_sfc before w *= a, and a sensor has no direct part.
+template <int BLOCK, bool GRID_LDS, bool SENSOR, bool EMIT>
 __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
@@ -289,6 +299,19 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       r.oy = r.oy + (double)r.dy * (double)t;
       if (end == END_SURFACE) {
         r.oz = p.zSurf;
+        if constexpr (EMIT) {
+          // The surface emits (1 - a) S_sfc of the column march() ended in, then reflects the rest of the path.  The whole event,
+          // ending in `continue`: what follows is the solar event, left word for word as it was and dead in these instantiations
+          // (a scope around its sun ray moves the sensor instantiations' control flow: their assembly is held to the parent's)
+          const float a = camera_albedo(p, r.ox, r.oy);
+          sum += (w * (1.0f - a)) * cp.srcSurface[r.iy * p.nx + r.ix];
+          w *= a;
+          if (!(w > 0.0f)) break;
+          float mu = sqrtf(uX);
+          if (mu == 0.0f) mu = fmaxf(sqrtf(uZ), 1.52587890625e-05f);
+          lambert_direction(mu, uY, r.dx, r.dy, r.dz);
+          continue;
+        }
         w *= camera_albedo(p, r.ox, r.oy);
         if (!(w > 0.0f)) break;
         bool bound;
@@ -305,10 +328,17 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       int c = 0;  // component pick: findIndex over [0, cumExt(:)]
       for (int kc = 0; kc < p.nc - 1; kc++)
         if (uZ >= p.cum[(long long)kc * nvox + cell]) c = kc + 1;
-      w *= p.ssa[(long long)c * nvox + cell];
+      if constexpr (EMIT) {
+        // the cell's emission along the path, before the weight is cut: a purely absorbing medium deposits and ends
+        const float ssa = p.ssa[(long long)c * nvox + cell];
+        sum += (w * (1.0f - ssa)) * cp.srcCell[cell];
+        w *= ssa;
+      } else {
+        w *= p.ssa[(long long)c * nvox + cell];
+      }
       if (!(w > 0.0f)) break;
       const int pfEntry = p.pfi[(long long)c * nvox + cell];
-      {
+      if constexpr (!EMIT) {
         // the local estimate toward the sun: Theta between the sun's direction of travel and -d, the direction the light
         // travels along this leg; P by the reference's linear interpolation in angle (lookUpPhaseFuncValsFromTable)
         float proj = r.dx * cp.sun[0] + r.dy * cp.sun[1] + r.dz * cp.sun[2];
@@ -362,7 +392,13 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
         r.dz = r.dz * cs - copysignf(fabsf(B), r.dz * B);
       }
     }
-    if constexpr (SENSOR) {
+    if constexpr (SENSOR && EMIT) {
+      // no direct part (c = 0 for every sensor): one bin array, the sum in units of the largest source value
+      const bool ok = !dropped && sum == sum;
+      if (valid && !ok) atomicAdd(cp.dropped, 1ull);
+      const long long vEmitted = ok ? __double2ll_rn(fmin((double)sum * cp.invSrcMax * cp.scale, cp.pathMax)) : 0;
+      wave_add(cp.bins, bin32, vEmitted, lane);
+    } else if constexpr (SENSOR) {
       // (a NaN from a table: counted like a path a bound ended, contributes to neither part)
       // The direct beam on the receiver at the path's origin, found again from the path's first block: nothing of it is carried
       // through the legs (registers).  A sun ray a bound ends drops the path.
@@ -391,6 +427,8 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
     } else {
       if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
         nDropped++;
+      } else if constexpr (EMIT) {
+        pend += __double2ll_rn(fmin((double)sum * cp.invSrcMax * cp.scale, cp.pathMax));
       } else {
         pend += __double2ll_rn(fmin((double)sum * cp.scale, cp.pathMax));
       }
@@ -470,6 +508,9 @@ int choose_grid_lds(const CameraContext &v, int asked) {
 
 // One launch of a kernel that has an instantiation for the grid in LDS and one for the grid in global memory
 using BackwardKernel = void (*)(const DevParams, const CamParams);
+// The solar instantiations (EMIT = false) by the three parameters they have had since section 4.20
+template <int BLOCK, bool GRID_LDS, bool SENSOR>
+constexpr BackwardKernel solar_camera_kernel() { return camera_kernel<BLOCK, GRID_LDS, SENSOR, false>; }
 int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp) {
   const BackwardKernel kernel = lds ? inLds : inGlobal;
   const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
@@ -487,7 +528,10 @@ struct Entry {
   const char *subject, *needs;     // "the backward camera", "the backward camera needs"
   unsigned long long arrays;       // bin arrays: 1, or 2 (diffuse, then direct)
   BackwardKernel inLds, inGlobal;  // workgroups of 512 and of 256 lanes
+  bool emit = false;               // an emission render: no sun, no forward tables, no rule about the source
 };
+// The sources of an emission render, as the caller handed them over: checked by emission_sources() before they are uploaded
+struct EmissionSources { const float *cell, *surface; double srcMax; };
 struct Counts { unsigned long long n; int64_t samples; int32_t numBatches; uint64_t firstSample; };  // n: pixels or sensors
 
 int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat_camera_fail(c, (std::string(e.name) + ": " + text).c_str()); }
@@ -505,19 +549,39 @@ int check_counts(mcbrat_ctx *c, const Entry &e, const Counts &k) {
 int backward_context(mcbrat_ctx *c, const Entry &e, CameraContext &v) {
   if (mcbrat_camera_context(c, &v, false)) return 1;
   if (!v.haveGrid || !v.haveOptics) return fail(c, e, "problem not completely specified (grid and optical properties).");
-  if (!v.haveSource || !v.solarDirectional) return fail(c, e, std::string(e.needs) + " the Directional solar source.");
+  if (!e.emit && (!v.haveSource || !v.solarDirectional)) return fail(c, e, std::string(e.needs) + " the Directional solar source.");
   if (v.brdfSurface) return fail(c, e, std::string("a BRDF surface is not supported by ") + e.subject + " (Lambertian surfaces only).");
+  return 0;
+}
+
+// An emission entry's own check of its two source arrays against the grid: every value finite and not negative, not all zero.
+// -> src.srcMax, the largest value
+int emission_sources(mcbrat_ctx *c, const Entry &e, const CameraContext &v, EmissionSources &src) {
+  const size_t ncol = (size_t)v.p.nx * (size_t)v.p.ny, nvox = ncol * (size_t)v.p.nz;
+  float largest = 0.0f;
+  for (int part = 0; part < 2; ++part) {
+    const float *s = part ? src.surface : src.cell;
+    const size_t n = part ? ncol : nvox;
+    for (size_t i = 0; i < n; ++i) {
+      if (!std::isfinite(s[i]) || s[i] < 0.0f) return fail(c, e, std::string(part ? "surfaceSource" : "cellSource") + " holds a value that is negative or not finite.");
+      largest = std::max(largest, s[i]);
+    }
+  }
+  if (!(largest > 0.0f)) return fail(c, e, "cellSource and surfaceSource are all zero: nothing emits.");
+  src.srcMax = (double)largest;
   return 0;
 }
 
 // Stage 3, after the entry's own checks against the domain: the forward and the inverse tables, the LDS share, then the launch.
 // cp: zeroed but for the entry's own members; geo: the sensors, or NULL; largestOwn: the largest estimate the entry adds to the
-// paths' (0: none).  -> bins [arrays][numBatches][n] in units of 1 / cp.scale, *dropped
+// paths' (0: none); src: the checked sources of an emission entry, or NULL -- then no sun is set up, no forward table is read and
+// the bins are in units of src->srcMax / cp.scale.  -> bins [arrays][numBatches][n] in units of 1 / cp.scale, *dropped
 int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInLds, const Counts &k, uint64_t seed, CamParams &cp,
-                    const std::vector<SensorGeometry> *geo, double largestOwn, std::vector<long long> &bins, int64_t *dropped) {
+                    const std::vector<SensorGeometry> *geo, double largestOwn, std::vector<long long> &bins, int64_t *dropped,
+                    const EmissionSources *src = nullptr) {
   std::vector<float> fwdAll;  // the forward tables, components concatenated, and the largest value they hold
   float fwdMax = 0.0f;
-  for (int i = 0; i < v.nc; ++i) {
+  for (int i = 0; i < (src ? 0 : v.nc); ++i) {
     if ((int)v.fwd->size() <= i || (*v.fwd)[i].empty()) return fail(c, e, "no forward phase function table for component " + std::to_string(i + 1));
     if ((*v.maxPfi)[i] >= (*v.fwdNEntries)[i]) return fail(c, e, "phaseFunctionIndex exceeds forward table entries for component " + std::to_string(i + 1));
     cp.fwdOffset[i] = (int)fwdAll.size(); cp.fwdNAngles[i] = (*v.fwdNAngles)[i];
@@ -531,9 +595,10 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   const unsigned long long nBins = k.n * (unsigned long long)k.numBatches;
   cp.spp = (unsigned long long)k.samples; cp.npix = k.n; cp.firstSample = k.firstSample;
   cp.total = nBins * cp.spp;
-  sun_setup(v.p, cp);
+  if (!src) sun_setup(v.p, cp);
   cp.maxLegCross = leg_bound(v.p.nx, v.p.ny, v.p.nz, v.p.zMax - v.p.z0, v.p.Lx, v.p.Ly); cp.maxEvents = kCameraMaxEvents;
-  const FixedPoint fixed = fixed_point(k.samples, {(double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846, largestOwn});
+  // (an emission path's deposits are tallied in units of the largest source value: the candidate is 1)
+  const FixedPoint fixed = src ? fixed_point(k.samples, {1.0}) : fixed_point(k.samples, {(double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846, largestOwn});
   cp.scale = fixed.scale; cp.pathMax = fixed.pathMax;
   v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
 
@@ -541,6 +606,7 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   DeviceBuffer<float> dFwd;
   DeviceBuffer<unsigned long long> dDropped;
   DeviceBuffer<SensorGeometry> dGeo;
+  DeviceBuffer<float> dSrcCell, dSrcSurface;
   const size_t allBins = (size_t)(e.arrays * nBins);
   CAM_HIP(c, dBins.allocate(allBins));
   CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
@@ -549,6 +615,14 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
   CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
   cp.bins = dBins.get(); cp.binsDirect = e.arrays == 2 ? dBins.get() + nBins : nullptr; cp.fwd = dFwd.get(); cp.dropped = dDropped.get();
+  if (src) {
+    const size_t ncol = (size_t)v.p.nx * (size_t)v.p.ny, nvox = ncol * (size_t)v.p.nz;
+    CAM_HIP(c, dSrcCell.allocate(nvox));
+    CAM_HIP(c, dSrcSurface.allocate(ncol));
+    CAM_HIP(c, hipMemcpyAsync(dSrcCell.get(), src->cell, sizeof(float) * nvox, hipMemcpyHostToDevice, v.stream));
+    CAM_HIP(c, hipMemcpyAsync(dSrcSurface.get(), src->surface, sizeof(float) * ncol, hipMemcpyHostToDevice, v.stream));
+    cp.srcCell = dSrcCell.get(); cp.srcSurface = dSrcSurface.get(); cp.invSrcMax = 1.0 / src->srcMax;
+  }
   if (geo) {
     CAM_HIP(c, dGeo.allocate(geo->size()));
     CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo->data(), sizeof(SensorGeometry) * geo->size(), hipMemcpyHostToDevice, v.stream));
@@ -621,7 +695,7 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
 int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed, uint64_t firstSample, int64_t samplesPerPixel,
                          int32_t numBatches, float *radiance, float *radianceStdErr, float *batchMeans, int64_t *dropped) {
   const Entry e = {"renderCamera", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the backward camera", "the backward camera needs", 1,
-                   camera_kernel<512, true, false>, camera_kernel<256, false, false>};
+                   solar_camera_kernel<512, true, false>(), solar_camera_kernel<256, false, false>()};
   if (!c) return 1;
   if (!cam || !radiance) return fail(c, e, "no camera or no array for the radiance.");
   if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
@@ -663,7 +737,7 @@ int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors
                           int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds, float *diffuse, float *direct,
                           float *diffuseStdErr, float *directStdErr, float *totalStdErr, float *batchMeans, int64_t *dropped) {
   const Entry e = {"renderSensors", "samplesPerSensor", "the sensors' batches (2 * n * numBatches)", "the backward sensors", "the backward sensors need", 2,
-                   camera_kernel<512, true, true>, camera_kernel<256, false, true>};
+                   solar_camera_kernel<512, true, true>(), solar_camera_kernel<256, false, true>()};
   if (!c) return 1;
   if (n < 1) return fail(c, e, "at least one sensor is needed (n < 1).");
   if (!sensors || !diffuse || !direct) return fail(c, e, "no sensors or no arrays for the diffuse and the direct part.");
@@ -724,6 +798,96 @@ int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors
     float *err[3] = {diffuseStdErr, directStdErr, totalStdErr};
     for (int q = 0; q < 3; ++q)
       if (err[q]) err[q][i] = (float)s[q].error(numBatches);
+  }
+  return 0;
+}
+
+// ---- the emission renders: the same stages, an Entry with `emit`, one bin array, the caller's sources ----
+
+int mcbrat_render_camera_emission(mcbrat_ctx *c, const mcbrat_camera *cam, const float *cellSource, const float *surfaceSource, uint64_t seed,
+                                  uint64_t firstSample, int64_t samplesPerPixel, int32_t numBatches, float *radiance, float *radianceStdErr,
+                                  float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderCameraEmission", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the emission camera", "the emission camera needs", 1,
+                   camera_kernel<512, true, false, true>, camera_kernel<256, false, false, true>, true};
+  if (!c) return 1;
+  if (!cam || !radiance) return fail(c, e, "no camera or no array for the radiance.");
+  if (!cellSource || !surfaceSource) return fail(c, e, "no cellSource or no surfaceSource array (a null pointer).");
+  if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
+  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy;
+  const Counts k = {npix, samplesPerPixel, numBatches, firstSample};
+  CameraContext v;
+  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
+  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
+  EmissionSources src = {cellSource, surfaceSource, 0.0};
+  if (emission_sources(c, e, v, src)) return 1;
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
+  std::vector<long long> bins;
+  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped, &src)) return 1;
+
+  // (the bins are in units of srcMax: the caller's units come back here, in double)
+  const double unit = src.srcMax / (cp.scale * (double)samplesPerPixel);
+  for (unsigned long long px = 0; px < npix; ++px) {
+    const double m0 = (double)bins[px] * unit;
+    BatchSeries s;
+    for (int b = 0; b < numBatches; ++b) {
+      const double m = (double)bins[(size_t)b * npix + px] * unit;
+      if (batchMeans) batchMeans[(size_t)b * npix + px] = (float)m;
+      s.add(m - m0);
+    }
+    radiance[px] = (float)(m0 + s.shift(numBatches));
+    if (radianceStdErr) radianceStdErr[px] = (float)s.error(numBatches);
+  }
+  return 0;
+}
+
+int mcbrat_render_sensors_emission(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, const float *cellSource, const float *surfaceSource,
+                                   uint64_t seed, uint64_t firstSample, int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds,
+                                   float *irradiance, float *irradianceStdErr, float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderSensorsEmission", "samplesPerSensor", "the sensors' batches (n * numBatches)", "the emission sensors", "the emission sensors need", 1,
+                   camera_kernel<512, true, true, true>, camera_kernel<256, false, true, true>, true};
+  if (!c) return 1;
+  if (n < 1) return fail(c, e, "at least one sensor is needed (n < 1).");
+  if (!sensors || !irradiance) return fail(c, e, "no sensors or no array for the irradiance.");
+  if (!cellSource || !surfaceSource) return fail(c, e, "no cellSource or no surfaceSource array (a null pointer).");
+  if (gridInLds < -1 || gridInLds > 1) return fail(c, e, "gridInLds must be -1, 0 or 1.");
+  const unsigned long long ns = (unsigned long long)n;
+  const Counts k = {ns, samplesPerSensor, numBatches, firstSample};
+  if (check_counts(c, e, k)) return 1;
+  for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
+    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+  CameraContext v;
+  if (backward_context(c, e, v)) return 1;
+  for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
+    const mcbrat_sensor &s = sensors[i / 4];
+    if (!inside(v.p, s.position[2] + ((i & 1) ? s.e1[2] : 0.0) + ((i & 2) ? s.e2[2] : 0.0)))
+      return fail(c, e, "a corner of a sensor's receiver lies outside the domain [z0, zMax].");
+  }
+  EmissionSources src = {cellSource, surfaceSource, 0.0};
+  if (emission_sources(c, e, v, src)) return 1;
+  std::vector<SensorGeometry> geo((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    sensor_geometry(sensors[i], geo[(size_t)i]);
+    geo[(size_t)i].direct = 0.0f;  // (no direct part: nothing comes in from above)
+  }
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  std::vector<long long> bins;  // [numBatches][n]
+  if (backward_render(c, e, v, gridInLds, k, seed, cp, &geo, 0.0, bins, dropped, &src)) return 1;
+
+  const double unit = src.srcMax / (cp.scale * (double)samplesPerSensor);
+  for (unsigned long long i = 0; i < ns; ++i) {
+    const double u = unit * (sensors[i].kind == 0 ? 3.14159265358979323846 : 4.0 * 3.14159265358979323846);  // w0: pi (planar), 4 pi (spherical)
+    const double f0 = (double)bins[i] * u;
+    BatchSeries s;
+    for (int b = 0; b < numBatches; ++b) {
+      const double f = (double)bins[(size_t)b * ns + i] * u;
+      if (batchMeans) batchMeans[(size_t)b * ns + i] = (float)f;
+      s.add(f - f0);
+    }
+    irradiance[i] = (float)(f0 + s.shift(numBatches));
+    if (irradianceStdErr) irradianceStdErr[i] = (float)s.error(numBatches);
   }
   return 0;
 }

@@ -282,6 +282,30 @@ extern "C" int mcbrat_hybrid_phase_functions(int32_t nAngles, int32_t nEntries, 
   return 0;
 }
 
+// The Planck function of emission_weightingNEW (:449-470), stated once: mcbrat_emission_weighting and mcbrat_planck_radiance both
+// call it, every operation in the order the reference has it.  The constants are the reference's single-precision ones.
+namespace {
+struct PlanckLine { double twoHC2, hck, lam5; };  // what depends on the wavelength alone
+PlanckLine planck_line(double lambdaMicrons) {
+  const double planckH = (double)6.62606957e-34f, lightC = (double)2.99792458e+8f, boltzK = (double)1.3806488e-23f;
+  PlanckLine l;
+  l.twoHC2 = 2.0 * planckH * std::pow(lightC, 2.0);
+  const double lambda = lambdaMicrons / std::pow(10.0, 6.0);
+  l.hck = planckH * lightC / (boltzK * lambda);
+  l.lam5 = std::pow(lambda, 5.0);
+  return l;
+}
+// W m-2 sr-1 um-1
+double planck_radiance(const PlanckLine &l, double T) { return (l.twoHC2 / (l.lam5 * (std::exp(l.hck / T) - 1.0))) / std::pow(10.0, 6.0); }
+}  // namespace
+
+extern "C" int mcbrat_planck_radiance(double lambdaMicrons, int64_t n, const double *temps, double *out) {
+  if (n < 0 || (n > 0 && (!temps || !out)) || !(lambdaMicrons > 0.0)) return 1;
+  const PlanckLine line = planck_line(lambdaMicrons);
+  for (int64_t i = 0; i < n; ++i) out[i] = planck_radiance(line, temps[i]);
+  return 0;
+}
+
 // emission_weightingNEW, src/emissionAndBroadBandWeights.f95:424-550.
 extern "C" int mcbrat_emission_weighting(int32_t nx, int32_t ny, int32_t nz, int32_t nc, const double *xe,
                                          const double *ye, const double *ze, const double *temps,
@@ -289,14 +313,10 @@ extern "C" int mcbrat_emission_weighting(int32_t nx, int32_t ny, int32_t nz, int
                                          double albedo, double lambdaMicrons, double sfcTemp, double dLambda,
                                          double *voxelWeights, double *fracAtmsPower, double *totalFlux) {
   if (nx < 1 || ny < 1 || nz < 1 || nc < 1 || !voxelWeights || !fracAtmsPower) return 1;
-  const double planckH = (double)6.62606957e-34f, lightC = (double)2.99792458e+8f, boltzK = (double)1.3806488e-23f;
-  const double twoHC2 = 2.0 * planckH * std::pow(lightC, 2.0);
   const double pi = 4.0 * std::atan(1.0);
   const size_t nvox = (size_t)nx * ny * nz;
-  const double lambda = lambdaMicrons / std::pow(10.0, 6.0);
-  const double hck = planckH * lightC / (boltzK * lambda);
-  const double lam5 = std::pow(lambda, 5.0);
-  auto planck = [&](double T) { return (twoHC2 / (lam5 * (std::exp(hck / T) - 1.0))) / std::pow(10.0, 6.0); };
+  const PlanckLine line = planck_line(lambdaMicrons);
+  auto planck = [&](double T) { return planck_radiance(line, T); };
   const double emiss = 1.0 - albedo;
   const double wx = xe[nx] - xe[0], wy = ye[ny] - ye[0], km2 = std::pow(1000.0, 2.0);
   double sfcPower = 0.0;

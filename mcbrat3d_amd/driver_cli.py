@@ -25,14 +25,16 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     "filenames": dict(physdomainfile="", domainfilename="", sspfilename="", solarsourcefile="", instrresponsefile="",
                       outputfluxfile="", outputabsproffile="", outputabsvolumefile="", outputnetcdffile="", outputradfile=""),
     # the backward camera (no counterpart in the reference driver): absent -- cameraKind empty -- it changes
-    # nothing.  cameraFootprint = xLo, xHi, yLo, yHi (default: the domain), cameraHeight (default: the top of the domain)
+    # nothing.  cameraFootprint = xLo, xHi, yLo, yHi (default: the domain), cameraHeight (default: the top of the domain).
+    # emission = .true. (here and in /sensors/; read as cameraEmission and sensorsEmission): the emission render of DESIGN.md
+    # section 4.22 on the Planck radiances of the domain's temperatures and surfaceTemp, instead of the solar one
     "camera": dict(camerakind="", camerapixels=[1, 1], cameraposition=[0.0, 0.0, 0.0], cameralook=[0.0, 0.0, -1.0],
                    cameraup=[0.0, 1.0, 0.0], camerafov=60.0, cameramu=1.0, cameraphi=0.0, camerafootprint=[], cameraheight=None,
-                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile=""),
+                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile="", emission=False),
     # backward sensors (no counterpart in the reference driver): absent -- sensorKind empty -- they change
     # nothing.  sensorPositions = x, y, z of every sensor in turn; sensorTilt, sensorAzimuth in degrees, one for all or one per sensor
     "sensors": dict(sensorkind="", sensorpositions=[], sensortilt=0.0, sensorazimuth=0.0, sensorsamples=10000, sensorbatches=10,
-                    outputsensorfile=""),
+                    outputsensorfile="", emission=False),
 }
 
 
@@ -72,6 +74,8 @@ def read_namelists(path):
     for g, d in DEFAULTS.items():
         cfg.update({k.lower(): v for k, v in d.items()})
         cfg.update(groups.get(g, {}))
+        if "emission" in d:  # (one key in two groups: kept apart as cameraemission and sensorsemission)
+            cfg[g + "emission"] = bool(cfg.pop("emission"))
     return cfg
 
 
@@ -352,8 +356,13 @@ def main(argv=None):
                        solarFlux=1.0, dist=dist, moments_tensor=moments)
     cameraResult = None
     if camera is not None and rank == 0:  # the image: rank 0 renders it after the forward run, with sample indices of its own stream
-        cameraResult = integ.renderCamera(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
-                                          int(cfg["camerabatches"]))
+        if cfg["cameraemission"]:
+            cellSource, surfaceSource = M.planck_sources(dom, cfg["surfacetemp"])
+            cameraResult = integ.renderCameraEmission(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
+                                                      int(cfg["camerabatches"]), cellSource=cellSource, surfaceSource=surfaceSource)
+        else:
+            cameraResult = integ.renderCamera(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
+                                              int(cfg["camerabatches"]))
         cameraResult["samplesPerPixel"] = int(cfg["camerasamplesperpixel"])
         print(" camera %s %d x %d: mean radiance %.6g, largest standard error %.3g, %d paths dropped" % (
             camera.kind, camera.npx, camera.npy, cameraResult["radiance"].mean(), cameraResult["radiance_StdErr"].max(), cameraResult["dropped"]))
@@ -361,9 +370,18 @@ def main(argv=None):
             ncio.writeCamera_netcdf(cfg["outputcamerafile"], camera, cameraResult)
     sensorResult = None
     if sensors is not None and rank == 0:  # rank 0 renders the sensors after the forward run, with sample indices of their own stream
-        sensorResult = integ.renderSensors(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]), int(cfg["sensorbatches"]))
+        if cfg["sensorsemission"]:
+            cellSource, surfaceSource = M.planck_sources(dom, cfg["surfacetemp"])
+            sensorResult = integ.renderSensorsEmission(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]),
+                                                       int(cfg["sensorbatches"]), cellSource=cellSource, surfaceSource=surfaceSource)
+        else:
+            sensorResult = integ.renderSensors(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]), int(cfg["sensorbatches"]))
         sensorResult["samplesPerSensor"] = int(cfg["sensorsamples"])
         for i in range(len(sensors)):
+            if cfg["sensorsemission"]:
+                print(" sensor %3d %-9s at %9.4f %9.4f %9.4f: emitted %12.6g +-%12.6g" % (
+                    i, sensors.kindNames()[i], *sensors.positions[i], sensorResult["irradiance"][i], sensorResult["irradiance_StdErr"][i]))
+                continue
             print(" sensor %3d %-9s at %9.4f %9.4f %9.4f: %9.6f +-%9.6f  direct/diffuse: %9.6f  %9.6f" % (
                 i, sensors.kindNames()[i], *sensors.positions[i], sensorResult["irradiance"][i], sensorResult["irradiance_StdErr"][i],
                 sensorResult["direct"][i], sensorResult["diffuse"][i]))

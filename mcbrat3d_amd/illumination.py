@@ -53,6 +53,29 @@ def emission_weighting(thisDomain, theseWeights, sfcTemp, dLambda=1.0):
     return flux.value
 
 
+def planck_radiance(lambda_um, temps):
+    """The Planck function as emission_weighting evaluates it (mcbrat_planck_radiance), W m-2 sr-1 um-1, in double; the
+    shape of `temps` is kept."""
+    t = np.ascontiguousarray(temps, np.float64)
+    out = np.zeros(t.shape, np.float64)
+    if lib().mcbrat_planck_radiance(float(lambda_um), t.size, ptr(t), ptr(out)) != 0:
+        raise McbratError("planck_radiance: the wavelength must be positive")
+    return out
+
+
+def planck_sources(thisDomain, surfaceTemp):
+    """(cellSource, surfaceSource) for Integrator.renderCameraEmission / renderSensorsEmission: the
+    Planck radiance of the domain's temperatures, [nz, ny, nx] float32, and that of surfaceTemp, [ny, nx] float32 (one value for
+    every column), at the domain's wavelength, in W m-2 sr-1 um-1."""
+    info = thisDomain.getInfo_Domain()
+    if info["temps"] is None:
+        raise McbratError("planck_sources: domain has no temperatures")
+    nx, ny = info["numX"], info["numY"]
+    cell = planck_radiance(thisDomain.lambda_um, np.ascontiguousarray(info["temps"].transpose(2, 1, 0)))
+    sfc = planck_radiance(thisDomain.lambda_um, np.full((ny, nx), float(surfaceTemp)))
+    return cell.astype(np.float32), sfc.astype(np.float32)
+
+
 def _check_mu(solarMu):
     if abs(solarMu) > 1.0 or abs(solarMu) <= np.finfo(np.float32).tiny:
         raise McbratError("setIllumination: solarMu out of bounds")

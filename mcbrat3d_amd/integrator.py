@@ -504,6 +504,58 @@ class Integrator:
         return {"irradiance": dif + dirc, "irradiance_StdErr": eTot, "diffuse": dif, "direct": dirc, "diffuse_StdErr": eDif,
                 "direct_StdErr": eDir, "batchMeans": means, "dropped": int(dropped.value)}
 
+    # -- the emission renders ----------------------------------------
+    def prepareDomain(self, thisDomain):
+        """What prepare() uploads of the domain -- optical grids and tables -- without a source: all an emission render needs."""
+        self.specifyParameters()
+        self._load_domain(thisDomain)
+
+    def _emission_sources(self, name, cellSource, surfaceSource):
+        if self._loaded_domain is None:
+            raise McbratError(name + ": no domain loaded: call prepareDomain(domain), prepare(domain, photons) or "
+                              "computeRadiativeTransfer first.")
+        if cellSource is None or surfaceSource is None:
+            raise McbratError(name + ": cellSource and surfaceSource are needed (mcbrat3d_amd.planck_sources).")
+        nx, ny, nz = self._dims
+        cell, sfc = np.ascontiguousarray(cellSource, np.float32), np.ascontiguousarray(surfaceSource, np.float32)
+        if cell.size != nx * ny * nz or sfc.size != nx * ny:
+            raise McbratError(name + ": cellSource must hold numZ x numY x numX values and surfaceSource numY x numX.")
+        return cell, sfc
+
+    def renderCameraEmission(self, camera, randomNumbers, samplesPerPixel, numBatches=1, cellSource=None, surfaceSource=None):
+        """The emitted (thermal) radiance at `camera` by backward Monte Carlo: renderCamera's paths, which deposit the source
+        function where they collide and where they meet the surface instead of looking toward the sun.  cellSource [nz, ny, nx]
+        and surfaceSource [ny, nx] are Planck radiances (mcbrat3d_amd.planck_sources); the result has their units.  The loaded
+        source is not consulted (none need be loaded: prepareDomain).  Returns what renderCamera returns."""
+        cell, sfc = self._emission_sources("renderCameraEmission", cellSource, surfaceSource)
+        s = camera.struct()
+        npx, npy, nb = camera.npx, camera.npy, int(numBatches)
+        rad, err = np.zeros((npy, npx), np.float32), np.zeros((npy, npx), np.float32)
+        means = np.zeros((max(nb, 1), npy, npx), np.float32)
+        dropped = C.c_int64(0)
+        self._check(self._lib.mcbrat_render_camera_emission(self._ctx, C.addressof(s), ptr(cell), ptr(sfc), randomNumbers.seed,
+                                                            randomNumbers.nextPhotonId, int(samplesPerPixel), nb, ptr(rad), ptr(err),
+                                                            ptr(means), C.addressof(dropped)))
+        randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
+        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value), "emission": True}
+
+    def renderSensorsEmission(self, sensors, randomNumbers, samplesPerSensor, numBatches=1, cellSource=None, surfaceSource=None,
+                              gridInLds=-1):
+        """The emitted (thermal) irradiance (planar sensors: a pyrgeometer) and actinic flux (spherical ones) at `sensors`, in
+        the sources' units times steradians.  Returns "irradiance", "irradiance_StdErr" (one value per sensor), "batchMeans"
+        [numBatches, n] and "dropped"; there is no direct part ("emission": True marks the dict for the NetCDF writers)."""
+        cell, sfc = self._emission_sources("renderSensorsEmission", cellSource, surfaceSource)
+        n, nb = len(sensors), int(numBatches)
+        arr = sensors.structs()
+        irr, err = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        means = np.zeros((max(nb, 1), n), np.float32)
+        dropped = C.c_int64(0)
+        self._check(self._lib.mcbrat_render_sensors_emission(self._ctx, n, C.addressof(arr), ptr(cell), ptr(sfc), randomNumbers.seed,
+                                                             randomNumbers.nextPhotonId, int(samplesPerSensor), nb, int(gridInLds),
+                                                             ptr(irr), ptr(err), ptr(means), C.addressof(dropped)))
+        randomNumbers.nextPhotonId += int(samplesPerSensor) * nb
+        return {"irradiance": irr, "irradiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value), "emission": True}
+
     def sunTransmittance(self, points):
         """exp(-optical depth) from each point (an [n, 3] array of x, y, z) toward the sun up to the top of the loaded
         domain: the direct transmittance at a point, without noise (mcbrat_sun_transmittance)."""

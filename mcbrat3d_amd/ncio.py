@@ -252,6 +252,10 @@ def writeResults_netcdf(outputFileName, domainFileName, stats, xPosition, yPosit
 
 
 SENSOR_VARIABLES = ("sensorIrradiance", "sensorIrradiance_StdErr", "sensorDiffuse", "sensorDirect")
+# an emission render (result["emission"]): the emitted irradiance, in the sources' units times steradians
+SENSOR_EMISSION_VARIABLES = ("sensorEmission", "sensorEmission_StdErr")
+CAMERA_VARIABLES = ("cameraRadiance", "cameraRadiance_StdErr")
+CAMERA_EMISSION_VARIABLES = ("cameraEmission", "cameraEmission_StdErr")
 
 
 def _add_sensors(f, sensors, result):
@@ -267,7 +271,8 @@ def _add_sensors(f, sensors, result):
     f.createVariable("sensorPosition", "d", ("sensor", "xyz"))[:] = np.asarray(sensors.positions, np.float64)
     f.createVariable("sensorNormal", "d", ("sensor", "xyz"))[:] = np.asarray(sensors.normals, np.float64)
     f.createVariable("sensorKind", "i", ("sensor",))[:] = np.asarray(sensors.kinds, np.int32)
-    for name, key in zip(SENSOR_VARIABLES, ("irradiance", "irradiance_StdErr", "diffuse", "direct")):
+    names = SENSOR_EMISSION_VARIABLES if result.get("emission") else SENSOR_VARIABLES
+    for name, key in zip(names, ("irradiance", "irradiance_StdErr", "diffuse", "direct")):
         f.createVariable(name, "f", ("sensor",))[:] = np.asarray(result[key], np.float32)
 
 
@@ -289,7 +294,8 @@ def readSensors_netcdf(fileName):
     try:
         if "sensor" not in f.dimensions:
             return None
-        out = {k: np.array(f.variables[k][:]) for k in ("sensorPosition", "sensorNormal", "sensorKind") + SENSOR_VARIABLES}
+        names = SENSOR_EMISSION_VARIABLES if SENSOR_EMISSION_VARIABLES[0] in f.variables else SENSOR_VARIABLES
+        out = {k: np.array(f.variables[k][:]) for k in ("sensorPosition", "sensorNormal", "sensorKind") + names}
         out.update(sensorSamples=float(f.sensorSamples), sensorBatches=int(f.sensorBatches), sensorDroppedPaths=float(f.sensorDroppedPaths))
         return out
     finally:
@@ -311,8 +317,25 @@ def _add_camera(f, camera, result):
     f.cameraDroppedPaths = np.float64(result["dropped"])
     f.createDimension("cameraX", camera.npx)
     f.createDimension("cameraY", camera.npy)
-    f.createVariable("cameraRadiance", "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance"], np.float32)
-    f.createVariable("cameraRadiance_StdErr", "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance_StdErr"], np.float32)
+    names = CAMERA_EMISSION_VARIABLES if result.get("emission") else CAMERA_VARIABLES
+    f.createVariable(names[0], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance"], np.float32)
+    f.createVariable(names[1], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance_StdErr"], np.float32)
+
+
+def readCamera_netcdf(fileName):
+    """The camera variables of a file writeResults_netcdf or writeCamera_netcdf wrote, as a dict of arrays -- cameraRadiance and
+    cameraRadiance_StdErr, or cameraEmission and cameraEmission_StdErr for an emission render -- (None where the file holds no image)."""
+    f = netcdf_file(fileName, "r", mmap=False)
+    try:
+        if "cameraX" not in f.dimensions:
+            return None
+        names = CAMERA_EMISSION_VARIABLES if CAMERA_EMISSION_VARIABLES[0] in f.variables else CAMERA_VARIABLES
+        out = {k: np.array(f.variables[k][:]) for k in names}
+        out.update(cameraSamplesPerPixel=float(f.cameraSamplesPerPixel), cameraBatches=int(f.cameraBatches),
+                   cameraDroppedPaths=float(f.cameraDroppedPaths))
+        return out
+    finally:
+        f.close()
 
 
 def writeCamera_netcdf(outputFileName, camera, result):
