@@ -35,7 +35,8 @@ module mcbrat_hip_integrator
             specifySideFluxes, reportSideFluxes, &
             camera, renderCamera, sunTransmittance, &
             sensor, renderSensors, &
-            renderCameraEmission, renderSensorsEmission
+            renderCameraEmission, renderSensorsEmission, &
+            renderCameraPathLengths
 
   ! mcbrat_camera of include/mcbrat.h, member for member (the backward camera, DESIGN.md section 4.19): kind 0 orthographic --
   ! mu, phiDeg, the footprint xLo .. yHi and the height z -- or 1 pinhole -- position, look, up, fovXDeg
@@ -274,6 +275,20 @@ module mcbrat_hip_integrator
       import :: c_ptr, c_int, c_int32_t, c_int64_t, camera
       type(c_ptr), value :: ctx
       type(camera), intent(in) :: cam
+      integer(c_int64_t), value :: seed, firstSample, samplesPerPixel
+      integer(c_int32_t), value :: numBatches
+      type(c_ptr), value :: radiance, radianceStdErr, batchMeans   ! (c_null_ptr: not wanted; radiance is needed)
+      integer(c_int64_t), intent(out) :: dropped
+      integer(c_int) :: rc
+    end function
+    function mcbrat_render_camera_pathlengths(ctx, cam, numBins, pathEdges, seed, firstSample, samplesPerPixel, numBatches, &
+                                              radiance, radianceStdErr, batchMeans, dropped) &
+                                              bind(C, name="mcbrat_render_camera_pathlengths") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_float, camera
+      type(c_ptr), value :: ctx
+      type(camera), intent(in) :: cam
+      integer(c_int32_t), value :: numBins
+      real(c_float), intent(in) :: pathEdges(*)
       integer(c_int64_t), value :: seed, firstSample, samplesPerPixel
       integer(c_int32_t), value :: numBatches
       type(c_ptr), value :: radiance, radianceStdErr, batchMeans   ! (c_null_ptr: not wanted; radiance is needed)
@@ -958,6 +973,36 @@ contains
                                 pErr, c_null_ptr, dropped)
     if (present(numDropped)) numDropped = dropped
   end subroutine renderCamera
+
+  ! The radiance by photon path length (include/mcbrat.h: mcbrat_render_camera_pathlengths): renderCamera's paths, every estimate in
+  ! the bin of its path length.  pathEdges: the bins' lower edges (the first 0, ascending, at most 256; the last bin is open
+  ! above); radiance(npx, npy, size(pathEdges)) sums over its last dimension to renderCamera's image.
+  subroutine renderCameraPathLengths(this, cam, pathEdges, seed, firstSample, samplesPerPixel, numBatches, radiance, radianceStdErr, &
+                                     numDropped, ierr)
+    type(integrator), intent(inout) :: this
+    type(camera), intent(in) :: cam
+    real, dimension(:), contiguous, intent(in) :: pathEdges
+    integer(c_int64_t), intent(in) :: seed, firstSample, samplesPerPixel
+    integer, intent(in) :: numBatches
+    real, dimension(:, :, :), contiguous, target, intent(out) :: radiance
+    real, dimension(:, :, :), contiguous, optional, target, intent(out) :: radianceStdErr
+    integer(c_int64_t), optional, intent(out) :: numDropped
+    integer, intent(out) :: ierr
+    type(c_ptr) :: pErr
+    integer(c_int64_t) :: dropped
+    ierr = 1
+    if (size(pathEdges) < 1) return
+    if (any(shape(radiance) /= (/ cam%npx, cam%npy, size(pathEdges) /))) return
+    pErr = c_null_ptr
+    if (present(radianceStdErr)) then
+      if (any(shape(radianceStdErr) /= (/ cam%npx, cam%npy, size(pathEdges) /))) return
+      pErr = c_loc(radianceStdErr)
+    end if
+    dropped = 0
+    ierr = mcbrat_render_camera_pathlengths(this%ctx, cam, int(size(pathEdges), c_int32_t), pathEdges, seed, firstSample, &
+                                            samplesPerPixel, int(numBatches, c_int32_t), c_loc(radiance), pErr, c_null_ptr, dropped)
+    if (present(numDropped)) numDropped = dropped
+  end subroutine renderCameraPathLengths
 
   ! Backward sensors (include/mcbrat.h: mcbrat_render_sensors): numBatches batches of samplesPerSensor paths per sensor for the
   ! domain and the Directional solar source the integrator holds (the forward tables must have been set: setForwardTable).

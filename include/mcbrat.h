@@ -370,6 +370,8 @@ int mcbrat_set_tuning(mcbrat_ctx *ctx, int32_t blocksPerCU, int32_t eventThresho
  *                 and the parallel sun compiled in would do (default 0: automatic; both trace every photon bit for bit alike --
  *                 tests/test_gpu_blockwalk_rare.py)
  *   "cameraGridInLds"  where mcbrat_sun_transmittance reads the grid: -1 (default) LDS where it fits, 0 global memory, 1 LDS
+ *   "cameraPathBinsInLds"  0: mcbrat_render_camera_pathlengths adds every estimate straight to global memory (default 1: a
+ *                 histogram per wave in LDS; integer sums, the same bytes either way)
  * One option does change results, within their noise -- it chooses between two unbiased estimators:
  *   "glintSampling"  1 (default): a reflection off a Cox-Munk patch draws its direction from the mixture of the glint lobe and
  *                 the Lambertian draw (mcbrat_set_surface_brdf); 0: the Lambertian draw times R, as the land models
@@ -543,6 +545,27 @@ int mcbrat_render_sensors_emission(mcbrat_ctx *ctx, int64_t n, const mcbrat_sens
  * in W m-2 sr-1 um-1, so that forward `intensity` x totalFlux / dLambda and the emission camera's radiance on these sources are
  * one quantity.  Host arithmetic only.  Returns 1 for a null array, a negative n or a wavelength that is not positive. */
 int mcbrat_planck_radiance(double lambdaMicrons, int64_t n, const double *temps, double *out);
+
+/* ---- the radiance by photon path length (an addition under ABI version 3) ---------------------------------
+ * mcbrat_render_camera's radiance split by how far the light travelled inside the domain: the same camera, sample indices,
+ * Philox counters, batches and statistics -- the same (seed, sample range) walks the same paths --, every local estimate tallied
+ * on its own in the bin of its path length L = sum of the backward legs walked up to the event + (zMax - z_event) / mu0, the
+ * geometric length (in the domain's length unit) from where the light enters at zMax to the camera.  Bins are given by numBins
+ * LOWER edges, floats: pathEdges[0] = 0, strictly ascending, finite; bin b holds pathEdges[b] <= L < pathEdges[b + 1], the last
+ * bin is open above, so the bins of a pixel sum to its radiance (to the rounding of a per-estimate fixed point against
+ * mcbrat_render_camera's per-path one).  1 <= numBins <= 256.  The sums are integers: an image is bitwise independent of
+ * scheduling and of gridInLds.  By the equivalence theorem, sum_b I_b exp(-k L_b) is the radiance under a uniform absorber k.
+ * `dropped` counts the paths a bound ended or that produced a NaN estimate; unlike mcbrat_render_camera's, such a path keeps
+ * what it had deposited before.  Option "cameraPathBinsInLds" (mcbrat_set_option: 1 default, 0 every deposit straight to global
+ * memory -- the same integers, a measurement of what the histograms in LDS buy).
+ * Refused, before any launch, with texts that begin "renderCameraPathLengths:": a null array; what mcbrat_render_camera refuses
+ * about the camera's own members; numBins outside [1, 256]; edges that are not finite, do not begin at 0 or do not ascend; then
+ * everything mcbrat_render_camera refuses, in its order (the budget counts npx * npy * numBins * numBatches sums); gridInLds = 1
+ * where the grid fits the LDS share alone but not with the histograms (-1 then renders from global memory). */
+int mcbrat_render_camera_pathlengths(mcbrat_ctx *ctx, const mcbrat_camera *cam, int32_t numBins, const float *pathEdges /* [numBins] */,
+                                     uint64_t seed, uint64_t firstSample, int64_t samplesPerPixel /* per batch */, int32_t numBatches,
+                                     float *radiance /* [numBins][npy][npx] */, float *radianceStdErr /* same shape, may be NULL */,
+                                     float *batchMeans /* [numBatches][numBins][npy][npx], may be NULL */, int64_t *dropped /* may be NULL */);
 
 /* Walk options (negative = leave unchanged).
  * layerSkip (default 1): inside a horizontal layer whose cells all carry one extinction value -- the clear air

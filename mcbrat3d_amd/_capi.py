@@ -119,6 +119,7 @@ SYMBOLS = {
     "mcbrat_render_camera_emission": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_render_sensors_emission": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_planck_radiance": (C.c_int, [_d, _i64, _vp, _vp]),
+    "mcbrat_render_camera_pathlengths": (C.c_int, [_vp, _vp, _i32, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),
     "mcbrat_inverse_table_legendre": (C.c_int, [_i32, _vp, _i32, _vp]),
     "mcbrat_inverse_table_tabulated": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
@@ -128,7 +129,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes, mcbrat_settings_refusal, the backward camera and the backward sensors are additions under 3)
+ABI_VERSION = 3  # MCBRAT_ABI_VERSION of include/mcbrat.h this binding was written against (badPhotons since 2, mcbrat_set_option since 3; surface BRDFs, level fluxes, their direct / diffuse separation, the actinic flux, side fluxes, mcbrat_settings_refusal, the backward camera, the backward sensors, the emission renders and the radiance by path length are additions under 3)
 
 
 def hip_runtimes():

@@ -102,3 +102,41 @@ def new_Camera(kind="orthographic", npx=1, npy=1, jitter=True, gridInLds=-1, mu=
     if not (0.0 < fov < 180.0):
         raise McbratError("new_Camera: the field of view must be in (0, 180) degrees.")
     return Camera(kind, int(npx), int(npy), bool(jitter), int(gridInLds), 1.0, 0.0, (0.0, 1.0, 0.0, 1.0), 0.0, position, look, up, fov)
+
+
+# -- the radiance by photon path length (Integrator.renderCameraPathLengths) ---------------------------
+def _by_length(radianceByLength, pathEdges):
+    rad = np.asarray(radianceByLength, np.float64)
+    e = np.asarray(pathEdges, np.float64).reshape(-1)
+    if rad.ndim < 1 or rad.shape[0] != e.size or e.size < 1:
+        raise McbratError("path lengths: radianceByLength must be [bin, ...] with one bin per edge of pathEdges.")
+    return rad, e.reshape((-1,) + (1,) * (rad.ndim - 1))
+
+
+def absorbed_radiance(radianceByLength, pathEdges, k):
+    """(lower, upper) bounds of the radiance under a uniform absorber of extinction k (per unit length of pathEdges), from a
+    render WITHOUT it -- the equivalence theorem, I(k) = sum_b I_b exp(-k L_b), with every length of bin b put at its upper edge
+    (lower: the open last bin gives 0) and at its lower edge (upper).  radianceByLength is [bin, ...]; the bounds have its
+    remaining shape.  k = 0: both are the sum of the bins."""
+    rad, e = _by_length(radianceByLength, pathEdges)
+    k = float(k)
+    if not (k >= 0.0) or not math.isfinite(k):
+        raise McbratError("absorbed_radiance: k must be finite and not negative.")
+    upper = (rad * np.exp(-k * e)).sum(axis=0)
+    if k == 0.0:
+        return upper.copy(), upper
+    lower = (rad[:-1] * np.exp(-k * e[1:])).sum(axis=0)
+    return lower, upper
+
+
+def mean_path_length(radianceByLength, pathEdges):
+    """(lower, upper) bounds of the radiance-weighted mean path length <L> = sum_b I_b L_b / sum_b I_b over the CLOSED bins (all but
+    the open last one, whose lengths have no upper bound): every length at its bin's lower edge, and at its upper edge.  NaN
+    where the closed bins hold nothing."""
+    rad, e = _by_length(radianceByLength, pathEdges)
+    closed = rad[:-1]
+    total = closed.sum(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lower = (closed * e[:-1]).sum(axis=0) / total
+        upper = (closed * e[1:]).sum(axis=0) / total
+    return lower, upper

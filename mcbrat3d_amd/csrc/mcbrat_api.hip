@@ -195,6 +195,7 @@ struct mcbrat_ctx {
   DeviceBuffer<double> dFreqCdf;
   DeviceBuffer<unsigned long long> dFreqCounts;
   int cameraGridInLds = -1;  // option "cameraGridInLds": where mcbrat_sun_transmittance reads the grid (-1: LDS where it fits)
+  int cameraPathBinsInLds = 1;  // option "cameraPathBinsInLds": 0, a path-length render deposits straight to global memory
   bool countersOn = false;
   float lastTraceMs = 0.f;
   mcbrat_counters lastCounters{};
@@ -1067,7 +1068,7 @@ int mcbrat_camera_context(mcbrat_ctx *c, CameraContext *out, bool needTables) {
   out->haveGrid = c->haveGrid; out->haveOptics = c->haveGrid && c->haveOptics; out->haveSource = c->haveSource;
   out->solarDirectional = c->haveSource && c->srcKind == 0 && c->solarKind == 0;
   out->brdfSurface = c->surfNumX > 0 && c->surfKind != 0;
-  out->nc = c->nc; out->gridInLds = c->cameraGridInLds;
+  out->nc = c->nc; out->gridInLds = c->cameraGridInLds; out->pathBinsInLds = c->cameraPathBinsInLds;
   out->xe = &c->xe; out->ye = &c->ye; out->ze = &c->ze;
   out->fwd = &c->fwdOrig; out->fwdNAngles = &c->fwdNAngles; out->fwdNEntries = &c->fwdNEntries; out->maxPfi = &c->maxPfi;
   if (!out->haveOptics) return 0;
@@ -1693,6 +1694,7 @@ int mcbrat_set_option(mcbrat_ctx *c, const char *name, int32_t value) {
   else if (n == "blockRareKernel") c->blockRareKernel = value != 0;
   else if (n == "glintSampling") c->glintSampling = value != 0;
   else if (n == "cameraGridInLds") c->cameraGridInLds = std::max(-1, std::min(1, (int)value));
+  else if (n == "cameraPathBinsInLds") c->cameraPathBinsInLds = value != 0;
   else return fail(c, "set_option: unknown option '" + n + "'");
   return 0;
 }

@@ -17,12 +17,12 @@ constexpr double kFlattestLeg = 65536.0;                // 1 / |cosine| of the f
 
 // A ray toward the sun (`sun`: unit vector toward it) from anywhere in a domain H high and Lx x Ly wide, to the top: nz layers,
 // and nx (ny) faces per domain length travelled along x (y), one length more for the part periods at both ends
-struct SunBound { unsigned maxCross; float invFourPiMu0; };
+struct SunBound { unsigned maxCross; float invFourPiMu0, invMu0; };  // invMu0: the ray's length per unit height (section 4.23)
 inline SunBound sun_bound(int nx, int ny, int nz, double H, double Lx, double Ly, const float sun[3]) {
   const double muz = std::max((double)std::fabs(sun[2]), (double)FLT_MIN);
   const double wrapsX = std::floor(H * std::fabs((double)sun[0]) / muz / Lx) + 2.0, wrapsY = std::floor(H * std::fabs((double)sun[1]) / muz / Ly) + 2.0;
   const double n = (double)nz + wrapsX * nx + wrapsY * ny + 8.0;
-  return {(unsigned)std::min(n, 4294967295.0), (float)(1.0 / (4.0 * 3.14159265358979323846 * muz))};
+  return {(unsigned)std::min(n, 4294967295.0), (float)(1.0 / (4.0 * 3.14159265358979323846 * muz)), (float)(1.0 / muz)};
 }
 
 // A leg: as a ray whose |cosine| is 2^-16; a flatter one that has not ended by then (in a vacuum) is dropped and counted
@@ -58,6 +58,11 @@ inline LaunchShape launch_shape(unsigned long long total, int numCUs, int block)
   const unsigned long long perLane = std::max<unsigned long long>(1, (total + lanes - 1) / lanes), perBlock = perLane * (unsigned long long)block;
   return {perLane, (total + perBlock - 1) / perBlock};
 }
+
+// A path-length render keeps, behind the grid's share of LDS (rounded up to the 8 bytes a sum needs),
+// one histogram of numBins 8-byte sums per wave of the workgroup and then the numBins edges as floats
+constexpr size_t path_lds_offset(size_t gridBytes) { return (gridBytes + 7) & ~(size_t)7; }
+constexpr size_t path_lds_bytes(int numBins, int block) { return (size_t)numBins * (8 * (size_t)(block / 64) + 4); }
 
 // One series of batch means, given as its DIFFERENCES to the first batch (identical batches: exactly 0 throughout): the mean of
 // the series is the first batch's value plus shift(), error() is the standard error of that mean

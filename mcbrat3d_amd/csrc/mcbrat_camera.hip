@@ -31,6 +31,11 @@
 // true> is the same path with the thermal estimator -- a collision deposits w (1 - omega0) S_cell and the surface w (1 - a) S_sfc
 // before the weight is cut, no ray walks toward the sun, a sensor has no direct part.
 //
+// The radiance by photon path length (mcbrat_render_camera_pathlengths): camera_kernel<.., PATHLEN = true>
+// is the solar camera's path with the lane carrying the length of the legs walked -- every estimate goes to fixed point on its
+// own and is added to the bin (mcbrat_pathbins.h) of that length plus the sun ray's (zMax - z) / mu0: a histogram per wave in
+// LDS, flushed to the strip [batch][pixel][bin] of global memory when the wave moves on to another pixel.
+//
 // Component pick, roulette, scattering angle and new direction are written out here as they are in trace_kernel
 // (mcbrat_kernels.hip, HOT ROWS) and trace_block_kernel (mcbrat_blockwalk.hip, HOT ROWS): a change to one of those rules is made
 // in all three.  What mcbrat_photon.h shares (Philox, u01, lambert_direction, find_cell, surface_reflectance, ...) is called.
@@ -48,6 +53,7 @@
 #include "mcbrat_sensor_ray.h"
 #include "mcbrat_camera_ctx.h"
 #include "mcbrat_backward.h"
+#include "mcbrat_pathbins.h"
 #include "mcbrat_devmem.h"
 
 namespace mcbrat {
@@ -85,6 +91,11 @@ struct CamParams {
   const float *srcCell;            // [nz][ny][nx], x fastest
   const float *srcSurface;         // [ny][nx]
   double invSrcMax;                // 1 / the largest source value: a path's sum is tallied in units of it
+  // mcbrat_render_camera_pathlengths (PATHLEN instantiations): bins is [nBatches][npix][numBins]
+  const float *pathEdges;          // [numBins] lower edges of the path-length bins
+  int numBins;
+  int pathDirect;                  // every deposit straight to global memory (option cameraPathBinsInLds = 0: a measurement)
+  float invMu0;                    // 1 / mu0: the sun ray's geometric length is (zMax - z) / mu0
 };
 
 struct GridView { const double *xe, *ye, *ze; const float *ext; };
@@ -213,15 +224,64 @@ __device__ __forceinline__ void wave_add(long long *bins, uint32_t bin, long lon
   }
 }
 
+// One estimate of a path of a PATHLEN instantiation: to fixed point on its own, capped by what the path
+// has left of its budget, and added to bin path_bin(L) of the path's pixel -- in the wave's histogram in LDS (`hist`, where the
+// wave's 64 indices share a pixel: `toLds`) or straight in global memory (`strip`: the pixel's numBins sums).  false: the
+// estimate is a NaN, nothing is deposited
+using LdsSum = __attribute__((address_space(3))) unsigned long long;  // a sum of a wave's histogram: in LDS by its type
+__device__ __forceinline__ bool path_deposit(const CamParams &cp, const float *edges, LdsSum *hist, bool toLds, long long *strip, float est,
+                                             float L, long long &left) {
+  if (!(est == est)) return false;
+  long long v = __double2ll_rn(fmin((double)est * cp.scale, cp.pathMax));
+  v = v < left ? v : left;
+  left -= v;
+  if (v != 0) {
+    const int b = path_bin(edges, cp.numBins, L);
+    if (toLds) __hip_atomic_fetch_add(hist + b, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    else atomicAdd(reinterpret_cast<unsigned long long *>(strip + b), (unsigned long long)v);
+  }
+  return true;
+}
+
+// Every lane of a wave calls this in step: the wave's non-empty sums go to the strip of its pixel in global memory, one atomic
+// each, and the histogram is empty again
+__device__ __forceinline__ void path_flush(LdsSum *hist, long long *strip, int numBins, int lane) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  for (int b = lane; b < numBins; b += kWave) {
+    const unsigned long long v = hist[b];
+    if (v != 0ull) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(strip + b), v);
+      hist[b] = 0ull;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
 // SENSOR: the path starts on a receiver (mcbrat_sensor_ray.h) instead of in a pixel, the sensor's id
 // stands where the pixel stands in the counter, and a second sum takes the direct beam at the origin; from there on the path is
 // the camera's.
 // EMIT: the thermal estimator on the same path.  No ray toward the sun and no forward table: a collision
 // deposits w (1 - omega0) S_cell BEFORE w *= omega0, the surface w (1 - a) S_sfc before w *= a, and a sensor has no direct part.
-template <int BLOCK, bool GRID_LDS, bool SENSOR, bool EMIT>
+// PATHLEN (the solar camera only): the radiance by photon path length.  The lane carries the length L of
+// the legs walked; every estimate is tallied on its own, at L plus the sun ray's (zMax - z) / mu0, in a histogram per wave.
+template <int BLOCK, bool GRID_LDS, bool SENSOR, bool EMIT, bool PATHLEN = false>
 __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
+  static_assert(!PATHLEN || (!SENSOR && !EMIT), "path lengths: the solar camera only");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
+  // PATHLEN: behind the grid, a histogram per wave and the edges (mcbrat_backward.h: path_lds_offset, path_lds_bytes)
+  LdsSum *hist = nullptr;
+  const float *edges = nullptr;
+  if constexpr (PATHLEN) {
+    const size_t gridBytes = GRID_LDS ? sizeof(double) * (size_t)(p.nx + p.ny + p.nz + 3) + sizeof(float) * (size_t)p.nx * p.ny * p.nz : 0;
+    unsigned long long *s_hist = reinterpret_cast<unsigned long long *>(smem_raw + path_lds_offset(gridBytes));
+    float *s_edges = reinterpret_cast<float *>(s_hist + (size_t)(BLOCK / kWave) * cp.numBins);
+    for (int i = threadIdx.x; i < (BLOCK / kWave) * cp.numBins; i += BLOCK) s_hist[i] = 0ull;
+    for (int i = threadIdx.x; i < cp.numBins; i += BLOCK) s_edges[i] = cp.pathEdges[i];
+    __syncthreads();
+    hist = (LdsSum *)(s_hist + (size_t)(threadIdx.x >> 6) * cp.numBins);
+    edges = s_edges;
+  }
   constexpr float kPi = 3.14159265358979312f;
   const int lane = threadIdx.x & (kWave - 1);
   const unsigned long long wave = ((unsigned long long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
@@ -231,9 +291,24 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
   unsigned long long pendBin = ~0ull;  // the bin the lane is summing for, and its sum (the camera; a sensor's wave adds after every path)
   long long pend = 0;
   unsigned nDropped = 0;
+  unsigned long long tag = ~0ull;      // PATHLEN: the (batch, pixel) the wave's histogram holds sums of; ~0: none
+  bool shared = false;                 // PATHLEN: the round's 64 indices share a (batch, pixel): its deposits go to the histogram
 
   for (unsigned long long j = 0; j < cp.pathsPerLane; ++j) {
     const unsigned long long index = chunk + j * kWave + (unsigned long long)lane;
+    if constexpr (PATHLEN) {
+      // the same for every lane of the wave, and before any lane leaves the loop: all 64 take part in a flush
+      const unsigned long long base = chunk + j * kWave;
+      if (base >= cp.total) break;
+      const unsigned long long last = base + (kWave - 1) < cp.total ? base + (kWave - 1) : cp.total - 1;
+      const unsigned long long binFirst = base / cp.spp;
+      shared = !cp.pathDirect && last / cp.spp == binFirst;
+      if (tag != ~0ull && !(shared && tag == binFirst)) {
+        path_flush(hist, cp.bins + tag * (unsigned long long)cp.numBins, cp.numBins, lane);
+        tag = ~0ull;
+      }
+      if (shared) tag = binFirst;
+    }
     if constexpr (!SENSOR) {
       if (index >= cp.total) break;
     }
@@ -245,7 +320,7 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
     const unsigned long long sample = cp.firstSample + batch * cp.spp + k;
     const uint32_t sLo = (uint32_t)sample, sHi = (uint32_t)(sample >> 32);
     uint32_t pix = (uint32_t)pixel;
-    if constexpr (!SENSOR) {
+    if constexpr (!SENSOR && !PATHLEN) {
       if (bin != pendBin) {
         if (pend != 0) atomicAdd(reinterpret_cast<unsigned long long *>(cp.bins + pendBin), (unsigned long long)pend);
         pendBin = bin; pend = 0;
@@ -281,6 +356,9 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       locate(p, g, r);
     }
     float w = 1.0f, sum = 0.0f;
+    float pathL = 0.0f;                  // PATHLEN: the length of the legs walked, and what the path may still deposit
+    long long left = (long long)cp.pathMax;
+    long long *const strip = PATHLEN ? cp.bins + bin * (unsigned long long)cp.numBins : nullptr;
     for (uint32_t event = 1;; ++event) {
       if constexpr (SENSOR) {
         if (dropped) break;
@@ -297,6 +375,7 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       // where the leg ended, in the periodic image the walk stands in
       r.ox = r.ox + (double)r.dx * (double)t;
       r.oy = r.oy + (double)r.dy * (double)t;
+      if constexpr (PATHLEN) pathL += t;
       if (end == END_SURFACE) {
         r.oz = p.zSurf;
         if constexpr (EMIT) {
@@ -317,7 +396,12 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
         bool bound;
         const float T = sun_transmittance(p, cp, g, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, bound);
         if (bound) { dropped = true; break; }
-        sum += w * T * (1.0f / kPi);
+        if constexpr (PATHLEN) {
+          const float Lsun = (float)(p.zMax - r.oz) * cp.invMu0;
+          if (!path_deposit(cp, edges, hist, shared, strip, w * T * (1.0f / kPi), pathL + Lsun, left)) { dropped = true; break; }
+        } else {
+          sum += w * T * (1.0f / kPi);
+        }
         float mu = sqrtf(uX);
         if (mu == 0.0f) mu = fmaxf(sqrtf(uZ), 1.52587890625e-05f);  // (a draw of exactly 0: the spare number, at least 2^-16)
         lambert_direction(mu, uY, r.dx, r.dy, r.dz);
@@ -358,7 +442,12 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
         bool bound;
         const float T = sun_transmittance(p, cp, g, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, bound);
         if (bound) { dropped = true; break; }
-        sum += (w * val) * (T * cp.invFourPiMu0);
+        if constexpr (PATHLEN) {
+          const float Lsun = (float)(p.zMax - r.oz) * cp.invMu0;
+          if (!path_deposit(cp, edges, hist, shared, strip, (w * val) * (T * cp.invFourPiMu0), pathL + Lsun, left)) { dropped = true; break; }
+        } else {
+          sum += (w * val) * (T * cp.invFourPiMu0);
+        }
       }
       if (p.useRR && w < 0.5f) {  // Russian roulette, RussianRouletteW = 1
         uint32_t q1[4];
@@ -424,6 +513,9 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       const long long vDirect = ok ? __double2ll_rn(fmin((double)sumDirect * cp.scale, cp.pathMax)) : 0;
       wave_add(cp.bins, bin32, vDiffuse, lane);
       wave_add(cp.binsDirect, bin32, vDirect, lane);
+    } else if constexpr (PATHLEN) {
+      // (what the path deposited before a bound or a NaN ended it stays in its bins: the plain camera drops such a path whole)
+      if (dropped) nDropped++;
     } else {
       if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
         nDropped++;
@@ -435,7 +527,10 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
     }
   }
 
-  if constexpr (!SENSOR) {
+  if constexpr (PATHLEN) {
+    if (tag != ~0ull) path_flush(hist, cp.bins + tag * (unsigned long long)cp.numBins, cp.numBins, lane);
+  }
+  if constexpr (!SENSOR && !PATHLEN) {
     // The lanes of a wave mostly hold sums for ONE bin (pixel-major indices, samplesPerPixel >= 64): then one add per wave.
     const bool have = pend != 0;
     const unsigned long long haveMask = __ballot(have);
@@ -496,12 +591,12 @@ bool inside(const DevParams &p, double z) { return z >= p.z0 && z <= p.zMax; }
 void sun_setup(const DevParams &p, CamParams &cp) {
   for (int a = 0; a < 3; ++a) cp.sun[a] = -p.dir0[a];
   const SunBound b = sun_bound(p.nx, p.ny, p.nz, p.zMax - p.z0, p.Lx, p.Ly, cp.sun);
-  cp.maxSunCross = b.maxCross; cp.invFourPiMu0 = b.invFourPiMu0;
+  cp.maxSunCross = b.maxCross; cp.invFourPiMu0 = b.invFourPiMu0; cp.invMu0 = b.invMu0;
 }
 
-// 0: global memory, 1: LDS; -1 refused (asked for, does not fit)
-int choose_grid_lds(const CameraContext &v, int asked) {
-  const bool fits = grid_lds_bytes(v.p) <= std::min(kCameraGridLds, v.ldsPerCU / 2);
+// 0: global memory, 1: LDS; -1 refused (asked for, does not fit).  extra: what the entry keeps in LDS beside the grid
+int choose_grid_lds(const CameraContext &v, int asked, size_t extra = 0) {
+  const bool fits = (extra ? path_lds_offset(grid_lds_bytes(v.p)) : grid_lds_bytes(v.p)) + extra <= std::min(kCameraGridLds, v.ldsPerCU / 2);
   if (asked == 1 && !fits) return -1;
   return asked == 0 ? 0 : (fits ? 1 : 0);
 }
@@ -511,9 +606,11 @@ using BackwardKernel = void (*)(const DevParams, const CamParams);
 // The solar instantiations (EMIT = false) by the three parameters they have had since section 4.20
 template <int BLOCK, bool GRID_LDS, bool SENSOR>
 constexpr BackwardKernel solar_camera_kernel() { return camera_kernel<BLOCK, GRID_LDS, SENSOR, false>; }
-int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp) {
+// extra: the entry's own LDS behind the grid's (a path-length render's histograms and edges, at path_lds_offset), or 0
+int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp,
+           size_t extra = 0) {
   const BackwardKernel kernel = lds ? inLds : inGlobal;
-  const size_t bytes = lds ? grid_lds_bytes(v.p) : 0;
+  const size_t gridBytes = lds ? grid_lds_bytes(v.p) : 0, bytes = extra ? path_lds_offset(gridBytes) + extra : gridBytes;
   if (bytes > 48 * 1024) CAM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), bytes, v.stream, v.p, cp);
   CAM_HIP(c, hipGetLastError());
@@ -532,7 +629,8 @@ struct Entry {
 };
 // The sources of an emission render, as the caller handed them over: checked by emission_sources() before they are uploaded
 struct EmissionSources { const float *cell, *surface; double srcMax; };
-struct Counts { unsigned long long n; int64_t samples; int32_t numBatches; uint64_t firstSample; };  // n: pixels or sensors
+// n: pixels or sensors; slots: the sums each of them has per batch (the path-length bins of a pixel)
+struct Counts { unsigned long long n; int64_t samples; int32_t numBatches; uint64_t firstSample; unsigned long long slots = 1; };
 
 int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat_camera_fail(c, (std::string(e.name) + ": " + text).c_str()); }
 
@@ -540,7 +638,7 @@ int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat
 int check_counts(mcbrat_ctx *c, const Entry &e, const Counts &k) {
   if (k.samples < 1) return fail(c, e, std::string(e.samples) + " must be at least 1.");
   if (k.numBatches < 1) return fail(c, e, "numBatches must be at least 1.");
-  if (!bins_fit(k.n, (unsigned long long)k.numBatches, (int)e.arrays)) return fail(c, e, std::string("the bins of ") + e.bins + " do not fit the tally budget of 4 GiB.");
+  if (!bins_fit(k.n * k.slots, (unsigned long long)k.numBatches, (int)e.arrays)) return fail(c, e, std::string("the bins of ") + e.bins + " do not fit the tally budget of 4 GiB.");
   if (!paths_fit(k.n * (unsigned long long)k.numBatches, k.samples, k.firstSample, k.numBatches)) return fail(c, e, "more paths than a 64-bit index counts.");
   return 0;
 }
@@ -575,7 +673,7 @@ int emission_sources(mcbrat_ctx *c, const Entry &e, const CameraContext &v, Emis
 // Stage 3, after the entry's own checks against the domain: the forward and the inverse tables, the LDS share, then the launch.
 // cp: zeroed but for the entry's own members; geo: the sensors, or NULL; largestOwn: the largest estimate the entry adds to the
 // paths' (0: none); src: the checked sources of an emission entry, or NULL -- then no sun is set up, no forward table is read and
-// the bins are in units of src->srcMax / cp.scale.  -> bins [arrays][numBatches][n] in units of 1 / cp.scale, *dropped
+// the bins are in units of src->srcMax / cp.scale.  -> bins [arrays][numBatches][n][slots] in units of 1 / cp.scale, *dropped
 int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInLds, const Counts &k, uint64_t seed, CamParams &cp,
                     const std::vector<SensorGeometry> *geo, double largestOwn, std::vector<long long> &bins, int64_t *dropped,
                     const EmissionSources *src = nullptr) {
@@ -589,8 +687,10 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
     for (float x : (*v.fwd)[i]) if (x > fwdMax) fwdMax = x;  // (a NaN never compares greater)
   }
   if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
-  const int lds = choose_grid_lds(v, gridInLds);
-  if (lds < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+  // (a path-length render: histograms and edges for the 512 lanes of the LDS instantiation count against the share with the grid)
+  if (choose_grid_lds(v, gridInLds) < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+  const int lds = choose_grid_lds(v, gridInLds, cp.numBins ? path_lds_bytes(cp.numBins, 512) : 0);
+  if (lds < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the path-length histograms do not fit the LDS share together.");
 
   const unsigned long long nBins = k.n * (unsigned long long)k.numBatches;
   cp.spp = (unsigned long long)k.samples; cp.npix = k.n; cp.firstSample = k.firstSample;
@@ -607,7 +707,7 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   DeviceBuffer<unsigned long long> dDropped;
   DeviceBuffer<SensorGeometry> dGeo;
   DeviceBuffer<float> dSrcCell, dSrcSurface;
-  const size_t allBins = (size_t)(e.arrays * nBins);
+  const size_t allBins = (size_t)(e.arrays * nBins * k.slots);
   CAM_HIP(c, dBins.allocate(allBins));
   CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
   CAM_HIP(c, dDropped.allocate(1));
@@ -623,6 +723,12 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
     CAM_HIP(c, hipMemcpyAsync(dSrcSurface.get(), src->surface, sizeof(float) * ncol, hipMemcpyHostToDevice, v.stream));
     cp.srcCell = dSrcCell.get(); cp.srcSurface = dSrcSurface.get(); cp.invSrcMax = 1.0 / src->srcMax;
   }
+  DeviceBuffer<float> dEdges;
+  if (cp.numBins) {  // (a path-length render: cp.pathEdges comes in as the caller's checked array)
+    CAM_HIP(c, dEdges.allocate((size_t)cp.numBins));
+    CAM_HIP(c, hipMemcpyAsync(dEdges.get(), cp.pathEdges, sizeof(float) * (size_t)cp.numBins, hipMemcpyHostToDevice, v.stream));
+    cp.pathEdges = dEdges.get();
+  }
   if (geo) {
     CAM_HIP(c, dGeo.allocate(geo->size()));
     CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo->data(), sizeof(SensorGeometry) * geo->size(), hipMemcpyHostToDevice, v.stream));
@@ -634,7 +740,7 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   const LaunchShape shape = launch_shape(cp.total, v.numCUs, block);
   cp.pathsPerLane = shape.pathsPerLane;
   if (shape.blocks > 0x7fffffffull) return fail(c, e, "more paths than one launch takes.");
-  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp)) return 1;
+  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp, cp.numBins ? path_lds_bytes(cp.numBins, block) : 0)) return 1;
   bins.resize(allBins);
   unsigned long long nDropped = 0;
   CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * allBins, hipMemcpyDeviceToHost, v.stream));
@@ -721,6 +827,51 @@ int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed,
     }
     radiance[px] = (float)(m0 + s.shift(numBatches));
     if (radianceStdErr) radianceStdErr[px] = (float)s.error(numBatches);
+  }
+  return 0;
+}
+
+// ---- the radiance by photon path length: mcbrat_render_camera's paths, every estimate tallied on its own
+// in the path-length bin of its pixel; the same stages, numBins sums per pixel and batch ----
+
+int mcbrat_render_camera_pathlengths(mcbrat_ctx *c, const mcbrat_camera *cam, int32_t numBins, const float *pathEdges, uint64_t seed,
+                                     uint64_t firstSample, int64_t samplesPerPixel, int32_t numBatches, float *radiance, float *radianceStdErr,
+                                     float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderCameraPathLengths", "samplesPerPixel", "the image's batches (npx * npy * numBins * numBatches)", "the backward camera",
+                   "the backward camera needs", 1, camera_kernel<512, true, false, false, true>, camera_kernel<256, false, false, false, true>};
+  if (!c) return 1;
+  if (!cam || !radiance || !pathEdges) return fail(c, e, "no camera, no array for the radiance or no pathEdges array.");
+  if (const char *msg = camera_refusal(*cam)) {  // (the camera's own texts, under this entry's name)
+    const char *colon = std::strchr(msg, ':');
+    return fail(c, e, colon ? colon + 2 : msg);
+  }
+  if (const char *msg = path_edges_refusal(pathEdges, numBins)) return fail(c, e, msg);
+  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy, nb = (unsigned long long)numBins;
+  const Counts k = {npix, samplesPerPixel, numBatches, firstSample, nb};
+  CameraContext v;
+  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
+  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
+  CamParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
+  cp.numBins = numBins; cp.pathDirect = v.pathBinsInLds == 0;
+  cp.pathEdges = pathEdges;     // (the caller's array: backward_render uploads it)
+  std::vector<long long> bins;  // [numBatches][npix][numBins]: a pixel's bins lie together on the device
+  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped)) return 1;
+
+  const double unit = 1.0 / (cp.scale * (double)samplesPerPixel);
+  for (unsigned long long b = 0; b < nb; ++b) {
+    for (unsigned long long px = 0; px < npix; ++px) {
+      const double m0 = (double)bins[px * nb + b] * unit;
+      BatchSeries s;
+      for (int q = 0; q < numBatches; ++q) {
+        const double m = (double)bins[((size_t)q * npix + px) * nb + b] * unit;
+        if (batchMeans) batchMeans[((size_t)q * nb + b) * npix + px] = (float)m;
+        s.add(m - m0);
+      }
+      radiance[b * npix + px] = (float)(m0 + s.shift(numBatches));
+      if (radianceStdErr) radianceStdErr[b * npix + px] = (float)s.error(numBatches);
+    }
   }
   return 0;
 }

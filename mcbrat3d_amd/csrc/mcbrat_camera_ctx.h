@@ -20,6 +20,7 @@ struct CameraContext {
   bool haveInverseTables = false; // every component has one, uploaded (asked for with needTables)
   int nc = 0;
   int gridInLds = -1;              // option "cameraGridInLds" (mcbrat_sun_transmittance)
+  int pathBinsInLds = 1;           // option "cameraPathBinsInLds" (mcbrat_render_camera_pathlengths)
   const std::vector<double> *xe = nullptr, *ye = nullptr, *ze = nullptr;
   // forward tables per component as mcbrat_set_forward_table stored them ([nEntries][nAngles]; the original ones of a hybrid pair)
   const std::vector<std::vector<float>> *fwd = nullptr;

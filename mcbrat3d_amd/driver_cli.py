@@ -30,7 +30,9 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     # section 4.22 on the Planck radiances of the domain's temperatures and surfaceTemp, instead of the solar one
     "camera": dict(camerakind="", camerapixels=[1, 1], cameraposition=[0.0, 0.0, 0.0], cameralook=[0.0, 0.0, -1.0],
                    cameraup=[0.0, 1.0, 0.0], camerafov=60.0, cameramu=1.0, cameraphi=0.0, camerafootprint=[], cameraheight=None,
-                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile="", emission=False),
+                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile="", emission=False,
+                   # pathLengthEdges = 0., e1, ...: the image also by photon path length, the bins' lower edges
+                   pathlengthedges=[]),
     # backward sensors (no counterpart in the reference driver): absent -- sensorKind empty -- they change
     # nothing.  sensorPositions = x, y, z of every sensor in turn; sensorTilt, sensorAzimuth in degrees, one for all or one per sensor
     "sensors": dict(sensorkind="", sensorpositions=[], sensortilt=0.0, sensorazimuth=0.0, sensorsamples=10000, sensorbatches=10,
@@ -129,6 +131,12 @@ def writeResults_ASCII_radiance(path, cfg, domainName, stats, xe, ye, ze, solarF
                 for i in range(nx):
                     f.write("%7.3f%7.3f %9.4f %9.4f\n" % (0.5 * (xe[i] + xe[i + 1]), 0.5 * (ye[j] + ye[j + 1]),
                                                         stats["intensity"][i, j, k], stats["intensity_StdErr"][i, j, k]))
+
+
+def path_length_edges(cfg):
+    """pathLengthEdges of the /camera/ group as an array of floats, or None where the key is absent (the library checks them)."""
+    edges = np.atleast_1d(np.asarray(cfg.get("pathlengthedges", []), np.float32)).reshape(-1)
+    return edges if edges.size else None
 
 
 def camera_from_namelist(cfg, xe, ye, ze):
@@ -363,6 +371,14 @@ def main(argv=None):
         else:
             cameraResult = integ.renderCamera(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
                                               int(cfg["camerabatches"]))
+        edges = path_length_edges(cfg)
+        if edges is not None:  # the same paths once more, every estimate in the bin of its path length (the image itself stays what it was)
+            if cfg["cameraemission"]:
+                raise SystemExit("pathLengthEdges: an emission render has no path-length bins.")
+            byLength = integ.renderCameraPathLengths(camera, edges, int(cfg["camerasamplesperpixel"]), int(cfg["camerabatches"]),
+                                                     seed=new_RandomNumberSequence(cfg["iseed"]).seed, firstSample=0)
+            cameraResult.update(radianceByPathLength=byLength["radiance"], radianceByPathLength_StdErr=byLength["radiance_StdErr"],
+                                pathLengthEdges=byLength["pathEdges"], dropped=cameraResult["dropped"] + byLength["dropped"])
         cameraResult["samplesPerPixel"] = int(cfg["camerasamplesperpixel"])
         print(" camera %s %d x %d: mean radiance %.6g, largest standard error %.3g, %d paths dropped" % (
             camera.kind, camera.npx, camera.npy, cameraResult["radiance"].mean(), cameraResult["radiance_StdErr"].max(), cameraResult["dropped"]))

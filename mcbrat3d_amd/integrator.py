@@ -504,6 +504,23 @@ class Integrator:
         return {"irradiance": dif + dirc, "irradiance_StdErr": eTot, "diffuse": dif, "direct": dirc, "diffuse_StdErr": eDif,
                 "direct_StdErr": eDir, "batchMeans": means, "dropped": int(dropped.value)}
 
+    def renderCameraPathLengths(self, camera, pathEdges, samplesPerPixel, numBatches=1, seed=0, firstSample=0):
+        """renderCamera's radiance split by photon path length (DESIGN.md section 4.23): the geometric length, in the domain's
+        length unit, from where the light enters the domain at its top to the camera.  pathEdges: the bins' LOWER edges, floats,
+        pathEdges[0] = 0, strictly ascending, at most 256; the last bin is open above, so the bins sum to renderCamera's image.
+        The same (seed, firstSample) walks the paths of renderCamera with new_RandomNumberSequence(seed, firstSample).  Returns {"radiance" [bin, y, x], "radiance_StdErr", "batchMeans"
+        [batch, bin, y, x], "pathEdges", "dropped"}; mcbrat3d_amd.camera.absorbed_radiance and mean_path_length read them."""
+        self._load_camera_tables()
+        edges = np.ascontiguousarray(np.asarray(pathEdges, np.float32).reshape(-1))
+        s = camera.struct()
+        npx, npy, nb, nbin = camera.npx, camera.npy, int(numBatches), max(int(edges.size), 1)
+        rad, err = np.zeros((nbin, npy, npx), np.float32), np.zeros((nbin, npy, npx), np.float32)
+        means = np.zeros((max(nb, 1), nbin, npy, npx), np.float32)
+        dropped = C.c_int64(0)
+        self._check(self._lib.mcbrat_render_camera_pathlengths(self._ctx, C.addressof(s), int(edges.size), ptr(edges), int(seed), int(firstSample),
+                                                               int(samplesPerPixel), nb, ptr(rad), ptr(err), ptr(means), C.addressof(dropped)))
+        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "pathEdges": edges, "dropped": int(dropped.value)}
+
     # -- the emission renders (DESIGN.md section 4.22) ----------------------------------------
     def prepareDomain(self, thisDomain):
         """What prepare() uploads of the domain -- optical grids and tables -- without a source: all an emission render needs."""

@@ -256,6 +256,8 @@ SENSOR_VARIABLES = ("sensorIrradiance", "sensorIrradiance_StdErr", "sensorDiffus
 SENSOR_EMISSION_VARIABLES = ("sensorEmission", "sensorEmission_StdErr")
 CAMERA_VARIABLES = ("cameraRadiance", "cameraRadiance_StdErr")
 CAMERA_EMISSION_VARIABLES = ("cameraEmission", "cameraEmission_StdErr")
+# the image by photon path length, on (cameraPathBin, cameraY, cameraX), and the bins' lower edges
+CAMERA_PATH_VARIABLES = ("cameraRadianceByPathLength", "cameraRadianceByPathLength_StdErr", "cameraPathLengthEdges")
 
 
 def _add_sensors(f, sensors, result):
@@ -320,6 +322,13 @@ def _add_camera(f, camera, result):
     names = CAMERA_EMISSION_VARIABLES if result.get("emission") else CAMERA_VARIABLES
     f.createVariable(names[0], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance"], np.float32)
     f.createVariable(names[1], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance_StdErr"], np.float32)
+    if result.get("radianceByPathLength") is not None:  # (without the key the file is byte for byte what it was)
+        edges = np.asarray(result["pathLengthEdges"], np.float32).reshape(-1)
+        f.createDimension("cameraPathBin", edges.size)
+        dims = ("cameraPathBin", "cameraY", "cameraX")
+        f.createVariable(CAMERA_PATH_VARIABLES[0], "f", dims)[:] = np.asarray(result["radianceByPathLength"], np.float32)
+        f.createVariable(CAMERA_PATH_VARIABLES[1], "f", dims)[:] = np.asarray(result["radianceByPathLength_StdErr"], np.float32)
+        f.createVariable(CAMERA_PATH_VARIABLES[2], "f", ("cameraPathBin",))[:] = edges
 
 
 def readCamera_netcdf(fileName):
@@ -331,6 +340,7 @@ def readCamera_netcdf(fileName):
             return None
         names = CAMERA_EMISSION_VARIABLES if CAMERA_EMISSION_VARIABLES[0] in f.variables else CAMERA_VARIABLES
         out = {k: np.array(f.variables[k][:]) for k in names}
+        out.update({k: np.array(f.variables[k][:]) for k in CAMERA_PATH_VARIABLES if k in f.variables})
         out.update(cameraSamplesPerPixel=float(f.cameraSamplesPerPixel), cameraBatches=int(f.cameraBatches),
                    cameraDroppedPaths=float(f.cameraDroppedPaths))
         return out
