@@ -76,4 +76,37 @@ struct BatchSeries {
   }
 };
 
+// The one reduction of a render's integer bins [arrays][numBatches][n][slots] -- n receivers (pixels, sensors) with `slots` sums
+// each per batch (the path-length bins of a pixel), `arrays` 1 or 2 (the sensors' diffuse part, then their direct part) -- to
+// floats: a value is its bin times unit[receiver], in double; every series is taken as differences to its first batch.
+// mean, error: [array][slot][n]; totalError [slot][n]: of the per-batch sum of the two arrays, a series of its own formed as
+// (f - f0) + (d - d0); batchMeans [batch][array][slot][n].  Any output pointer may be NULL.
+struct BatchOutputs { float *mean[2], *error[2], *totalError, *batchMeans; };
+inline void reduce_batches(const long long *bins, int arrays, int numBatches, size_t n, size_t slots, const double *unit, const BatchOutputs &out) {
+  const size_t perArray = (size_t)numBatches * n * slots;
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t s = 0; s < slots; ++s) {
+      const long long *firstBin = bins + i * slots + s;  // of batch 0 of array 0: batch b of array a lies a * perArray + b * n * slots on
+      double first[2] = {0.0, 0.0};
+      for (int a = 0; a < arrays; ++a) first[a] = (double)firstBin[(size_t)a * perArray] * unit[i];
+      BatchSeries series[3];
+      for (int b = 0; b < numBatches; ++b) {
+        double diff[2] = {0.0, 0.0};
+        for (int a = 0; a < arrays; ++a) {
+          const double m = (double)firstBin[(size_t)a * perArray + (size_t)b * n * slots] * unit[i];
+          if (out.batchMeans) out.batchMeans[(((size_t)b * arrays + a) * slots + s) * n + i] = (float)m;
+          diff[a] = m - first[a];
+          series[a].add(diff[a]);
+        }
+        series[2].add(diff[0] + diff[1]);
+      }
+      for (int a = 0; a < arrays; ++a) {
+        if (out.mean[a]) out.mean[a][s * n + i] = (float)(first[a] + series[a].shift(numBatches));
+        if (out.error[a]) out.error[a][s * n + i] = (float)series[a].error(numBatches);
+      }
+      if (out.totalError) out.totalError[s * n + i] = (float)series[2].error(numBatches);
+    }
+  }
+}
+
 }  // namespace mcbrat

@@ -2,10 +2,11 @@
 // mcbrat_camera_ray, mcbrat_sun_transmittance).  A translation unit of its own: camera_kernel and its host code; the tracing
 // kernels, their variant table and their parameter block are not touched.
 //
-// The host half: mcbrat_render_camera and mcbrat_render_sensors are front ends -- arguments, geometry,
-// output arrays -- over one path in three stages, check_counts(), backward_context() and backward_render(), worded by the entry's
-// Entry; its arithmetic (bounds, scale, capacity, launch shape, batch statistics) is mcbrat_backward.h's, plain C++ that runs
-// without a GPU.  launch() is the one LDS-or-global launch, mcbrat_sun_transmittance's too.
+// The host half: the five render entries keep their null checks and go through camera_front() or
+// sensor_front() -- the receiver's rules, check_counts(), backward_context(), height or corners, geometry --, backward_render() of
+// a Request and reduce_batches(), worded by the entry's Entry; the arithmetic (bounds, scale, capacity, launch shape, the
+// reduction of the bins) is mcbrat_backward.h's, plain C++ that runs without a GPU.  launch() is the one LDS-or-global launch,
+// mcbrat_sun_transmittance's too.
 //
 // One lane per path.  A path starts at the sensor (mcbrat_camera_ray.h) and walks BACKWARD.  Leg: tau = -ln u, cell face by cell
 // face through the periodic grid until tau is used up, the top (the path ends: nothing diffuse comes in from above) or the
@@ -45,6 +46,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -575,6 +577,10 @@ using namespace mcbrat;
 namespace {
 
 constexpr size_t kCameraGridLds = 80 * 1024 - 1024;   // half of a compute unit's 160 KB, less the static part: two workgroups of 512 lanes
+constexpr double kPi = 3.14159265358979323846;
+// the refusals more than one entry words the same
+constexpr const char *kNoCamera = "no camera or no array for the radiance.", *kNoSensor = "at least one sensor is needed (n < 1).",
+                     *kNoSources = "no cellSource or no surfaceSource array (a null pointer).";
 
 #define CAM_HIP(c, call)                                                                                          \
   do {                                                                                                            \
@@ -594,10 +600,12 @@ void sun_setup(const DevParams &p, CamParams &cp) {
   cp.maxSunCross = b.maxCross; cp.invFourPiMu0 = b.invFourPiMu0; cp.invMu0 = b.invMu0;
 }
 
-// 0: global memory, 1: LDS; -1 refused (asked for, does not fit).  extra: what the entry keeps in LDS beside the grid
-int choose_grid_lds(const CameraContext &v, int asked, size_t extra = 0) {
-  const bool fits = (extra ? path_lds_offset(grid_lds_bytes(v.p)) : grid_lds_bytes(v.p)) + extra <= std::min(kCameraGridLds, v.ldsPerCU / 2);
-  if (asked == 1 && !fits) return -1;
+// 0: global memory, 1: LDS; refused (asked for, does not fit): -1 the grid and the edges alone, -2 those with `extra`, what the
+// entry keeps in LDS beside them (at path_lds_offset; 0: nothing)
+int choose_grid_lds(const CameraContext &v, int asked, size_t extra) {
+  const size_t share = std::min(kCameraGridLds, v.ldsPerCU / 2), grid = grid_lds_bytes(v.p);
+  const bool gridFits = grid <= share, fits = extra ? path_lds_offset(grid) + extra <= share : gridFits;
+  if (asked == 1 && !fits) return gridFits ? -2 : -1;
   return asked == 0 ? 0 : (fits ? 1 : 0);
 }
 
@@ -608,7 +616,7 @@ template <int BLOCK, bool GRID_LDS, bool SENSOR>
 constexpr BackwardKernel solar_camera_kernel() { return camera_kernel<BLOCK, GRID_LDS, SENSOR, false>; }
 // extra: the entry's own LDS behind the grid's (a path-length render's histograms and edges, at path_lds_offset), or 0
 int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp,
-           size_t extra = 0) {
+           size_t extra) {
   const BackwardKernel kernel = lds ? inLds : inGlobal;
   const size_t gridBytes = lds ? grid_lds_bytes(v.p) : 0, bytes = extra ? path_lds_offset(gridBytes) + extra : gridBytes;
   if (bytes > 48 * 1024) CAM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -622,15 +630,26 @@ struct Entry {
   const char *name;                // the prefix of every message
   const char *samples;             // its argument for the samples per bin
   const char *bins;                // its bins, as the budget's refusal names them
-  const char *subject, *needs;     // "the backward camera", "the backward camera needs"
+  const char *subject;             // "the backward camera", "the backward sensors"
   unsigned long long arrays;       // bin arrays: 1, or 2 (diffuse, then direct)
   BackwardKernel inLds, inGlobal;  // workgroups of 512 and of 256 lanes
-  bool emit = false;               // an emission render: no sun, no forward tables, no rule about the source
+  bool ownName = false;            // camera_refusal's texts go out under `name` (false: as they are, under the solar camera's)
 };
-// The sources of an emission render, as the caller handed them over: checked by emission_sources() before they are uploaded
-struct EmissionSources { const float *cell, *surface; double srcMax; };
 // n: pixels or sensors; slots: the sums each of them has per batch (the path-length bins of a pixel)
 struct Counts { unsigned long long n; int64_t samples; int32_t numBatches; uint64_t firstSample; unsigned long long slots = 1; };
+// The sources of an emission render, as the caller handed them over; srcMax, the largest value: emission_sources()'s
+struct EmissionSources { const float *cell, *surface; double srcMax; };
+struct PathEdges { const float *edges; int numBins; };  // the caller's array: checked by the camera front, uploaded by backward_render
+// One backward render, as its entry asks for it: host only.  What not every entry has is a member that is present or absent
+struct Request {
+  Counts counts;                          // (n and slots: the front's)
+  uint64_t seed;
+  int gridInLds;                          // (a camera's: the front's)
+  std::vector<SensorGeometry> sensors;    // a sensor entry: the receivers (the front's); empty: a camera, its geometry is cp.g
+  std::optional<double> largestOwn;       // the largest estimate the entry adds to the paths' own
+  std::optional<EmissionSources> sources; // an emission render: no sun, no forward tables, no rule about the source
+  std::optional<PathEdges> path;          // a render by path length
+};
 
 int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat_camera_fail(c, (std::string(e.name) + ": " + text).c_str()); }
 
@@ -643,13 +662,60 @@ int check_counts(mcbrat_ctx *c, const Entry &e, const Counts &k) {
   return 0;
 }
 
-// Stage 2: the view of the context, and what a backward render needs of it
-int backward_context(mcbrat_ctx *c, const Entry &e, CameraContext &v) {
+// Stage 2: the view of the context, and what a backward render needs of it (solar: the Directional source too)
+int backward_context(mcbrat_ctx *c, const Entry &e, bool solar, CameraContext &v) {
   if (mcbrat_camera_context(c, &v, false)) return 1;
   if (!v.haveGrid || !v.haveOptics) return fail(c, e, "problem not completely specified (grid and optical properties).");
-  if (!e.emit && (!v.haveSource || !v.solarDirectional)) return fail(c, e, std::string(e.needs) + " the Directional solar source.");
-  if (v.brdfSurface) return fail(c, e, std::string("a BRDF surface is not supported by ") + e.subject + " (Lambertian surfaces only).");
+  const std::string subject = e.subject;
+  if (solar && (!v.haveSource || !v.solarDirectional)) return fail(c, e, subject + (subject.back() == 's' ? " need" : " needs") + " the Directional solar source.");
+  if (v.brdfSurface) return fail(c, e, "a BRDF surface is not supported by " + subject + " (Lambertian surfaces only).");
   return 0;
+}
+
+// The front of the three camera entries, behind their own null checks: the camera's rules and the edges', stage 1 with the
+// entry's slots, stage 2, the height.  -> q.counts, q.gridInLds, v, and cp zeroed but for the camera's geometry
+int camera_front(mcbrat_ctx *c, const Entry &e, const mcbrat_camera &cam, Request &q, CameraContext &v, CamParams &cp) {
+  if (const char *msg = camera_refusal(cam)) {
+    const char *colon = std::strchr(msg, ':');
+    return e.ownName ? fail(c, e, colon ? colon + 2 : msg) : mcbrat_camera_fail(c, msg);
+  }
+  if (q.path)
+    if (const char *msg = path_edges_refusal(q.path->edges, q.path->numBins)) return fail(c, e, msg);
+  q.counts.n = (unsigned long long)cam.npx * (unsigned long long)cam.npy;
+  q.counts.slots = q.path ? (unsigned long long)q.path->numBins : 1;
+  q.gridInLds = cam.gridInLds;
+  if (check_counts(c, e, q.counts) || backward_context(c, e, !q.sources, v)) return 1;
+  if (!inside(v.p, cam.kind == 0 ? cam.z : cam.position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
+  std::memset(&cp, 0, sizeof(cp));
+  camera_geometry(cam, cp.g); cp.jitter = cam.jitter != 0;
+  return 0;
+}
+
+// The front of the two sensor entries, behind their own null checks: gridInLds, stage 1, the sensors' rules, stage 2, the
+// corners.  -> q.counts, q.sensors (direct: 0), v, and cp zeroed
+int sensor_front(mcbrat_ctx *c, const Entry &e, int64_t n, const mcbrat_sensor *sensors, Request &q, CameraContext &v, CamParams &cp) {
+  if (q.gridInLds < -1 || q.gridInLds > 1) return fail(c, e, "gridInLds must be -1, 0 or 1.");
+  q.counts.n = (unsigned long long)n;
+  if (check_counts(c, e, q.counts)) return 1;
+  for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
+    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+  if (backward_context(c, e, !q.sources, v)) return 1;
+  for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
+    const mcbrat_sensor &s = sensors[i / 4];
+    if (!inside(v.p, s.position[2] + ((i & 1) ? s.e1[2] : 0.0) + ((i & 2) ? s.e2[2] : 0.0)))
+      return fail(c, e, "a corner of a sensor's receiver lies outside the domain [z0, zMax].");
+  }
+  q.sensors.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) sensor_geometry(sensors[i], q.sensors[(size_t)i]);
+  std::memset(&cp, 0, sizeof(cp));
+  return 0;
+}
+// w0, the solid angle a sensor's parts are tallied in units of: pi (planar), 4 pi (spherical); the value of one count of its bins
+double sensor_w0(const mcbrat_sensor &s) { return s.kind == 0 ? kPi : 4.0 * kPi; }
+std::vector<double> sensor_units(int64_t n, const mcbrat_sensor *sensors, double unit) {
+  std::vector<double> units((size_t)n);
+  for (int64_t i = 0; i < n; ++i) units[(size_t)i] = unit * sensor_w0(sensors[i]);
+  return units;
 }
 
 // An emission entry's own check of its two source arrays against the grid: every value finite and not negative, not all zero.
@@ -670,16 +736,15 @@ int emission_sources(mcbrat_ctx *c, const Entry &e, const CameraContext &v, Emis
   return 0;
 }
 
-// Stage 3, after the entry's own checks against the domain: the forward and the inverse tables, the LDS share, then the launch.
-// cp: zeroed but for the entry's own members; geo: the sensors, or NULL; largestOwn: the largest estimate the entry adds to the
-// paths' (0: none); src: the checked sources of an emission entry, or NULL -- then no sun is set up, no forward table is read and
-// the bins are in units of src->srcMax / cp.scale.  -> bins [arrays][numBatches][n][slots] in units of 1 / cp.scale, *dropped
-int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInLds, const Counts &k, uint64_t seed, CamParams &cp,
-                    const std::vector<SensorGeometry> *geo, double largestOwn, std::vector<long long> &bins, int64_t *dropped,
-                    const EmissionSources *src = nullptr) {
+// Stage 3, behind the front and the entry's own checks: the forward and the inverse tables, the LDS share, then the launch.
+// cp: as the front left it.  With q.sources no sun is set up and no forward table is read.
+// -> bins [arrays][numBatches][n][slots] and `unit`, the value of one count of a bin in the caller's units; *dropped
+int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, const Request &q, CamParams &cp, std::vector<long long> &bins, double &unit,
+                    int64_t *dropped) {
+  const Counts &k = q.counts;
   std::vector<float> fwdAll;  // the forward tables, components concatenated, and the largest value they hold
   float fwdMax = 0.0f;
-  for (int i = 0; i < (src ? 0 : v.nc); ++i) {
+  for (int i = 0; i < (q.sources ? 0 : v.nc); ++i) {
     if ((int)v.fwd->size() <= i || (*v.fwd)[i].empty()) return fail(c, e, "no forward phase function table for component " + std::to_string(i + 1));
     if ((*v.maxPfi)[i] >= (*v.fwdNEntries)[i]) return fail(c, e, "phaseFunctionIndex exceeds forward table entries for component " + std::to_string(i + 1));
     cp.fwdOffset[i] = (int)fwdAll.size(); cp.fwdNAngles[i] = (*v.fwdNAngles)[i];
@@ -688,25 +753,26 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   }
   if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
   // (a path-length render: histograms and edges for the 512 lanes of the LDS instantiation count against the share with the grid)
-  if (choose_grid_lds(v, gridInLds) < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
-  const int lds = choose_grid_lds(v, gridInLds, cp.numBins ? path_lds_bytes(cp.numBins, 512) : 0);
-  if (lds < 0) return fail(c, e, "gridInLds = 1, but the extinction grid and the path-length histograms do not fit the LDS share together.");
+  const int numBins = q.path ? q.path->numBins : 0;
+  const int lds = choose_grid_lds(v, q.gridInLds, numBins ? path_lds_bytes(numBins, 512) : 0);
+  if (lds == -1) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+  if (lds == -2) return fail(c, e, "gridInLds = 1, but the extinction grid and the path-length histograms do not fit the LDS share together.");
 
   const unsigned long long nBins = k.n * (unsigned long long)k.numBatches;
   cp.spp = (unsigned long long)k.samples; cp.npix = k.n; cp.firstSample = k.firstSample;
   cp.total = nBins * cp.spp;
-  if (!src) sun_setup(v.p, cp);
+  cp.numBins = numBins; cp.pathDirect = q.path && v.pathBinsInLds == 0;
+  if (!q.sources) sun_setup(v.p, cp);
   cp.maxLegCross = leg_bound(v.p.nx, v.p.ny, v.p.nz, v.p.zMax - v.p.z0, v.p.Lx, v.p.Ly); cp.maxEvents = kCameraMaxEvents;
   // (an emission path's deposits are tallied in units of the largest source value: the candidate is 1)
-  const FixedPoint fixed = src ? fixed_point(k.samples, {1.0}) : fixed_point(k.samples, {(double)fwdMax * (double)cp.invFourPiMu0, 1.0 / 3.14159265358979323846, largestOwn});
+  const FixedPoint fixed = q.sources ? fixed_point(k.samples, {1.0}) : fixed_point(k.samples, {(double)fwdMax * (double)cp.invFourPiMu0, 1.0 / kPi, q.largestOwn.value_or(0.0)});
   cp.scale = fixed.scale; cp.pathMax = fixed.pathMax;
-  v.p.seedLo = (uint32_t)seed; v.p.seedHi = (uint32_t)(seed >> 32);
+  v.p.seedLo = (uint32_t)q.seed; v.p.seedHi = (uint32_t)(q.seed >> 32);
 
   DeviceBuffer<long long> dBins;
-  DeviceBuffer<float> dFwd;
+  DeviceBuffer<float> dFwd, dSrcCell, dSrcSurface, dEdges;
   DeviceBuffer<unsigned long long> dDropped;
   DeviceBuffer<SensorGeometry> dGeo;
-  DeviceBuffer<float> dSrcCell, dSrcSurface;
   const size_t allBins = (size_t)(e.arrays * nBins * k.slots);
   CAM_HIP(c, dBins.allocate(allBins));
   CAM_HIP(c, dFwd.allocate(std::max<size_t>(fwdAll.size(), 1)));
@@ -715,23 +781,22 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   CAM_HIP(c, hipMemsetAsync(dDropped.get(), 0, sizeof(unsigned long long), v.stream));
   CAM_HIP(c, hipMemcpyAsync(dFwd.get(), fwdAll.data(), sizeof(float) * fwdAll.size(), hipMemcpyHostToDevice, v.stream));
   cp.bins = dBins.get(); cp.binsDirect = e.arrays == 2 ? dBins.get() + nBins : nullptr; cp.fwd = dFwd.get(); cp.dropped = dDropped.get();
-  if (src) {
+  if (q.sources) {
     const size_t ncol = (size_t)v.p.nx * (size_t)v.p.ny, nvox = ncol * (size_t)v.p.nz;
     CAM_HIP(c, dSrcCell.allocate(nvox));
     CAM_HIP(c, dSrcSurface.allocate(ncol));
-    CAM_HIP(c, hipMemcpyAsync(dSrcCell.get(), src->cell, sizeof(float) * nvox, hipMemcpyHostToDevice, v.stream));
-    CAM_HIP(c, hipMemcpyAsync(dSrcSurface.get(), src->surface, sizeof(float) * ncol, hipMemcpyHostToDevice, v.stream));
-    cp.srcCell = dSrcCell.get(); cp.srcSurface = dSrcSurface.get(); cp.invSrcMax = 1.0 / src->srcMax;
+    CAM_HIP(c, hipMemcpyAsync(dSrcCell.get(), q.sources->cell, sizeof(float) * nvox, hipMemcpyHostToDevice, v.stream));
+    CAM_HIP(c, hipMemcpyAsync(dSrcSurface.get(), q.sources->surface, sizeof(float) * ncol, hipMemcpyHostToDevice, v.stream));
+    cp.srcCell = dSrcCell.get(); cp.srcSurface = dSrcSurface.get(); cp.invSrcMax = 1.0 / q.sources->srcMax;
   }
-  DeviceBuffer<float> dEdges;
-  if (cp.numBins) {  // (a path-length render: cp.pathEdges comes in as the caller's checked array)
-    CAM_HIP(c, dEdges.allocate((size_t)cp.numBins));
-    CAM_HIP(c, hipMemcpyAsync(dEdges.get(), cp.pathEdges, sizeof(float) * (size_t)cp.numBins, hipMemcpyHostToDevice, v.stream));
+  if (q.path) {
+    CAM_HIP(c, dEdges.allocate((size_t)numBins));
+    CAM_HIP(c, hipMemcpyAsync(dEdges.get(), q.path->edges, sizeof(float) * (size_t)numBins, hipMemcpyHostToDevice, v.stream));
     cp.pathEdges = dEdges.get();
   }
-  if (geo) {
-    CAM_HIP(c, dGeo.allocate(geo->size()));
-    CAM_HIP(c, hipMemcpyAsync(dGeo.get(), geo->data(), sizeof(SensorGeometry) * geo->size(), hipMemcpyHostToDevice, v.stream));
+  if (!q.sensors.empty()) {
+    CAM_HIP(c, dGeo.allocate(q.sensors.size()));
+    CAM_HIP(c, hipMemcpyAsync(dGeo.get(), q.sensors.data(), sizeof(SensorGeometry) * q.sensors.size(), hipMemcpyHostToDevice, v.stream));
     cp.sensors = dGeo.get();
   }
 
@@ -740,13 +805,31 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, int gridInL
   const LaunchShape shape = launch_shape(cp.total, v.numCUs, block);
   cp.pathsPerLane = shape.pathsPerLane;
   if (shape.blocks > 0x7fffffffull) return fail(c, e, "more paths than one launch takes.");
-  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp, cp.numBins ? path_lds_bytes(cp.numBins, block) : 0)) return 1;
+  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp, numBins ? path_lds_bytes(numBins, block) : 0)) return 1;
   bins.resize(allBins);
   unsigned long long nDropped = 0;
   CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * allBins, hipMemcpyDeviceToHost, v.stream));
   CAM_HIP(c, hipMemcpyAsync(&nDropped, dDropped.get(), sizeof(nDropped), hipMemcpyDeviceToHost, v.stream));
   CAM_HIP(c, hipStreamSynchronize(v.stream));
   if (dropped) *dropped = (int64_t)nDropped;
+  // (an emission render's bins are in units of srcMax: the caller's units come back here, in double)
+  unit = (q.sources ? q.sources->srcMax : 1.0) / (cp.scale * (double)k.samples);
+  return 0;
+}
+
+// The three camera entries behind their null checks: the front, the emission entry's sources, stage 3, the reduction to images
+// [slot][pixel]
+int render_camera(mcbrat_ctx *c, const Entry &e, const mcbrat_camera &cam, Request &q, float *radiance, float *radianceStdErr, float *batchMeans,
+                  int64_t *dropped) {
+  CameraContext v;
+  CamParams cp;
+  if (camera_front(c, e, cam, q, v, cp)) return 1;
+  if (q.sources && emission_sources(c, e, v, *q.sources)) return 1;
+  std::vector<long long> bins;  // [numBatches][npix][slots]: a pixel's bins lie together on the device
+  double unit;
+  if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
+  const std::vector<double> units((size_t)q.counts.n, unit);
+  reduce_batches(bins.data(), 1, q.counts.numBatches, (size_t)q.counts.n, (size_t)q.counts.slots, units.data(), {{radiance, nullptr}, {radianceStdErr, nullptr}, nullptr, batchMeans});
   return 0;
 }
 
@@ -773,7 +856,7 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
     if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !inside(v.p, xyz[3 * i + 2]))
       return mcbrat_camera_fail(c, "sunTransmittance: a point is not finite or lies outside [z0, zMax].");
   if (n == 0) return 0;
-  const int lds = choose_grid_lds(v, v.gridInLds);
+  const int lds = choose_grid_lds(v, v.gridInLds, 0);
   if (lds < 0) return mcbrat_camera_fail(c, "sunTransmittance: the grid does not fit the LDS share (option cameraGridInLds = 1).");
   DeviceBuffer<double> dPoints;
   DeviceBuffer<float> dT;
@@ -789,7 +872,7 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
   cp.points = dPoints.get(); cp.transmittance = dT.get(); cp.nPoints = n; cp.dropped = dDropped.get();
   constexpr int kBlock = 256;
   const unsigned grid = (unsigned)std::min<long long>((n + kBlock - 1) / kBlock, (long long)v.numCUs * 8);
-  if (launch(c, v, lds, sun_transmittance_kernel<kBlock, true>, sun_transmittance_kernel<kBlock, false>, grid, kBlock, cp)) return 1;
+  if (launch(c, v, lds, sun_transmittance_kernel<kBlock, true>, sun_transmittance_kernel<kBlock, false>, grid, kBlock, cp, 0)) return 1;
   unsigned long long dropped = 0;
   CAM_HIP(c, hipMemcpyAsync(transmittance, dT.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v.stream));
   CAM_HIP(c, hipMemcpyAsync(&dropped, dDropped.get(), sizeof(dropped), hipMemcpyDeviceToHost, v.stream));
@@ -800,80 +883,26 @@ int mcbrat_sun_transmittance(mcbrat_ctx *c, int64_t n, const double *xyz, float 
 
 int mcbrat_render_camera(mcbrat_ctx *c, const mcbrat_camera *cam, uint64_t seed, uint64_t firstSample, int64_t samplesPerPixel,
                          int32_t numBatches, float *radiance, float *radianceStdErr, float *batchMeans, int64_t *dropped) {
-  const Entry e = {"renderCamera", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the backward camera", "the backward camera needs", 1,
+  const Entry e = {"renderCamera", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the backward camera", 1,
                    solar_camera_kernel<512, true, false>(), solar_camera_kernel<256, false, false>()};
   if (!c) return 1;
-  if (!cam || !radiance) return fail(c, e, "no camera or no array for the radiance.");
-  if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
-  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy;
-  const Counts k = {npix, samplesPerPixel, numBatches, firstSample};
-  CameraContext v;
-  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
-  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
-  CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
-  std::vector<long long> bins;
-  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped)) return 1;
-
-  const double unit = 1.0 / (cp.scale * (double)samplesPerPixel);
-  for (unsigned long long px = 0; px < npix; ++px) {
-    const double m0 = (double)bins[px] * unit;
-    BatchSeries s;
-    for (int b = 0; b < numBatches; ++b) {
-      const double m = (double)bins[(size_t)b * npix + px] * unit;
-      if (batchMeans) batchMeans[(size_t)b * npix + px] = (float)m;
-      s.add(m - m0);
-    }
-    radiance[px] = (float)(m0 + s.shift(numBatches));
-    if (radianceStdErr) radianceStdErr[px] = (float)s.error(numBatches);
-  }
-  return 0;
+  if (!cam || !radiance) return fail(c, e, kNoCamera);
+  Request q = {{0, samplesPerPixel, numBatches, firstSample}, seed};
+  return render_camera(c, e, *cam, q, radiance, radianceStdErr, batchMeans, dropped);
 }
 
-// ---- the radiance by photon path length: mcbrat_render_camera's paths, every estimate tallied on its own
-// in the path-length bin of its pixel; the same stages, numBins sums per pixel and batch ----
-
+// The radiance by photon path length: mcbrat_render_camera's paths, every estimate tallied on its own in
+// the path-length bin of its pixel; numBins sums per pixel and batch
 int mcbrat_render_camera_pathlengths(mcbrat_ctx *c, const mcbrat_camera *cam, int32_t numBins, const float *pathEdges, uint64_t seed,
                                      uint64_t firstSample, int64_t samplesPerPixel, int32_t numBatches, float *radiance, float *radianceStdErr,
                                      float *batchMeans, int64_t *dropped) {
-  const Entry e = {"renderCameraPathLengths", "samplesPerPixel", "the image's batches (npx * npy * numBins * numBatches)", "the backward camera",
-                   "the backward camera needs", 1, camera_kernel<512, true, false, false, true>, camera_kernel<256, false, false, false, true>};
+  const Entry e = {"renderCameraPathLengths", "samplesPerPixel", "the image's batches (npx * npy * numBins * numBatches)", "the backward camera", 1,
+                   camera_kernel<512, true, false, false, true>, camera_kernel<256, false, false, false, true>, true};
   if (!c) return 1;
   if (!cam || !radiance || !pathEdges) return fail(c, e, "no camera, no array for the radiance or no pathEdges array.");
-  if (const char *msg = camera_refusal(*cam)) {  // (the camera's own texts, under this entry's name)
-    const char *colon = std::strchr(msg, ':');
-    return fail(c, e, colon ? colon + 2 : msg);
-  }
-  if (const char *msg = path_edges_refusal(pathEdges, numBins)) return fail(c, e, msg);
-  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy, nb = (unsigned long long)numBins;
-  const Counts k = {npix, samplesPerPixel, numBatches, firstSample, nb};
-  CameraContext v;
-  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
-  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
-  CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
-  cp.numBins = numBins; cp.pathDirect = v.pathBinsInLds == 0;
-  cp.pathEdges = pathEdges;     // (the caller's array: backward_render uploads it)
-  std::vector<long long> bins;  // [numBatches][npix][numBins]: a pixel's bins lie together on the device
-  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped)) return 1;
-
-  const double unit = 1.0 / (cp.scale * (double)samplesPerPixel);
-  for (unsigned long long b = 0; b < nb; ++b) {
-    for (unsigned long long px = 0; px < npix; ++px) {
-      const double m0 = (double)bins[px * nb + b] * unit;
-      BatchSeries s;
-      for (int q = 0; q < numBatches; ++q) {
-        const double m = (double)bins[((size_t)q * npix + px) * nb + b] * unit;
-        if (batchMeans) batchMeans[((size_t)q * nb + b) * npix + px] = (float)m;
-        s.add(m - m0);
-      }
-      radiance[b * npix + px] = (float)(m0 + s.shift(numBatches));
-      if (radianceStdErr) radianceStdErr[b * npix + px] = (float)s.error(numBatches);
-    }
-  }
-  return 0;
+  Request q = {{0, samplesPerPixel, numBatches, firstSample}, seed};
+  q.path = PathEdges{pathEdges, numBins};
+  return render_camera(c, e, *cam, q, radiance, radianceStdErr, batchMeans, dropped);
 }
 
 int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a, double cc, double origin[3], double direction[3]) {
@@ -887,161 +916,73 @@ int mcbrat_sensor_ray(const mcbrat_sensor *sensor, double u, double v, double a,
 int mcbrat_render_sensors(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, uint64_t seed, uint64_t firstSample,
                           int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds, float *diffuse, float *direct,
                           float *diffuseStdErr, float *directStdErr, float *totalStdErr, float *batchMeans, int64_t *dropped) {
-  const Entry e = {"renderSensors", "samplesPerSensor", "the sensors' batches (2 * n * numBatches)", "the backward sensors", "the backward sensors need", 2,
+  const Entry e = {"renderSensors", "samplesPerSensor", "the sensors' batches (2 * n * numBatches)", "the backward sensors", 2,
                    solar_camera_kernel<512, true, true>(), solar_camera_kernel<256, false, true>()};
   if (!c) return 1;
-  if (n < 1) return fail(c, e, "at least one sensor is needed (n < 1).");
+  if (n < 1) return fail(c, e, kNoSensor);
   if (!sensors || !diffuse || !direct) return fail(c, e, "no sensors or no arrays for the diffuse and the direct part.");
-  if (gridInLds < -1 || gridInLds > 1) return fail(c, e, "gridInLds must be -1, 0 or 1.");
-  const unsigned long long ns = (unsigned long long)n;
-  const Counts k = {ns, samplesPerSensor, numBatches, firstSample};
-  if (check_counts(c, e, k)) return 1;
-  for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
-    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+  Request q = {{0, samplesPerSensor, numBatches, firstSample}, seed, gridInLds};
   CameraContext v;
-  if (backward_context(c, e, v)) return 1;
-  for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
-    const mcbrat_sensor &s = sensors[i / 4];
-    if (!inside(v.p, s.position[2] + ((i & 1) ? s.e1[2] : 0.0) + ((i & 2) ? s.e2[2] : 0.0)))
-      return fail(c, e, "a corner of a sensor's receiver lies outside the domain [z0, zMax].");
-  }
-  const double kPi = 3.14159265358979323846;
+  CamParams cp;
+  if (sensor_front(c, e, n, sensors, q, v, cp)) return 1;
   // the sun in double, as mcbrat_set_source_solar's float direction gives it; mu0 = its cosine
   double sun[3], sn = 0.0;
   for (int a = 0; a < 3; ++a) { sun[a] = -(double)v.p.dir0[a]; sn += sun[a] * sun[a]; }
   sn = std::sqrt(sn);
   for (int a = 0; a < 3; ++a) sun[a] /= sn;
   const double mu0 = std::max(std::fabs(sun[2]), (double)FLT_MIN);
-  std::vector<SensorGeometry> geo((size_t)n);
-  std::vector<double> w0((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
-    sensor_geometry(sensors[i], geo[(size_t)i]);
     double cDirect = 1.0 / mu0;
     if (sensors[i].kind == 0) {
-      const double *nv = geo[(size_t)i].n;
+      const double *nv = q.sensors[(size_t)i].n;
       cDirect = std::max(0.0, nv[0] * sun[0] + nv[1] * sun[1] + nv[2] * sun[2]) / mu0;
     }
-    w0[(size_t)i] = sensors[i].kind == 0 ? kPi : 4.0 * kPi;
-    geo[(size_t)i].direct = (float)(cDirect / w0[(size_t)i]);  // (both parts are tallied in units of w0)
+    q.sensors[(size_t)i].direct = (float)(cDirect / sensor_w0(sensors[i]));  // (both parts are tallied in units of w0)
   }
-  CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  std::vector<long long> bins;  // [2][numBatches][n]: diffuse, then direct
-  if (backward_render(c, e, v, gridInLds, k, seed, cp, &geo, 1.0 / (kPi * mu0), bins, dropped)) return 1;  // (the direct estimate, c / w0, is at most 1 / (pi mu0))
-
+  q.largestOwn = 1.0 / (kPi * mu0);  // (the direct estimate, c / w0, is at most 1 / (pi mu0))
+  std::vector<long long> bins;      // [2][numBatches][n]: diffuse, then direct
+  double unit;
+  if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
   // the diffuse part, the direct part and the per-batch sum of the two, each a series of its own
-  const size_t nBins = (size_t)ns * (size_t)numBatches;
-  const double unit = 1.0 / (cp.scale * (double)samplesPerSensor);
-  for (unsigned long long i = 0; i < ns; ++i) {
-    const double u = unit * w0[(size_t)i];
-    const double f0 = (double)bins[i] * u, d0 = (double)bins[nBins + i] * u;
-    BatchSeries s[3];
-    for (int b = 0; b < numBatches; ++b) {
-      const double f = (double)bins[(size_t)b * ns + i] * u, d = (double)bins[nBins + (size_t)b * ns + i] * u;
-      if (batchMeans) {
-        batchMeans[((size_t)b * 2 + 0) * ns + i] = (float)f;
-        batchMeans[((size_t)b * 2 + 1) * ns + i] = (float)d;
-      }
-      s[0].add(f - f0); s[1].add(d - d0); s[2].add((f - f0) + (d - d0));
-    }
-    diffuse[i] = (float)(f0 + s[0].shift(numBatches));
-    direct[i] = (float)(d0 + s[1].shift(numBatches));
-    float *err[3] = {diffuseStdErr, directStdErr, totalStdErr};
-    for (int q = 0; q < 3; ++q)
-      if (err[q]) err[q][i] = (float)s[q].error(numBatches);
-  }
+  reduce_batches(bins.data(), 2, numBatches, (size_t)n, 1, sensor_units(n, sensors, unit).data(), {{diffuse, direct}, {diffuseStdErr, directStdErr}, totalStdErr, batchMeans});
   return 0;
 }
 
-// ---- the emission renders: the same stages, an Entry with `emit`, one bin array, the caller's sources ----
-
+// The emission camera: one bin array, the caller's sources
 int mcbrat_render_camera_emission(mcbrat_ctx *c, const mcbrat_camera *cam, const float *cellSource, const float *surfaceSource, uint64_t seed,
                                   uint64_t firstSample, int64_t samplesPerPixel, int32_t numBatches, float *radiance, float *radianceStdErr,
                                   float *batchMeans, int64_t *dropped) {
-  const Entry e = {"renderCameraEmission", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the emission camera", "the emission camera needs", 1,
-                   camera_kernel<512, true, false, true>, camera_kernel<256, false, false, true>, true};
+  const Entry e = {"renderCameraEmission", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the emission camera", 1,
+                   camera_kernel<512, true, false, true>, camera_kernel<256, false, false, true>};
   if (!c) return 1;
-  if (!cam || !radiance) return fail(c, e, "no camera or no array for the radiance.");
-  if (!cellSource || !surfaceSource) return fail(c, e, "no cellSource or no surfaceSource array (a null pointer).");
-  if (const char *msg = camera_refusal(*cam)) return mcbrat_camera_fail(c, msg);
-  const unsigned long long npix = (unsigned long long)cam->npx * (unsigned long long)cam->npy;
-  const Counts k = {npix, samplesPerPixel, numBatches, firstSample};
-  CameraContext v;
-  if (check_counts(c, e, k) || backward_context(c, e, v)) return 1;
-  if (!inside(v.p, cam->kind == 0 ? cam->z : cam->position[2])) return fail(c, e, "the camera's height lies outside the domain [z0, zMax].");
-  EmissionSources src = {cellSource, surfaceSource, 0.0};
-  if (emission_sources(c, e, v, src)) return 1;
-  CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  camera_geometry(*cam, cp.g); cp.jitter = cam->jitter != 0;
-  std::vector<long long> bins;
-  if (backward_render(c, e, v, cam->gridInLds, k, seed, cp, nullptr, 0.0, bins, dropped, &src)) return 1;
-
-  // (the bins are in units of srcMax: the caller's units come back here, in double)
-  const double unit = src.srcMax / (cp.scale * (double)samplesPerPixel);
-  for (unsigned long long px = 0; px < npix; ++px) {
-    const double m0 = (double)bins[px] * unit;
-    BatchSeries s;
-    for (int b = 0; b < numBatches; ++b) {
-      const double m = (double)bins[(size_t)b * npix + px] * unit;
-      if (batchMeans) batchMeans[(size_t)b * npix + px] = (float)m;
-      s.add(m - m0);
-    }
-    radiance[px] = (float)(m0 + s.shift(numBatches));
-    if (radianceStdErr) radianceStdErr[px] = (float)s.error(numBatches);
-  }
-  return 0;
+  if (!cam || !radiance) return fail(c, e, kNoCamera);
+  if (!cellSource || !surfaceSource) return fail(c, e, kNoSources);
+  Request q = {{0, samplesPerPixel, numBatches, firstSample}, seed};
+  q.sources = EmissionSources{cellSource, surfaceSource, 0.0};
+  return render_camera(c, e, *cam, q, radiance, radianceStdErr, batchMeans, dropped);
 }
 
+// The emission sensors: one bin array, no direct part (nothing comes in from above)
 int mcbrat_render_sensors_emission(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, const float *cellSource, const float *surfaceSource,
                                    uint64_t seed, uint64_t firstSample, int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds,
                                    float *irradiance, float *irradianceStdErr, float *batchMeans, int64_t *dropped) {
-  const Entry e = {"renderSensorsEmission", "samplesPerSensor", "the sensors' batches (n * numBatches)", "the emission sensors", "the emission sensors need", 1,
-                   camera_kernel<512, true, true, true>, camera_kernel<256, false, true, true>, true};
+  const Entry e = {"renderSensorsEmission", "samplesPerSensor", "the sensors' batches (n * numBatches)", "the emission sensors", 1,
+                   camera_kernel<512, true, true, true>, camera_kernel<256, false, true, true>};
   if (!c) return 1;
-  if (n < 1) return fail(c, e, "at least one sensor is needed (n < 1).");
+  if (n < 1) return fail(c, e, kNoSensor);
   if (!sensors || !irradiance) return fail(c, e, "no sensors or no array for the irradiance.");
-  if (!cellSource || !surfaceSource) return fail(c, e, "no cellSource or no surfaceSource array (a null pointer).");
-  if (gridInLds < -1 || gridInLds > 1) return fail(c, e, "gridInLds must be -1, 0 or 1.");
-  const unsigned long long ns = (unsigned long long)n;
-  const Counts k = {ns, samplesPerSensor, numBatches, firstSample};
-  if (check_counts(c, e, k)) return 1;
-  for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
-    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+  if (!cellSource || !surfaceSource) return fail(c, e, kNoSources);
+  Request q = {{0, samplesPerSensor, numBatches, firstSample}, seed, gridInLds};
+  q.sources = EmissionSources{cellSource, surfaceSource, 0.0};
   CameraContext v;
-  if (backward_context(c, e, v)) return 1;
-  for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
-    const mcbrat_sensor &s = sensors[i / 4];
-    if (!inside(v.p, s.position[2] + ((i & 1) ? s.e1[2] : 0.0) + ((i & 2) ? s.e2[2] : 0.0)))
-      return fail(c, e, "a corner of a sensor's receiver lies outside the domain [z0, zMax].");
-  }
-  EmissionSources src = {cellSource, surfaceSource, 0.0};
-  if (emission_sources(c, e, v, src)) return 1;
-  std::vector<SensorGeometry> geo((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    sensor_geometry(sensors[i], geo[(size_t)i]);
-    geo[(size_t)i].direct = 0.0f;  // (no direct part: nothing comes in from above)
-  }
   CamParams cp;
-  std::memset(&cp, 0, sizeof(cp));
+  if (sensor_front(c, e, n, sensors, q, v, cp) || emission_sources(c, e, v, *q.sources)) return 1;
+  for (SensorGeometry &g : q.sensors) g.direct = 0.0f;
   std::vector<long long> bins;  // [numBatches][n]
-  if (backward_render(c, e, v, gridInLds, k, seed, cp, &geo, 0.0, bins, dropped, &src)) return 1;
-
-  const double unit = src.srcMax / (cp.scale * (double)samplesPerSensor);
-  for (unsigned long long i = 0; i < ns; ++i) {
-    const double u = unit * (sensors[i].kind == 0 ? 3.14159265358979323846 : 4.0 * 3.14159265358979323846);  // w0: pi (planar), 4 pi (spherical)
-    const double f0 = (double)bins[i] * u;
-    BatchSeries s;
-    for (int b = 0; b < numBatches; ++b) {
-      const double f = (double)bins[(size_t)b * ns + i] * u;
-      if (batchMeans) batchMeans[(size_t)b * ns + i] = (float)f;
-      s.add(f - f0);
-    }
-    irradiance[i] = (float)(f0 + s.shift(numBatches));
-    if (irradianceStdErr) irradianceStdErr[i] = (float)s.error(numBatches);
-  }
+  double unit;
+  if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
+  reduce_batches(bins.data(), 1, numBatches, (size_t)n, 1, sensor_units(n, sensors, unit).data(), {{irradiance, nullptr}, {irradianceStdErr, nullptr}, nullptr, batchMeans});
   return 0;
 }
 
 }  // extern "C"
-

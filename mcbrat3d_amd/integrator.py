@@ -465,6 +465,30 @@ class Integrator:
             self._check(self._lib.mcbrat_set_forward_table(self._ctx, c + 1, t.shape[1], t.shape[0], ptr(t), None))
         self._camera_token = token
 
+    def _render_camera(self, entry, camera, before, seed, firstSample, samplesPerPixel, numBatches, randomNumbers=None, bins=(), **more):
+        """One camera-shaped call: entry(ctx, camera, *before, seed, firstSample, samples, batches, radiance, error, batch means,
+        dropped) into zeroed arrays [*bins, npy, npx]; the sample indices of randomNumbers, where given, move on."""
+        s, nb, shape = camera.struct(), int(numBatches), tuple(bins) + (camera.npy, camera.npx)
+        rad, err, means = np.zeros(shape, np.float32), np.zeros(shape, np.float32), np.zeros((max(nb, 1),) + shape, np.float32)
+        dropped = C.c_int64(0)
+        self._check(entry(self._ctx, C.addressof(s), *before, int(seed), int(firstSample), int(samplesPerPixel), nb, ptr(rad), ptr(err), ptr(means),
+                          C.addressof(dropped)))
+        if randomNumbers is not None:
+            randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
+        return dict({"radiance": rad, "radiance_StdErr": err, "batchMeans": means}, dropped=int(dropped.value), **more)
+
+    def _render_sensors(self, entry, sensors, before, randomNumbers, samplesPerSensor, numBatches, gridInLds, values, parts=()):
+        """One sensor-shaped call: entry(ctx, n, sensors, *before, seed, firstSample, samples, batches, gridInLds, the `values`
+        arrays of one float per sensor, batch means, dropped) into zeroed arrays; batch means [numBatches, *parts, n].
+        -> (the value arrays, the batch means, dropped); the sample indices of randomNumbers move on."""
+        n, nb, arr = len(sensors), int(numBatches), sensors.structs()
+        out, means = [np.zeros(n, np.float32) for _ in range(values)], np.zeros((max(nb, 1),) + tuple(parts) + (n,), np.float32)
+        dropped = C.c_int64(0)
+        self._check(entry(self._ctx, n, C.addressof(arr), *before, randomNumbers.seed, randomNumbers.nextPhotonId, int(samplesPerSensor), nb,
+                          int(gridInLds), *[ptr(a) for a in out], ptr(means), C.addressof(dropped)))
+        randomNumbers.nextPhotonId += int(samplesPerSensor) * nb
+        return out, means, int(dropped.value)
+
     def renderCamera(self, camera, randomNumbers, samplesPerPixel, numBatches=1):
         """The radiance at `camera` (mcbrat3d_amd.camera.new_Camera) by backward Monte Carlo, numBatches batches of
         samplesPerPixel paths per pixel, for the domain and the Directional solar source this integrator has loaded (prepare,
@@ -473,15 +497,8 @@ class Integrator:
         paths a loop bound ended.  Sample indices continue from randomNumbers.nextPhotonId; tallies, moments and settings of the
         integrator are left alone."""
         self._load_camera_tables()
-        s = camera.struct()
-        npx, npy, nb = camera.npx, camera.npy, int(numBatches)
-        rad, err = np.zeros((npy, npx), np.float32), np.zeros((npy, npx), np.float32)
-        means = np.zeros((max(nb, 1), npy, npx), np.float32)
-        dropped = C.c_int64(0)
-        self._check(self._lib.mcbrat_render_camera(self._ctx, C.addressof(s), randomNumbers.seed, randomNumbers.nextPhotonId,
-                                                   int(samplesPerPixel), nb, ptr(rad), ptr(err), ptr(means), C.addressof(dropped)))
-        randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
-        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value)}
+        return self._render_camera(self._lib.mcbrat_render_camera, camera, (), randomNumbers.seed, randomNumbers.nextPhotonId, samplesPerPixel,
+                                   numBatches, randomNumbers)
 
     def renderSensors(self, sensors, randomNumbers, samplesPerSensor, numBatches=1, gridInLds=-1):
         """Irradiance (planar sensors) and actinic flux (spherical ones) at `sensors` (mcbrat3d_amd.sensors.new_Sensors) by
@@ -492,17 +509,10 @@ class Integrator:
         (diffuse, direct) and "dropped", the number of paths a loop bound ended.  Sample indices continue from
         randomNumbers.nextPhotonId; tallies, moments and settings of the integrator are left alone."""
         self._load_camera_tables()
-        n, nb = len(sensors), int(numBatches)
-        arr = sensors.structs()
-        dif, dirc, eDif, eDir, eTot = (np.zeros(n, np.float32) for _ in range(5))
-        means = np.zeros((max(nb, 1), 2, n), np.float32)
-        dropped = C.c_int64(0)
-        self._check(self._lib.mcbrat_render_sensors(self._ctx, n, C.addressof(arr), randomNumbers.seed, randomNumbers.nextPhotonId,
-                                                    int(samplesPerSensor), nb, int(gridInLds), ptr(dif), ptr(dirc), ptr(eDif),
-                                                    ptr(eDir), ptr(eTot), ptr(means), C.addressof(dropped)))
-        randomNumbers.nextPhotonId += int(samplesPerSensor) * nb
+        (dif, dirc, eDif, eDir, eTot), means, dropped = self._render_sensors(self._lib.mcbrat_render_sensors, sensors, (), randomNumbers,
+                                                                             samplesPerSensor, numBatches, gridInLds, 5, parts=(2,))
         return {"irradiance": dif + dirc, "irradiance_StdErr": eTot, "diffuse": dif, "direct": dirc, "diffuse_StdErr": eDif,
-                "direct_StdErr": eDir, "batchMeans": means, "dropped": int(dropped.value)}
+                "direct_StdErr": eDir, "batchMeans": means, "dropped": dropped}
 
     def renderCameraPathLengths(self, camera, pathEdges, samplesPerPixel, numBatches=1, seed=0, firstSample=0):
         """renderCamera's radiance split by photon path length (DESIGN.md section 4.23): the geometric length, in the domain's
@@ -512,14 +522,8 @@ class Integrator:
         [batch, bin, y, x], "pathEdges", "dropped"}; mcbrat3d_amd.camera.absorbed_radiance and mean_path_length read them."""
         self._load_camera_tables()
         edges = np.ascontiguousarray(np.asarray(pathEdges, np.float32).reshape(-1))
-        s = camera.struct()
-        npx, npy, nb, nbin = camera.npx, camera.npy, int(numBatches), max(int(edges.size), 1)
-        rad, err = np.zeros((nbin, npy, npx), np.float32), np.zeros((nbin, npy, npx), np.float32)
-        means = np.zeros((max(nb, 1), nbin, npy, npx), np.float32)
-        dropped = C.c_int64(0)
-        self._check(self._lib.mcbrat_render_camera_pathlengths(self._ctx, C.addressof(s), int(edges.size), ptr(edges), int(seed), int(firstSample),
-                                                               int(samplesPerPixel), nb, ptr(rad), ptr(err), ptr(means), C.addressof(dropped)))
-        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "pathEdges": edges, "dropped": int(dropped.value)}
+        return self._render_camera(self._lib.mcbrat_render_camera_pathlengths, camera, (int(edges.size), ptr(edges)), seed, firstSample, samplesPerPixel,
+                                   numBatches, bins=(max(int(edges.size), 1),), pathEdges=edges)
 
     # -- the emission renders (DESIGN.md section 4.22) ----------------------------------------
     def prepareDomain(self, thisDomain):
@@ -545,16 +549,8 @@ class Integrator:
         and surfaceSource [ny, nx] are Planck radiances (mcbrat3d_amd.planck_sources); the result has their units.  The loaded
         source is not consulted (none need be loaded: prepareDomain).  Returns what renderCamera returns."""
         cell, sfc = self._emission_sources("renderCameraEmission", cellSource, surfaceSource)
-        s = camera.struct()
-        npx, npy, nb = camera.npx, camera.npy, int(numBatches)
-        rad, err = np.zeros((npy, npx), np.float32), np.zeros((npy, npx), np.float32)
-        means = np.zeros((max(nb, 1), npy, npx), np.float32)
-        dropped = C.c_int64(0)
-        self._check(self._lib.mcbrat_render_camera_emission(self._ctx, C.addressof(s), ptr(cell), ptr(sfc), randomNumbers.seed,
-                                                            randomNumbers.nextPhotonId, int(samplesPerPixel), nb, ptr(rad), ptr(err),
-                                                            ptr(means), C.addressof(dropped)))
-        randomNumbers.nextPhotonId += int(samplesPerPixel) * nb
-        return {"radiance": rad, "radiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value), "emission": True}
+        return self._render_camera(self._lib.mcbrat_render_camera_emission, camera, (ptr(cell), ptr(sfc)), randomNumbers.seed, randomNumbers.nextPhotonId,
+                                   samplesPerPixel, numBatches, randomNumbers, emission=True)
 
     def renderSensorsEmission(self, sensors, randomNumbers, samplesPerSensor, numBatches=1, cellSource=None, surfaceSource=None,
                               gridInLds=-1):
@@ -562,16 +558,9 @@ class Integrator:
         the sources' units times steradians.  Returns "irradiance", "irradiance_StdErr" (one value per sensor), "batchMeans"
         [numBatches, n] and "dropped"; there is no direct part ("emission": True marks the dict for the NetCDF writers)."""
         cell, sfc = self._emission_sources("renderSensorsEmission", cellSource, surfaceSource)
-        n, nb = len(sensors), int(numBatches)
-        arr = sensors.structs()
-        irr, err = np.zeros(n, np.float32), np.zeros(n, np.float32)
-        means = np.zeros((max(nb, 1), n), np.float32)
-        dropped = C.c_int64(0)
-        self._check(self._lib.mcbrat_render_sensors_emission(self._ctx, n, C.addressof(arr), ptr(cell), ptr(sfc), randomNumbers.seed,
-                                                             randomNumbers.nextPhotonId, int(samplesPerSensor), nb, int(gridInLds),
-                                                             ptr(irr), ptr(err), ptr(means), C.addressof(dropped)))
-        randomNumbers.nextPhotonId += int(samplesPerSensor) * nb
-        return {"irradiance": irr, "irradiance_StdErr": err, "batchMeans": means, "dropped": int(dropped.value), "emission": True}
+        (irr, err), means, dropped = self._render_sensors(self._lib.mcbrat_render_sensors_emission, sensors, (ptr(cell), ptr(sfc)), randomNumbers,
+                                                          samplesPerSensor, numBatches, gridInLds, 2)
+        return {"irradiance": irr, "irradiance_StdErr": err, "batchMeans": means, "dropped": dropped, "emission": True}
 
     def sunTransmittance(self, points):
         """exp(-optical depth) from each point (an [n, 3] array of x, y, z) toward the sun up to the top of the loaded

@@ -8,6 +8,9 @@
 //   shape total numCUs block             -> pathsPerLane blocks
 //   stats m0 m1 ...                      -> mean error                     (one series of batch means)
 //   sum f0 f1 ... | d0 d1 ...            -> error                          (the per-batch sum of two series, as the sensors form it)
+//   reduce arrays numBatches n slots unit[n] bins[arrays][numBatches][n][slots]
+//                                        -> mean[2][slots][n] error[2][slots][n] totalError[slots][n] batchMeans[numBatches][arrays][slots][n]
+//                                           (reduce_batches with every output; -1: not written)
 // A stand-alone host program (plain C++, no HIP): tests/test_backward_host.py builds it with the address and undefined-behaviour
 // sanitizers and holds the lines to closed forms written out in numpy.
 #include <cstdio>
@@ -53,6 +56,25 @@ int main() {
       mcbrat::BatchSeries s;
       for (size_t b = 0; b < nb; ++b) s.add((d(1 + b) - d(1)) + (d(d0 + b) - d(d0)));
       printf("%.17g\n", s.error((int)nb));
+    } else if (w[0] == "reduce" && n >= 4 && n == 4 + u(3) + u(1) * u(2) * u(3) * u(4)) {
+      const int arrays = (int)u(1), numBatches = (int)u(2);
+      const size_t nr = u(3), slots = u(4), values = nr * slots;
+      std::vector<double> unit(nr);
+      std::vector<long long> bins((size_t)arrays * numBatches * values);
+      for (size_t i = 0; i < nr; ++i) unit[i] = d(5 + i);
+      for (size_t i = 0; i < bins.size(); ++i) bins[i] = strtoll(w.at(5 + nr + i).c_str(), nullptr, 10);
+      // every output is asked for, poisoned first: what the reduction does not write shows
+      std::vector<float> mean(2 * values, -1.0f), error(2 * values, -1.0f), total(values, -1.0f), means(bins.size(), -1.0f);
+      mcbrat::reduce_batches(bins.data(), arrays, numBatches, nr, slots, unit.data(),
+                             {{mean.data(), arrays == 2 ? mean.data() + values : nullptr}, {error.data(), arrays == 2 ? error.data() + values : nullptr},
+                              arrays == 2 ? total.data() : nullptr, means.data()});
+      for (const std::vector<float> *v : {&mean, &error, &total, &means})
+        for (float x : *v) printf("%.9g ", (double)x);
+      printf("\n");
+      // ... and none but the means: the same means, nothing else touched
+      std::vector<float> alone(values, -1.0f);
+      mcbrat::reduce_batches(bins.data(), arrays, numBatches, nr, slots, unit.data(), {{alone.data(), nullptr}, {nullptr, nullptr}, nullptr, nullptr});
+      if (memcmp(alone.data(), mean.data(), sizeof(float) * values) != 0) return 3;
     } else {
       fprintf(stderr, "backward_dump: cannot read '%s ...'\n", w[0].c_str());
       return 2;

@@ -1,7 +1,8 @@
 """The host rules of a backward render without a GPU: tests/backward_dump.cpp, a stand-alone program over
 mcbrat3d_amd/csrc/mcbrat_backward.h alone, plain and under the address and undefined-behaviour sanitizers, held to closed forms
 written out here in double -- the two crossing bounds, the fixed-point scale, the capacity predicates at their edges, the launch
-shape, the statistics of the batch means -- and that mcbrat_camera.hip's host half states none of them a second time."""
+shape, the statistics of the batch means, the one reduction of the bins to the five entries' output layouts -- and that
+mcbrat_camera.hip's host half states none of them, and no sentence of a refusal, a second time."""
 import math
 import os
 import re
@@ -57,8 +58,16 @@ def test_the_host_half_states_each_rule_once():
     assert "65536.0" not in cam and "4.611686018427387904e18" not in cam
     assert cam.count("hipLaunchKernelGGL") <= 3
     assert cam.count("forward phase function table") == 1 and cam.count("phaseFunctionIndex exceeds forward table entries") == 1
-    for call in ("sun_bound(", "leg_bound(", "fixed_point(", "bins_fit(", "paths_fit(", "launch_shape(", "BatchSeries"):
+    for call in ("sun_bound(", "leg_bound(", "fixed_point(", "bins_fit(", "paths_fit(", "launch_shape(", "reduce_batches("):
         assert call in cam, call
+    # five entries, each rule once: no sentence of a refusal is worded twice, the batch statistics are the header's reduction alone,
+    # the receivers' geometry is mapped in one front each (and in mcbrat_camera_ray, mcbrat_sensor_ray)
+    sentences = re.findall(r'"([^"\n]{20,}\.)"', cam)
+    assert len(sentences) >= 20 and [s for s in set(sentences) if sentences.count(s) > 1] == []
+    for name in os.listdir(CSRC):
+        if name.endswith((".h", ".hip", ".cpp")) and name != "mcbrat_backward.h":
+            assert "BatchSeries" not in open(os.path.join(CSRC, name)).read(), name
+    assert 1 <= cam.count("camera_geometry(") <= 2 and 1 <= cam.count("sensor_geometry(") <= 2 and 1 <= cam.count("std::memset(&cp") <= 3
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -192,6 +201,85 @@ def test_batch_statistics(exes):
     from_differences = series([(a - f[0]) + (b - d[0]) for a, b in zip(f, d)])[1]
     from_sums = series([(a + b) - (f[0] + d[0]) for a, b in zip(f, d)])[1]
     assert float(got[5][0]) == from_differences != from_sums
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the one reduction of the bins to means, standard errors and batch means
+# ---------------------------------------------------------------------------------------------------------------------------------
+def reduce_reference(bins, unit):
+    """bins [arrays, numBatches, n, slots] (int64), unit [n] -> (mean [2, slots, n], error [2, slots, n], totalError [slots, n],
+    batchMeans [numBatches, arrays, slots, n]): reduce_batches' operations in its order, in double, then float32; -1: not written"""
+    arrays, nb, n, slots = bins.shape
+    m = bins.astype(np.float64) * np.asarray(unit, np.float64)[None, None, :, None]
+    diff = m - m[:, :1]
+    both = diff.sum(axis=0) if arrays == 2 else diff[0]     # (f - f0) + (d - d0)
+    nbf = float(nb)
+
+    def stats(d):  # d [numBatches, n, slots] -> (shift, error), each [slots, n]
+        s1, s2 = np.zeros(d.shape[1:]), np.zeros(d.shape[1:])
+        for b in range(nb):
+            s1 = s1 + d[b]
+            s2 = s2 + d[b] * d[b]
+        dm = s1 / nbf
+        err = np.sqrt(np.maximum(0.0, s2 - nbf * dm * dm) / (nbf * (nbf - 1.0))) if nb > 1 else np.zeros(dm.shape)
+        return dm.T, err.T
+
+    mean, error, total = np.full((2, slots, n), -1.0, np.float32), np.full((2, slots, n), -1.0, np.float32), np.full((slots, n), -1.0, np.float32)
+    for a in range(arrays):
+        shift, err = stats(diff[a])
+        mean[a], error[a] = (m[a, 0].T + shift).astype(np.float32), err.astype(np.float32)
+    if arrays == 2:
+        total[:] = stats(both)[1].astype(np.float32)
+    return mean, error, total, m.transpose(1, 0, 3, 2).astype(np.float32)
+
+
+def reduced(exes, bins, unit):
+    bins = np.asarray(bins, np.int64)
+    arrays, nb, n, slots = bins.shape
+    words = ask(exes, [("reduce", arrays, nb, n, slots) + tuple(float(x) for x in unit) + tuple(int(x) for x in bins.reshape(-1))])[0]
+    got = np.array([np.float32(float(x)) for x in words], np.float32)
+    v = slots * n
+    assert got.size == 5 * v + bins.size
+    got = got[:2 * v].reshape(2, slots, n), got[2 * v:4 * v].reshape(2, slots, n), got[4 * v:5 * v].reshape(slots, n), got[5 * v:].reshape(nb, arrays, slots, n)
+    for g, w, what in zip(got, reduce_reference(bins, unit), ("mean", "error", "totalError", "batchMeans")):
+        assert g.tobytes() == w.tobytes(), (what, g, w)
+    return got
+
+
+def test_the_reduction_is_the_arithmetic_written_out(exes):
+    rng = np.random.default_rng(11)
+    unit = 2.0 ** -40 / 197.0
+    # one batch: the errors are exactly 0
+    mean, error, total, means = reduced(exes, rng.integers(1, 2 ** 50, (1, 1, 3, 1)), [unit] * 3)
+    assert np.all(error[0] == 0.0) and np.all(mean[0] > 0) and np.all(mean[1] == -1.0) and np.all(total == -1.0) and means.tobytes() == mean[0].tobytes()
+    # the path-length layout, every bin another: [batch][n][slot] -> [slot][n] and [batch][slot][n]
+    bins = (1 + np.arange(3 * 2 * 4, dtype=np.int64).reshape(1, 3, 2, 4)) * 2 ** 30
+    mean, error, total, means = reduced(exes, bins, [unit, 1.0009765625 * unit])
+    assert len(set(bins.reshape(-1))) == 24 and len(set(means.reshape(-1))) == 24
+    for b in range(3):
+        for i in range(2):
+            for s in range(4):
+                assert means[b, 0, s, i] == np.float32(float(bins[0, b, i, s]) * (unit, 1.0009765625 * unit)[i])
+    assert mean.shape == (2, 4, 2) and np.all(error[0] > 0) and np.all(mean[1] == -1.0)
+    # the sensors' three series, a unit per receiver of pi and 4 pi: the total's error is the sum series', not a sum of errors
+    bins = rng.integers(2 ** 40, 2 ** 41, (2, 4, 3, 1))
+    units = [unit * math.pi, unit * 4.0 * math.pi, unit * math.pi]
+    mean, error, total, means = reduced(exes, bins, units)
+    for i in range(3):
+        f, d = ([float(bins[a, b, i, 0]) * units[i] for b in range(4)] for a in (0, 1))
+        assert total[0, i] == np.float32(series([(x - f[0]) + (y - d[0]) for x, y in zip(f, d)])[1])
+        assert error[0, 0, i] == np.float32(series([x - f[0] for x in f])[1]) and mean[1, 0, i] == np.float32(d[0] + series([y - d[0] for y in d])[0])
+        assert 0 < total[0, i] < error[0, 0, i] + error[1, 0, i]
+    assert means.shape == (4, 2, 1, 3) and np.all(means[:, 1, 0] == (bins[1, :, :, 0].astype(np.float64) * np.array(units)).astype(np.float32))
+    # identical batches: errors exactly 0, the mean the first batch's value to the bit
+    one = rng.integers(1, 2 ** 55, (2, 1, 3, 2))
+    mean, error, total, means = reduced(exes, np.repeat(one, 5, axis=1), units)
+    assert np.all(error == 0.0) and np.all(total == 0.0)
+    assert mean.tobytes() == (one[:, 0].astype(np.float64) * np.array(units)[None, :, None]).transpose(0, 2, 1).astype(np.float32).tobytes()
+    # bins near 2^61 (a bin's sum stays below 2^62)
+    big = 2 ** 61 - rng.integers(0, 2 ** 20, (2, 3, 2, 2))
+    mean, error, total, means = reduced(exes, big, [unit, unit])
+    assert np.all(np.abs(mean / np.float32(2.0 ** 61 * unit) - 1.0) < 1e-6) and np.all(np.isfinite(error)) and np.all(np.isfinite(total))
 
 
 def test_a_question_the_program_cannot_read_is_an_error(exes):

@@ -34,24 +34,32 @@ SENSOR_KEYS = ("diffuse", "direct", "diffuse_StdErr", "direct_StdErr", "irradian
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the renders
 # ---------------------------------------------------------------------------------------------------------------------------------
-def renders(seed):
-    """-> {"camera 0": {array: hex of its bytes, "dropped": count}, "camera 1", "sensors 0", "sensors 1"} (0 | 1: gridInLds)"""
-    from mcbrat3d_amd.integrator import new_RandomNumberSequence
+def scene():
+    """-> (the integrator, its domain, the three sensors, camera(gridInLds): the 5 x 3 pinhole)"""
     from mcbrat3d_amd.sensors import new_Sensors
     from tests import cases
     from tests.test_gpu_camera import _integrator, _pinhole
     case = cases.step_cloud(ssa=0.99)
     case["albedo"] = 0.2
-    integ, _ = _integrator(case, 0.5, 30.0)
+    integ, dom = _integrator(case, 0.5, 30.0)
     point = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
     sensors = new_Sensors([(0.13, 0.2, 0.05), (0.2, 0.1, 0.0), (0.35, 0.3, 0.12)], tilt=[35.0, 0.0, 0.0], azimuth=[200.0, 0.0, 0.0],
                           kind=["planar", "planar", "spherical"], extents=[point, ((0.1, 0.0, 0.0), (0.0, 0.2, 0.0)), point])
+    return integ, dom, sensors, lambda lds: _pinhole(5, 3, (0.13, 0.2, 0.05), (0.4, 0.1, 1.0), fov=80.0, gridInLds=lds)
+
+
+def packed(res, keys):
+    return dict({k: np.ascontiguousarray(res[k]).tobytes().hex() for k in keys}, dropped=res["dropped"])
+
+
+def renders(seed):
+    """-> {"camera 0": {array: hex of its bytes, "dropped": count}, "camera 1", "sensors 0", "sensors 1"} (0 | 1: gridInLds)"""
+    from mcbrat3d_amd.integrator import new_RandomNumberSequence
+    integ, _, sensors, camera = scene()
     out = {}
     for lds in (0, 1):
-        cam = _pinhole(5, 3, (0.13, 0.2, 0.05), (0.4, 0.1, 1.0), fov=80.0, gridInLds=lds)
-        for name, keys, res in (("camera", CAMERA_KEYS, integ.renderCamera(cam, new_RandomNumberSequence(seed), SAMPLES, BATCHES)),
-                                ("sensors", SENSOR_KEYS, integ.renderSensors(sensors, new_RandomNumberSequence(seed), SAMPLES, BATCHES, gridInLds=lds))):
-            out["%s %d" % (name, lds)] = dict({k: np.ascontiguousarray(res[k]).tobytes().hex() for k in keys}, dropped=res["dropped"])
+        out["camera %d" % lds] = packed(integ.renderCamera(camera(lds), new_RandomNumberSequence(seed), SAMPLES, BATCHES), CAMERA_KEYS)
+        out["sensors %d" % lds] = packed(integ.renderSensors(sensors, new_RandomNumberSequence(seed), SAMPLES, BATCHES, gridInLds=lds), SENSOR_KEYS)
     integ.finalize()
     return out
 
@@ -59,9 +67,9 @@ def renders(seed):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the refusals
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _bare(L, ptr, step, big=False):
-    """a context with nothing (step 0); the grid (1); optics and the solar source, no table (2); the forward table alone (3).
-    big: 128 x 128 x 64 cells, which no LDS share holds, instead of 2 x 2 x 2"""
+def _bare(L, ptr, step, big=False, rpv=False):
+    """a context with nothing (step 0); the grid (1); optics and the solar source, no table (2); the forward table alone (3); the
+    inverse table too (4).  big: 128 x 128 x 64 cells, which no LDS share holds, instead of 2 x 2 x 2; rpv: a BRDF surface"""
     ctx = L.mcbrat_create(0)
     assert ctx
     nx, nz = (128, 64) if big else (2, 2)
@@ -73,6 +81,12 @@ def _bare(L, ptr, step, big=False):
         assert L.mcbrat_set_source_solar(ctx, C.c_float(0.5), C.c_float(0.0)) == 0
     if step >= 3:
         assert L.mcbrat_set_forward_table(ctx, 1, 181, 1, ptr(np.ones(181, np.float32)), None) == 0
+    if step >= 4:
+        inv, coef = np.zeros(101, np.float32), np.zeros(2, np.float32)
+        assert L.mcbrat_inverse_table_legendre(len(coef), ptr(coef), len(inv), ptr(inv)) == 0
+        assert L.mcbrat_set_inverse_table(ctx, 1, len(inv), 1, ptr(inv)) == 0
+    if rpv:
+        assert L.mcbrat_set_surface_brdf(ctx, 1, 2, 2, ptr(np.array([0.0, 1.0])), ptr(np.array([0.0, 1.0])), 4, ptr(np.array([0.1, 0.8, -0.1, 0.5], np.float32))) == 0
     return ctx
 
 
@@ -92,8 +106,9 @@ class _Contexts:
                 if name.endswith("rpv"):
                     c.ok(c.setters["rpv"]())
                 self.made[name] = c.ctx
-            else:  # "bare 0" .. "bare 3", "big bare 3"
-                self.made[name] = _bare(self.L, self.ptr, int(name[-1]), big=name.startswith("big"))
+            else:  # "bare 0" .. "bare 4", "big bare 3", "bare 1 rpv"
+                step = name.replace(" rpv", "")
+                self.made[name] = _bare(self.L, self.ptr, int(step[-1]), big=name.startswith("big"), rpv=step != name)
         return self.made[name]
 
     def close(self):
@@ -180,18 +195,25 @@ def refusals():
     return out
 
 
-def _first_of_each_pair_refuses(rec):
-    """what needs no golden file: in every pair the EARLIER rule of the order is the one that speaks"""
-    words = {"no array": "no camera or no array", "bad camera": "camera kind", "samples": "samplesPer", "batches": "numBatches", "budget": "tally budget",
-             "index count": "64-bit index", "grid and optics": "not completely specified", "source": "Directional solar source",
-             "BRDF surface": "BRDF surface", "height": "height", "forward tables": "forward phase function table",
-             "inverse tables": "inverse phase function table", "n < 1": "n < 1", "null arrays": "no sensors or no arrays", "gridInLds": "gridInLds must be",
-             "bad sensor": "sensor kind", "corners": "corner"}
-    for entry, prefix in (("camera order", "renderCamera:"), ("sensors order", "renderSensors:")):
+WORDS = {"no array": "no camera or no array", "bad camera": "camera kind", "samples": "samplesPer", "batches": "numBatches", "budget": "tally budget",
+         "index count": "64-bit index", "grid and optics": "not completely specified", "source": "Directional solar source",
+         "BRDF surface": "BRDF surface", "height": "height", "forward tables": "forward phase function table",
+         "inverse tables": "inverse phase function table", "n < 1": "n < 1", "null arrays": "no sensors or no arrays", "gridInLds": "gridInLds must be",
+         "bad sensor": "sensor kind", "corners": "corner"}
+ENTRIES = (("camera order", "renderCamera:"), ("sensors order", "renderSensors:"))
+
+
+def _first_of_each_pair_refuses(rec, entries=ENTRIES, words=WORDS, raw=()):
+    """what needs no golden file: in every pair the EARLIER rule of the order is the one that speaks.  raw: (entry, rule)s whose
+    text is the receiver's own, under the solar entry's name"""
+    for entry, prefix in entries:
         for pair, text in rec[entry].items():
             first, second = pair.split(", ")
             assert words[first] in text, (entry, pair, text)
-            assert text.startswith(prefix) or first == "inverse tables", (entry, pair, text)   # (those: the context's own text)
+            if (entry, first) in raw:
+                assert text.startswith(dict(ENTRIES)[entry.split()[-2] + " order"]), (entry, pair, text)
+            else:
+                assert text.startswith(prefix) or first == "inverse tables", (entry, pair, text)   # (those: the context's own text)
             assert second == "context" or second == "LDS share" or words[second] not in text, (entry, pair, text)
 
 
