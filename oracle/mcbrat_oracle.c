@@ -1599,6 +1599,273 @@ static int64_t compute_rt(const orc_problem *P, const orc_source *S, orc_rng *R,
   return nPhotons;
 }
 
+/* ------------------------------------------------------------------------ */
+/* Backward paths: DESIGN.md sections 4.19, 4.20, 4.22, 4.23 (ours, restated  */
+/* from those sections; not in the reference)                                */
+/* ------------------------------------------------------------------------ */
+typedef struct { uint32_t key[2], id, lo, hi; } bw_stream;
+static void bw_block(const bw_stream *s, uint32_t event, uint32_t block, float u[4]) {
+  const uint32_t ctr[4] = {event | (block << 24), s->id, s->lo, s->hi};
+  uint32_t out[4];
+  orc_philox4x32_10(ctr, s->key, out);
+  for (int e = 0; e < 4; e++) u[e] = (float)out[e] * 2.3283064365386963e-10f;
+}
+
+static double bw_round(const orc_backward *B, double v) { return B->floatState ? (double)(float)v : v; }
+
+/* the fold of a point into the domain and its cell (1-based); zMax belongs to the top layer */
+static void bw_locate(const orc_problem *P, double pos[3], int32_t idx[3]) {
+  const double *edge[3] = {P->xe, P->ye, P->ze};
+  const int ncell[3] = {P->nx, P->ny, P->nz};
+  for (int a = 0; a < 2; a++) {
+    const double lo = edge[a][0], hi = edge[a][ncell[a]], len = hi - lo;
+    pos[a] -= floor((pos[a] - lo) / len) * len;
+    if (pos[a] < lo) pos[a] += len;
+    if (pos[a] >= hi) pos[a] -= len;
+  }
+  for (int a = 0; a < 3; a++) {
+    int i = orc_find_index_double(pos[a], edge[a], ncell[a] + 1, 0);
+    idx[a] = i < 1 ? 1 : (i > ncell[a] ? ncell[a] : i);
+  }
+}
+
+/* optical depth from pos in cell idx along dir up to the boundary of the domain (the walker without a target); *length: km */
+static double bw_depth_to_boundary(const orc_problem *P, level_tally *T, const float dir[3], const double pos[3], const int32_t idx[3],
+                                   double *length) {
+  double p[3] = {pos[0], pos[1], pos[2]};
+  int32_t i[3] = {idx[0], idx[1], idx[2]};
+  const double before = T->path;
+  const float tau = accumulate_extinction(P, dir, p, i, 0, 0.0f, NULL, T);
+  if (length) *length = T->path - before;
+  T->path = before;
+  return (double)tau;
+}
+
+/* P(Theta) of one table entry; nearest: the table read at the nearest angle (a mutation) */
+static double bw_phase(const float *table, int nA, double theta, int nearest) {
+  if (!nearest) return (double)orc_lookup_phase_value(table, nA, (float)theta);
+  long k = lrint(theta / (kPiD / (double)(nA - 1)));
+  if (k < 0) k = 0;
+  if (k > nA - 1) k = nA - 1;
+  return (double)table[k];
+}
+
+static uint64_t bw_hash(uint64_t h, int32_t v) {
+  for (int b = 0; b < 4; b++) { h ^= (uint64_t)((uint32_t)v >> (8 * b)) & 0xffu; h *= 1099511628211ull; }
+  return h;
+}
+
+int64_t orc_backward_paths(const orc_problem *P, const orc_intensity *I, orc_backward *B, uint64_t seed, int64_t n,
+                           const double *origin, const double *direction, const uint32_t *id, const uint64_t *sample) {
+  const int nx = P->nx, ny = P->ny, nz = P->nz, nc = P->nc;
+  const size_t ncol = (size_t)nx * ny, nbins = ncol * ((size_t)nz + 1);
+  const double z0 = P->ze[0], zMax = P->ze[nz];
+  const double Lxy[2] = {P->xe[nx] - P->xe[0], P->ye[ny] - P->ye[0]};
+  const double kMargin = 64.0 * ldexp(1.0, -23), kDraw = ldexp(1.0, -20);
+  const int solar = B->mode != ORC_BW_EMISSION, pathlen = B->mode == ORC_BW_PATHLEN;
+  double *lup = (double *)calloc(nbins, sizeof(double)), *ldn = (double *)calloc(nbins, sizeof(double));
+  level_tally T; /* (the walker's own bookkeeping: the length of a leg is read from T.path) */
+  memset(&T, 0, sizeof(T));
+  T.up = lup; T.down = ldn; T.weight = 1.0f;
+  /* the sun: the unit vector TOWARD it, minus the float direction of travel of a Directional source (launch_directional) */
+  float sunf[3] = {0.f, 0.f, 1.f};
+  double sun[3], mu0 = 1.0;
+  if (solar) {
+    float travel[3];
+    make_direction_cosines(-fabsf(B->solarMu), (B->solarAzimuthDeg * acosf(-1.0f)) / 180.0f, travel);
+    for (int a = 0; a < 3; a++) sunf[a] = -travel[a];
+    mu0 = fabs((double)sunf[2]);
+  }
+  for (int a = 0; a < 3; a++) sun[a] = (double)sunf[a];
+  B->nDeposits = 0;
+
+  for (int64_t ip = 0; ip < n; ip++) {
+    const bw_stream S = {{(uint32_t)seed, (uint32_t)(seed >> 32)}, id[ip], (uint32_t)sample[ip], (uint32_t)(sample[ip] >> 32)};
+    double pos[3] = {origin[3 * ip], origin[3 * ip + 1], origin[3 * ip + 2]};
+    double d[3] = {direction[3 * ip], direction[3 * ip + 1], direction[3 * ip + 2]};
+    if (B->floatState) for (int a = 0; a < 3; a++) d[a] = (double)(float)d[a];
+    int32_t idx[3];
+    bw_locate(P, pos, idx);
+    double w = 1.0, sum = 0.0, pathL = 0.0, km = 0.0, directPart = 0.0;
+    int flagged = 0, fate = ORC_BW_BOUND, nEvents = 0, lastWasSurface = 0;
+    int32_t cls[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t hash = 1469598103934665603ull;
+    if (B->binSum) for (int b = 0; b < B->numEdges; b++) B->binSum[(size_t)ip * B->numEdges + b] = 0.0;
+    /* an origin on a face of its column: the fold or the cell may fall either way */
+    if (near_any(pos[0], P->xe, nx + 1, ldexp(1.0, -40)) || near_any(pos[1], P->ye, ny + 1, ldexp(1.0, -40))) flagged = 1;
+    if (solar && B->direct > 0.0) { /* section 4.20: the direct beam on the receiver at the path's origin */
+      const double T0 = bw_round(B, exp(-bw_depth_to_boundary(P, &T, sunf, pos, idx, NULL)));
+      directPart = T0 * B->direct;
+    }
+
+    for (uint32_t event = 1;; event++) {
+      if ((int32_t)event > B->maxEvents) { fate = ORC_BW_BOUND; break; }
+      float u[4];
+      bw_block(&S, event, 0, u);
+      const double tau = bw_round(B, fmax(-log(fmax((double)u[0], (double)FLT_MIN)), (double)FLT_MIN));
+      const float df[3] = {(float)d[0], (float)d[1], (float)d[2]};
+      /* what the leg would walk through up to the top or the surface: the depth it is compared with */
+      const double tauOut = bw_depth_to_boundary(P, &T, df, pos, idx, NULL);
+      if (fabs(tau - tauOut) <= kMargin * fmax(1.0, km) * tauOut) flagged = 1;
+      const double before[3] = {pos[0], pos[1], pos[2]};
+      T.path = 0.0;
+      const float walked = accumulate_extinction(P, df, pos, idx, 1, (float)tau, NULL, &T);
+      if (walked < 0.0f) { fate = ORC_BW_BOUND; break; }
+      double t = T.path;
+      nEvents++;
+      int32_t rec[ORC_BW_RECORD] = {0, 0, -1, -1, 0};
+      int wrapped = 0;
+      for (int a = 0; a < 2; a++)
+        if (fabs(before[a] + t * (double)df[a] - pos[a]) > 0.5 * Lxy[a]) wrapped = 1;
+      cls[5] += wrapped;
+      if (idx[2] > nz) { /* the top: nothing diffuse comes in from above */
+        rec[0] = 1;
+        for (int e = 0; e < ORC_BW_RECORD; e++) hash = bw_hash(hash, rec[e]);
+        if (B->record && nEvents <= B->recordCap) memcpy(B->record + ((size_t)ip * B->recordCap + (nEvents - 1)) * ORC_BW_RECORD, rec, sizeof(rec));
+        fate = ORC_BW_TOP;
+        break;
+      }
+      /* the leg's length as the path carries it; the end point moves with it along the leg */
+      const double tCarried = bw_round(B, t);
+      for (int a = 0; a < 3; a++) pos[a] += (double)df[a] * (tCarried - t);
+      t = tCarried;
+      km += t;
+      pathL = bw_round(B, pathL + t);
+      const double delta = kMargin * km;
+      double estimate = 0.0, zEvent;
+      int ended = 0;
+      if (idx[2] < 1) { /* the surface (Lambertian) */
+        idx[2] = 1;
+        pos[2] = z0;
+        zEvent = z0;
+        rec[0] = 2;
+        rec[1] = (idx[0] - 1) + nx * (idx[1] - 1);
+        cls[1]++;
+        float a;
+        if (P->surfNumX > 0) {
+          if (near_any(pos[0], P->surfXPosition, P->surfNumX, delta) || near_any(pos[1], P->surfYPosition, P->surfNumY, delta)) flagged = 1;
+          size_t patch = surface_patch_index(P, pos[0], pos[1]);
+          if (B->mutation == ORC_BW_MUT_UNFOLDED_ALBEDO) { /* the patch looked up without the fold: the nearest one of the description */
+            const double ux = before[0] + t * (double)df[0], uy = before[1] + t * (double)df[1];
+            int xi = orc_find_index_mixed((float)ux, P->surfXPosition, P->surfNumX, 0), yi = orc_find_index_mixed((float)uy, P->surfYPosition, P->surfNumY, 0);
+            xi = xi < 1 ? 1 : (xi > P->surfNumX - 1 ? P->surfNumX - 1 : xi);
+            yi = yi < 1 ? 1 : (yi > P->surfNumY - 1 ? P->surfNumY - 1 : yi);
+            patch = (size_t)(xi - 1) + (size_t)(P->surfNumX - 1) * (yi - 1);
+          }
+          rec[3] = (int32_t)patch;
+          a = P->surfReflectance[patch];
+        } else {
+          a = (float)P->albedo;
+        }
+        if (!solar) sum += bw_round(B, (w * (1.0 - (double)a)) * (double)B->surfaceSource[rec[1]]);
+        w = bw_round(B, w * (double)a);
+        if (!(w > 0.0)) { fate = ORC_BW_WEIGHT0; ended = 1; }
+        else if (solar) {
+          const double Tsun = bw_round(B, exp(-bw_depth_to_boundary(P, &T, sunf, pos, idx, NULL)));
+          estimate = bw_round(B, w * Tsun / kPiD);
+        }
+        if (!ended) { /* the cosine-weighted upward direction; a draw of exactly 0 takes the spare number, at least 2^-16 */
+          double mu = sqrt((double)u[1]);
+          if (mu == 0.0) mu = fmax(sqrt((double)u[3]), ldexp(1.0, -16));
+          float c, s;
+          sincos_2pi(u[2], &c, &s);
+          const double sinTheta = sqrt(1.0 - mu * mu);
+          d[0] = bw_round(B, sinTheta * (double)c); d[1] = bw_round(B, sinTheta * (double)s); d[2] = bw_round(B, mu);
+        }
+        lastWasSurface = 1;
+      } else { /* a collision */
+        zEvent = pos[2];
+        const size_t cell = IDX3(P, idx[0], idx[1], idx[2]);
+        rec[1] = (int32_t)cell;
+        cls[0]++;
+        if (lastWasSurface) cls[2]++;
+        lastWasSurface = 0;
+        if (pos[0] - P->xe[idx[0] - 1] <= delta || P->xe[idx[0]] - pos[0] <= delta || pos[1] - P->ye[idx[1] - 1] <= delta ||
+            P->ye[idx[1]] - pos[1] <= delta || pos[2] - P->ze[idx[2] - 1] <= delta || P->ze[idx[2]] - pos[2] <= delta)
+          flagged = 1;
+        int comp = 0; /* the component: the first whose cumulative extinction lies above the draw */
+        for (int k = 0; k < nc - 1; k++) {
+          const double threshold = P->cumExt[cell + ncol * nz * (size_t)k];
+          if (fabs((double)u[3] - threshold) <= kDraw) flagged = 1;
+          if ((double)u[3] >= threshold) comp = k + 1;
+        }
+        rec[2] = comp;
+        if (comp > 0) cls[4]++;
+        const double ssa = (double)(float)P->ssa[cell + ncol * nz * (size_t)comp];
+        const int pfi = P->pfIndex[cell + ncol * nz * (size_t)comp];
+        if (!solar) { /* section 4.22: the cell's emission along the path, before the weight is cut */
+          const double wDeposit = B->mutation == ORC_BW_MUT_EMIT_AFTER_CUT ? w * ssa : w;
+          sum += bw_round(B, (wDeposit * (1.0 - ssa)) * (double)B->cellSource[cell]);
+        }
+        const double wBefore = w;
+        w = bw_round(B, w * ssa);
+        if (!(w > 0.0)) { fate = ORC_BW_WEIGHT0; ended = 1; }
+        else if (solar) { /* the local estimate toward the sun: Theta between the sun's direction of travel and -d */
+          double proj = d[0] * sun[0] + d[1] * sun[1] + d[2] * sun[2];
+          if (B->mutation == ORC_BW_MUT_THETA_PLUS_D) proj = -proj;
+          const double theta = acos(clamp1(proj));
+          const int nA = I->fwdNAngles[comp];
+          const float *table = I->fwdTables + I->fwdOffset[comp] + (size_t)(pfi - 1) * nA;
+          const double phase = bw_round(B, bw_phase(table, nA, theta, B->mutation == ORC_BW_MUT_NEAREST_ANGLE));
+          const double Tsun = bw_round(B, exp(-bw_depth_to_boundary(P, &T, sunf, pos, idx, NULL)));
+          const double wEstimate = B->mutation == ORC_BW_MUT_ESTIMATE_BEFORE_CUT ? wBefore : w;
+          estimate = bw_round(B, wEstimate * phase * Tsun / (4.0 * kPiD * mu0));
+        }
+        if (!ended && P->useRussianRoulette && w < (B->mutation == ORC_BW_MUT_ROULETTE_049 ? 0.49 : 0.5)) {
+          float u1[4];
+          bw_block(&S, event, 1, u1);
+          if (fabs((double)u1[1] - w) <= kDraw * w) flagged = 1;
+          if ((double)u1[1] >= w) { rec[4] = 2; fate = ORC_BW_ROULETTE; ended = 1; }
+          else { rec[4] = 1; w = 1.0; cls[3]++; }
+        }
+        if (!ended) { /* the new direction from the inverse table about the old one */
+          const int ns = P->invNSteps[comp];
+          const float *tbl = P->invTables + P->invOffset[comp] + (size_t)(pfi - 1) * ns;
+          const double sc = cos((double)compute_scattering_angle(u[1], tbl, ns));
+          float fx, fy;
+          sincos_2pi(u[2], &fx, &fy);
+          double Bq = sqrt(fmax(1.0 - sc * sc, 0.0));
+          const double AX = (double)fx * Bq, AY = (double)fy * Bq;
+          Bq = d[0] * AX - d[1] * AY;
+          const double D = sc - Bq / (1.0 + fabs(d[2]));
+          d[0] = bw_round(B, d[0] * D + AX);
+          d[1] = bw_round(B, d[1] * D - AY);
+          d[2] = bw_round(B, d[2] * sc - copysign(fabs(Bq), d[2] * Bq));
+        }
+      }
+      if (solar && estimate != 0.0) {
+        if (pathlen) { /* section 4.23: the estimate by the length of the legs walked plus the sun ray's (zMax - z) / mu0 */
+          const double L = B->mutation == ORC_BW_MUT_NO_SUN_LENGTH ? pathL : bw_round(B, pathL + bw_round(B, (zMax - zEvent) / mu0));
+          int bin = 0;
+          for (int b = 0; b < B->numEdges; b++) {
+            if (L >= (double)B->pathEdges[b]) bin = b;
+            if (fabs(L - (double)B->pathEdges[b]) <= kMargin * (km + (zMax - zEvent) / mu0)) flagged = 1;
+          }
+          if (B->binSum) B->binSum[(size_t)ip * B->numEdges + bin] += estimate;
+          if (B->nDeposits < B->depositCap && B->depositPath) {
+            B->depositPath[B->nDeposits] = (int32_t)ip; B->depositBin[B->nDeposits] = bin;
+            B->depositValue[B->nDeposits] = estimate; B->depositLength[B->nDeposits] = L;
+          }
+          B->nDeposits++;
+        }
+        sum += estimate;
+      }
+      for (int e = 0; e < ORC_BW_RECORD; e++) hash = bw_hash(hash, rec[e]);
+      if (B->record && nEvents <= B->recordCap) memcpy(B->record + ((size_t)ip * B->recordCap + (nEvents - 1)) * ORC_BW_RECORD, rec, sizeof(rec));
+      if (ended) break;
+    }
+    B->sum[ip] = sum;
+    if (B->directPart) B->directPart[ip] = directPart;
+    if (B->nEvents) B->nEvents[ip] = nEvents;
+    if (B->fate) B->fate[ip] = fate;
+    if (B->near) B->near[ip] = (uint8_t)flagged;
+    if (B->recordHash) B->recordHash[ip] = hash;
+    if (B->classes) memcpy(B->classes + 6 * (size_t)ip, cls, sizeof(cls));
+  }
+  free(lup); free(ldn);
+  return n;
+}
+
 void orc_normalize_intensity(const orc_problem *P, const orc_intensity *I, int64_t numPhotonsProcessed,
                              float *intensity, float *intensityByComponent, const float *intensityExcess) {
   const int nx = P->nx, ny = P->ny, nc = P->nc, nDir = I->nDirections;

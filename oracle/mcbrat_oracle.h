@@ -249,6 +249,50 @@ typedef struct {
 int64_t orc_compute_rt_brdf(const orc_problem *P, const orc_source *S, orc_rng *R, int64_t numPhotons, float *fluxUp,
                             float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption, orc_counters *C, orc_fate *fates,
                             const orc_intensity *I, float *intensity, orc_brdf *B);
+/* ---- backward paths (DESIGN.md sections 4.19, 4.20, 4.22, 4.23; not in the reference) -------------------------------- */
+/* One call traces n backward paths of ONE receiver (a camera's pixels, or one sensor) from given origins and directions, in
+ * double, with the reference's walker (orc_accumulate_extinction) for the legs and the sun rays.  Random numbers: Philox4x32-10
+ * keyed by the seed, counter (event | block << 24, id[i], sample[i] lo, hi).  Every output pointer but sum may be NULL. */
+enum { ORC_BW_SOLAR = 0, ORC_BW_EMISSION = 1, ORC_BW_PATHLEN = 2 };
+enum { ORC_BW_TOP = 0, ORC_BW_WEIGHT0 = 1, ORC_BW_ROULETTE = 2, ORC_BW_BOUND = 3 };
+/* mutation: one rule deliberately misstated (the power check of tests/test_oracle_backward.py); 0: none */
+enum { ORC_BW_MUT_ROULETTE_049 = 1, ORC_BW_MUT_ESTIMATE_BEFORE_CUT = 2, ORC_BW_MUT_THETA_PLUS_D = 3, ORC_BW_MUT_NEAREST_ANGLE = 4,
+       ORC_BW_MUT_UNFOLDED_ALBEDO = 5, ORC_BW_MUT_EMIT_AFTER_CUT = 6, ORC_BW_MUT_NO_SUN_LENGTH = 7 };
+#define ORC_BW_RECORD 5   /* int32 per recorded event: how the leg ended (0 collision, 1 top, 2 surface), cell (0-based, x
+                           * fastest) or column, component (0-based; -1 surface), patch (-1: none), roulette (0 not played,
+                           * 1 survived, 2 ended the path) */
+typedef struct {
+  int32_t mode;                      /* ORC_BW_*                                                               */
+  int32_t floatState;                /* round to float, where they are read: the direction after each scattering or reflection,
+                                      * tau, the leg length, the weight, T_sun, P and each estimate            */
+  int32_t mutation;
+  float solarMu, solarAzimuthDeg;    /* the sun (solar modes), as orc_source holds it                          */
+  const float *cellSource;           /* emission: [nz][ny][nx], x fastest                                      */
+  const float *surfaceSource;        /* emission: [ny][nx]                                                     */
+  int32_t numEdges;                  /* path lengths: lower edges of the bins, the first 0, ascending          */
+  const float *pathEdges;
+  double direct;                     /* a sensor's factor of the direct beam, c / w0 (0: none is computed)     */
+  int32_t maxEvents;                 /* a path that has not ended by then: fate ORC_BW_BOUND                   */
+  int32_t recordCap;                 /* events recorded per path in `record` (the hash covers all of them)     */
+  int64_t depositCap;                /* deposits listed in all (path lengths)                                  */
+  /* out, per path */
+  double *sum;                       /* [n] the sum of the path's estimates                                    */
+  double *directPart;                /* [n] T_sun(origin) * direct                                             */
+  double *binSum;                    /* [n][numEdges] path lengths: the estimates by bin                       */
+  int32_t *nEvents, *fate;           /* [n]                                                                    */
+  uint8_t *near;                     /* [n] a discrete decision of the path lies within the margins of DESIGN.md section 3 */
+  uint64_t *recordHash;              /* [n] FNV-1a over every event's five record words                        */
+  int32_t *record;                   /* [n][recordCap][ORC_BW_RECORD]                                          */
+  int32_t *classes;                  /* [n][6] collisions, surface reflections, reflections followed by a collision, roulette
+                                      * survivals, picks of a component other than the first, legs with a periodic wrap */
+  /* out, per call (path lengths): the first depositCap deposits in order */
+  int64_t nDeposits;
+  int32_t *depositPath, *depositBin; /* [depositCap]                                                           */
+  double *depositValue, *depositLength;
+} orc_backward;
+int64_t orc_backward_paths(const orc_problem *P, const orc_intensity *I, orc_backward *B, uint64_t seed, int64_t n,
+                           const double *origin, const double *direction, const uint32_t *id, const uint64_t *sample);
+
 /* normalisation of computeRadiativeTransfer (:328-364), in place. */
 void orc_normalize(const orc_problem *P, int64_t numPhotonsProcessed, float *fluxUp,
                    float *fluxDown, float *fluxAbsorbed, float *volumeAbsorption);

@@ -130,6 +130,8 @@ def lib():
         L.orc_emission_weighting.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_double] * 4 + [C.c_void_p] * 3
         L.orc_philox_init.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         L.orc_frequency_distribution.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.orc_backward_paths.restype = C.c_int64
+        L.orc_backward_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64] + [C.c_void_p] * 4
         L.orc_surface_reflectance.restype = C.c_float
         L.orc_surface_reflectance.argtypes = [C.c_void_p, C.c_double, C.c_double]
         _LIB = L
@@ -677,6 +679,75 @@ def compute_radiative_transfer_intensity(problem, source, rng, n_photons, inten)
     norm.update(meanFluxUp=mu, meanFluxDown=md, meanFluxAbsorbed=ma, absorbedProfile=prof, n=raw["n"],
                 counters=raw["counters"], intensity=I, intensityByComponent=byc, meanIntensity=mean_i)
     return norm
+
+
+class OrcBackward(C.Structure):
+    _fields_ = ([("mode", C.c_int32), ("floatState", C.c_int32), ("mutation", C.c_int32), ("solarMu", C.c_float), ("solarAzimuthDeg", C.c_float),
+                 ("cellSource", C.c_void_p), ("surfaceSource", C.c_void_p), ("numEdges", C.c_int32), ("pathEdges", C.c_void_p),
+                 ("direct", C.c_double), ("maxEvents", C.c_int32), ("recordCap", C.c_int32), ("depositCap", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("sum", "directPart", "binSum", "nEvents", "fate", "near", "recordHash", "record", "classes")]
+                + [("nDeposits", C.c_int64)] + [(n, C.c_void_p) for n in ("depositPath", "depositBin", "depositValue", "depositLength")])
+
+
+BACKWARD_MODES = {"solar": 0, "emission": 1, "pathlengths": 2}
+BACKWARD_FATES = ("top", "weight 0", "roulette", "bound")
+BACKWARD_MUTATIONS = {None: 0, "roulette threshold 0.49": 1, "estimate before the cut": 2, "Theta against +d": 3, "nearest angle": 4,
+                      "unfolded albedo": 5, "emission after the cut": 6, "L without the sun ray": 7}
+BACKWARD_CLASSES = ("collisions", "reflections", "reflectionThenCollision", "rouletteSurvivals", "secondComponent", "wrappedLegs")
+
+
+def backward_paths(problem, intensity, seed, origins, directions, ids, samples, mode="solar", sun=None, float_state=False, mutation=None,
+                   cell_source=None, surface_source=None, path_edges=None, direct=0.0, max_events=1 << 20, record_cap=0, deposits=False):
+    """The backward paths of DESIGN.md sections 4.19, 4.20, 4.22, 4.23 in double (orc_backward_paths; not in the reference): path i
+    starts at origins[i] along directions[i] and draws from the Philox counter (event | block << 24, ids[i], samples[i] lo, hi).
+    sun = (mu0, azimuth in degrees) for the solar modes; cell_source [nz, ny, nx] and surface_source [ny, nx] for "emission";
+    path_edges (lower edges) for "pathlengths"; direct: a sensor's c / w0.  float_state and mutation: test infrastructure (the
+    header says what they do).  -> dict(sum, direct, nEvents, fate, near, hash [n]; classes: name -> [n]; binSum [n, bins];
+    record [n, record_cap, 5]; with deposits: depositPath, depositBin, depositValue, depositLength)."""
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+    n = o.shape[0]
+    idv = np.ascontiguousarray(np.broadcast_to(np.asarray(ids, np.uint32), (n,)))
+    smp = np.ascontiguousarray(samples, np.uint64).reshape(-1)
+    assert d.shape[0] == n and smp.size == n
+    B = OrcBackward()
+    B.mode, B.floatState, B.mutation = BACKWARD_MODES[mode], int(bool(float_state)), BACKWARD_MUTATIONS[mutation]
+    keep = []
+    if mode == "emission":
+        cs, ss = np.ascontiguousarray(cell_source, np.float32).reshape(-1), np.ascontiguousarray(surface_source, np.float32).reshape(-1)
+        assert cs.size == problem.nx * problem.ny * problem.nz and ss.size == problem.nx * problem.ny
+        B.cellSource, B.surfaceSource = _p(cs), _p(ss)
+        keep += [cs, ss]
+    else:
+        B.solarMu, B.solarAzimuthDeg = float(sun[0]), float(sun[1])
+    nb = 0
+    if mode == "pathlengths":
+        edges = np.ascontiguousarray(path_edges, np.float32).reshape(-1)
+        nb, B.numEdges, B.pathEdges = edges.size, edges.size, _p(edges)
+        keep.append(edges)
+    B.direct, B.maxEvents, B.recordCap = float(direct), int(max_events), int(record_cap)
+    out = dict(sum=np.zeros(n), direct=np.zeros(n), nEvents=np.zeros(n, np.int32), fate=np.zeros(n, np.int32), near=np.zeros(n, np.uint8),
+               hash=np.zeros(n, np.uint64), binSum=np.zeros((n, nb)), record=np.full((n, max(int(record_cap), 0), 5), -1, np.int32))
+    cls = np.zeros((n, 6), np.int32)
+    B.sum, B.directPart, B.nEvents, B.fate, B.near, B.recordHash, B.classes = (_p(out["sum"]), _p(out["direct"]), _p(out["nEvents"]), _p(out["fate"]),
+                                                                            _p(out["near"]), _p(out["hash"]), _p(cls))
+    if nb:
+        B.binSum = _p(out["binSum"])
+    if record_cap > 0:
+        B.record = _p(out["record"])
+    if deposits:
+        cap = 64 * max(n, 1)
+        dep = dict(depositPath=np.zeros(cap, np.int32), depositBin=np.zeros(cap, np.int32), depositValue=np.zeros(cap), depositLength=np.zeros(cap))
+        B.depositCap = cap
+        B.depositPath, B.depositBin, B.depositValue, B.depositLength = (_p(dep[k]) for k in ("depositPath", "depositBin", "depositValue", "depositLength"))
+    lib().orc_backward_paths(C.addressof(problem.c), C.addressof(intensity.c) if intensity is not None else None, C.addressof(B), int(seed), n,
+                         _p(o), _p(d), _p(idv), _p(smp))
+    out["near"] = out["near"].astype(bool)
+    out["classes"] = {name: cls[:, k].copy() for k, name in enumerate(BACKWARD_CLASSES)}
+    if deposits:
+        m = min(int(B.nDeposits), B.depositCap)
+        out.update({k: v[:m] for k, v in dep.items()}, nDeposits=int(B.nDeposits))
+    return out
 
 
 def normalize(problem, n_done, res):
