@@ -35,7 +35,7 @@ module mcbrat_hip_integrator
             specifySideFluxes, reportSideFluxes, &
             camera, renderCamera, sunTransmittance, &
             sensor, renderSensors, &
-            renderCameraEmission, renderSensorsEmission, &
+            renderCameraEmission, renderSensorsEmission, renderCameraEmissionExpected, renderSensorsEmissionExpected, &
             renderCameraPathLengths
 
   ! mcbrat_camera of include/mcbrat.h, member for member (the backward camera, DESIGN.md section 4.19): kind 0 orthographic --
@@ -324,6 +324,33 @@ module mcbrat_hip_integrator
     function mcbrat_render_sensors_emission(ctx, n, sensors, cellSource, surfaceSource, seed, firstSample, samplesPerSensor, &
                                             numBatches, gridInLds, irradiance, irradianceStdErr, batchMeans, dropped) &
                                             bind(C, name="mcbrat_render_sensors_emission") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_float, sensor
+      type(c_ptr), value :: ctx
+      integer(c_int64_t), value :: n, seed, firstSample, samplesPerSensor
+      type(sensor), intent(in) :: sensors(*)
+      real(c_float), intent(in) :: cellSource(*), surfaceSource(*)
+      integer(c_int32_t), value :: numBatches, gridInLds
+      real(c_float), intent(out) :: irradiance(*)
+      type(c_ptr), value :: irradianceStdErr, batchMeans   ! (c_null_ptr: not wanted)
+      integer(c_int64_t), intent(out) :: dropped
+      integer(c_int) :: rc
+    end function
+    function mcbrat_render_camera_emission_expected(ctx, cam, cellSource, surfaceSource, seed, firstSample, samplesPerPixel, numBatches, &
+                                           radiance, radianceStdErr, batchMeans, dropped) &
+                                           bind(C, name="mcbrat_render_camera_emission_expected") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_float, camera
+      type(c_ptr), value :: ctx
+      type(camera), intent(in) :: cam
+      real(c_float), intent(in) :: cellSource(*), surfaceSource(*)
+      integer(c_int64_t), value :: seed, firstSample, samplesPerPixel
+      integer(c_int32_t), value :: numBatches
+      type(c_ptr), value :: radiance, radianceStdErr, batchMeans   ! (c_null_ptr: not wanted; radiance is needed)
+      integer(c_int64_t), intent(out) :: dropped
+      integer(c_int) :: rc
+    end function
+    function mcbrat_render_sensors_emission_expected(ctx, n, sensors, cellSource, surfaceSource, seed, firstSample, samplesPerSensor, &
+                                            numBatches, gridInLds, irradiance, irradianceStdErr, batchMeans, dropped) &
+                                            bind(C, name="mcbrat_render_sensors_emission_expected") result(rc)
       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_float, sensor
       type(c_ptr), value :: ctx
       integer(c_int64_t), value :: n, seed, firstSample, samplesPerSensor
@@ -1093,6 +1120,66 @@ contains
                                           pErr, c_null_ptr, dropped)
     if (present(numDropped)) numDropped = dropped
   end subroutine renderSensorsEmission
+
+  ! The emission renders with the expected-value estimator (include/mcbrat.h: mcbrat_render_camera_emission_expected,
+  ! mcbrat_render_sensors_emission_expected): the arguments of renderCameraEmission and renderSensorsEmission, the same paths;
+  ! every leg deposits the emission along its whole ray, collisions and surface hits deposit nothing.
+  subroutine renderCameraEmissionExpected(this, cam, cellSource, surfaceSource, seed, firstSample, samplesPerPixel, numBatches, radiance, &
+                                  radianceStdErr, numDropped, ierr)
+    type(integrator), intent(inout) :: this
+    type(camera), intent(in) :: cam
+    real, dimension(:, :, :), contiguous, intent(in) :: cellSource
+    real, dimension(:, :), contiguous, intent(in) :: surfaceSource
+    integer(c_int64_t), intent(in) :: seed, firstSample, samplesPerPixel
+    integer, intent(in) :: numBatches
+    real, dimension(:, :), contiguous, target, intent(out) :: radiance
+    real, dimension(:, :), contiguous, optional, target, intent(out) :: radianceStdErr
+    integer(c_int64_t), optional, intent(out) :: numDropped
+    integer, intent(out) :: ierr
+    type(c_ptr) :: pErr
+    integer(c_int64_t) :: dropped
+    ierr = 1
+    if (any(shape(radiance) /= (/ cam%npx, cam%npy /))) return
+    if (any(shape(cellSource) /= (/ this%numX, this%numY, this%numZ /)) .or. any(shape(surfaceSource) /= (/ this%numX, this%numY /))) return
+    pErr = c_null_ptr
+    if (present(radianceStdErr)) then
+      if (any(shape(radianceStdErr) /= (/ cam%npx, cam%npy /))) return
+      pErr = c_loc(radianceStdErr)
+    end if
+    dropped = 0
+    ierr = mcbrat_render_camera_emission_expected(this%ctx, cam, cellSource, surfaceSource, seed, firstSample, samplesPerPixel, &
+                                         int(numBatches, c_int32_t), c_loc(radiance), pErr, c_null_ptr, dropped)
+    if (present(numDropped)) numDropped = dropped
+  end subroutine renderCameraEmissionExpected
+
+  subroutine renderSensorsEmissionExpected(this, sensors, cellSource, surfaceSource, seed, firstSample, samplesPerSensor, numBatches, &
+                                   irradiance, irradianceStdErr, numDropped, ierr)
+    type(integrator), intent(inout) :: this
+    type(sensor), dimension(:), contiguous, intent(in) :: sensors
+    real, dimension(:, :, :), contiguous, intent(in) :: cellSource
+    real, dimension(:, :), contiguous, intent(in) :: surfaceSource
+    integer(c_int64_t), intent(in) :: seed, firstSample, samplesPerSensor
+    integer, intent(in) :: numBatches
+    real, dimension(:), contiguous, intent(out) :: irradiance
+    real, dimension(:), contiguous, optional, target, intent(out) :: irradianceStdErr
+    integer(c_int64_t), optional, intent(out) :: numDropped
+    integer, intent(out) :: ierr
+    type(c_ptr) :: pErr
+    integer(c_int64_t) :: dropped
+    ierr = 1
+    if (size(irradiance) /= size(sensors)) return
+    if (any(shape(cellSource) /= (/ this%numX, this%numY, this%numZ /)) .or. any(shape(surfaceSource) /= (/ this%numX, this%numY /))) return
+    pErr = c_null_ptr
+    if (present(irradianceStdErr)) then
+      if (size(irradianceStdErr) /= size(sensors)) return
+      pErr = c_loc(irradianceStdErr)
+    end if
+    dropped = 0
+    ierr = mcbrat_render_sensors_emission_expected(this%ctx, int(size(sensors), c_int64_t), sensors, cellSource, surfaceSource, seed, &
+                                          firstSample, samplesPerSensor, int(numBatches, c_int32_t), -1_c_int32_t, irradiance, &
+                                          pErr, c_null_ptr, dropped)
+    if (present(numDropped)) numDropped = dropped
+  end subroutine renderSensorsEmissionExpected
 
   ! exp(-optical depth) from each point xyz(3, n) toward the sun up to the top of the domain (mcbrat_sun_transmittance)
   subroutine sunTransmittance(this, xyz, transmittance, ierr)

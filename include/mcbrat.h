@@ -541,6 +541,33 @@ int mcbrat_render_sensors_emission(mcbrat_ctx *ctx, int64_t n, const mcbrat_sens
                                    int32_t gridInLds /* -1 library's choice, 0, 1 */,
                                    float *irradiance /* [n] */, float *irradianceStdErr /* [n], may be NULL */,
                                    float *batchMeans /* [numBatches][n], may be NULL */, int64_t *dropped /* may be NULL */);
+/* The emission renders with the expected-value (track-length) estimator (additions under ABI version 3).
+ * Arguments, checks, refusals (worded under the entries' own names), outputs and units are those of mcbrat_render_camera_emission
+ * and mcbrat_render_sensors_emission.  The same (seed, sample range) walks the collision estimator's paths: the same origins,
+ * directions, Philox counters, leg lengths, collision points, components, weights, roulette and reflections.  Only the deposits
+ * differ.  Collisions and surface hits deposit nothing; every leg, with the weight w it starts with, deposits the formal
+ * solution along its whole ray, on past its collision point up to the domain's boundary:
+ *     w sum over the cells v crossed  E[v] e^(-tau_in) (1 - e^(-dtau))   +   w e^(-tau_sfc) (1 - a(x, y)) surfaceSource[column]
+ * with tau counted from the leg's origin, the second term where the ray meets the surface (nothing at the top), and
+ * E[v] = cellSource[v] sum_c f_c(v) (1 - omega0[c, v]), f_c the extinction share of component c (0 where the extinction is 0).
+ * The two estimators have the same mean; a medium that does not scatter is rendered without variance.  A ray stops adding
+ * behind optical depth 30: what is left is below e^(-30) < 2^-43 of the largest source value, an eighth of the finest step of
+ * the tally.  A path's sum is not bounded by the largest source value; a path whose sum reaches the tally's saturation value is
+ * dropped and counted in `dropped`, as is one whose ray a loop bound ends -- the RAY, which goes on past the leg's collision
+ * point: for the same seed `dropped` may be larger than the collision estimator's, whose leg ended inside the bound (a nearly
+ * horizontal leg through a near-vacuum).  gridInLds = 1 asks for the extinction grid AND E[v]
+ * in LDS (8 bytes per cell) and is refused where the pair does not fit; -1 then renders from global memory. */
+int mcbrat_render_camera_emission_expected(mcbrat_ctx *ctx, const mcbrat_camera *cam, const float *cellSource /* [nz][ny][nx] */,
+                                           const float *surfaceSource /* [ny][nx] */, uint64_t seed, uint64_t firstSample,
+                                           int64_t samplesPerPixel /* per batch */, int32_t numBatches,
+                                           float *radiance /* [npy][npx] */, float *radianceStdErr /* may be NULL */,
+                                           float *batchMeans /* [numBatches][npy][npx], may be NULL */, int64_t *dropped /* may be NULL */);
+int mcbrat_render_sensors_emission_expected(mcbrat_ctx *ctx, int64_t n, const mcbrat_sensor *sensors, const float *cellSource,
+                                            const float *surfaceSource, uint64_t seed, uint64_t firstSample,
+                                            int64_t samplesPerSensor /* per batch */, int32_t numBatches,
+                                            int32_t gridInLds /* -1 library's choice, 0, 1 */,
+                                            float *irradiance /* [n] */, float *irradianceStdErr /* [n], may be NULL */,
+                                            float *batchMeans /* [numBatches][n], may be NULL */, int64_t *dropped /* may be NULL */);
 /* The Planck function exactly as mcbrat_emission_weighting evaluates it (one function serves both): out[i] = B(lambda, temps[i])
  * in W m-2 sr-1 um-1, so that forward `intensity` x totalFlux / dLambda and the emission camera's radiance on these sources are
  * one quantity.  Host arithmetic only.  Returns 1 for a null array, a negative n or a wavelength that is not positive. */

@@ -118,6 +118,8 @@ SYMBOLS = {
     "mcbrat_sensor_ray": (C.c_int, [_vp, _d, _d, _d, _d, _vp, _vp]),
     "mcbrat_render_camera_emission": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_render_sensors_emission": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mcbrat_render_camera_emission_expected": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "mcbrat_render_sensors_emission_expected": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _u64, _u64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_planck_radiance": (C.c_int, [_d, _i64, _vp, _vp]),
     "mcbrat_render_camera_pathlengths": (C.c_int, [_vp, _vp, _i32, _vp, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mcbrat_trace_fates": (C.c_int, [_vp, _u64, _u64, _i64, _vp]),

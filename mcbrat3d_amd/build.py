@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmcbrat_hip.so")
 SOURCES = ["mcbrat_api.hip", "mcbrat_host.cpp", "mcbrat_camera.hip"]  # (mcbrat_camera.hip: the backward camera, a translation unit of its own)
-DEPS = SOURCES + ["mcbrat_kernels.hip", "mcbrat_blockwalk.hip", "mcbrat_photon.h", "mcbrat_device.h", "mcbrat_brdf.h", "mcbrat_layout.h", "mcbrat_variants.h", "mcbrat_devmem.h", "mcbrat_camera_ray.h", "mcbrat_sensor_ray.h", "mcbrat_camera_ctx.h", "mcbrat_backward.h", "mcbrat_pathbins.h", os.path.join("..", "..", "include", "mcbrat.h")]
+DEPS = SOURCES + ["mcbrat_kernels.hip", "mcbrat_blockwalk.hip", "mcbrat_photon.h", "mcbrat_device.h", "mcbrat_brdf.h", "mcbrat_layout.h", "mcbrat_variants.h", "mcbrat_devmem.h", "mcbrat_camera_ray.h", "mcbrat_sensor_ray.h", "mcbrat_camera_ctx.h", "mcbrat_backward.h", "mcbrat_pathbins.h", "mcbrat_expected.h", os.path.join("..", "..", "include", "mcbrat.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 

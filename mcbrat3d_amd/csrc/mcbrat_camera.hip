@@ -2,7 +2,7 @@
 // mcbrat_camera_ray, mcbrat_sun_transmittance).  A translation unit of its own: camera_kernel and its host code; the tracing
 // kernels, their variant table and their parameter block are not touched.
 //
-// The host half: the five render entries keep their null checks and go through camera_front() or
+// The host half: the seven render entries keep their null checks and go through camera_front() or
 // sensor_front() -- the receiver's rules, check_counts(), backward_context(), height or corners, geometry --, backward_render() of
 // a Request and reduce_batches(), worded by the entry's Entry; the arithmetic (bounds, scale, capacity, launch shape, the
 // reduction of the bins) is mcbrat_backward.h's, plain C++ that runs without a GPU.  launch() is the one LDS-or-global launch,
@@ -37,6 +37,11 @@
 // own and is added to the bin (mcbrat_pathbins.h) of that length plus the sun ray's (zMax - z) / mu0: a histogram per wave in
 // LDS, flushed to the strip [batch][pixel][bin] of global memory when the wave moves on to another pixel.
 //
+// The expected-value estimator of the emission renders (mcbrat_render_camera_emission_expected,
+// mcbrat_render_sensors_emission_expected): camera_kernel<.., EMIT = true, .., EXPECT = true> walks the collision estimator's
+// paths -- the same counters, legs, collision points, weights -- with march_expected() for march(): every leg deposits the formal
+// solution along its whole ray (mcbrat_expected.h), collisions and surface hits deposit nothing.
+//
 // Component pick, roulette, scattering angle and new direction are written out here as they are in trace_kernel
 // (mcbrat_kernels.hip, HOT ROWS) and trace_block_kernel (mcbrat_blockwalk.hip, HOT ROWS): a change to one of those rules is made
 // in all three.  What mcbrat_photon.h shares (Philox, u01, lambert_direction, find_cell, surface_reflectance, ...) is called.
@@ -56,6 +61,7 @@
 #include "mcbrat_camera_ctx.h"
 #include "mcbrat_backward.h"
 #include "mcbrat_pathbins.h"
+#include "mcbrat_expected.h"
 #include "mcbrat_devmem.h"
 
 namespace mcbrat {
@@ -98,6 +104,8 @@ struct CamParams {
   int numBins;
   int pathDirect;                  // every deposit straight to global memory (option cameraPathBinsInLds = 0: a measurement)
   float invMu0;                    // 1 / mu0: the sun ray's geometric length is (zMax - z) / mu0
+  // the expected-value estimator (EXPECT instantiations)
+  const float *emisCell;           // [nz][ny][nx] E[v], the cell's emission per unit extinction: emission_grid_kernel's, per render
 };
 
 struct GridView { const double *xe, *ye, *ze; const float *ext; };
@@ -195,6 +203,91 @@ __device__ __forceinline__ int march(const DevParams &p, const GridView &g, Ray 
   return end;
 }
 
+__device__ __forceinline__ float camera_albedo(const DevParams &p, double x, double y) {
+  return p.surfNumX > 0 ? surface_reflectance(p, x, y) : p.albedo;
+}
+
+// How the RAY of a leg ended (march_expected): at the top, on the surface (in `column`, behind optical depth tauSfc), at
+// maxCross crossings, or behind kExpectedTauCut
+enum : int { RAY_TOP = END_TOP, RAY_SURFACE = END_SURFACE, RAY_BOUND = END_BOUND, RAY_CUT = 4 };
+struct RayEnd { int how, column; float tauSfc; };
+
+// The walk of an EXPECT instantiation: march() for the leg -- the same cells in the same order, the
+// same sums in the same order, so the value returned, tEnd, acc and r's cell and periodic image are march()'s bit for bit -- and
+// in the same pass the emission of the whole ray, on past the collision point to the boundary or to the cut:
+//     emitted = sum over the segments  E[v] e^(-tau_in) (1 - e^(-dtau))  +  e^(-tau_sfc) (1 - a) S_sfc where it meets the surface
+// with tau from the leg's origin (mcbrat_expected.h: expected_segment).  `emis`: E[v], in LDS or in global memory.
+__device__ __forceinline__ int march_expected(const DevParams &p, const CamParams &cp, const GridView &g, const float *emis, Ray &r, float target,
+                                              unsigned maxCross, float &tEnd, float &acc, float &emitted, RayEnd &ray) {
+  const float jx = fabsf(r.dx) >= 2.0f * FLT_MIN ? 1.0f / r.dx : 0.0f;
+  const float jy = fabsf(r.dy) >= 2.0f * FLT_MIN ? 1.0f / r.dy : 0.0f;
+  const float jz = fabsf(r.dz) >= 2.0f * FLT_MIN ? 1.0f / r.dz : 0.0f;
+  const int hx = r.dx >= 0.0f ? 1 : 0, hy = r.dy >= 0.0f ? 1 : 0, hz = r.dz >= 0.0f ? 1 : 0;
+  int ix = r.ix, iy = r.iy, iz = r.iz;
+  double ox = r.ox, oy = r.oy;
+  float tx = jx != 0.0f ? (float)(g.xe[ix + hx] - ox) * jx : FLT_MAX;
+  float ty = jy != 0.0f ? (float)(g.ye[iy + hy] - oy) * jy : FLT_MAX;
+  float tz = jz != 0.0f ? (float)(g.ze[iz + hz] - r.oz) * jz : FLT_MAX;
+  float tcur = 0.0f;
+  float tau = 0.0f;   // the ray's optical depth: the leg's while the leg is open
+  bool open = true;   // the leg has not ended
+  int end = END_BOUND;
+  emitted = 0.0f;
+  ray.how = RAY_BOUND;
+  for (unsigned n = 0; n < maxCross; ++n) {
+    const int cell = (iz * p.ny + iy) * p.nx + ix;
+    const float e = g.ext[cell];
+    const float tmin = fminf(tx, fminf(ty, tz));
+    const float seg = fmaxf(tmin - tcur, 0.0f);
+    const float tauSeg = seg * e;
+    if (open && e > 0.0f && tau + tauSeg >= target) {
+      // the collision point, as march() finds it; the ray goes on, and the cell's segment is deposited whole below
+      tEnd = fminf(tcur + (target - tau) / e, fmaxf(tmin, tcur));
+      acc = target;
+      end = END_COLLISION;
+      open = false;
+      r.ix = ix; r.iy = iy; r.iz = iz; r.ox = ox; r.oy = oy;
+    }
+    if (tauSeg > 0.0f) {
+      const float E = emis[cell];
+      if (E > 0.0f) emitted += E * expected_segment(tau, tauSeg);
+    }
+    tau += tauSeg;
+    if (!open && tau >= kExpectedTauCut) { ray.how = RAY_CUT; break; }
+    tcur = fmaxf(tmin, tcur);
+    if (tz <= tx && tz <= ty) {
+      iz += hz ? 1 : -1;
+      if (iz < 0) { iz = 0; ray.how = RAY_SURFACE; break; }
+      if (iz >= p.nz) { iz = p.nz - 1; ray.how = RAY_TOP; break; }
+      tz = (float)(g.ze[iz + hz] - r.oz) * jz;
+    } else if (tx <= ty) {
+      ix += hx ? 1 : -1;
+      if (ix < 0) { ix = p.nx - 1; ox += p.Lx; }
+      if (ix >= p.nx) { ix = 0; ox -= p.Lx; }
+      tx = (float)(g.xe[ix + hx] - ox) * jx;
+    } else {
+      iy += hy ? 1 : -1;
+      if (iy < 0) { iy = p.ny - 1; oy += p.Ly; }
+      if (iy >= p.ny) { iy = 0; oy -= p.Ly; }
+      ty = (float)(g.ye[iy + hy] - oy) * jy;
+    }
+  }
+  ray.column = iy * p.nx + ix;
+  ray.tauSfc = tau;
+  if (ray.how == RAY_SURFACE) {
+    // (the point as the caller forms it where the leg itself ends here: the same albedo to the bit)
+    const float a = camera_albedo(p, ox + (double)r.dx * (double)tcur, oy + (double)r.dy * (double)tcur);
+    emitted += expf(-tau) * ((1.0f - a) * cp.srcSurface[ray.column]);
+  }
+  if (open) {  // the leg is the ray: it ends where march() ends it
+    end = ray.how;
+    r.ix = ix; r.iy = iy; r.iz = iz; r.ox = ox; r.oy = oy;
+    tEnd = tcur;
+    acc = tau;
+  }
+  return end;
+}
+
 // exp(-optical depth) from (x, y, z) in cell (ix, iy, iz) toward the sun up to the top; `bound`: the walk did not get there
 __device__ __forceinline__ float sun_transmittance(const DevParams &p, const CamParams &cp, const GridView &g, double x, double y, double z,
                                                    int ix, int iy, int iz, bool &bound) {
@@ -203,10 +296,6 @@ __device__ __forceinline__ float sun_transmittance(const DevParams &p, const Cam
   const int end = march(p, g, s, FLT_MAX, cp.maxSunCross, t, tau);
   bound = end != END_TOP;
   return expf(-tau);
-}
-
-__device__ __forceinline__ float camera_albedo(const DevParams &p, double x, double y) {
-  return p.surfNumX > 0 ? surface_reflectance(p, x, y) : p.albedo;
 }
 
 // Every lane of a wave calls this in step: adds the lanes' values to their bins -- one atomic for the wave where the lanes that
@@ -266,10 +355,25 @@ __device__ __forceinline__ void path_flush(LdsSum *hist, long long *strip, int n
 // deposits w (1 - omega0) S_cell BEFORE w *= omega0, the surface w (1 - a) S_sfc before w *= a, and a sensor has no direct part.
 // PATHLEN (the solar camera only): the radiance by photon path length.  The lane carries the length L of
 // the legs walked; every estimate is tallied on its own, at L plus the sun ray's (zMax - z) / mu0, in a histogram per wave.
-template <int BLOCK, bool GRID_LDS, bool SENSOR, bool EMIT, bool PATHLEN = false>
+// EXPECT (the emission renders only): the expected-value estimator on EMIT's path.  march_expected() is
+// the walk; the leg deposits w times its ray's emission, whatever ends it; EMIT's two deposits are not compiled.  A path whose
+// sum reaches pathMax is dropped and counted: a leg's deposit is not tied to the weight lost on it, so srcMax does not bound it.
+template <int BLOCK, bool GRID_LDS, bool SENSOR, bool EMIT, bool PATHLEN = false, bool EXPECT = false>
 __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_MIN_WAVES_PER_SIMD) camera_kernel(const DevParams p, const CamParams cp) {
   static_assert(!PATHLEN || (!SENSOR && !EMIT), "path lengths: the solar camera only");
+  static_assert(!EXPECT || (EMIT && !PATHLEN), "the expected-value estimator: the emission renders only");
   extern __shared__ __align__(16) unsigned char smem_raw[];
+  // EXPECT: E[v], staged behind the grid where the grid is staged (expected_lds_offset: the one statement of where, the host's
+  // too), before grid_view() and under its barrier
+  const float *emis = nullptr;
+  if constexpr (EXPECT) {
+    emis = cp.emisCell;
+    if constexpr (GRID_LDS) {
+      float *s_emis = reinterpret_cast<float *>(smem_raw + expected_lds_offset(p.nx, p.ny, p.nz));
+      for (int i = threadIdx.x; i < p.nx * p.ny * p.nz; i += BLOCK) s_emis[i] = cp.emisCell[i];
+      emis = s_emis;
+    }
+  }
   const GridView g = grid_view<BLOCK, GRID_LDS>(p, smem_raw);
   // PATHLEN: behind the grid, a histogram per wave and the edges (mcbrat_backward.h: path_lds_offset, path_lds_bytes)
   LdsSum *hist = nullptr;
@@ -371,7 +475,17 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       const float uX = u01(q[1]), uY = u01(q[2]), uZ = u01(q[3]);
       const float tau = fmaxf(-logf(fmaxf(u01(q[0]), FLT_MIN)), FLT_MIN);
       float t, acc;
-      const int end = march(p, g, r, tau, cp.maxLegCross, t, acc);
+      int end;
+      if constexpr (EXPECT) {
+        // the leg's whole ray, with the weight the leg starts with; a ray a bound ends drops the path, as a leg does
+        float emitted;
+        RayEnd ray;
+        end = march_expected(p, cp, g, emis, r, tau, cp.maxLegCross, t, acc, emitted, ray);
+        if (ray.how == RAY_BOUND) { dropped = true; break; }
+        sum += w * emitted;
+      } else {
+        end = march(p, g, r, tau, cp.maxLegCross, t, acc);
+      }
       if (end == END_TOP) break;
       if (end == END_BOUND) { dropped = true; break; }
       // where the leg ended, in the periodic image the walk stands in
@@ -385,7 +499,7 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
           // ending in `continue`: what follows is the solar event, left word for word as it was and dead in these instantiations
           // (a scope around its sun ray moves the sensor instantiations' control flow: their assembly is held to the parent's)
           const float a = camera_albedo(p, r.ox, r.oy);
-          sum += (w * (1.0f - a)) * cp.srcSurface[r.iy * p.nx + r.ix];
+          if constexpr (!EXPECT) sum += (w * (1.0f - a)) * cp.srcSurface[r.iy * p.nx + r.ix];
           w *= a;
           if (!(w > 0.0f)) break;
           float mu = sqrtf(uX);
@@ -417,7 +531,7 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       if constexpr (EMIT) {
         // the cell's emission along the path, before the weight is cut: a purely absorbing medium deposits and ends
         const float ssa = p.ssa[(long long)c * nvox + cell];
-        sum += (w * (1.0f - ssa)) * cp.srcCell[cell];
+        if constexpr (!EXPECT) sum += (w * (1.0f - ssa)) * cp.srcCell[cell];
         w *= ssa;
       } else {
         w *= p.ssa[(long long)c * nvox + cell];
@@ -485,7 +599,8 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
     }
     if constexpr (SENSOR && EMIT) {
       // no direct part (c = 0 for every sensor): one bin array, the sum in units of the largest source value
-      const bool ok = !dropped && sum == sum;
+      bool ok = !dropped && sum == sum;
+      if constexpr (EXPECT) ok = ok && (double)sum * cp.invSrcMax * cp.scale < cp.pathMax;
       if (valid && !ok) atomicAdd(cp.dropped, 1ull);
       const long long vEmitted = ok ? __double2ll_rn(fmin((double)sum * cp.invSrcMax * cp.scale, cp.pathMax)) : 0;
       wave_add(cp.bins, bin32, vEmitted, lane);
@@ -520,6 +635,8 @@ __global__ void __launch_bounds__(BLOCK, SENSOR ? kSensorWavesPerSimd : MCBRAT_M
       if (dropped) nDropped++;
     } else {
       if (dropped || !(sum == sum)) {  // (a NaN from a table: counted like a path a bound ended, contributes nothing)
+        nDropped++;
+      } else if (EXPECT && !((double)sum * cp.invSrcMax * cp.scale < cp.pathMax)) {
         nDropped++;
       } else if constexpr (EMIT) {
         pend += __double2ll_rn(fmin((double)sum * cp.invSrcMax * cp.scale, cp.pathMax));
@@ -570,6 +687,13 @@ __global__ void __launch_bounds__(BLOCK) sun_transmittance_kernel(const DevParam
   if (nDropped != 0u) atomicAdd(cp.dropped, (unsigned long long)nDropped);
 }
 
+// The set-up of a render with the expected-value estimator: E[v] of every cell, from the context's dense
+// grids and the caller's cellSource (mcbrat_expected.h: expected_emission), one lane per cell
+__global__ void __launch_bounds__(256) emission_grid_kernel(const DevParams p, const float *srcCell, float *emis) {
+  const long long nvox = (long long)p.nx * p.ny * p.nz, i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < nvox) emis[i] = expected_emission(p.nc, p.nc > 1 ? p.cum + i : nullptr, p.ssa + i, nvox, p.ext[i], srcCell[i]);
+}
+
 }  // namespace mcbrat
 
 using namespace mcbrat;
@@ -588,9 +712,9 @@ constexpr const char *kNoCamera = "no camera or no array for the radiance.", *kN
     if (e_ != hipSuccess) return mcbrat_camera_fail(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
   } while (0)
 
-size_t grid_lds_bytes(const DevParams &p) {
-  return sizeof(double) * (size_t)(p.nx + p.ny + p.nz + 3) + sizeof(float) * (size_t)p.nx * p.ny * p.nz;
-}
+size_t grid_lds_bytes(const DevParams &p) { return mcbrat::grid_lds_bytes(p.nx, p.ny, p.nz); }  // (mcbrat_expected.h: the kernel's too)
+static_assert(expected_lds_offset(24, 24, 24) == path_lds_offset(mcbrat::grid_lds_bytes(24, 24, 24)) && expected_lds_offset(1, 1, 2) == path_lds_offset(mcbrat::grid_lds_bytes(1, 1, 2)),
+              "the emission grid lies where launch() and choose_grid_lds() count it: at path_lds_offset of the grid's bytes");
 bool inside(const DevParams &p, double z) { return z >= p.z0 && z <= p.zMax; }
 
 // the sun: unit vector toward it, the bound on the crossings of a ray toward it, 1 / (4 pi mu0)
@@ -601,7 +725,8 @@ void sun_setup(const DevParams &p, CamParams &cp) {
 }
 
 // 0: global memory, 1: LDS; refused (asked for, does not fit): -1 the grid and the edges alone, -2 those with `extra`, what the
-// entry keeps in LDS beside them (at path_lds_offset; 0: nothing)
+// entry keeps in LDS beside them (at path_lds_offset; 0: nothing): a path-length render's histograms, the emission grid of the
+// expected-value estimator
 int choose_grid_lds(const CameraContext &v, int asked, size_t extra) {
   const size_t share = std::min(kCameraGridLds, v.ldsPerCU / 2), grid = grid_lds_bytes(v.p);
   const bool gridFits = grid <= share, fits = extra ? path_lds_offset(grid) + extra <= share : gridFits;
@@ -614,7 +739,8 @@ using BackwardKernel = void (*)(const DevParams, const CamParams);
 // The solar instantiations (EMIT = false) by the three parameters they have had since section 4.20
 template <int BLOCK, bool GRID_LDS, bool SENSOR>
 constexpr BackwardKernel solar_camera_kernel() { return camera_kernel<BLOCK, GRID_LDS, SENSOR, false>; }
-// extra: the entry's own LDS behind the grid's (a path-length render's histograms and edges, at path_lds_offset), or 0
+// extra: the entry's own LDS behind the grid's (a path-length render's histograms and edges, the expected-value estimator's
+// emission grid, at path_lds_offset), or 0
 int launch(mcbrat_ctx *c, const CameraContext &v, int lds, BackwardKernel inLds, BackwardKernel inGlobal, unsigned grid, int block, const CamParams &cp,
            size_t extra) {
   const BackwardKernel kernel = lds ? inLds : inGlobal;
@@ -649,9 +775,15 @@ struct Request {
   std::optional<double> largestOwn;       // the largest estimate the entry adds to the paths' own
   std::optional<EmissionSources> sources; // an emission render: no sun, no forward tables, no rule about the source
   std::optional<PathEdges> path;          // a render by path length
+  bool expected = false;                  // an emission render with the expected-value estimator
 };
 
 int fail(mcbrat_ctx *c, const Entry &e, const std::string &text) { return mcbrat_camera_fail(c, (std::string(e.name) + ": " + text).c_str()); }
+// A text of camera_refusal or sensor_refusal: as it is, under the solar entry's name, or under the entry's own
+int receiver_fail(mcbrat_ctx *c, const Entry &e, const char *msg) {
+  const char *colon = std::strchr(msg, ':');
+  return e.ownName ? fail(c, e, colon ? colon + 2 : msg) : mcbrat_camera_fail(c, msg);
+}
 
 // Stage 1, before anything of the call's arrays or of the context is read: samples, batches, budget, index count
 int check_counts(mcbrat_ctx *c, const Entry &e, const Counts &k) {
@@ -675,10 +807,7 @@ int backward_context(mcbrat_ctx *c, const Entry &e, bool solar, CameraContext &v
 // The front of the three camera entries, behind their own null checks: the camera's rules and the edges', stage 1 with the
 // entry's slots, stage 2, the height.  -> q.counts, q.gridInLds, v, and cp zeroed but for the camera's geometry
 int camera_front(mcbrat_ctx *c, const Entry &e, const mcbrat_camera &cam, Request &q, CameraContext &v, CamParams &cp) {
-  if (const char *msg = camera_refusal(cam)) {
-    const char *colon = std::strchr(msg, ':');
-    return e.ownName ? fail(c, e, colon ? colon + 2 : msg) : mcbrat_camera_fail(c, msg);
-  }
+  if (const char *msg = camera_refusal(cam)) return receiver_fail(c, e, msg);
   if (q.path)
     if (const char *msg = path_edges_refusal(q.path->edges, q.path->numBins)) return fail(c, e, msg);
   q.counts.n = (unsigned long long)cam.npx * (unsigned long long)cam.npy;
@@ -698,7 +827,7 @@ int sensor_front(mcbrat_ctx *c, const Entry &e, int64_t n, const mcbrat_sensor *
   q.counts.n = (unsigned long long)n;
   if (check_counts(c, e, q.counts)) return 1;
   for (int64_t i = 0; i < n; ++i)  // (after the budget: n sensors are read)
-    if (const char *msg = sensor_refusal(sensors[i])) return mcbrat_camera_fail(c, msg);
+    if (const char *msg = sensor_refusal(sensors[i])) return receiver_fail(c, e, msg);
   if (backward_context(c, e, !q.sources, v)) return 1;
   for (int64_t i = 0; i < 4 * n; ++i) {  // (sensor i / 4, corner i % 4)
     const mcbrat_sensor &s = sensors[i / 4];
@@ -753,9 +882,12 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, const Reque
   }
   if (mcbrat_camera_context(c, &v, true)) return 1;  // (the inverse tables: the context's own refusal text where one is missing)
   // (a path-length render: histograms and edges for the 512 lanes of the LDS instantiation count against the share with the grid)
+  // (the expected-value estimator: the emission grid, as large as the extinction grid, counts in the same way)
   const int numBins = q.path ? q.path->numBins : 0;
-  const int lds = choose_grid_lds(v, q.gridInLds, numBins ? path_lds_bytes(numBins, 512) : 0);
+  const size_t emisBytes = q.expected ? expected_lds_bytes(v.p.nx, v.p.ny, v.p.nz) : 0;
+  const int lds = choose_grid_lds(v, q.gridInLds, numBins ? path_lds_bytes(numBins, 512) : emisBytes);
   if (lds == -1) return fail(c, e, "gridInLds = 1, but the extinction grid and the edges do not fit the LDS share.");
+  if (lds == -2 && q.expected) return fail(c, e, "gridInLds = 1, but the extinction grid and the emission grid do not fit the LDS share together.");
   if (lds == -2) return fail(c, e, "gridInLds = 1, but the extinction grid and the path-length histograms do not fit the LDS share together.");
 
   const unsigned long long nBins = k.n * (unsigned long long)k.numBatches;
@@ -770,7 +902,7 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, const Reque
   v.p.seedLo = (uint32_t)q.seed; v.p.seedHi = (uint32_t)(q.seed >> 32);
 
   DeviceBuffer<long long> dBins;
-  DeviceBuffer<float> dFwd, dSrcCell, dSrcSurface, dEdges;
+  DeviceBuffer<float> dFwd, dSrcCell, dSrcSurface, dEdges, dEmis;
   DeviceBuffer<unsigned long long> dDropped;
   DeviceBuffer<SensorGeometry> dGeo;
   const size_t allBins = (size_t)(e.arrays * nBins * k.slots);
@@ -788,6 +920,12 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, const Reque
     CAM_HIP(c, hipMemcpyAsync(dSrcCell.get(), q.sources->cell, sizeof(float) * nvox, hipMemcpyHostToDevice, v.stream));
     CAM_HIP(c, hipMemcpyAsync(dSrcSurface.get(), q.sources->surface, sizeof(float) * ncol, hipMemcpyHostToDevice, v.stream));
     cp.srcCell = dSrcCell.get(); cp.srcSurface = dSrcSurface.get(); cp.invSrcMax = 1.0 / q.sources->srcMax;
+    if (q.expected) {
+      CAM_HIP(c, dEmis.allocate(nvox));
+      hipLaunchKernelGGL(emission_grid_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, v.stream, v.p, cp.srcCell, dEmis.get());
+      CAM_HIP(c, hipGetLastError());
+      cp.emisCell = dEmis.get();
+    }
   }
   if (q.path) {
     CAM_HIP(c, dEdges.allocate((size_t)numBins));
@@ -805,7 +943,7 @@ int backward_render(mcbrat_ctx *c, const Entry &e, CameraContext &v, const Reque
   const LaunchShape shape = launch_shape(cp.total, v.numCUs, block);
   cp.pathsPerLane = shape.pathsPerLane;
   if (shape.blocks > 0x7fffffffull) return fail(c, e, "more paths than one launch takes.");
-  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp, numBins ? path_lds_bytes(numBins, block) : 0)) return 1;
+  if (launch(c, v, lds, e.inLds, e.inGlobal, (unsigned)shape.blocks, block, cp, numBins ? path_lds_bytes(numBins, block) : (lds ? emisBytes : 0))) return 1;
   bins.resize(allBins);
   unsigned long long nDropped = 0;
   CAM_HIP(c, hipMemcpyAsync(bins.data(), dBins.get(), sizeof(long long) * allBins, hipMemcpyDeviceToHost, v.stream));
@@ -830,6 +968,28 @@ int render_camera(mcbrat_ctx *c, const Entry &e, const mcbrat_camera &cam, Reque
   if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
   const std::vector<double> units((size_t)q.counts.n, unit);
   reduce_batches(bins.data(), 1, q.counts.numBatches, (size_t)q.counts.n, (size_t)q.counts.slots, units.data(), {{radiance, nullptr}, {radianceStdErr, nullptr}, nullptr, batchMeans});
+  return 0;
+}
+
+// The two emission sensor entries behind their Entry: the null checks, the front, the sources, stage 3, the reduction
+int render_sensors_emission(mcbrat_ctx *c, const Entry &e, bool expected, int64_t n, const mcbrat_sensor *sensors, const float *cellSource,
+                            const float *surfaceSource, uint64_t seed, uint64_t firstSample, int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds,
+                            float *irradiance, float *irradianceStdErr, float *batchMeans, int64_t *dropped) {
+  if (!c) return 1;
+  if (n < 1) return fail(c, e, kNoSensor);
+  if (!sensors || !irradiance) return fail(c, e, "no sensors or no array for the irradiance.");
+  if (!cellSource || !surfaceSource) return fail(c, e, kNoSources);
+  Request q = {{0, samplesPerSensor, numBatches, firstSample}, seed, gridInLds};
+  q.sources = EmissionSources{cellSource, surfaceSource, 0.0};
+  q.expected = expected;
+  CameraContext v;
+  CamParams cp;
+  if (sensor_front(c, e, n, sensors, q, v, cp) || emission_sources(c, e, v, *q.sources)) return 1;
+  for (SensorGeometry &g : q.sensors) g.direct = 0.0f;
+  std::vector<long long> bins;  // [numBatches][n]
+  double unit;
+  if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
+  reduce_batches(bins.data(), 1, numBatches, (size_t)n, 1, sensor_units(n, sensors, unit).data(), {{irradiance, nullptr}, {irradianceStdErr, nullptr}, nullptr, batchMeans});
   return 0;
 }
 
@@ -968,21 +1128,33 @@ int mcbrat_render_sensors_emission(mcbrat_ctx *c, int64_t n, const mcbrat_sensor
                                    float *irradiance, float *irradianceStdErr, float *batchMeans, int64_t *dropped) {
   const Entry e = {"renderSensorsEmission", "samplesPerSensor", "the sensors' batches (n * numBatches)", "the emission sensors", 1,
                    camera_kernel<512, true, true, true>, camera_kernel<256, false, true, true>};
+  return render_sensors_emission(c, e, false, n, sensors, cellSource, surfaceSource, seed, firstSample, samplesPerSensor, numBatches, gridInLds, irradiance,
+                                 irradianceStdErr, batchMeans, dropped);
+}
+
+// The emission renders with the expected-value estimator: the emission entries' arguments, checks and
+// outputs; the collision estimator's paths, every leg depositing its whole ray
+int mcbrat_render_camera_emission_expected(mcbrat_ctx *c, const mcbrat_camera *cam, const float *cellSource, const float *surfaceSource, uint64_t seed,
+                                           uint64_t firstSample, int64_t samplesPerPixel, int32_t numBatches, float *radiance, float *radianceStdErr,
+                                           float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderCameraEmissionExpected", "samplesPerPixel", "the image's batches (npx * npy * numBatches)", "the emission camera", 1,
+                   camera_kernel<512, true, false, true, false, true>, camera_kernel<256, false, false, true, false, true>, true};
   if (!c) return 1;
-  if (n < 1) return fail(c, e, kNoSensor);
-  if (!sensors || !irradiance) return fail(c, e, "no sensors or no array for the irradiance.");
+  if (!cam || !radiance) return fail(c, e, kNoCamera);
   if (!cellSource || !surfaceSource) return fail(c, e, kNoSources);
-  Request q = {{0, samplesPerSensor, numBatches, firstSample}, seed, gridInLds};
+  Request q = {{0, samplesPerPixel, numBatches, firstSample}, seed};
   q.sources = EmissionSources{cellSource, surfaceSource, 0.0};
-  CameraContext v;
-  CamParams cp;
-  if (sensor_front(c, e, n, sensors, q, v, cp) || emission_sources(c, e, v, *q.sources)) return 1;
-  for (SensorGeometry &g : q.sensors) g.direct = 0.0f;
-  std::vector<long long> bins;  // [numBatches][n]
-  double unit;
-  if (backward_render(c, e, v, q, cp, bins, unit, dropped)) return 1;
-  reduce_batches(bins.data(), 1, numBatches, (size_t)n, 1, sensor_units(n, sensors, unit).data(), {{irradiance, nullptr}, {irradianceStdErr, nullptr}, nullptr, batchMeans});
-  return 0;
+  q.expected = true;
+  return render_camera(c, e, *cam, q, radiance, radianceStdErr, batchMeans, dropped);
+}
+
+int mcbrat_render_sensors_emission_expected(mcbrat_ctx *c, int64_t n, const mcbrat_sensor *sensors, const float *cellSource, const float *surfaceSource,
+                                            uint64_t seed, uint64_t firstSample, int64_t samplesPerSensor, int32_t numBatches, int32_t gridInLds,
+                                            float *irradiance, float *irradianceStdErr, float *batchMeans, int64_t *dropped) {
+  const Entry e = {"renderSensorsEmissionExpected", "samplesPerSensor", "the sensors' batches (n * numBatches)", "the emission sensors", 1,
+                   camera_kernel<512, true, true, true, false, true>, camera_kernel<256, false, true, true, false, true>, true};
+  return render_sensors_emission(c, e, true, n, sensors, cellSource, surfaceSource, seed, firstSample, samplesPerSensor, numBatches, gridInLds, irradiance,
+                                 irradianceStdErr, batchMeans, dropped);
 }
 
 }  // extern "C"

@@ -27,16 +27,18 @@ DEFAULTS = {  # monteCarloDriver.f95:58-99
     # the backward camera (no counterpart in the reference driver): absent -- cameraKind empty -- it changes
     # nothing.  cameraFootprint = xLo, xHi, yLo, yHi (default: the domain), cameraHeight (default: the top of the domain).
     # emission = .true. (here and in /sensors/; read as cameraEmission and sensorsEmission): the emission render of DESIGN.md
-    # section 4.22 on the Planck radiances of the domain's temperatures and surfaceTemp, instead of the solar one
+    # section 4.22 on the Planck radiances of the domain's temperatures and surfaceTemp, instead of the solar one.
+    # emissionEstimator = 'collision' | 'expected' (here and in /sensors/, read as emission is): the estimator of the emission
+    # render, 'expected' the expected-value one of DESIGN.md section 4.24; an error where it is given without emission = .true.
     "camera": dict(camerakind="", camerapixels=[1, 1], cameraposition=[0.0, 0.0, 0.0], cameralook=[0.0, 0.0, -1.0],
                    cameraup=[0.0, 1.0, 0.0], camerafov=60.0, cameramu=1.0, cameraphi=0.0, camerafootprint=[], cameraheight=None,
-                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile="", emission=False,
+                   camerasamplesperpixel=1000, camerabatches=10, outputcamerafile="", emission=False, emissionestimator="collision",
                    # pathLengthEdges = 0., e1, ...: the image also by photon path length, the bins' lower edges
                    pathlengthedges=[]),
     # backward sensors (no counterpart in the reference driver): absent -- sensorKind empty -- they change
     # nothing.  sensorPositions = x, y, z of every sensor in turn; sensorTilt, sensorAzimuth in degrees, one for all or one per sensor
     "sensors": dict(sensorkind="", sensorpositions=[], sensortilt=0.0, sensorazimuth=0.0, sensorsamples=10000, sensorbatches=10,
-                    outputsensorfile="", emission=False),
+                    outputsensorfile="", emission=False, emissionestimator="collision"),
 }
 
 
@@ -78,6 +80,12 @@ def read_namelists(path):
         cfg.update(groups.get(g, {}))
         if "emission" in d:  # (one key in two groups: kept apart as cameraemission and sensorsemission)
             cfg[g + "emission"] = bool(cfg.pop("emission"))
+            estimator = cfg.pop("emissionestimator")
+            if estimator not in ("collision", "expected"):
+                raise SystemExit("%s: emissionEstimator must be 'collision' or 'expected' (got %r)." % (g, estimator))
+            if estimator == "expected" and not cfg[g + "emission"]:
+                raise SystemExit("%s: emissionEstimator = 'expected' needs emission = .true. (the solar render has one estimator)." % g)
+            cfg[g + "emissionestimator"] = estimator
     return cfg
 
 
@@ -367,7 +375,8 @@ def main(argv=None):
         if cfg["cameraemission"]:
             cellSource, surfaceSource = M.planck_sources(dom, cfg["surfacetemp"])
             cameraResult = integ.renderCameraEmission(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
-                                                      int(cfg["camerabatches"]), cellSource=cellSource, surfaceSource=surfaceSource)
+                                                      int(cfg["camerabatches"]), cellSource=cellSource, surfaceSource=surfaceSource,
+                                                      estimator=cfg["cameraemissionestimator"])
         else:
             cameraResult = integ.renderCamera(camera, new_RandomNumberSequence(cfg["iseed"]), int(cfg["camerasamplesperpixel"]),
                                               int(cfg["camerabatches"]))
@@ -389,7 +398,8 @@ def main(argv=None):
         if cfg["sensorsemission"]:
             cellSource, surfaceSource = M.planck_sources(dom, cfg["surfacetemp"])
             sensorResult = integ.renderSensorsEmission(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]),
-                                                       int(cfg["sensorbatches"]), cellSource=cellSource, surfaceSource=surfaceSource)
+                                                       int(cfg["sensorbatches"]), cellSource=cellSource, surfaceSource=surfaceSource,
+                                                       estimator=cfg["sensorsemissionestimator"])
         else:
             sensorResult = integ.renderSensors(sensors, new_RandomNumberSequence(cfg["iseed"]), int(cfg["sensorsamples"]), int(cfg["sensorbatches"]))
         sensorResult["samplesPerSensor"] = int(cfg["sensorsamples"])

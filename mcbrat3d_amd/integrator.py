@@ -543,24 +543,36 @@ class Integrator:
             raise McbratError(name + ": cellSource must hold numZ x numY x numX values and surfaceSource numY x numX.")
         return cell, sfc
 
-    def renderCameraEmission(self, camera, randomNumbers, samplesPerPixel, numBatches=1, cellSource=None, surfaceSource=None):
+    def _emission_entry(self, name, estimator, collision, expected):
+        """The library's entry for `estimator`: "collision"  or "expected" (section 4.24)"""
+        if estimator not in ("collision", "expected"):
+            raise McbratError(name + ": estimator must be 'collision' or 'expected' (got %r)." % (estimator,))
+        return getattr(self._lib, expected if estimator == "expected" else collision)
+
+    def renderCameraEmission(self, camera, randomNumbers, samplesPerPixel, numBatches=1, cellSource=None, surfaceSource=None, estimator="collision"):
         """The emitted (thermal) radiance at `camera` by backward Monte Carlo: renderCamera's paths, which deposit the source
         function where they collide and where they meet the surface instead of looking toward the sun.  cellSource [nz, ny, nx]
         and surfaceSource [ny, nx] are Planck radiances (mcbrat3d_amd.planck_sources); the result has their units.  The loaded
-        source is not consulted (none need be loaded: prepareDomain).  Returns what renderCamera returns."""
+        source is not consulted (none need be loaded: prepareDomain).  Returns what renderCamera returns, and "estimator".
+        estimator="expected"  walks the same paths with the expected-value estimator: every leg deposits
+        the emission along its whole ray, collisions deposit nothing -- the same mean, no variance without scattering, and far
+        less of it in optically thin air."""
+        entry = self._emission_entry("renderCameraEmission", estimator, "mcbrat_render_camera_emission", "mcbrat_render_camera_emission_expected")
         cell, sfc = self._emission_sources("renderCameraEmission", cellSource, surfaceSource)
-        return self._render_camera(self._lib.mcbrat_render_camera_emission, camera, (ptr(cell), ptr(sfc)), randomNumbers.seed, randomNumbers.nextPhotonId,
-                                   samplesPerPixel, numBatches, randomNumbers, emission=True)
+        return self._render_camera(entry, camera, (ptr(cell), ptr(sfc)), randomNumbers.seed, randomNumbers.nextPhotonId,
+                                   samplesPerPixel, numBatches, randomNumbers, emission=True, estimator=estimator)
 
     def renderSensorsEmission(self, sensors, randomNumbers, samplesPerSensor, numBatches=1, cellSource=None, surfaceSource=None,
-                              gridInLds=-1):
+                              gridInLds=-1, estimator="collision"):
         """The emitted (thermal) irradiance (planar sensors: a pyrgeometer) and actinic flux (spherical ones) at `sensors`, in
         the sources' units times steradians.  Returns "irradiance", "irradiance_StdErr" (one value per sensor), "batchMeans"
-        [numBatches, n] and "dropped"; there is no direct part ("emission": True marks the dict for the NetCDF writers)."""
+        [numBatches, n], "dropped" and "estimator"; there is no direct part ("emission": True marks the dict for the NetCDF
+        writers).  estimator="expected": as for renderCameraEmission."""
+        entry = self._emission_entry("renderSensorsEmission", estimator, "mcbrat_render_sensors_emission", "mcbrat_render_sensors_emission_expected")
         cell, sfc = self._emission_sources("renderSensorsEmission", cellSource, surfaceSource)
-        (irr, err), means, dropped = self._render_sensors(self._lib.mcbrat_render_sensors_emission, sensors, (ptr(cell), ptr(sfc)), randomNumbers,
+        (irr, err), means, dropped = self._render_sensors(entry, sensors, (ptr(cell), ptr(sfc)), randomNumbers,
                                                           samplesPerSensor, numBatches, gridInLds, 2)
-        return {"irradiance": irr, "irradiance_StdErr": err, "batchMeans": means, "dropped": dropped, "emission": True}
+        return {"irradiance": irr, "irradiance_StdErr": err, "batchMeans": means, "dropped": dropped, "emission": True, "estimator": estimator}
 
     def sunTransmittance(self, points):
         """exp(-optical depth) from each point (an [n, 3] array of x, y, z) toward the sun up to the top of the loaded

@@ -260,6 +260,19 @@ CAMERA_EMISSION_VARIABLES = ("cameraEmission", "cameraEmission_StdErr")
 CAMERA_PATH_VARIABLES = ("cameraRadianceByPathLength", "cameraRadianceByPathLength_StdErr", "cameraPathLengthEdges")
 
 
+def _mark_estimator(variable, result):
+    """The expected-value estimator is an attribute of the emission variable, written only where it was
+    used: a file of the collision estimator is byte for byte what it was."""
+    if result.get("emission") and result.get("estimator") == "expected":
+        variable.estimator = "expected"
+
+
+def _estimator(variable):
+    """-> {"estimator": ...} where the variable carries the attribute, else nothing"""
+    value = getattr(variable, "estimator", None)
+    return {} if value is None else {"estimator": value.decode() if isinstance(value, bytes) else str(value)}
+
+
 def _add_sensors(f, sensors, result):
     """The backward sensors, dimension `sensor`: where they are (sensorPosition, sensorNormal (sensor,
     xyz), sensorKind: 0 planar, 1 spherical) and what they measure (sensorIrradiance = sensorDiffuse + sensorDirect with its
@@ -276,6 +289,7 @@ def _add_sensors(f, sensors, result):
     names = SENSOR_EMISSION_VARIABLES if result.get("emission") else SENSOR_VARIABLES
     for name, key in zip(names, ("irradiance", "irradiance_StdErr", "diffuse", "direct")):
         f.createVariable(name, "f", ("sensor",))[:] = np.asarray(result[key], np.float32)
+    _mark_estimator(f.variables[names[0]], result)
 
 
 def writeSensors_netcdf(outputFileName, sensors, result):
@@ -299,6 +313,8 @@ def readSensors_netcdf(fileName):
         names = SENSOR_EMISSION_VARIABLES if SENSOR_EMISSION_VARIABLES[0] in f.variables else SENSOR_VARIABLES
         out = {k: np.array(f.variables[k][:]) for k in ("sensorPosition", "sensorNormal", "sensorKind") + names}
         out.update(sensorSamples=float(f.sensorSamples), sensorBatches=int(f.sensorBatches), sensorDroppedPaths=float(f.sensorDroppedPaths))
+        if "estimator" in _estimator(f.variables[names[0]]):
+            out["sensorEstimator"] = _estimator(f.variables[names[0]])["estimator"]
         return out
     finally:
         f.close()
@@ -322,6 +338,7 @@ def _add_camera(f, camera, result):
     names = CAMERA_EMISSION_VARIABLES if result.get("emission") else CAMERA_VARIABLES
     f.createVariable(names[0], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance"], np.float32)
     f.createVariable(names[1], "f", ("cameraY", "cameraX"))[:] = np.asarray(result["radiance_StdErr"], np.float32)
+    _mark_estimator(f.variables[names[0]], result)
     if result.get("radianceByPathLength") is not None:  # (without the key the file is byte for byte what it was)
         edges = np.asarray(result["pathLengthEdges"], np.float32).reshape(-1)
         f.createDimension("cameraPathBin", edges.size)
@@ -343,6 +360,8 @@ def readCamera_netcdf(fileName):
         out.update({k: np.array(f.variables[k][:]) for k in CAMERA_PATH_VARIABLES if k in f.variables})
         out.update(cameraSamplesPerPixel=float(f.cameraSamplesPerPixel), cameraBatches=int(f.cameraBatches),
                    cameraDroppedPaths=float(f.cameraDroppedPaths))
+        if "estimator" in _estimator(f.variables[names[0]]):
+            out["cameraEstimator"] = _estimator(f.variables[names[0]])["estimator"]
         return out
     finally:
         f.close()
